@@ -7,26 +7,33 @@ full reduction over GF(32003), Gebauer-Moeller update, lead-monomial observation
 finished episodes draw their next ideal on the device).  Workload = BASELINE.json configs[1]:
 3-20-10-weighted, batch 4096 per GPU, k=2, random-selection agent.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Measurement protocol (so that the line means the same at --steps 20 and at --steps 1024):
+A plain run does only what the headline figure needs:
   * pre-roll: every environment runs `preroll_steps` (>= 256) untimed steps first, so that the batch is in its steady
     state (a mix of episode phases) rather than all environments in their first episode;
-  * W warm-up steps (one launch), then eight chained calibration launches of K steps (untimed);
-  * timed region: R back-to-back launches of K steps each (`repeats`; R is chosen so that the region lasts >= 0.5 s),
-    enqueued asynchronously, bracketed by barrier + synchronize on both sides; `ms_per_step` is the region's wall time /
-    (R*K), `value` = batch * R * K / wall time (max over ranks).  The launches go through a persistent session
-    (bbx_persistent, include/bbx.h): the first starts the step kernel, the others raise a device-visible step counter
-    its waves look at, so environments never wait for each other between launches (`config.launch_path`;
-    --no-persistent issues one kernel per launch, the round-2 path);
+  * W warm-up steps (one launch);
+  * timed region: ONE launch of exactly K steps (`repeats` = 1; --repeats R times R launches of K steps), bracketed by
+    barrier + synchronize on both sides; `ms_per_step` is the region's wall time / (R*K), `value` = batch * R * K / wall
+    time (max over ranks).  The launch goes through a persistent session (bbx_persistent, include/bbx.h): environments
+    never wait for each other between steps (`config.launch_path`; --no-persistent issues one kernel per launch);
+  * --dump-outputs DIR: what the timed launch handed its caller after its last step (rewards, dones, observation row
+    counts, the observation block with the rows past each environment's count set to -1) as DIR/<name>.npy.
+
+--full adds everything else the line carries (its timed region means the same at --steps 20 and at --steps 1024):
+  * chained calibration launches of K steps (untimed; 64 with a persistent session, 8 without) and, unless --repeats is
+    given, R launches of K steps in the timed region with R chosen so that the region lasts >= 0.5 s (the first launch
+    starts the session's step kernel, the others raise a device-visible step counter its waves look at);
   * `roofline.kernel_ms_per_launch` = HIP-event time of the region / R: the events are recorded on the caller's stream,
     the first before the first launch, the second behind bbx_join (which makes that stream wait, on the device, for the
-    session's kernels).
+    session's kernels); the algorithmic bytes come from an accounting replay of the timed steps on a copy of the batch;
+  * `long_launch`: the same workload in launches of 1024 steps after the timed region;
+  * `cpu_baseline` / `cpu_baseline_all_cores`: the CPU code on a sample of the same environments.
 
-Prints ONE JSON line on rank 0 with `roofline` and `cpu_baseline` objects (the only thing that reaches stdout: everything
-else, native libraries' chatter included, is sent to stderr).  With --gpus N > 1 and no launcher
-environment, the ranks are started here as fresh child processes (before anything touches the GPU).
+Prints ONE JSON line on rank 0 (the only thing that reaches stdout: everything else, native libraries' chatter included,
+is sent to stderr).  With --gpus N > 1 and no launcher environment, the ranks are started here as fresh child processes
+(before anything touches the GPU).
 """
 import argparse
 import json
@@ -46,6 +53,7 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec
 PREROLL = 256
 MIN_REGION_MS = 500.0  # a sustained figure: long enough to contain the rare environments whose bases grow large
 LONG_REGION_MS = 250.0
+DUMP_OBS_BYTES = 56 << 20  # --dump-outputs: the observation block's share of the 64 MB the files may take
 PMC_PROFILES = [os.path.join("profiles", "r04_pmc_fast_kernel.json"), os.path.join("profiles", "r03_pmc_fast_kernel.json")]
 
 
@@ -56,7 +64,13 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--dist", default=DIST)
-    ap.add_argument("--repeats", type=int, default=0, help="launches of K steps in the timed region (0 = enough for >= 0.5 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also calibrate the timed region to >= 0.5 s, time the long launches, replay the steps for the roofline and "
+                         "run the CPU baselines (a plain run times exactly --steps steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed launch returned after its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="launches of K steps in the timed region (default: 1; with --full, 0 = enough for >= 0.5 s)")
     ap.add_argument("--preroll", type=int, default=PREROLL)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--generic-kernel", action="store_true",
@@ -121,8 +135,12 @@ def spawn_ranks(args):
 
 def main():
     args = parse_args()
-    if args.gpus < 1 or args.steps < 1 or args.warmup < 0:
-        raise SystemExit("--gpus and --steps must be positive, --warmup non-negative")
+    if args.gpus < 1 or args.steps < 1 or args.warmup < 0 or (args.repeats is not None and args.repeats < 0):
+        raise SystemExit("--gpus and --steps must be positive, --warmup and --repeats non-negative")
+    if args.repeats == 0 and not args.full:
+        raise SystemExit("--repeats 0 (a timed region calibrated to >= 0.5 s) needs --full")
+    if args.dump_outputs and args.rehearse_plumbing:
+        raise SystemExit("--dump-outputs needs the device: a plumbing rehearsal computes nothing")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))               # nothing has touched the GPU in this process
     # Exactly ONE line goes to stdout: whatever libraries print there from native code (gloo announces its rendezvous on
@@ -209,20 +227,24 @@ def main():
     if Wm > 0:
         launch(Wm); env.sync()
     gpu_sync()
-    t0 = time.perf_counter()
-    ncal = (64 if persistent else 8) if chain else 1 # calibration (also the untimed warm-up of this launch shape): chained
-    for _ in range(ncal):                             # launches, so that the synchronisation is not mistaken for launch time
-        launch(K)
-    env.sync(); gpu_sync()
-    t_launch = (time.perf_counter() - t0) / ncal
-    R = args.repeats if args.repeats > 0 else int(min(1 << 16, max(3, MIN_REGION_MS * 1e-3 / max(t_launch, 1e-6) + 1)))
+    R = args.repeats if args.repeats is not None else (0 if args.full else 1)
+    ncal = 0
+    if args.full:
+        t0 = time.perf_counter()
+        ncal = (64 if persistent else 8) if chain else 1 # calibration (also the untimed warm-up of this launch shape): chained
+        for _ in range(ncal):                             # launches, so that the synchronisation is not mistaken for launch time
+            launch(K)
+        env.sync(); gpu_sync()
+        t_launch = (time.perf_counter() - t0) / ncal
+        if R == 0:
+            R = int(min(1 << 16, max(3, MIN_REGION_MS * 1e-3 / max(t_launch, 1e-6) + 1)))
     if world > 1:
         r_all = [None] * world
         dist.all_gather_object(r_all, R)
         R = max(r_all)
     st0 = env.stats()
     sess0 = env.session_stats()
-    twin = env.copy()                               # same state, same generator state: replayed after the timed region
+    twin = env.copy() if args.full else None        # same state, same generator state: replayed after the timed region
 
     gpu_sync()
     if world > 1:
@@ -241,12 +263,14 @@ def main():
         dist.barrier()
     elapsed = t1 - t0
     region_ms = ev0.elapsed_time(ev1)               # HIP events on the stream the kernels were launched on
+    if args.dump_outputs:                           # (before anything else steps the batch)
+        dump_outputs(args.dump_outputs, rank, d_rew, d_done, d_rows, d_obs)
     st1 = env.stats()
     # context, outside the timed region: the same kernel in launches of 1024 steps (how a rollout would normally be
     # issued; launches of few steps end with the waves that met an episode reset)
     long_launch = None
     sess = env.session_stats()
-    if not args.no_long_launch and world == 1:
+    if args.full and not args.no_long_launch and world == 1:
         launch(64)                                  # (the statistics call above closed the session: a new one gets going)
         env.join(stream.cuda_stream)
         n_long = int(max(8, LONG_REGION_MS / max(1024 * region_ms / (R * K), 1e-6) + 1))
@@ -269,15 +293,17 @@ def main():
     assert (st1[:, 4] == 0).all(), "an environment reported an error status"
     assert rehearsal or int(d_rows.max().item()) <= obs_rows
     additions = int(d[:, 1].sum())
-    # algorithmic bytes of exactly these steps: replay them on the twin with the accounting kernel (untimed)
-    twin.accounting(True)
-    for _ in range(R):
-        twin.rollout("random", K, auto_reset=True)
-    st_twin = twin.stats()
-    dt = st_twin - st0
-    assert np.array_equal(dt[:, :2], d[:, :2]) and np.array_equal(st_twin[:, 7], st1[:, 7]), "accounting replay diverged"
-    alg_bytes = int(dt[:, 6].sum())
-    del twin
+    alg_bytes = 0
+    if args.full:
+        # algorithmic bytes of exactly these steps: replay them on the twin with the accounting kernel (untimed)
+        twin.accounting(True)
+        for _ in range(R):
+            twin.rollout("random", K, auto_reset=True)
+        st_twin = twin.stats()
+        dt = st_twin - st0
+        assert np.array_equal(dt[:, :2], d[:, :2]) and np.array_equal(st_twin[:, 7], st1[:, 7]), "accounting replay diverged"
+        alg_bytes = int(dt[:, 6].sum())
+        del twin
 
     per_rank = [steps_done / elapsed]
     if world > 1:
@@ -291,7 +317,7 @@ def main():
         steps_done, additions, alg_bytes = int(s[0]), int(s[1]), int(s[2])
 
     cpu = cpu_all = None
-    if rank == 0 and not args.no_cpu_baseline and not rehearsal:
+    if rank == 0 and args.full and not args.no_cpu_baseline and not rehearsal:
         cpu = cpu_baseline(args, st1, int(st1[0, 0]), B)
         if not args.no_cpu_all_cores:
             cpu_all = cpu_baseline_all_cores(args, st1, int(st1[0, 0]), B, cpu)
@@ -345,7 +371,7 @@ def main():
                        "global_batch": B * world, "steps_per_launch": K, "parallelism": "env-sharded x%d, no collectives" % world,
                        "devices_visible": ndev, "launch_path": "persistent session (bbx_persistent)" if persistent else "one kernel per launch"},
             "oversubscribed": bool(oversubscribed), "per_rank_value": [None] * world if rehearsal else per_rank,
-            "rehearsal": bool(rehearsal),
+            "rehearsal": bool(rehearsal), "full": bool(args.full),
             "additions": None if rehearsal else additions,
             "additions_per_s": None if rehearsal else additions / elapsed,
             "long_launch": long_launch,
@@ -353,7 +379,7 @@ def main():
                                "note": "spills = environments that left the register/LDS class (basis beyond 256 elements or 512 pairs) and "
                                        "were continued by the HBM-resident pass; later_kernel_steps = env-steps taken by closing kernels"}
                               if persistent else None),
-            "roofline": None if rehearsal else roof,
+            "roofline": roof if args.full and not rehearsal else None,
             "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_all,
         }
@@ -362,6 +388,32 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(directory, rank, d_rew, d_done, d_rows, d_obs):
+    """--dump-outputs: what the timed launch handed its caller after its last step, as float32 / float64 .npy files —
+    rewards [B] (float64, as returned), dones [B], rows [B] (observation rows per environment) and obs [n, nr, cols]: the
+    observation block cut to the batch's largest row count nr, rows past an environment's own count set to -1 (the launch
+    leaves them unwritten).  When all B environments would take more than DUMP_OBS_BYTES, obs holds a fixed sample of them
+    (seeded, sorted), listed in obs_env_ids.  Ranks other than 0 add _rank<r> to the names."""
+    import numpy as np
+    rew = d_rew.cpu().numpy().astype(np.float64)
+    done = d_done.cpu().numpy().astype(np.float32)
+    rows = d_rows.cpu().numpy()
+    obs = d_obs.cpu().numpy()
+    B, _, cols = obs.shape
+    nr = max(1, int(rows.max()))
+    ids = np.arange(B)
+    if B * nr * cols * 4 > DUMP_OBS_BYTES:
+        n = max(1, DUMP_OBS_BYTES // (nr * cols * 4))
+        ids = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    block = obs[ids, :nr].astype(np.float32)
+    block[np.arange(nr)[None, :] >= rows[ids, None]] = -1.0
+    os.makedirs(directory, exist_ok=True)
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, a in (("rewards", rew), ("dones", done), ("rows", rows.astype(np.float32)), ("obs", block),
+                    ("obs_env_ids", ids.astype(np.float64))):
+        np.save(os.path.join(directory, name + suffix + ".npy"), a)
 
 
 def cpu_baseline(args, st_final, steps_per_env, B):

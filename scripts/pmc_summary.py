@@ -1,8 +1,8 @@
 """Summarise the rocprofv3 runs of scripts/profile_bench.sh into profiles/<tag>_pmc_fast_kernel.json and copy the kernel-trace
 stats.  The step kernel of the bench line is the kernel of a persistent session: a run has a handful of its dispatches
 (pre-roll, warm-up, calibration, the 10 ms slices of the timed region), so counters are SUMMED over the dispatches of a
-pass and divided by the batch steps the run pushed through the kernel (bench.py reports them:
-roofline.batch_steps_through_kernel).  HBM traffic = (2 FETCH_SIZE + WRITE_SIZE) KiB (FETCH doubled, MI355X_MICROARCH.md);
+pass and divided by the batch steps the run pushed through the kernel (bench.py --full reports them:
+roofline.batch_steps_through_kernel).  The runs are read from $PROF_OUT (prof_out by default), where profile_bench.sh left them.  HBM traffic = (2 FETCH_SIZE + WRITE_SIZE) KiB (FETCH doubled, MI355X_MICROARCH.md);
 scalar-issue bound = scalar-pipe instructions per cycle per CU against the one scalar unit of a CU.
     python scripts/pmc_summary.py r03"""
 import collections, csv, glob, json, os, shutil, sys
@@ -10,6 +10,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 kern = sys.argv[2] if len(sys.argv) > 2 else "bbx_fast_headline_persistent_kernel"      # the kernel of the bench line (kernel-trace stats)
 pmc_kern = "bbx_fast_headline_kernel"                    # the same step code, one kernel per launch: what the PMC passes run
 B = 4096
+OUT = os.environ.get("PROF_OUT", "prof_out")
 
 
 def bench_line(path):
@@ -21,10 +22,10 @@ def bench_line(path):
 
 counters, per_pass = {}, []
 for i in range(1, 5):
-    files = sorted(glob.glob("gpurun_out/pmc_%s_%d/**/*counter_collection.csv" % (tag, i), recursive=True))
+    files = sorted(glob.glob("%s/pmc_%s_%d/**/*counter_collection.csv" % (OUT, tag, i), recursive=True))
     if not files:
-        sys.exit("pass %d of the PMC runs is missing (gpurun_out/pmc_%s_%d): not summarising stale numbers" % (i, tag, i))
-    line = bench_line("gpurun_out/pmc_%s_%d.json" % (tag, i))
+        sys.exit("pass %d of the PMC runs is missing (%s/pmc_%s_%d): not summarising stale numbers" % (i, OUT, tag, i))
+    line = bench_line("%s/pmc_%s_%d.json" % (OUT, tag, i))
     steps = line["roofline"]["batch_steps_through_kernel"]
     acc = collections.defaultdict(float); dur = {}
     for f in files:
@@ -39,7 +40,7 @@ for i in range(1, 5):
     for c, v in acc.items():
         counters[c] = v / steps                            # per batch step (4096 environment steps)
 res = {"round": int(tag.lstrip("r") or 0), "kernel": pmc_kern,
-       "workload": "bench.py --steps 1024 --warmup 64 --no-persistent: 3-20-10-weighted, 4096 envs, k=2, obs every step, ideals drawn on the device, "
+       "workload": "bench.py --full --steps 1024 --warmup 64 --no-persistent: 3-20-10-weighted, 4096 envs, k=2, obs every step, ideals drawn on the device, "
                    "one kernel per launch (counter collection serialises kernels: see scripts/profile_bench.sh)",
        "passes": per_pass, "counters_per_batch_step": counters}
 if "FETCH_SIZE" in counters and "WRITE_SIZE" in counters:
@@ -61,12 +62,12 @@ if "SQ_INSTS_SALU" in counters and "SQ_BUSY_CYCLES" in counters:
 os.makedirs("profiles", exist_ok=True)
 json.dump(res, open("profiles/%s_pmc_fast_kernel.json" % tag, "w"), indent=1)
 for k in (20, 1024):
-    found = glob.glob("gpurun_out/prof_%s_k%d/**/*kernel_stats.csv" % (tag, k), recursive=True)
+    found = glob.glob("%s/prof_%s_k%d/**/*kernel_stats.csv" % (OUT, tag, k), recursive=True)
     if not found:
         sys.exit("kernel-trace stats of K=%d are missing" % k)
     shutil.copy(found[0], "profiles/%s_bench_k%d_kernel_stats.csv" % (tag, k))
-    shutil.copy("gpurun_out/prof_%s_k%d.json" % (tag, k), "profiles/%s_bench_k%d_line.json" % (tag, k))
-    line = bench_line("gpurun_out/prof_%s_k%d.json" % (tag, k))
+    shutil.copy("%s/prof_%s_k%d.json" % (OUT, tag, k), "profiles/%s_bench_k%d_line.json" % (tag, k))
+    line = bench_line("%s/prof_%s_k%d.json" % (OUT, tag, k))
     for r in csv.DictReader(open(found[0])):
         if kern in r["Name"]:
             tot = float(r["TotalDurationNs"]); steps = line["roofline"]["batch_steps_through_kernel"]
