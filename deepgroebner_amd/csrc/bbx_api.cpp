@@ -235,7 +235,7 @@ int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) 
     // rollout; a single host-driven step does without it: an environment that spills reports BBX_ST_SPILL and
     // finish() continues it (one launch less on the latency path)
     // (asynchronous calls on caller buffers always get it: nobody polls their status words between steps)
-    if (!b->staged || pol_hbm_only || resume || p.nsteps > 1 || b->obs_external || b->device_async) kinds[nk++] = 0;
+    if (!b->staged || pol_hbm_only || resume || p.nsteps > 1 || b->flight.obs_external || b->flight.device_async) kinds[nk++] = 0;
   }
   // wide class with more workgroups than CUs: a second kernel for the tail of the launch (BbxParams::wide_tail)
   int tail_at = -1;
@@ -246,8 +246,8 @@ int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) 
   }
   // a host-driven zero-copy step whose only kernel is the hand-tuned one: the host spins on the status words in pinned
   // memory instead of waiting for the runtime's completion signal (read_lite)
-  b->poll_active = !resume && nk == 1 && kinds[0] == 3 && b->zc_active && p.lite != nullptr && !b->timing && b->poll_misses < 3 && !getenv("BBX_NO_POLL");
-  if (b->poll_active) {
+  b->flight.poll = !resume && nk == 1 && kinds[0] == 3 && outputs_pinned(b) && !b->timing && b->poll_misses < 3 && !getenv("BBX_NO_POLL");
+  if (b->flight.poll) {
     b->poll_seq = (b->poll_seq % 16000) + 1; p.done_seq = b->poll_seq;
     // the words the host is going to watch start out cleared: pinned memory is handed out uninitialised and may still hold
     // the status words — sequence numbers included — of a handle that was destroyed
@@ -323,23 +323,21 @@ int alloc_io(bbx_batch* b, int batch) {
   return BBX_OK;
 }
 
-// fetch the block the kernels of the last launch left behind (status words and the host-API outputs) in one copy
-int read_lite(bbx_batch* b, hipStream_t stream) {
+// fetch the block the kernels of the last launch left behind (status words and the host-API outputs) in one copy;
+// `pinned`: they wrote it into the pinned block themselves (outputs_pinned() of the call in flight)
+int read_lite(bbx_batch* b, hipStream_t stream, bool pinned) {
   b->h_lite.resize((size_t)b->B * 4);
-  if (!b->zc_active) HIPCHK(hipMemcpyAsync(b->h_io, b->d_out, b->io_bytes, hipMemcpyDeviceToHost, stream));
+  if (!pinned) HIPCHK(hipMemcpyAsync(b->h_io, b->d_out, b->io_bytes, hipMemcpyDeviceToHost, stream));
   bool seen = false;
-  if (b->zc_active && b->poll_active) {              // spin on the status words the kernel writes last (a few microseconds
-    const volatile int32_t* w = (const volatile int32_t*)b->h_io;   // earlier than the runtime's signal); 2 ms, then the normal wait
-    const auto t0 = std::chrono::steady_clock::now();
+  if (pinned && b->flight.poll) {                    // spin on the status words the kernel writes last (a few microseconds
+    const auto t0 = std::chrono::steady_clock::now();   // earlier than the runtime's signal); 2 ms, then the normal wait
     for (int spins = 0;; spins++) {
-      bool all = true;
-      for (int e = 0; e < b->B; e++) all = all && (((uint32_t)w[(size_t)e * 4]) >> 17) == (uint32_t)b->poll_seq;
-      if (all) { seen = true; b->poll_misses = 0; break; }
+      if (scan_seq(b, (uint32_t)b->poll_seq, 0).all) { seen = true; b->poll_misses = 0; break; }
       if ((spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     }
     std::atomic_thread_fence(std::memory_order_acquire);
     if (!seen) b->poll_misses++;                  // (three in a row: the writes do not arrive early on this system; stop spinning)
-    b->poll_active = false;
+    b->flight.poll = false;
   }
   // (every so often the runtime gets its wait as well, so that it can retire the commands it queued)
   if (!seen || (++b->polled_launches & 63) == 0) HIPCHK(hipStreamSynchronize(stream));   // (zero-copy launches wrote h_io themselves)
@@ -407,7 +405,7 @@ int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream) {
     b->cap_stale = true;
   } else HIPCHK(hipFree(b->d_recs));
   b->d_recs = nrecs; b->L = NL;
-  b->last.recs = nrecs; b->last.L = NL;
+  b->flight.p.recs = nrecs; b->flight.p.L = NL;
   b->grow_events++;
   if (getenv("BBX_VERBOSE"))
     fprintf(stderr, "[bbx] records enlarged (%s, environment %d): max_basis %u max_pairs %u arena_terms %u max_poly_terms %u, %zu MiB\n",
@@ -418,25 +416,21 @@ int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream) {
 // wait for the launch in flight; serve environments that ran out of queued ideals or outgrew the LDS class; surface
 // errors.  Whatever happens, the handle is left with nothing in flight: an error is reported once, not re-raised by
 // every later call, and environments that only needed service (STARVED / SPILL) have been served before the first
-// error of another environment is returned.
-int finish_impl(bbx_batch* b, hipStream_t stream);
-
-int finish(bbx_batch* b, hipStream_t stream) {
-  b->api_epoch++;
-  const bool mbox = b->ps_active && b->ps_mbox;              // (closing a mailbox session switches the pinned outputs on: off again behind it)
-  if (mbox) {
-    // nothing owed (the host waited for every step it issued): tell the waves to go, wait for the kernel, done — no closing kernel
-    bool settled = true;
-    const volatile int32_t* w = (const volatile int32_t*)b->h_io;
-    const uint32_t want = (uint32_t)(b->ps_target % 16000) + 1u;
-    for (int e = 0; e < b->B; e++) { const uint32_t v = (uint32_t)w[(size_t)e * 4]; settled = settled && (v >> 17) == want && (v & 0xffffu) == BBX_ST_OK; }
-    if (settled) {
+// error of another environment is returned (finish() ends the flight).
+int finish_impl(bbx_batch* b, hipStream_t stream) {
+  bbx_flight& f = b->flight;
+  if (b->ps_active && b->ps_mbox) {
+    // nothing owed (the host waited for every step it issued and every status word says OK — the observation-cut bit is not
+    // asked, unlike in mbox_step's scan: bbx_step_obs re-checks the rows itself): tell the waves to go, wait for the kernel,
+    // done — no closing kernel
+    const SeqScan s = scan_seq(b, (uint32_t)(b->ps_target % 16000) + 1u, 0);
+    if (s.all && !s.trouble) {
       b->ps_active = false;
-      int rc0 = ps_write_ctl(b, true);
-      if (rc0) return rc0;
+      if (int rc = ps_write_ctl(b, true)) return rc;
       b->ps_mbox = false;
       // every wave marks its status block when it has stored its environment and left (bbx_fast.h): a spin of a few
       // microseconds instead of the runtime's wait for the kernel (hundreds, once per episode of a gym loop)
+      const volatile int32_t* w = (const volatile int32_t*)b->h_io;
       bool gone = false;
       const auto t0 = std::chrono::steady_clock::now();
       for (unsigned spins = 0; !gone; spins++) {
@@ -446,46 +440,35 @@ int finish(bbx_batch* b, hipStream_t stream) {
       }
       std::atomic_thread_fence(std::memory_order_acquire);
       if (!gone) HIPCHK(hipStreamSynchronize(b->ps_stream));
-      b->last = b->ps_p; b->last.recs = b->d_recs; b->last.L = b->L; b->last.ctl = nullptr; b->last.sess_target = 0; b->last.set_budget = 0;
-      b->last.policy = nullptr; b->last.mbox = 0;
-      b->last_stream = b->ps_stream;
+      continue_session(b);
       b->h_lite.resize((size_t)b->B * 4);
       memcpy(b->h_lite.data(), b->h_io, (size_t)b->B * 16);
       for (int e = 0; e < b->B; e++) { b->h_lite[(size_t)e * 4 + 2] &= 0x3fffffff; b->h_head[e] = b->h_lite[(size_t)e * 4 + 1]; }
-      b->in_flight = false; b->async_chain = 0;
-      return BBX_OK;                                        // (every status word said OK: nothing to serve, nothing to report)
+      return BBX_OK;                                      // (every status word said OK: nothing to serve, nothing to report)
     }
   }
-  const int rc = finish_impl(b, stream);
-  if (mbox) b->zc_active = false;
-  return rc;
-}
-
-int finish_impl(bbx_batch* b, hipStream_t stream) {
   int err = BBX_OK;
-  const int async_chain = b->async_chain;              // (asynchronous external-action steps behind this wait)
-  b->async_chain = 0;
   auto note = [&err](int code) { if (err == BBX_OK) err = code; };
   if (b->ps_active) {                                // a persistent session: stop it; its kernels run in slices until nothing is owed
     int rc = session_close(b, false, nullptr, true);
-    if (rc) { b->in_flight = false; return rc; }
+    if (rc) return rc;
     stream = b->ps_stream;
     for (int guard = 0;; guard++) {
-      rc = read_lite(b, stream);
-      if (rc) { b->in_flight = false; return rc; }
+      rc = read_lite(b, stream, outputs_pinned(b));
+      if (rc) return rc;
       bool owed = false;
       for (int e = 0; e < b->B && !owed; e++) owed = (b->h_lite[(size_t)e * 4] & 0xffff) == BBX_ST_TIMESLICE;
       if (!owed) break;
-      if (guard >= 100000) { b->in_flight = false; return fail(BBX_E_DEVICE, "a persistent session still owes steps after 100000 time slices"); }
+      if (guard >= 100000) return fail(BBX_E_DEVICE, "a persistent session still owes steps after 100000 time slices");
       rc = session_kernel(b, false, nullptr, true);
-      if (rc) { b->in_flight = false; return rc; }
+      if (rc) return rc;
     }
   }
   for (int round = 0;; round++) {
-    int rc = read_lite(b, stream);
-    if (rc) { b->in_flight = false; return rc; }
+    int rc = read_lite(b, stream, outputs_pinned(b));
+    if (rc) return rc;
     rc = collect_events(b);
-    if (rc) { b->in_flight = false; return rc; }
+    if (rc) return rc;
     bool again = false;
     unsigned grow = 0; int grow_env = -1;
     for (int e = 0; e < b->B; e++) {
@@ -500,7 +483,7 @@ int finish_impl(bbx_batch* b, hipStream_t stream) {
       }
       if (st == BBX_ST_GEN_ZERO) { if (err == BBX_OK) note(fail(BBX_E_GENERATOR, "random polynomial cancelled to zero (undefined in the reference)")); }
       else if (st == BBX_ST_GEN_FAIL) { if (err == BBX_OK) note(fail(BBX_E_GENERATOR, "failed to generate two distinct random monomials after 1000 trials")); }
-      else if ((st == BBX_ST_STARVED || st == BBX_ST_SPILL) && b->policy_rollout) {
+      else if ((st == BBX_ST_STARVED || st == BBX_ST_SPILL) && f.policy_rollout) {
         // (the continuation pass runs right behind the first one; what is still unfinished here cannot be resumed: the
         // policy arguments belonged to the caller's frame)
         if (err == BBX_OK) note(fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s)", e, status_name(st)));
@@ -510,7 +493,7 @@ int finish_impl(bbx_batch* b, hipStream_t stream) {
       else if (bbx_st_capacity(st) && !b->no_growth) { grow |= 1u << st; if (grow_env < 0) grow_env = e; }
       else if (st != BBX_ST_OK && err == BBX_OK) {
         rc = read_headers(b, stream);
-        if (rc) { b->in_flight = false; return rc; }
+        if (rc) return rc;
         note(fail(BBX_E_CAPACITY, "environment %d: %s (|G|=%d |P|=%d terms=%d)", e, status_name(st),
                   b->h_hdr[e].nG, b->h_hdr[e].nP, b->h_hdr[e].arena_used));
       }
@@ -518,12 +501,12 @@ int finish_impl(bbx_batch* b, hipStream_t stream) {
     if (grow) {                                       // enlarge what was full; the environments then take the step they stopped at
       rc = grow_records(b, grow, grow_env, stream);
       if (rc) { note(rc); break; }
-      if (b->policy_rollout) {                        // (its per-step arrays belonged to the caller's frame: cannot be resumed)
+      if (f.policy_rollout) {                         // (its per-step arrays belonged to the caller's frame: cannot be resumed)
         note(fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s); the records have been enlarged, later rollouts have room",
                   grow_env, status_name(__builtin_ctz(grow))));
         break;
       }
-      if (b->device_async && b->last.agent == BBX_AGENT_EXTERNAL && async_chain > 1) {
+      if (f.device_async && f.p.agent == BBX_AGENT_EXTERNAL && f.async_chain > 1) {
         // several asynchronous steps with caller-supplied actions were queued behind each other (or replayed from a graph):
         // the environment stopped at one of them and sat out the rest; the action buffer now holds a later step's actions,
         // so the step it stopped at cannot be taken for it
@@ -537,17 +520,35 @@ int finish_impl(bbx_batch* b, hipStream_t stream) {
     if (!again) break;
     if (round > 100000) { note(fail(BBX_E_GENERATOR, "ideal queue starvation did not resolve")); break; }
     rc = fill_queues(b, 1, stream);
-    if (rc) { b->in_flight = false; return rc; }
-    rc = enqueue(b, b->last, true, stream);   // continue the rollout where each environment stopped
-    if (rc) { b->in_flight = false; return rc; }
+    if (rc) return rc;
+    rc = enqueue(b, f.p, true, stream);       // continue the rollout where each environment stopped
+    if (rc) return rc;
   }
-  b->in_flight = false;
-  if (err == BBX_OK && b->obs_external)
+  if (err == BBX_OK && f.obs_external)
     for (int e = 0; e < b->B; e++)
       if (b->h_lite[(size_t)e * 4] & BBX_LITE_OBS_TRUNC)
         return fail(BBX_E_CAPACITY, "environment %d: an observation had more rows than the caller's block holds (obs_rows = %d) or, in a policy "
-                                    "rollout, than the policy kernels score (%d); the extra rows were not written / scored", e, b->last.obs_rows, BBX_POLICY_MAX_ROWS);
+                                    "rollout, than the policy kernels score (%d); the extra rows were not written / scored", e, f.p.obs_rows, BBX_POLICY_MAX_ROWS);
   return err;
+}
+
+int finish(bbx_batch* b, hipStream_t stream) {
+  b->api_epoch++;
+  const int rc = finish_impl(b, stream);
+  b->flight.active = false; b->flight.async_chain = 0;
+  return rc;
+}
+
+// The two entries of a call that needs the batch.  settle(): finish the call in flight — wait for it, serve it, report its
+// error here.  quiesce() (stats, env_status, state_sizes, state_get, copy: calls that only read the records): close a running
+// session unsliced and wait for the device, but do NOT finish — the call stays in flight, and an error of it is still reported
+// by the next call that finishes it, not by a read.
+int settle(bbx_batch* b) { return b->flight.active ? finish(b, b->flight.stream) : BBX_OK; }
+
+int quiesce(bbx_batch* b) {
+  if (b->ps_active) { int rc = session_close(b, false, nullptr, false); if (rc) return rc; }
+  HIPCHK(hipDeviceSynchronize());
+  return BBX_OK;
 }
 
 // zero-copy launches: outputs and status words go straight to the pinned host block
@@ -784,8 +785,7 @@ void bbx_destroy(bbx_batch* b) { delete b; }
 int bbx_copy(const bbx_batch* s, bbx_batch** out) {
   if (!s || !out) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(s->device)); const_cast<bbx_batch*>(s)->api_epoch++;
-  if (s->ps_active) { int rc_ = session_close(const_cast<bbx_batch*>(s), false, nullptr, false); if (rc_) return rc_; }
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = quiesce(const_cast<bbx_batch*>(s))) return rc;
   auto b = std::make_unique<bbx_batch>();
   b->B = s->B; b->device = s->device; b->k = s->k; b->nvars = s->nvars; b->W = s->W;
   b->ncu = s->ncu;
@@ -828,7 +828,7 @@ int bbx_copy(const bbx_batch* s, bbx_batch** out) {
 int bbx_clone_envs(bbx_batch* b, int n, const int32_t* src, const int32_t* dst) {
   if (!b || n < 0 || (n && (!src || !dst))) return fail(BBX_E_ARG, "bad arguments");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+  if (int rc = settle(b)) return rc;
   {
     std::vector<uint8_t> role((size_t)b->B, 0);          // 1: read, 2: written (a destination may be named once)
     for (int i = 0; i < n; i++) {
@@ -842,7 +842,7 @@ int bbx_clone_envs(bbx_batch* b, int n, const int32_t* src, const int32_t* dst) 
     }
   }
   if (n == 0) return BBX_OK;
-  int rc = read_lite(b, 0);                       // current queue heads
+  int rc = read_lite(b, 0, false);                // current queue heads (nothing in flight: from the device block)
   if (rc) return rc;
   if (b->clone_cap < n) {                         // index arrays of the clone kernel: kept with the handle
     if (b->d_clone_idx) (void)hipFree(b->d_clone_idx);
@@ -879,7 +879,7 @@ int bbx_seed(bbx_batch* b, const int64_t* seeds) {
   if (b->fixed) return BBX_OK;                 // FixedIdealGenerator::seed is a no-op (ideals.h:94)
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   if (b->device_gen) {
-    if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+    if (int rc = settle(b)) return rc;
     std::vector<long long> s(seeds, seeds + b->B);
     for (int e = 0; e < b->B; e++) b->gens[e]->seed(seeds[e]);     // (kept in step for bbx_copy of a host-generating twin)
     return write_gen_states(b, s);
@@ -895,7 +895,7 @@ int bbx_seed(bbx_batch* b, const int64_t* seeds) {
 int bbx_seed_agent(bbx_batch* b, const uint32_t* seeds) {
   if (!b || !seeds) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc_ = finish(b, b->last_stream); if (rc_) return rc_; }   // (the headers are the truth only when nothing is resident)
+  if (int rc = settle(b)) return rc;   // (the headers are the truth only when nothing is resident)
   // written straight into the headers (field agent_seed), strided copy
   HIPCHK(hipMemcpy2D(b->d_recs + offsetof(BbxHdr, agent_seed), b->L.rec_bytes, seeds, sizeof(uint32_t), sizeof(uint32_t), b->B, hipMemcpyHostToDevice));
   // the agent's step counter restarts with a new seed
@@ -907,7 +907,7 @@ int bbx_seed_agent(bbx_batch* b, const uint32_t* seeds) {
 int bbx_seed_strategy(bbx_batch* b, const int64_t* seeds) {
   if (!b || !seeds) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+  if (int rc = settle(b)) return rc;
   // linear_congruential_engine<uint_fast32_t, 16807, 0, 2^31-1>::seed(s): the int seed converts to the 64-bit
   // unsigned result_type first; x = s mod m, and 0 becomes 1 (libstdc++-11 bits/random.tcc)
   std::vector<uint32_t> st(b->B);
@@ -923,7 +923,7 @@ int bbx_reset(bbx_batch* b, const uint8_t* mask, int32_t* rows) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   // (a session's waves hold their environments in registers: the mark below must meet the records they have stored)
-  if (b->in_flight) { int rc_ = finish(b, b->last_stream); if (rc_) return rc_; }
+  if (int rc = settle(b)) return rc;
   if (mask) HIPCHK(hipMemcpy(b->d_mask, mask, (size_t)b->B, hipMemcpyHostToDevice));
   int lrc = bbx_launch_mark_reset(b->d_recs, b->L.rec_bytes, b->B, mask ? b->d_mask : nullptr, 0);
   if (lrc) return fail(BBX_E_DEVICE, "launch failed: %s", hipGetErrorString((hipError_t)lrc));
@@ -953,14 +953,13 @@ static int step_host(bbx_batch* b, const int32_t* actions, double* rewards, uint
   }
   BbxParams p; fill_params(b, &p);
   p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset;
-  if (b->zero_copy) { p.actions = b->zc_act_dev; zc_outputs(b, &p); b->zc_active = true; }
+  if (b->zero_copy) { p.actions = b->zc_act_dev; zc_outputs(b, &p); }
   else {
     HIPCHK(hipMemcpyAsync(b->d_actions, b->h_act, (size_t)b->B * sizeof(int32_t), hipMemcpyHostToDevice, 0));
     p.actions = b->d_actions; p.rewards = b->d_rewards; p.dones = b->d_dones; p.rows = b->d_rows;
   }
   int rc = launch(b, p, 0);
   if (!rc) rc = finish(b, 0);
-  b->zc_active = false;
   if (rc) return rc;
   b->mbox_epoch = b->api_epoch;
   return copy_out(b, rewards, dones, rows);
@@ -1024,10 +1023,8 @@ int bbx_step_obs(bbx_batch* b, const int32_t* actions, int auto_reset, double* r
       if (rc) return rc;
     }
     if (!used) {
-      b->zc_active = zc;
       rc = launch(b, p, 0);
       if (!rc) rc = finish(b, 0);
-      b->zc_active = false;
       if (rc) return rc;
     }
     if (!attempt) copy_out(b, rewards, dones, rows);
@@ -1305,8 +1302,8 @@ int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, doub
 int bbx_sync(bbx_batch* b) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (!b->in_flight) { HIPCHK(hipDeviceSynchronize()); return BBX_OK; }
-  return finish(b, b->last_stream);
+  if (!b->flight.active) { HIPCHK(hipDeviceSynchronize()); return BBX_OK; }
+  return settle(b);
 }
 
 int bbx_accounting(bbx_batch* b, int enable) {
@@ -1318,8 +1315,7 @@ int bbx_accounting(bbx_batch* b, int enable) {
 int bbx_prefetch(bbx_batch* b) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
-  else { int rc = read_headers(b); if (rc) return rc; }
+  if (int rc = b->flight.active ? settle(b) : read_headers(b)) return rc;
   return fill_queues(b, (int)b->nslots);
 }
 

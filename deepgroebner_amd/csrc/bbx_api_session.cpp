@@ -27,6 +27,16 @@ namespace bbx_host {
 // 4.1.1) — and they bound how long a consumer that went away keeps the device busy.
 constexpr uint32_t PS_SLICE_TICKS = 1000000u;            // 10 ms of the 100 MHz clock
 
+// the session's kernel stream, the stream of the writes to its control word and the event that orders them: made by the first
+// session of either kind (bbx_persistent, mbox_step), kept for the handle's lifetime
+int ensure_session_streams(bbx_batch* b) {
+  if (b->ps_stream) return BBX_OK;
+  HIPCHK(hipStreamCreateWithFlags(&b->ps_stream, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&b->ps_ctl_stream, hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(&b->ps_ev, hipEventDisableTiming));
+  return BBX_OK;
+}
+
 int ps_write_ctl(bbx_batch* b, bool stop) {              // all writes to the control word travel on one stream, in order
   if (b->ps_mbox) {                                        // (a mailbox session's word is in host memory: the host writes it itself)
     std::atomic_thread_fence(std::memory_order_release);
@@ -78,7 +88,6 @@ int session_close(bbx_batch* b, bool wait, hipStream_t then, bool sliced) {
   b->ps_active = false;
   int rc = ps_write_ctl(b, true);
   if (rc) return rc;
-  const bool was_mbox = b->ps_mbox;
   if (!sliced) {
     // The host will not be there to start the next kernel when a slice ends, and ONE kernel without time limit would keep
     // every environment that leaves the register/LDS class on the HBM-resident pass until the very end (a straggler of
@@ -95,15 +104,22 @@ int session_close(bbx_batch* b, bool wait, hipStream_t then, bool sliced) {
   b->ps_recent.clear();
   rc = session_kernel(b, false, nullptr, sliced);
   if (rc) return rc;
-  b->last = b->ps_p; b->last.recs = b->d_recs; b->last.L = b->L;   // (a resumed pass continues from the budgets left in the headers)
-  b->last.ctl = nullptr; b->last.sess_target = 0; b->last.set_budget = 0; b->last.policy = nullptr; b->last.mbox = 0;
-  b->last_stream = b->ps_stream;
-  if (was_mbox) { b->ps_mbox = false; b->zc_active = true; }   // (its outputs are in the pinned block: finish() reads them there)
+  continue_session(b);
+  b->ps_mbox = false;
   if (wait) {                                              // (`then` may be the null stream)
     HIPCHK(hipEventRecord(b->ps_ev, b->ps_stream));
     HIPCHK(hipStreamWaitEvent(then, b->ps_ev, 0));
   }
   return BBX_OK;
+}
+
+// The flight that continues a closed session: its closing kernels on its stream, with the parameters of the call that began it
+// (a resumed pass continues from the budgets in the headers; a mailbox session's outputs stay pinned: outputs_pinned()).
+void continue_session(bbx_batch* b) {
+  BbxParams& q = b->flight.p;
+  q = b->ps_p; q.recs = b->d_recs; q.L = b->L;
+  q.ctl = nullptr; q.sess_target = 0; q.set_budget = 0; q.policy = nullptr; q.mbox = 0;
+  b->flight.stream = b->ps_stream;
 }
 
 bool session_same_call(const BbxParams& a, const BbxParams& c) {
@@ -137,15 +153,26 @@ static bool session_same_policy(const bbx_batch* b, const BbxParams& p) {
                         c->u == a->u + (size_t)b->ps_target * (size_t)b->B);
 }
 
+// The call p becomes the call in flight.  A session's calls are continued by its own kernels, which keep their policy (ps_pol):
+// only a plain launch is a policy rollout that cannot be resumed, or counts towards a chain of asynchronous external steps.
+void start_flight(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external, bool device_async) {
+  bbx_flight& f = b->flight;
+  const bool plain = !b->ps_active;
+  f.active = true; f.stream = stream; f.obs_external = obs_external; f.device_async = device_async; f.poll = false;
+  f.p = p; f.p.ctl = nullptr; f.p.policy = nullptr;
+  f.policy_rollout = plain && p.policy && p.policy->rollout;
+  if (plain && device_async && p.agent == BBX_AGENT_EXTERNAL && p.nsteps >= 1) f.async_chain++;
+}
+
 static int launch_session_join(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external) {
   b->ps_target += p.nsteps;                                // the waves see the new total the next time they look
   ps_note_steps(b, p.nsteps);
   int rc = ps_write_ctl(b, false);
   if (rc) return rc;
+  start_flight(b, p, b->ps_stream, obs_external, true);
   // the session's kernel may have left meanwhile (its slice was over, or no news for 20 ms): the next one
   if (hipStreamQuery(b->ps_stream) == hipSuccess) { rc = session_kernel(b, false, stream, true, true); if (rc) return rc; }
   b->ps_joined++;
-  b->in_flight = true; b->obs_external = obs_external; b->device_async = true;
   return BBX_OK;
 }
 static int launch_session_begin(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external) {
@@ -163,22 +190,12 @@ static int launch_session_begin(bbx_batch* b, const BbxParams& p, hipStream_t st
   }
   int rc = ps_write_ctl(b, false);
   if (rc) return rc;
-  b->last = p; b->last.ctl = nullptr; b->last.policy = nullptr;
-  b->policy_rollout = false; b->last_stream = b->ps_stream; b->in_flight = true; b->obs_external = obs_external; b->device_async = true;
+  start_flight(b, p, b->ps_stream, obs_external, true);
   return session_kernel(b, true, stream, true, true);
 }
 static int launch_plain(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external, bool device_async, bool capturing) {
-  if (device_async && p.agent == BBX_AGENT_EXTERNAL && p.nsteps >= 1) b->async_chain++;
-  b->last = p; b->last.ctl = nullptr;
-  b->policy_rollout = p.policy && p.policy->rollout;
-  b->last.policy = nullptr;                 // (a host pointer of the caller's frame: never kept)
-  b->last_stream = stream;
-  b->in_flight = true;
-  b->obs_external = obs_external;
-  b->device_async = device_async;
-  if (capturing) {                          // what bbx_graph_replayed restores: the call the replays repeat
-    b->cap_last = b->last; b->cap_valid = true; b->cap_stale = false; b->cap_obs_external = obs_external; b->cap_policy_rollout = b->policy_rollout;
-  }
+  start_flight(b, p, stream, obs_external, device_async);
+  if (capturing) { b->cap = b->flight; b->cap_valid = true; b->cap_stale = false; }   // what bbx_graph_replayed restores: the call the replays repeat
   return enqueue(b, p, false, stream);
 }
 
@@ -236,27 +253,21 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
     // (value() per step, pg.py:461-465) is served by one launch per step as before: four steps in a row start a session
     b->mbox_streak = (b->api_epoch == b->mbox_epoch + 1) ? b->mbox_streak + 1 : 0;   // (+ 1: this call's own entry)
     if (b->mbox_streak < 4) return BBX_OK;
-    if (!b->h_mbox) {                                       // (the session's streams exist from the first session on, not before)
+    if (!b->h_mbox) {                                       // (the pinned control word exists from the first session on, not before)
       HIPCHK(hipHostMalloc((void**)&b->h_mbox, 64, hipHostMallocCoherent | hipHostMallocMapped));
       HIPCHK(hipHostGetDevicePointer((void**)&b->mbox_dev, b->h_mbox, 0));
-      if (!b->ps_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&b->ps_stream, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&b->ps_ctl_stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&b->ps_ev, hipEventDisableTiming));
-      }
     }
-    if (b->in_flight) { rc = finish(b, b->last_stream); if (rc) return rc; }
-    rc = fill_queues(b, 1, nullptr);
+    rc = ensure_session_streams(b);
+    if (!rc) rc = settle(b);
+    if (!rc) rc = fill_queues(b, 1, nullptr);
     if (rc) return rc;
     for (int e = 0; e < b->B; e++) ((volatile int32_t*)b->h_io)[(size_t)e * 4] = 0;
-    p.mbox = 1;
     b->ps_p = p; b->ps_p.ctl = nullptr; b->ps_p.policy = nullptr;
     b->ps_mbox = true; b->ps_active = true; b->ps_target = 1; b->ps_sessions++;
     b->ps_recent.clear();
     rc = ps_write_ctl(b, false);
     if (rc) return rc;
-    b->last = p; b->last.ctl = nullptr; b->last.policy = nullptr; b->last.mbox = 0;
-    b->policy_rollout = false; b->last_stream = b->ps_stream; b->in_flight = true; b->obs_external = false; b->device_async = false;
+    start_flight(b, p, b->ps_stream, false, false);
     rc = session_kernel(b, true, nullptr, true);
     if (rc) return rc;
   } else {
@@ -266,26 +277,20 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
     b->ps_joined++;
     if (hipStreamQuery(b->ps_stream) == hipSuccess) { rc = session_kernel(b, false, nullptr, true); if (rc) return rc; }   // (slice over, or idle for 20 ms)
   }
-  // the step's sequence number on every environment's status word — or something else to look at
+  // the step's sequence number on every environment's status word — or something else to look at (here an observation cut
+  // for lack of rows is trouble too: finish() then reports it)
   const uint32_t want = (uint32_t)(b->ps_target % 16000) + 1u;
   const volatile int32_t* w = (const volatile int32_t*)b->h_io;
   const auto t0 = std::chrono::steady_clock::now();
-  bool all = false, trouble = false, timed_out = false;
+  SeqScan s{false, false}; bool timed_out = false;
   for (unsigned spins = 0;; spins++) {
-    all = true;
-    for (int e = 0; e < b->B; e++) {
-      const uint32_t v = (uint32_t)w[(size_t)e * 4];
-      if ((v >> 17) != want) all = false;
-      else if ((v & 0xffffu) != BBX_ST_OK || (v & BBX_LITE_OBS_TRUNC)) trouble = true;
-    }
-    if (all || trouble) break;
+    s = scan_seq(b, want, BBX_LITE_OBS_TRUNC);
+    if (s.all || s.trouble) break;
     if ((spins & 63) == 63) {
       if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(3)) { timed_out = true; break; }
       // the kernel may have left (its slice, 20 ms without news, an environment that needs the host): the next one takes the step
       if (hipStreamQuery(b->ps_stream) == hipSuccess) {
-        bool seen = true;
-        for (int e = 0; e < b->B; e++) seen = seen && (((uint32_t)w[(size_t)e * 4]) >> 17) == want;
-        if (seen) { all = true; break; }
+        if (scan_seq(b, want, 0).all) { s.all = true; break; }
         bool stopped = false;                                // an environment that left with something to report ends the mailbox
         for (int e = 0; e < b->B; e++) { const uint32_t st = (uint32_t)w[(size_t)e * 4] & 0xffffu; stopped = stopped || (st != BBX_ST_OK && st != BBX_ST_TIMESLICE); }
         if (stopped) break;
@@ -296,7 +301,7 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   *used = true;
-  if (all && !trouble) {
+  if (s.all && !s.trouble) {
     b->mbox_misses = 0;
     b->h_lite.resize((size_t)b->B * 4);
     memcpy(b->h_lite.data(), b->h_io, (size_t)b->B * 16);
@@ -316,13 +321,11 @@ extern "C" {
 int bbx_persistent(bbx_batch* b, int enable) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+  if (int rc = settle(b)) return rc;
   if (enable && !b->d_ctl) {
     HIPCHK(hipMalloc((void**)&b->d_ctl, 65536));          // (word 0: control, word 8: statistics; the rest: scripts/patches)
     HIPCHK(hipMemset(b->d_ctl, 0, 65536));
-    HIPCHK(hipStreamCreateWithFlags(&b->ps_stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&b->ps_ctl_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&b->ps_ev, hipEventDisableTiming));
+    if (int rc = ensure_session_streams(b)) return rc;
     HIPCHK(hipDeviceSynchronize());
   }
   b->ps_enabled = enable != 0;
@@ -334,7 +337,7 @@ int bbx_session_stats(bbx_batch* b, int64_t* out5) {   // out: 5 values
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   out5[0] = b->ps_sessions; out5[1] = b->ps_joined; out5[2] = 0; out5[3] = b->ps_kernels; out5[4] = 0;
   if (b->d_ctl) {
-    if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+    if (int rc = settle(b)) return rc;
     unsigned long long v[2] = {0, 0};
     HIPCHK(hipMemcpy(v, b->d_ctl + 8, sizeof v, hipMemcpyDeviceToHost));
     out5[2] = (int64_t)v[0]; out5[4] = (int64_t)v[1];
@@ -365,10 +368,9 @@ int bbx_graph_replayed(bbx_batch* b, void* stream) {
     return fail(BBX_E_CAPACITY, "the records of this batch were enlarged after the step was recorded: the graph steps the retired copy, "
                                 "the steps replayed since did not reach the batch — record the step again");
   }
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
-  b->last = b->cap_last; b->policy_rollout = b->cap_policy_rollout; b->obs_external = b->cap_obs_external; b->device_async = true;
-  b->in_flight = true; b->last_stream = (hipStream_t)stream;
-  b->async_chain = 2;                                   // (any number of replays)
+  if (int rc = settle(b)) return rc;
+  b->flight = b->cap; b->flight.stream = (hipStream_t)stream;
+  b->flight.async_chain = 2;                            // (any number of replays)
   return BBX_OK;
 }
 

@@ -14,8 +14,7 @@ int bbx_stats(bbx_batch* b, int64_t* out8) {
   int64_t* out6 = out8;
   if (!b || !out6) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->ps_active) { int rc_ = session_close(b, false, nullptr, false); if (rc_) return rc_; }
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = quiesce(b)) return rc;
   int rc = read_headers(b);
   if (rc) return rc;
   for (int e = 0; e < b->B; e++) {
@@ -31,7 +30,7 @@ int bbx_stats(bbx_batch* b, int64_t* out8) {
 int bbx_internal_records(bbx_batch* b, const char** recs, BbxLayout* L, int* device, int* W, int* batch) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+  if (int rc = settle(b)) return rc;
   HIPCHK(hipDeviceSynchronize());
   *recs = b->d_recs; *L = b->L; *device = b->device; *W = b->W; *batch = b->B;
   return BBX_OK;
@@ -46,8 +45,7 @@ int bbx_capacities(bbx_batch* b, int32_t* out5) {
 int bbx_env_status(bbx_batch* b, int32_t* status) {
   if (!b || !status) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->ps_active) { int rc_ = session_close(b, false, nullptr, false); if (rc_) return rc_; }
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = quiesce(b)) return rc;
   int rc = read_headers(b);
   if (rc) return rc;
   for (int e = 0; e < b->B; e++) status[e] = b->h_hdr[e].status;
@@ -57,8 +55,7 @@ int bbx_env_status(bbx_batch* b, int32_t* status) {
 int bbx_state_sizes(bbx_batch* b, int idx, int32_t* basis_size, int32_t* npairs, int32_t* nterms_total) {
   if (!b || idx < 0 || idx >= b->B) return fail(BBX_E_ARG, "bad environment index");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->ps_active) { int rc_ = session_close(b, false, nullptr, false); if (rc_) return rc_; }
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = quiesce(b)) return rc;
   BbxHdr h;
   HIPCHK(hipMemcpy(&h, b->d_recs + (size_t)idx * b->L.rec_bytes, sizeof h, hipMemcpyDeviceToHost));
   if (basis_size) *basis_size = h.nG;
@@ -70,8 +67,7 @@ int bbx_state_sizes(bbx_batch* b, int idx, int32_t* basis_size, int32_t* npairs,
 int bbx_state_get(bbx_batch* b, int idx, int32_t* nterms, int32_t* coefs, int32_t* exps, int32_t* pairs, int32_t* order) {
   if (!b || idx < 0 || idx >= b->B) return fail(BBX_E_ARG, "bad environment index");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->ps_active) { int rc_ = session_close(b, false, nullptr, false); if (rc_) return rc_; }
-  HIPCHK(hipDeviceSynchronize());
+  if (int rc = quiesce(b)) return rc;
   const char* rec = b->d_recs + (size_t)idx * b->L.rec_bytes;
   BbxHdr h;
   HIPCHK(hipMemcpy(&h, rec, sizeof h, hipMemcpyDeviceToHost));

@@ -35,7 +35,7 @@ uint32_t minstd_state_of_seed(long long seed) {
 // (grow_records) and the rollouts start again.
 int value_rollouts(bbx_batch* b, const std::vector<int32_t>& src, int agent, const std::vector<uint32_t>* seeds, double gamma, double* out) {
   const int n = (int)src.size();
-  if (b->in_flight) { int rc = finish(b, b->last_stream); if (rc) return rc; }
+  if (int rc = settle(b)) return rc;
   for (int attempt = 0; attempt < 40; attempt++) {
     if (n > b->vcap) {
       void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};

@@ -31,6 +31,21 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
                                    int32_t* actions, float* logprobs, hipStream_t stream);
 
 
+// The call in flight: what finish() waits for, continues and reports on.  Formed in two places only — start_flight() (a
+// call begins) and continue_session() (a closed session's closing kernels, bbx_api_session.cpp); grow_records moves its
+// records; finish() ends it.  A recorded call (bbx_batch::cap) is the same record, restored by bbx_graph_replayed.
+struct bbx_flight {
+  bool active = false;                // finish() has not yet waited for it
+  BbxParams p{};                      // its parameters, ctl and policy dropped (the policy is a host pointer of the caller's frame)
+  hipStream_t stream = 0;             // where it runs (the session stream for a session's call)
+  bool obs_external = false;          // writes observations into a caller-owned block: rows cut for lack of space are an error
+                                      // the caller must hear about (bbx_sync)
+  bool device_async = false;          // came through a *_device entry point (no host poll per step)
+  bool policy_rollout = false;        // a policy rollout outside a session: what it left unfinished cannot be resumed
+  bool poll = false;                  // its kernel signals completion through the pinned status words (enqueue -> read_lite)
+  int async_chain = 0;                // asynchronous steps with caller-supplied actions queued since the last wait
+};
+
 struct bbx_gen {
   std::unique_ptr<bbx::IdealGen> g;
   bbx::HIdeal last;
@@ -66,8 +81,9 @@ struct bbx_batch {
   int32_t* h_act = nullptr;                       // pinned staging of host actions
   // small batches (the single-environment drop-in): the kernels read the actions from and write their outputs and the
   // observation straight into pinned host memory — no copy calls on the latency path, one stream synchronisation per step
-  bool zero_copy = false, zc_active = false;
-  bool poll_active = false; int poll_seq = 0, poll_misses = 0; unsigned polled_launches = 0;                   // the launch in flight signals completion through h_io (done_seq)
+  // (whether the outputs of the call in flight are in the pinned block is a property of that call: outputs_pinned())
+  bool zero_copy = false;
+  int poll_seq = 0, poll_misses = 0; unsigned polled_launches = 0;   // completion through h_io (done_seq): bbx_flight::poll
   char* zc_io_dev = nullptr; int32_t* zc_act_dev = nullptr;     // device-side addresses of h_io / h_act
   int32_t* h_zobs = nullptr; int32_t* zc_obs_dev = nullptr; size_t zobs_rows_cap = 0;
   // ragged observations (bbx_step_obs): device offsets [B+1] + packed rows, and their pinned mirror handed to the caller
@@ -86,23 +102,15 @@ struct bbx_batch {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_open;
   double kernel_ms = 0.0; int kernel_launches = 0;
   std::vector<char> h_out;
-  // the rollout in flight (so bbx_sync can finish environments that waited for ideals)
-  BbxParams last{};
-  BbxParams cap_last{}; bool cap_valid = false, cap_obs_external = false, cap_policy_rollout = false;   // the last call recorded into a HIP graph (bbx_graph_replayed)
-  int async_chain = 0;                // asynchronous steps with caller-supplied actions queued since the last wait (finish())
+  bbx_flight flight;                  // the call in flight (so bbx_sync can finish environments that waited for ideals)
+  bbx_flight cap; bool cap_valid = false;   // the last call recorded into a HIP graph (bbx_graph_replayed)
   bool cap_stale = false; std::vector<void*> retired;   // the records were enlarged after the recording: the old arrays stay allocated (replays write there)
-  hipStream_t last_stream = 0;
-  bool in_flight = false;
-  bool policy_rollout = false;           // the launch in flight is a policy rollout (bbx_policy_rollout_device)
   int staged = 0, fast = 0, envs_per_block = 4;
   int fast_G = 0, fast_P = 0;          // capacities of the register/LDS-resident class (BbxParams::fast_G)
   int wide = 0;                       // > 0: waves per environment of the wide (one workgroup per environment) class
   int wide_terms = 0;                 // forced LDS capacity of the wide class (caps.wide_lds_terms), 0 = automatic
   int32_t* d_wide_done = nullptr;     // wide class: workgroups that have left the launch's first kernel (BbxParams::wide_tail)
   int ncu = 0;                        // compute units of the device
-  bool device_async = false;          // the launch in flight came through a *_device entry point (no host poll per step)
-  bool obs_external = false;          // the launch in flight writes observations into a caller-owned block: rows cut for
-                                      // lack of space are an error the caller must hear about (bbx_sync)
   // persistent sessions (bbx_persistent): see BbxParams::ctl
   bool ps_enabled = false, ps_active = false;
   // host mailbox sessions (BbxParams::mbox): host-driven steps of small zero-copy batches on the register/LDS-resident class
@@ -137,6 +145,23 @@ namespace bbx_host {
 // wait for the launch in flight, serve environments that need the host (queued ideals, larger records, the kernels of a
 // session), surface errors; the handle is left with nothing in flight
 int finish(bbx_batch* b, hipStream_t stream);
+int settle(bbx_batch* b);            // finish() whatever is in flight (the entry of every call that needs the batch quiet)
+int quiesce(bbx_batch* b);           // the read-only introspection calls: close a session and wait, WITHOUT finishing
+// the outputs and status words of the call in flight are in the pinned block (zero-copy host steps, a mailbox session)
+inline bool outputs_pinned(const bbx_batch* b) { return b->zero_copy && b->flight.p.lite == (int32_t*)b->zc_io_dev; }
+// The status words of the pinned block (the first of every environment's four) against sequence number `want` (bits 17..):
+// all — every one carries it; trouble — one that carries it reports a status other than OK, or one of the bits `flags`.
+struct SeqScan { bool all, trouble; };
+inline SeqScan scan_seq(const bbx_batch* b, uint32_t want, uint32_t flags) {
+  const volatile int32_t* w = (const volatile int32_t*)b->h_io;
+  SeqScan s{true, false};
+  for (int e = 0; e < b->B; e++) {
+    const uint32_t v = (uint32_t)w[(size_t)e * 4];
+    if ((v >> 17) != want) s.all = false;
+    else if ((v & 0xffffu) != BBX_ST_OK || (v & flags)) s.trouble = true;
+  }
+  return s;
+}
 int read_headers(bbx_batch* b, hipStream_t stream = 0);
 void fill_params(bbx_batch* b, BbxParams* p);
 int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream);
@@ -146,6 +171,9 @@ int fill_queues(bbx_batch* b, int min_avail = 1, hipStream_t stream = 0);
 int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream);   // the kernels of one logical launch
 // bbx_api_session.cpp
 int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external = false, bool device_async = false);
+void start_flight(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external, bool device_async);
+void continue_session(bbx_batch* b);
+int ensure_session_streams(bbx_batch* b);
 int ps_write_ctl(bbx_batch* b, bool stop);
 int session_kernel(bbx_batch* b, bool first, hipStream_t after, bool sliced, bool behind_after = false);   // behind_after: ordered behind what `after` (possibly the NULL stream) holds
 int session_close(bbx_batch* b, bool wait, hipStream_t then, bool sliced);

@@ -1,6 +1,7 @@
 """Randomised parity sweep of the host-stepped (Gym-style) surface (test infrastructure, GPU box): VecLeadMonomialsEnv.reset /
 step / masked reset / auto-reset and the single-environment classes with uniformly random actions, every observation matrix,
-reward and done flag against the CPU restatement's environment objects.   python scripts/fuzz_gym.py [ROUNDS] [SEED]"""
+reward and done flag against the CPU restatement's environment objects; now and then stats() / state() / copy() between the
+steps.   python scripts/fuzz_gym.py [ROUNDS] [SEED]"""
 import os, sys, random, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,7 +9,9 @@ from deepgroebner_amd import CLeadMonomialsEnv, LeadMonomialsEnv, VecLeadMonomia
 from oracle import ffi
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+rng = random.Random(seed)
+xrng = random.Random(seed + 1000003)                    # (reads between steps: a stream of their own, so that a seed's cases stay what they were)
 bo = ffi.load("bo")
 t0 = time.time()
 
@@ -88,6 +91,19 @@ for it in range(rounds):
                         oracles[e].reset()
                     elif arng.random() < 0.7:
                         mask[e] = 1
+            if xrng.random() < 0.05:
+                # a read between steps: closes a mailbox session without finishing the call in flight; what follows (a reset, a
+                # step of either form) must still find its own outputs
+                what = xrng.choice(["stats", "state", "copy"])
+                if what == "stats":
+                    env.stats()
+                elif what == "copy":
+                    env.copy()
+                else:
+                    e = xrng.randrange(B)
+                    if len(env.state(e)[1]) != oracles[e].nP:
+                        fail(tag + ": state() of env %d after step %d: %d pairs, oracle %d" % (e, t, len(env.state(e)[1]), oracles[e].nP))
+                how += " then " + what
             if not auto and mask.any():
                 obs = env.reset(mask)
                 for e in np.flatnonzero(mask):

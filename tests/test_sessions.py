@@ -234,6 +234,62 @@ def test_host_mailbox_session_is_invisible_except_in_time(B, auto_reset):
             assert np.array_equal(st[e], o.obs(k))
 
 
+@pytest.mark.parametrize("call", ["stats", "state", "copy", "join"])
+@pytest.mark.parametrize("B", [1, 3])
+def test_host_calls_after_a_mailbox_session_closed_without_a_wait(B, call):
+    """stats(), state(), copy() and join() close a host mailbox session without waiting for it: its last outputs are in the
+    pinned block.  The host calls after it write theirs to the device block and must read them from there — they read the
+    mailbox's last step instead (the rows of bbx_reset, the rewards / dones / rows of a rollout) until the next host step."""
+    from deepgroebner_amd import VecLeadMonomialsEnv, _ffi
+    bo = ffi.load("bo")
+    k = 2
+    env = VecLeadMonomialsEnv(DIST, batch=B, k=k)
+    env.seed(np.arange(B) + 500); env.accounting(False)
+    env.reset()
+    oracles = []
+    for e in range(B):
+        o = bo.env(DIST); o.seed(500 + e); o.reset(); oracles.append(o)
+    copies = []
+
+    def step_loop(t0):
+        sessions = env.session_stats()["sessions"]
+        for t in range(t0, t0 + 12):
+            acts = np.array([ffi.agent_hash(e + 1, t) % max(o.nP, 1) for e, o in enumerate(oracles)], dtype=np.int32)
+            states, rew, done, _ = env.step(acts, auto_reset=True)
+            for e, o in enumerate(oracles):
+                assert rew[e] == o.step(int(acts[e])), (t, e)
+                assert bool(done[e]) == (o.nP == 0), (t, e)
+                if o.nP == 0:
+                    o.reset()
+                assert np.array_equal(states[e], o.obs(k)), (t, e)
+        assert env.session_stats()["sessions"] > sessions      # (the steps went through a mailbox session)
+        if call == "stats":
+            env.stats()
+        elif call == "state":
+            env.state(B - 1)
+        elif call == "copy":
+            copies.append(env.copy())
+        else:
+            env.join()
+
+    step_loop(0)
+    rows = np.full(B, -1, dtype=np.int32)                    # (the C call: the wrapper's reset() rewrites env.rows behind it)
+    _ffi.check(_ffi.lib().bbx_reset(env._h, None, _ffi.ptr(rows)))
+    for o in oracles:
+        o.reset()
+    assert rows.tolist() == [o.nP for o in oracles]
+    step_loop(100)
+    env.seed_agent(np.arange(B) + 9)
+    for t in range(6):
+        rew, done, rows = env.rollout("random", 1, auto_reset=True)
+        for e, o in enumerate(oracles):
+            r = o.step(ffi.agent_action(9 + e, t, o.nP))
+            d = o.nP == 0
+            if d:
+                o.reset()
+            assert (rew[e], bool(done[e]), rows[e]) == (r, d, o.nP), (t, e)
+
+
 def test_sessions_of_different_shapes_back_to_back():
     """A call of another shape ends the running session and begins the next one at once.  The control word belongs to the
     handle: the kernels that close the first session (queued, perhaps not yet run) still poll it, and the next session's step
