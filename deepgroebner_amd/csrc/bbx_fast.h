@@ -531,6 +531,56 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     PA = pairs[lane];                                      // (consumed by the next step: the read has a whole phase to land)
   };
 
+  // A reset's whole ideal in one pass: the state n add_poly calls leave behind from an empty basis, in closed form.  The
+  // caller has written generator f of the insertion order to the basis-order arrays at f (lead coefficient 1, so 1/LC = 1
+  // and the sugar is the lead's degree); `in_order`: that order is already the reducer order (sort_input).  It guarantees
+  // n <= 11 (every pair fits a lane), limG >= n and limP >= n + n(n-1)/2 (none of the sequential loop's capacity checks
+  // could fire) and has cleared the reducers.
+  //   pair (i, j), i < j, is created when j enters iff no k < j has lcm(k, j) properly dividing lcm(i, j), i is the smallest
+  //     k < j with lcm(k, j) == lcm(i, j), and no such k has LM k coprime to LM j (the minimal-lcm peel of add_poly);
+  //   it is dropped by a later m iff LM m | lcm(i, j), lcm(i, j) != lcm(i, m) and lcm(i, j) != lcm(j, m) (add_poly's filter,
+  //     which looks at no other pair);
+  //   the survivors stay in (j, i) order: lane j(j-1)/2 + i holds pair (i, j), and one ballot compaction writes the list;
+  //   the reducers are the stable sort by lead monomial (std::upper_bound insertion): generator f goes to lane rank(f).
+  auto install_ideal = [&](int n, bool in_order) {
+    // (everything below that depends on the lane alone would otherwise be hoisted out of the step loop and held in
+    // vector registers across all of it: the lane number goes through an opaque copy)
+    int ln = lane; asm volatile("" : "+v"(ln));
+    const bool mine = ln < n;
+    const M2 L = lm[ln];                                 // (lanes >= n: stale entries, never used as a generator)
+    {
+      const M2 T = tm[ln];
+      const uint32_t c = gi[ln].x >> 16, sugar = m_deg(L);
+      const int rk = in_order ? ln : gen_sorted_rank<2>(L, n);
+      const int to = 4 * (mine ? rk : ln);              // (lanes >= n stay: a permutation)
+      auto put = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(to, (int)v); };
+      S.slm[0].w[0] = put(mine ? L.w[0] : FSENT); S.slm[0].w[1] = put(mine ? L.w[1] : FSENT);
+      S.stm[0].w[0] = put(T.w[0]); S.stm[0].w[1] = put(T.w[1]);
+      S.sin[0].x = put(c | (negmod(mulmod(c, 1u)) << 16)); S.sin[0].y = put(sugar | ((uint32_t)ln << 16));
+    }
+    int j = 0;                                             // lane -> (i, j): j = #{t >= 1 : t(t-1)/2 <= lane}
+#pragma unroll
+    for (int t = 1; t <= 10; t++) j += ln >= t * (t - 1) / 2 ? 1 : 0;
+    const int i = ln - ((j * (j - 1)) >> 1);
+    auto get = [&](int from, const M2& v) { M2 r; r.w[0] = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * from, (int)v.w[0]);
+                                            r.w[1] = (uint32_t)__builtin_amdgcn_ds_bpermute(4 * from, (int)v.w[1]); return r; };
+    const M2 Li = get(i, L), Lj = get(j, L), Lij = m_lcm(Li, Lj);
+    bool keep = ln < ((n * (n - 1)) >> 1);
+    for (int k = 0; k < n; k++) {
+      const M2 Lk = f_readlane(L, k);
+      const M2 Lkj = m_lcm(Lk, Lj);
+      const bool eq = m_eq(Lkj, Lij);
+      const bool not_new = (m_divides(Lkj, Lij) && !eq) || (eq && (k < i || m_coprime(Lk, Lj)));   // k < j: no pair (i, j)
+      const bool dropped = m_divides(Lk, Lij) && !eq && !m_eq(Lij, m_lcm(Li, Lk));                  // k > j: (i, j) dropped
+      keep = keep && !(k < j ? not_new : (k > j && dropped));
+    }
+    const uint64_t kept = ballot64(keep);
+    if (keep) pairs[f_prefix(kept)] = (uint32_t)i | ((uint32_t)j << 16);
+    nG = n; nP = __popcll(kept);
+    wave_sync();
+    PA = pairs[lane];
+  };
+
   for (;;) {
     // |P| is wave-uniform by construction, but the compiler's uniformity analysis loses that across the loop; pinned
     // here, every branch of the step is a scalar branch (without it the whole body runs under exec masks, with
@@ -546,12 +596,17 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         const uint32_t gflags = ldc(gtab + 3);
         const GenLanes GL = gen_lanes(gtab);
         uint32_t x = (uint32_t)uni((int)gen_state);
+        FSTAMP(0);
         for (;;) {
           const uint32_t x_start = x;
           nG = 0; nP = 0;
           clear_reducers();
-          // sort_input: all generators are drawn first (lane f keeps generator f), then enter in sorted order
+          // sort_input: all generators are drawn first (lane f keeps generator f), then enter in sorted order.  one_pass: the
+          // generators only go to the basis-order arrays as they are drawn and install_ideal sets up pairs and reducers at
+          // once (at most 11 generators within the caps: every ideal of the n <= 11 distributions); otherwise add_poly
+          // inserts them one by one (the draw is the same on every path: same calls, same order)
           const bool sorted = cq->sort_input != 0;
+          const bool one_pass = npoly <= 11 && limG >= npoly && limP >= npoly + ((npoly * (npoly - 1)) >> 1);
           M2 tabL = m_zero<2>(), tabT = m_zero<2>(); uint32_t tabC = 0; int rank = 0;
           if (sorted) {
             for (int fidx = 0; fidx < npoly && ok; fidx++) {
@@ -560,17 +615,30 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
               if (lane == fidx) { tabL = lead; tabT = tail; tabC = c; }
             }
             rank = gen_sorted_rank<2>(tabL, npoly);
+            FSTAMP(6);                                     // 6: reset: drawing the ideal
+            if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
           }
-          for (int fidx = 0; fidx < npoly && ok; fidx++) {
-            if (nG + 1 > limG || nP + nG > limP) { status = BBX_ST_SPILL; ok = false; x = x_start; break; }   // redone from the same draw
+          for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted); fidx++) {
+            if (!one_pass && (nG + 1 > limG || nP + nG > limP)) { status = BBX_ST_SPILL; ok = false; x = x_start; break; }   // redone from the same draw
             BTerm<2> t0, t1;
             t0.c = 1;
             if (sorted) {
               const int src = __builtin_ctzll(ballot64(lane < npoly && rank == fidx));
               t0.m = f_readlane(tabL, src); t1.m = f_readlane(tabT, src); t1.c = f_readlane(tabC, src);
             } else if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, t0.m, t1.m, t1.c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
+            if (!sorted) FSTAMP(6);
+            if (one_pass) {                                // basis-order arrays only: install_ideal does the rest
+              if (lane == 0) { lm[fidx] = t0.m; tm[fidx] = t1.m; gi[fidx] = make_uint2(1u | (t1.c << 16), 1u | (m_deg(t0.m) << 16)); }
+              continue;
+            }
             if (__builtin_expect(npoly <= 64, 1)) add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, 1>{});
             else add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, NBK>{});
+            FSTAMP(7);                                     // 7: reset: installing the ideal (basis, pairs, reducers)
+          }
+          if (one_pass && ok) {
+            wave_sync();
+            install_ideal(npoly, sorted);
+            FSTAMP(7);
           }
           if (!ok || nP != 0) break;                       // buchberger.cpp:313-314: redraw while the pair set is empty
         }
@@ -629,7 +697,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         }
       }
     }
-    FSTAMP(0);                                             // 0: loop top / reset
+    FSTAMP(0);                                             // 0: loop top / reset (a device-drawn reset's draw and install: 6, 7)
     if constexpr (PERSIST && POL == 0 && !HL) {
       // A host mailbox session: the host spins on this environment's status word for the step's sequence number.  The step's
       // outputs reach host memory first — here, behind the reset of an environment whose episode the step ended (auto-reset:

@@ -4,6 +4,14 @@
 #include "bbx_binom.h"
 #include "bbx_fast.h"
 
+#ifdef BBX_PROF_BUILD
+static unsigned long long bbx_fast_prof_acc[8];           // diagnostic build only: phase cycle sums over the launches since the last read
+extern "C" int bbx_fast_prof_read(unsigned long long* out, int reset) {
+  for (int i = 0; i < 8; i++) { out[i] = bbx_fast_prof_acc[i]; if (reset) bbx_fast_prof_acc[i] = 0; }
+  return 0;
+}
+#endif
+
 // kind 3: the hand-tuned LDS/register-resident kernel (bbx_fast.h) for W == 2 binomial, GM, sorted reducers
 extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int envs_per_block, hipStream_t stream) {
   BbxFastParams f{};
@@ -23,7 +31,7 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
   const size_t lds = (size_t)envs_per_block * FLay<FNBK_WIDE>::BYTES, lds_pol = (size_t)envs_per_block * FLay<FNBK_POL>::BYTES;
 #ifdef BBX_PROF_BUILD
   static unsigned long long* d_prof = nullptr;
-  if (getenv("BBX_PROF") && !p->trace) {          // diagnostic: per-phase cycle sums, printed by bbx_prof_dump()
+  if (getenv("BBX_PROF") && !p->trace) {          // diagnostic: per-phase cycle sums, printed here and summed for bbx_fast_prof_read()
     if (!d_prof) (void)hipMalloc((void**)&d_prof, (size_t)p->B * 8 * sizeof(unsigned long long));
     f.prof = d_prof;
     hipLaunchKernelGGL(bbx_fast_prof_kernel, dim3(blocks), dim3(threads), lds, stream, f);
@@ -31,9 +39,9 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
     std::vector<unsigned long long> h((size_t)p->B * 8);
     (void)hipMemcpy(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost);
     double s[8] = {0}; for (int e = 0; e < p->B; e++) for (int i = 0; i < 8; i++) s[i] += (double)h[(size_t)e * 8 + i];
-    double tot = 0; for (int i = 0; i < 8; i++) tot += s[i];
+    double tot = 0; for (int i = 0; i < 8; i++) { tot += s[i]; bbx_fast_prof_acc[i] += (unsigned long long)s[i]; }
     fprintf(stderr, "[bbx prof] nsteps=%d ticks/step/env:", p->nsteps);
-    for (int i = 0; i < 6; i++) fprintf(stderr, " p%d=%.0f(%.0f%%)", i, s[i] / p->B / (p->nsteps ? p->nsteps : 1), 100.0 * s[i] / tot);
+    for (int i = 0; i < 8; i++) fprintf(stderr, " p%d=%.0f(%.0f%%)", i, s[i] / p->B / (p->nsteps ? p->nsteps : 1), 100.0 * s[i] / tot);
     fprintf(stderr, "\n");
     return 0;
   }
