@@ -215,61 +215,72 @@ void fill_params(bbx_batch* b, BbxParams* p) {
   p->ctl_stats = b->d_ctl ? b->d_ctl + 8 : nullptr;
 }
 
-// enqueue the kernels of one logical launch: the LDS-staged pass (when the class allows) followed by the
-// HBM-resident pass that serves whatever the first could not hold; aux launches (nsteps == 0) use one kernel
-int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) {
-  BbxParams p = p0;
-  int kinds[3]; int nk = 0;
-  if (p.nsteps == 0 && !resume) kinds[nk++] = 2;
-  else if (p.ctl) { kinds[nk++] = 3; kinds[nk++] = 0; }   // a kernel of a persistent session, and behind it the HBM-resident
-                                                      // class for the environments that outgrew the register/LDS class
-  else if (b->wide) kinds[nk++] = 4;
-  else if (b->gen_to_wide) {                          // general class, <= 7 variables: wave-per-environment kernel, and behind it the
-    kinds[nk++] = 0; kinds[nk++] = 4;                 // workgroup-per-environment kernel for the environments whose polynomials got long
-    p.spill_terms = 384;
-  }
-  else {   // the register/LDS-resident class (the hand-tuned kernel where the batch has it), then the HBM-resident one
-    const bool pol_hbm_only = p.policy && p.policy->rollout == 2;     // a policy rollout outside the register/LDS class
-    if (b->staged && !pol_hbm_only) kinds[nk++] = b->fast ? 3 : 1;   // (the hand-tuned kernel knows every agent since round 4)
+// The kernels of one launch and the parameters of each, for every class and call shape: an aux launch (nsteps == 0), a
+// session's kernel (ctl: the hand-tuned one), or the class's first kernel and behind it the one that takes over what it
+// hands on.  `value`: value()'s rollouts — no LDS-staged pass but the hand-tuned one, no wide tail, no polling.
+LaunchPlan plan_launch(const bbx_batch* b, const BbxParams& p0, bool resume, bool value) {
+  LaunchPlan pl;
+  auto add = [&pl](BbxKernel k) { pl.kind[pl.n++] = k; };
+  if (p0.nsteps == 0 && !resume) add(BBX_K_AUX);
+  else if (p0.ctl) { add(BBX_K_FAST); add(BBX_K_HBM); }
+  else if (b->cls == BbxClass::WIDE) add(BBX_K_WIDE);
+  else if (b->cls == BbxClass::GENERAL_TO_WIDE) { add(BBX_K_HBM); add(BBX_K_WIDE); }
+  else {
+    const bool staged = lds_staged(b->cls), fast = b->cls == BbxClass::FAST;
+    const bool pol_hbm_only = p0.policy && p0.policy->rollout == 2;     // a policy rollout outside the register/LDS class
+    if (staged && !pol_hbm_only && (fast || !value)) add(fast ? BBX_K_FAST : BBX_K_STAGED);   // (the hand-tuned kernel knows every agent)
     // the HBM-resident pass behind the LDS-resident one serves environments that outgrow the LDS class inside a
     // rollout; a single host-driven step does without it: an environment that spills reports BBX_ST_SPILL and
     // finish() continues it (one launch less on the latency path)
     // (asynchronous calls on caller buffers always get it: nobody polls their status words between steps)
-    if (!b->staged || pol_hbm_only || resume || p.nsteps > 1 || b->flight.obs_external || b->flight.device_async) kinds[nk++] = 0;
+    if (!staged || pol_hbm_only || resume || p0.nsteps > 1 || b->flight.obs_external || b->flight.device_async) add(BBX_K_HBM);
   }
   // wide class with more workgroups than CUs: a second kernel for the tail of the launch (BbxParams::wide_tail)
-  int tail_at = -1;
-  if (nk > 0 && kinds[nk - 1] == 4 && nk < 3 && b->d_wide_done && b->B > b->ncu && p.L.W <= 4 && !getenv("BBX_NO_WIDE_TAIL")) {
-    HIPCHK(hipMemsetAsync(b->d_wide_done, 0, 256, stream));
-    tail_at = nk; kinds[nk++] = 4;
-    p.wide_done = b->d_wide_done; p.wide_ncu = b->ncu;
-  }
+  pl.wide_tail = !value && pl.kind[pl.n - 1] == BBX_K_WIDE && pl.n < 3 && b->d_wide_done && b->B > b->ncu && p0.L.W <= 4 && !getenv("BBX_NO_WIDE_TAIL");
+  if (pl.wide_tail) add(BBX_K_WIDE);
   // a host-driven zero-copy step whose only kernel is the hand-tuned one: the host spins on the status words in pinned
   // memory instead of waiting for the runtime's completion signal (read_lite)
-  b->flight.poll = !resume && nk == 1 && kinds[0] == 3 && outputs_pinned(b) && !b->timing && b->poll_misses < 3 && !getenv("BBX_NO_POLL");
-  if (b->flight.poll) {
-    b->poll_seq = (b->poll_seq % 16000) + 1; p.done_seq = b->poll_seq;
-    // the words the host is going to watch start out cleared: pinned memory is handed out uninitialised and may still hold
-    // the status words — sequence numbers included — of a handle that was destroyed
-    for (int e = 0; e < b->B; e++) ((volatile int32_t*)b->h_io)[(size_t)e * 4] = 0;
-    std::atomic_thread_fence(std::memory_order_release);
-  } else p.done_seq = 0;
-  for (int i = 0; i < nk; i++) {
+  pl.poll = !value && !resume && pl.n == 1 && pl.kind[0] == BBX_K_FAST && outputs_pinned(b) && !b->timing && b->poll_misses < 3;
+  BbxParams p = p0;
+  p.done_seq = 0;
+  if (pl.wide_tail) { p.wide_done = b->d_wide_done; p.wide_ncu = b->ncu; }
+  for (int i = 0; i < pl.n; i++) {
     if (resume || i > 0) { p.set_budget = 0; p.pass = 1; }
-    p.wide_tail = tail_at < 0 ? 0 : (i == tail_at ? 2 : (i == tail_at - 1 ? 1 : 0));
+    p.spill_terms = b->cls == BbxClass::GENERAL_TO_WIDE && pl.kind[i] == BBX_K_HBM ? 384 : 0;   // (hand long polynomials to the wide kernel)
+    p.wide_tail = !pl.wide_tail ? 0 : (i == pl.n - 1 ? 2 : (i == pl.n - 2 ? 1 : 0));
     if (i > 0 && p0.ctl) { p.ctl = nullptr; p.sess_target = p0.nsteps; }   // (what is owed of the session's total when it runs; slice_ticks
                                                                            // != 0 tells it that the host looks after environments it hands back)
     // a per-step policy call: only the first pass of the fast class evaluates the policy (the follow-up reads its actions);
     // a policy rollout: the HBM-resident continuation pass has the policy too
-    if (p.policy && !(p.policy->rollout ? (!resume && (kinds[i] == 3 || kinds[i] == 0)) : (!resume && i == 0 && kinds[i] == 3))) p.policy = nullptr;
+    if (p.policy && !(p.policy->rollout ? (!resume && (pl.kind[i] == BBX_K_FAST || pl.kind[i] == BBX_K_HBM))
+                                        : (!resume && i == 0 && pl.kind[i] == BBX_K_FAST))) p.policy = nullptr;
+    pl.pass[i] = p;
+    pl.waves[i] = pl.kind[i] == BBX_K_WIDE ? b->wide_waves : b->envs_per_block;
+  }
+  return pl;
+}
+
+// enqueue the kernels of one logical launch (plan_launch), timed where bbx_timing asks for it
+int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) {
+  LaunchPlan pl = plan_launch(b, p0, resume, false);
+  if (pl.wide_tail) HIPCHK(hipMemsetAsync(b->d_wide_done, 0, 256, stream));
+  b->flight.poll = pl.poll;
+  if (pl.poll) {
+    b->poll_seq = (b->poll_seq % 16000) + 1; pl.pass[0].done_seq = b->poll_seq;
+    // the words the host is going to watch start out cleared: pinned memory is handed out uninitialised and may still hold
+    // the status words — sequence numbers included — of a handle that was destroyed
+    for (int e = 0; e < b->B; e++) ((volatile int32_t*)b->h_io)[(size_t)e * 4] = 0;
+    std::atomic_thread_fence(std::memory_order_release);
+  }
+  for (int i = 0; i < pl.n; i++) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     // the primary (dominant) kernel of the sequence; where long polynomials continue in the wide kernel, that one too
-    const bool timed = b->timing && kinds[i] != 2 && (i == 0 || kinds[i] == 4);
+    const bool timed = b->timing && pl.kind[i] != BBX_K_AUX && (i == 0 || pl.kind[i] == BBX_K_WIDE);
     if (timed) {
       HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
       HIPCHK(hipEventRecord(e0, stream));
     }
-    int lrc = bbx_launch_step(&p, kinds[i], kinds[i] == 4 ? (b->wide ? b->wide : 8) : b->envs_per_block, stream);
+    int lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], stream);
     if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
     b->step_kernels++;
     if (timed) { HIPCHK(hipEventRecord(e1, stream)); b->ev_open.push_back({e0, e1}); }
@@ -315,7 +326,7 @@ int alloc_io(bbx_batch* b, int batch) {
   memset(b->h_io, 0, b->io_bytes);
   // (host-stepped batches of up to 64 environments: B = 16 / 32 / 64 step in 24 / 28 / 32 us this way, 49 / 59 / 63 us with device
   // buffers and copy calls — scripts/exp_small_batch.py)
-  { const char* zm = getenv("BBX_ZERO_COPY_MAX"); b->zero_copy = batch <= (zm ? atoi(zm) : 64) && !getenv("BBX_NO_ZERO_COPY"); }
+  b->zero_copy = batch <= 64;
   if (b->zero_copy) {
     HIPCHK(hipHostGetDevicePointer((void**)&b->zc_io_dev, b->h_io, 0));
     HIPCHK(hipHostGetDevicePointer((void**)&b->zc_act_dev, b->h_act, 0));
@@ -567,6 +578,19 @@ int copy_out(bbx_batch* b, double* rewards, uint8_t* dones, int32_t* rows) {
   return BBX_OK;
 }
 
+// The kernel class of a new handle; lg: the basis capacity of the LDS working copy
+static BbxClass kernel_class(const bbx_batch* b, bool binomial, bool listed, const bbx_caps& c, int lg) {
+  // long-polynomial environments (fixed ideals such as cyclic-n) in small batches: one workgroup per environment
+  if (b->fixed || listed) return c.wide_waves > 0 || (c.wide_waves == 0 && b->B <= 4096) ? BbxClass::WIDE : BbxClass::GENERAL_HBM;
+  // small binomial environments work out of LDS; the hand-tuned kernel covers exactly the reference C++ class's fixed
+  // options, its registers and LDS hold bases of 256 elements (bbx_fast.h FLay) whatever the staged working copy holds
+  if (binomial && b->W == 2 && c.lds_max_basis >= 0)
+    return !b->binom ? BbxClass::GENERAL_STAGED
+         : b->elim == BBX_GEBAUERMOELLER && b->sort_reducers && lg <= 256 ? BbxClass::FAST : BbxClass::BINOM_STAGED;
+  if (b->binom) return BbxClass::BINOM_HBM;
+  return c.wide_waves >= 0 ? BbxClass::GENERAL_TO_WIDE : BbxClass::GENERAL_HBM;   // (long polynomials: the wide kernel)
+}
+
 int create_common(std::unique_ptr<bbx::IdealGen> proto, int nvars_obs, int elimination, int rewards, int sort_input,
                   int sort_reducers, int k, int batch, int device, const bbx_caps* caps, bbx_batch** out,
                   const std::shared_ptr<const std::vector<bbx::HIdeal>>& list = nullptr) {
@@ -622,32 +646,22 @@ int create_common(std::unique_ptr<bbx::IdealGen> proto, int nvars_obs, int elimi
   // monomial layout from the basis capacity alone (bbx_fast.h F_HBM_PTRS), which is exact for even capacities
   if (c.max_basis & 1) c.max_basis += c.max_basis < 65535 ? 1 : -1;
   b->binom = binomial && !c.general_class;
-  // long-polynomial environments (fixed ideals such as cyclic-n) in small batches: one workgroup per environment
-  if (b->fixed || list) b->wide = c.wide_waves > 0 ? std::min(8, c.wide_waves) : (c.wide_waves < 0 ? 0 : (batch <= 4096 ? 8 : 0));
   if (c.wide_lds_terms < 0 || c.wide_lds_terms > 4096) return fail(BBX_E_ARG, "wide_lds_terms out of range");
   b->wide_terms = c.wide_lds_terms;
   b->no_growth = c.no_growth != 0;
-  // LDS-resident class: small binomial environments work out of LDS for the whole launch; anything that
-  // outgrows it continues in the HBM-resident pass of the same launch sequence
-  b->staged = 0;
-  if (binomial && b->W == 2 && c.lds_max_basis >= 0) {
-    int lg = c.lds_max_basis ? c.lds_max_basis : 128;
-    lg = std::min((lg + 15) & ~15, c.max_basis);       // the working copy never exceeds the HBM record
+  const int lg = std::min(((c.lds_max_basis ? c.lds_max_basis : 128) + 15) & ~15, c.max_basis);   // (the LDS working copy never exceeds the HBM record)
+  b->cls = kernel_class(b.get(), binomial, list != nullptr, c, lg);
+  if (b->cls == BbxClass::WIDE) b->wide_waves = c.wide_waves > 0 ? std::min(8, c.wide_waves) : 8;
+  if (b->cls == BbxClass::GENERAL_TO_WIDE) b->wide_waves = 8;
+  if (lds_staged(b->cls)) {
     b->LL = b->binom ? make_layout_binom(b->W, lg, std::min(2 * lg, c.max_pairs))
                      : make_layout(b->W, lg, std::min(2 * lg, c.max_pairs), std::min(2 * lg + 16, c.arena_terms), c.max_poly_terms);
-    b->staged = 1;
-    // the hand-tuned kernel covers exactly the reference C++ class's fixed options; its registers and LDS hold bases of
-    // 256 elements (bbx_fast.h FLay), independently of the staged class's working copy above
-    b->fast = b->binom && elimination == BBX_GEBAUERMOELLER && sort_reducers && lg <= 256;
     b->fast_G = std::min(c.lds_max_basis ? lg : 256, c.max_basis);
     b->fast_P = std::min(2 * b->fast_G, c.max_pairs);
   }
-  // non-binomial random ideals in <= 7 variables: wave-per-environment kernel, long-polynomial environments continue one
-  // workgroup each (bbx_wide.h) behind it
-  b->gen_to_wide = !b->binom && !b->wide && !b->staged && !b->fixed && !list && c.wide_waves >= 0;
   // (the counter of a two-kernel wide launch, BbxParams::wide_tail: allocated here, never inside a launch — a launch may be
   // recorded into a HIP graph)
-  if ((b->wide || b->gen_to_wide) && b->ncu > 0 && batch > b->ncu) HIPCHK(hipMalloc((void**)&b->d_wide_done, 256));
+  if (b->wide_waves && b->ncu > 0 && batch > b->ncu) HIPCHK(hipMalloc((void**)&b->d_wide_done, 256));
   if (c.max_basis > 65535 || c.max_poly_terms > (1 << 22) || c.max_basis < 2 || c.max_pairs < 2 || c.max_poly_terms < 4 || c.queue_slots < 1)
     return fail(BBX_E_ARG, "capacities out of range");
   b->L = b->binom ? make_layout_binom(b->W, c.max_basis, c.max_pairs)
@@ -787,15 +801,12 @@ int bbx_copy(const bbx_batch* s, bbx_batch** out) {
   HIPCHK(hipSetDevice(s->device)); const_cast<bbx_batch*>(s)->api_epoch++;
   if (int rc = quiesce(const_cast<bbx_batch*>(s))) return rc;
   auto b = std::make_unique<bbx_batch>();
-  b->B = s->B; b->device = s->device; b->k = s->k; b->nvars = s->nvars; b->W = s->W;
-  b->ncu = s->ncu;
-  b->elim = s->elim; b->rewards = s->rewards; b->sort_input = s->sort_input; b->sort_reducers = s->sort_reducers;
-  b->fixed = s->fixed; b->listed = s->listed; b->binom = s->binom; b->L = s->L; b->LL = s->LL; b->slot_words = s->slot_words; b->nslots = s->nslots;
+  // A copy carries over the configuration, the ideal queue, generators and seed stream, and the records.  It does not carry
+  // kernel timing (bbx_timing), persistent sessions (bbx_persistent) or any session state, the trace buffer, or statistics.
+  static_cast<bbx_config&>(*b) = *s;
   b->h_q = s->h_q; b->h_tail = s->h_tail; b->h_head = s->h_head; b->q_dirty = true;
-  b->no_growth = s->no_growth; b->value_rng = s->value_rng; b->gen_to_wide = s->gen_to_wide;
+  b->value_rng = s->value_rng;
   if (s->d_wide_done) HIPCHK(hipMalloc((void**)&b->d_wide_done, 256));
-  b->wide = s->wide; b->wide_terms = s->wide_terms; b->accounting = s->accounting; b->staged = s->staged; b->fast = s->fast; b->envs_per_block = s->envs_per_block;
-  b->fast_G = s->fast_G; b->fast_P = s->fast_P;
   if (s->device_gen) {
     b->gen_owner = s->gen_owner; b->d_gen = s->d_gen;      // (immutable: shared)
     b->device_gen = true; b->gen_words = s->gen_words;
@@ -1099,7 +1110,7 @@ static int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards
   BbxParams p; fill_params(b, &p);
   p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset; p.actions = d_actions;
   p.rewards = d_rewards; p.dones = d_dones; p.rows = d_rows; p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill;
-  if (b->d_trace && b->trace_cap < 1) p.trace = nullptr;
+  if (!traced(b)) p.trace = nullptr;
   return launch(b, p, (hipStream_t)stream, d_obs != nullptr, true);
 }
 
@@ -1228,9 +1239,7 @@ int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, co
   if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
   // one launch for policy + step where the step kernel has the policy built in (the register/LDS-resident class, lean
   // variant, 33..128 hidden units, at most 12 columns); everywhere else the two launches it replaces
-  const bool fused = b->fast && b->staged && !b->accounting && !(b->d_trace && b->trace_cap >= 1) && (pmlp_nb(hidden) == 2 || pmlp_nb(hidden) == 4) &&
-                     cols <= 12 && !getenv("BBX_NO_FUSED_POLICY");
-  if (!fused) {
+  if (!(lean_fast(b) && (pmlp_nb(hidden) == 2 || pmlp_nb(hidden) == 4) && cols <= 12)) {
     int rc = bbx_pmlp_act(d_obs, d_rows, b->B, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream);
     if (rc) return rc;
     return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 1);
@@ -1267,11 +1276,11 @@ int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden,
   // where the policy is built into the step kernels: binomial classes with 8- or 16-byte monomials, 33..128 hidden units,
   // observation widths whose prepared weights have 6 k-steps (or 10 with 16-byte monomials)
   const int ks = pmlp_ks(cols);
-  if (!b->binom || b->wide || (b->W != 2 && b->W != 4) || (pmlp_nb(hidden) != 2 && pmlp_nb(hidden) != 4) || !(ks == 6 || (b->W == 4 && ks == 10)))
+  if (!b->binom || (b->W != 2 && b->W != 4) || (pmlp_nb(hidden) != 2 && pmlp_nb(hidden) != 4) || !(ks == 6 || (b->W == 4 && ks == 10)))
     return fail(BBX_E_UNSUPPORTED, "policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 20 with "
                                    "more than 3 variables; 33..128 hidden units); drive this batch with bbx_policy_step_device");
   if (b->accounting) return fail(BBX_E_UNSUPPORTED, "policy rollouts run the lean kernel: call bbx_accounting(b, 0) first");
-  if (b->d_trace && b->trace_cap >= 1) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
+  if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
   if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   BbxPolicy pol{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0};
@@ -1282,7 +1291,7 @@ int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden,
   p.policy = &pol;
   // the register/LDS-resident kernel has the policy for 3 variables and k = 2; every other admitted shape runs in the
   // HBM-resident binomial kernel from the start
-  pol.rollout = (b->fast && b->staged && b->nvars == 3 && b->k == 2) ? 1 : 2;
+  pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;
   return launch(b, p, (hipStream_t)stream, true, true);   // (rows the policy could not score — more than the block or the kernel holds — are an error)
 }
 

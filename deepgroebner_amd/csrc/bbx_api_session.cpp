@@ -142,9 +142,9 @@ static bool is_policy_step_call(const BbxParams& p) { return p.policy && p.polic
 // asynchronous rollouts with a built-in agent (or per-step calls of the one-layer policy) on the register/LDS-resident class,
 // lean and untraced, ideals drawn on the device (nothing for the host to do between launches), every wave resident at once
 static bool session_admits(const bbx_batch* b, const BbxParams& p, bool device_async) {
-  return b->ps_enabled && device_async && b->fast && b->staged && b->device_gen && !b->accounting && p.nsteps >= 1 && p.auto_reset &&
+  return b->ps_enabled && device_async && lean_fast(b) && b->device_gen && p.nsteps >= 1 && p.auto_reset &&
          (is_policy_step_call(p) || (!p.policy && p.obs_fill == 0 && (p.agent == BBX_AGENT_HASH || p.agent == BBX_AGENT_DEGREE || p.agent == BBX_AGENT_FIRST))) &&
-         !(b->d_trace && b->trace_cap >= 1) && !b->timing && b->B <= 4096 && p.set_budget == 1;
+         !b->timing && b->B <= 4096 && p.set_budget == 1;
 }
 static bool session_same_policy(const bbx_batch* b, const BbxParams& p) {
   const BbxPolicy* a = b->ps_p.policy; const BbxPolicy* c = p.policy;
@@ -239,8 +239,7 @@ int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external, bo
 bool mbox_eligible(const bbx_batch* b) {
   // (up to 8 environments: measured at 16 / 32 / 64 a session is no faster than — 24 / 34 / 61 against 24 / 28 / 32 us — the
   // zero-copy launch per step, whose one kernel serves all of them at once)
-  return b->zero_copy && b->B <= 8 && b->fast && b->staged && b->device_gen && !b->accounting && !b->timing && !(b->d_trace && b->trace_cap >= 1) &&
-         b->mbox_misses < 3 && !getenv("BBX_NO_MAILBOX");
+  return b->zero_copy && b->B <= 8 && lean_fast(b) && b->device_gen && !b->timing && b->mbox_misses < 3;
 }
 // p: the step's parameters (external agent, zero-copy outputs, nsteps = 1).  Returns BBX_OK with the step taken and its outputs
 // in the pinned block, or an error; *used = false: not taken here (the caller launches as before).

@@ -60,15 +60,8 @@ int value_rollouts(bbx_batch* b, const std::vector<int32_t>& src, int agent, con
     p.recs = b->d_vrecs; p.B = n; p.nsteps = 1 << 30; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
     p.value_mode = 1; p.gamma = gamma; p.values = nullptr; p.trace = nullptr; p.accounting = 0;
     p.lite = nullptr;                                           // the clones are not the batch's environments
-    if (b->wide) lrc = bbx_launch_step(&p, 4, b->wide, 0);
-    else {
-      const bool vfast = b->fast && b->staged;                  // (every selection strategy: bbx_fast.h, f_select_ordered)
-      lrc = 0;
-      if (vfast) lrc = bbx_launch_step(&p, 3, b->envs_per_block, 0);
-      if (b->gen_to_wide) p.spill_terms = 384;
-      if (!lrc) { if (vfast) { p.set_budget = 0; p.pass = 1; } lrc = bbx_launch_step(&p, 0, b->envs_per_block, 0); }
-      if (!lrc && b->gen_to_wide) { p.set_budget = 0; p.pass = 1; p.spill_terms = 0; lrc = bbx_launch_step(&p, 4, 8, 0); }
-    }
+    const LaunchPlan pl = plan_launch(b, p, false, true);      // (the fast class: every selection strategy, bbx_fast.h f_select_ordered)
+    for (int i = 0; i < pl.n && !lrc; i++) lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], 0);
     if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
     lrc = bbx_launch_value_collect(b->d_vrecs, b->L.rec_bytes, n, b->d_vvals, 0);
     if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));

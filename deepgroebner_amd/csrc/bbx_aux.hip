@@ -4,8 +4,8 @@
 #include "bbx_pmlp.h"
 #include "bbx_binom.h"
 
-extern "C" int bbx_launch_general(const BbxParams* p, int kind, int blocks, int threads, size_t lds, hipStream_t stream);
-extern "C" int bbx_launch_binom(const BbxParams* p, int kind, int blocks, int threads, size_t lds, hipStream_t stream);
+extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream);
+extern "C" int bbx_launch_binom(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream);
 extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int envs_per_block, hipStream_t stream);
 extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream);
 
@@ -282,17 +282,16 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
 
 
 // ------------------------------------------------------------------ host-callable launcher
-// kind: 0 = HBM-resident step kernel, 1 = LDS-staged step kernel, 2 = aux (reset / observation only), 3 = the hand-tuned
-// register/LDS-resident kernel (bbx_fast.h), 4 = wide (envs_per_block is then the number of waves per environment)
-extern "C" int bbx_launch_step(const BbxParams* p, int kind, int envs_per_block, hipStream_t stream) {
+// (BBX_K_WIDE: envs_per_block is the number of waves per environment)
+extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_block, hipStream_t stream) {
   const int threads = envs_per_block * WAVE;
   const int blocks = (p->B + envs_per_block - 1) / envs_per_block;
-  if (kind == 3) { bbx_launch_fast(p, blocks, threads, envs_per_block, stream); return (int)hipGetLastError(); }
-  if (kind == 4) {
+  if (kind == BBX_K_FAST) { bbx_launch_fast(p, blocks, threads, envs_per_block, stream); return (int)hipGetLastError(); }
+  if (kind == BBX_K_WIDE) {
     if (p->L.W != 2 && p->L.W != 4 && p->L.W != 8) return (int)hipErrorInvalidValue;
     return bbx_launch_wide(p, envs_per_block, stream);
   }
-  const size_t lds = kind == 1 ? (size_t)envs_per_block * p->LL.rec_bytes : 0;
+  const size_t lds = kind == BBX_K_STAGED ? (size_t)envs_per_block * p->LL.rec_bytes : 0;
   const int rc = p->L.kind == 1 ? bbx_launch_binom(p, kind, blocks, threads, lds, stream) : bbx_launch_general(p, kind, blocks, threads, lds, stream);
   if (rc) return rc;
   return (int)hipGetLastError();

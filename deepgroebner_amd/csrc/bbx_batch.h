@@ -13,7 +13,7 @@
 #include "bbx_host.h"
 #include "bbx_ideals.h"
 
-extern "C" int bbx_launch_step(const BbxParams* p, int kind, int envs_per_block, hipStream_t stream);
+extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_block, hipStream_t stream);
 extern "C" int bbx_launch_clone(const char* src_recs, char* dst_recs, const BbxLayout* L, const int32_t* src, const int32_t* dst, int n,
                                 const uint32_t* seeds, int keep_counters, int seed_std, int ngen, uint8_t* flags, hipStream_t stream);
 extern "C" int bbx_launch_value_resort(char* recs, const BbxLayout* L, int n, const uint8_t* flags, hipStream_t stream);
@@ -51,14 +51,32 @@ struct bbx_gen {
   bbx::HIdeal last;
 };
 
-struct bbx_batch {
+// The kernel class of a handle, chosen once by create_common; which kernels a launch of each is made of: plan_launch
+// 
+enum class BbxClass { FAST, BINOM_STAGED, GENERAL_STAGED, BINOM_HBM, GENERAL_HBM, GENERAL_TO_WIDE, WIDE };
+inline bool lds_staged(BbxClass c) { return c == BbxClass::FAST || c == BbxClass::BINOM_STAGED || c == BbxClass::GENERAL_STAGED; }
+
+// What create_common decides about a handle, and all of it that bbx_copy carries over.  L changes when the records grow
+// (grow_records), accounting with bbx_accounting; nothing else changes after creation.
+struct bbx_config {
   int B = 0, device = 0, k = 1, nvars = 0, W = 2;
   int elim = 0, rewards = 0, sort_input = 0, sort_reducers = 1;
-  bool fixed = false, binom = false, listed = false;   // listed: the ideals come from a caller's list (bbx_create_ideals)
-  BbxLayout L{}, LL{};
+  bool fixed = false, binom = false, listed = false;   // binom: the record format; listed: ideals of bbx_create_ideals
+  BbxLayout L{}, LL{};                // the HBM record; the working copy of the LDS-staged classes
+  BbxClass cls = BbxClass::GENERAL_HBM;
+  uint32_t slot_words = 0, nslots = 0;   // ideal queue geometry
+  int envs_per_block = 4;
+  int fast_G = 0, fast_P = 0;          // capacities of the register/LDS-resident class (BbxParams::fast_G)
+  int wide_waves = 0;                 // waves per environment of the wide kernel (WIDE, GENERAL_TO_WIDE)
+  int wide_terms = 0;                 // forced LDS capacity of the wide class (caps.wide_lds_terms), 0 = automatic
+  int ncu = 0;                        // compute units of the device
+  bool no_growth = false;             // bbx_caps.no_growth: the configured capacities are hard limits (BBX_E_CAPACITY)
+  bool accounting = true;             // count algorithmic bytes (bbx_accounting)
+};
+
+struct bbx_batch : bbx_config {
   uint16_t* d_inv = nullptr;           // GF(32003) inverse table: one per device and process (bbx_host::inv_table), never freed
   std::vector<std::unique_ptr<bbx::IdealGen>> gens;   // one per environment (one shared when fixed)
-  uint32_t slot_words = 0, nslots = 0;
   std::vector<uint32_t> h_q;          // host mirror of the ideal queue
   std::vector<int32_t> h_tail, h_head;
   std::vector<BbxHdr> h_hdr;
@@ -97,7 +115,6 @@ struct bbx_batch {
   char* d_vrecs = nullptr; BbxHdr* d_vhdr = nullptr; int32_t* d_vsrc = nullptr; uint32_t* d_vseeds = nullptr; double* d_vvals = nullptr;
   int vcap = 0;
   // HIP-event timing of the step-kernel launches (bbx_timing)
-  bool accounting = true;             // count algorithmic bytes (bbx_accounting)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_open;
   double kernel_ms = 0.0; int kernel_launches = 0;
@@ -105,12 +122,7 @@ struct bbx_batch {
   bbx_flight flight;                  // the call in flight (so bbx_sync can finish environments that waited for ideals)
   bbx_flight cap; bool cap_valid = false;   // the last call recorded into a HIP graph (bbx_graph_replayed)
   bool cap_stale = false; std::vector<void*> retired;   // the records were enlarged after the recording: the old arrays stay allocated (replays write there)
-  int staged = 0, fast = 0, envs_per_block = 4;
-  int fast_G = 0, fast_P = 0;          // capacities of the register/LDS-resident class (BbxParams::fast_G)
-  int wide = 0;                       // > 0: waves per environment of the wide (one workgroup per environment) class
-  int wide_terms = 0;                 // forced LDS capacity of the wide class (caps.wide_lds_terms), 0 = automatic
   int32_t* d_wide_done = nullptr;     // wide class: workgroups that have left the launch's first kernel (BbxParams::wide_tail)
-  int ncu = 0;                        // compute units of the device
   // persistent sessions (bbx_persistent): see BbxParams::ctl
   bool ps_enabled = false, ps_active = false;
   // host mailbox sessions (BbxParams::mbox): host-driven steps of small zero-copy batches on the register/LDS-resident class
@@ -130,8 +142,6 @@ struct bbx_batch {
   int ps_sessions = 0, ps_joined = 0, ps_kernels = 0; // statistics: sessions begun, calls that joined a running one, kernels
   int32_t* d_clone_idx = nullptr; int clone_cap = 0;   // bbx_clone_envs: source / destination indices on the device
   std::mt19937_64 value_rng;          // seeds of value("random") / value("sample") rollouts when the caller gives none
-  bool gen_to_wide = false;           // general class with <= 16-byte monomials: long-polynomial environments continue in the wide class
-  bool no_growth = false;             // bbx_caps.no_growth: the configured capacities are hard limits (BBX_E_CAPACITY)
   int grow_events = 0;                // times the records were enlarged (bbx_capacities)
   long long step_kernels = 0;         // kernels enqueue() has launched for this handle (bbx_kernels_launched: what a call costs in launches)
   bbx_batch() = default;
@@ -162,6 +172,19 @@ inline SeqScan scan_seq(const bbx_batch* b, uint32_t want, uint32_t flags) {
   }
   return s;
 }
+inline bool traced(const bbx_batch* b) { return b->d_trace && b->trace_cap >= 1; }
+// the register/LDS-resident class, lean and untraced: what sessions, mailboxes and the fused policy step run on
+inline bool lean_fast(const bbx_batch* b) { return b->cls == BbxClass::FAST && !b->accounting && !traced(b); }
+// The kernels of one launch (plan_launch): kind[i] with parameters pass[i], waves[i] environments per workgroup (wide: waves per environment)
+struct LaunchPlan {
+  int n = 0;
+  BbxKernel kind[3];
+  int waves[3];
+  BbxParams pass[3];
+  bool wide_tail = false;             // the last kernel is the tail of a two-kernel wide launch (BbxParams::wide_tail)
+  bool poll = false;                  // bbx_flight::poll
+};
+LaunchPlan plan_launch(const bbx_batch* b, const BbxParams& p0, bool resume, bool value);
 int read_headers(bbx_batch* b, hipStream_t stream = 0);
 void fill_params(bbx_batch* b, BbxParams* p);
 int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream);

@@ -201,6 +201,10 @@ struct BbxParams {
   int32_t* wide_done;
 };
 
+// The step kernels a launch is made of (bbx_launch_step): HBM-resident, LDS-staged, aux (reset / observation only), the
+// hand-tuned register/LDS-resident kernel (bbx_fast.h), wide (one workgroup per environment, bbx_wide.h)
+enum BbxKernel { BBX_K_HBM = 0, BBX_K_STAGED = 1, BBX_K_AUX = 2, BBX_K_FAST = 3, BBX_K_WIDE = 4 };
+
 // Device-side ideal generation (RandomBinomialIdealGenerator, ideals.cpp:156-201): one immutable table per batch, words:
 //   [0] n  [1] d  [2] s  [3] flags (1 homogeneous, 2 pure, 4 polynomial distribution = RandomIdealGenerator, ideals.cpp:203-231)
 //   [4] #cumulative probabilities (0: degree is always 0)  [5] W  [6..7] exp(-lambda) of the polynomial distribution (double)

@@ -33,6 +33,16 @@
 
 #define WAVE 64
 
+// (host) raise a kernel's dynamic-LDS limit to what this launch asks for, then launch it; launch errors: hipGetLastError
+template <class... A>
+static int launch_lds(void (*kern)(A...), int blocks, int threads, size_t lds, hipStream_t stream, A... args) {
+  const hipError_t err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (err != hipSuccess) return (int)err;
+  void* argv[] = {(void*)&args...};
+  (void)hipLaunchKernel((const void*)kern, dim3(blocks), dim3(threads), argv, lds, stream);
+  return 0;
+}
+
 // ------------------------------------------------------------------ wave helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ void wave_sync() {

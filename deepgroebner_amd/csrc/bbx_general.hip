@@ -273,26 +273,18 @@ __global__ __launch_bounds__(256) void bbx_step_prof_kernel(BbxParams p, unsigne
 
 #endif
 
-// kind: 0 = HBM-resident step kernel, 1 = LDS-staged step kernel, 2 = aux (reset / observation only)
-#define BBX_LAUNCH(KERN) hipLaunchKernelGGL((KERN), dim3(blocks), dim3(threads), lds, stream, *p)
 template <int W>
-static int launch_general_w(const BbxParams* p, int kind, int blocks, int threads, size_t lds, hipStream_t stream) {
+static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
   const bool trace = p->trace != nullptr;
-  if (kind == 2) { BBX_LAUNCH(bbx_aux_kernel<W>); return 0; }
-  if (kind == 1) {
-    const void* fn = trace ? (const void*)bbx_step_kernel<W, true, true> : (const void*)bbx_step_kernel<W, true, false>;
-    hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) return (int)err;
-    if (trace) BBX_LAUNCH((bbx_step_kernel<W, true, true>)); else BBX_LAUNCH((bbx_step_kernel<W, true, false>));
-    return 0;
-  }
+  if (kind == BBX_K_AUX) { hipLaunchKernelGGL(bbx_aux_kernel<W>, dim3(blocks), dim3(threads), lds, stream, *p); return 0; }
+  if (kind == BBX_K_STAGED)
+    return launch_lds(trace ? bbx_step_kernel<W, true, true> : bbx_step_kernel<W, true, false>, blocks, threads, lds, stream, *p);
 #ifdef BBX_PROF_BUILD   // diagnostic build only (-DBBX_PROF_BUILD): per-phase s_memtime sums, never in the product library
   if (!trace && getenv("BBX_PROF")) {
     static unsigned long long* d_prof = nullptr;
     if (!d_prof) (void)hipMalloc((void**)&d_prof, (size_t)p->B * 10 * sizeof(unsigned long long));
     lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();
-    (void)hipFuncSetAttribute((const void*)bbx_step_prof_kernel<W>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((bbx_step_prof_kernel<W>), dim3(blocks), dim3(threads), lds, stream, *p, d_prof);
+    (void)launch_lds(bbx_step_prof_kernel<W>, blocks, threads, lds, stream, *p, d_prof);
     (void)hipStreamSynchronize(stream);
     std::vector<unsigned long long> h((size_t)p->B * 10);
     (void)hipMemcpy(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost);
@@ -306,13 +298,9 @@ static int launch_general_w(const BbxParams* p, int kind, int blocks, int thread
   }
 #endif
   lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();          // merge-path tile scratch, one per wave
-  const void* fn = trace ? (const void*)bbx_step_kernel<W, false, true> : (const void*)bbx_step_kernel<W, false, false>;
-  hipError_t err = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (err != hipSuccess) return (int)err;
-  if (trace) BBX_LAUNCH((bbx_step_kernel<W, false, true>)); else BBX_LAUNCH((bbx_step_kernel<W, false, false>));
-  return 0;
+  return launch_lds(trace ? bbx_step_kernel<W, false, true> : bbx_step_kernel<W, false, false>, blocks, threads, lds, stream, *p);
 }
-extern "C" int bbx_launch_general(const BbxParams* p, int kind, int blocks, int threads, size_t lds, hipStream_t stream) {
+extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
   return p->L.W == 2 ? launch_general_w<2>(p, kind, blocks, threads, lds, stream)
        : p->L.W == 4 ? launch_general_w<4>(p, kind, blocks, threads, lds, stream) : launch_general_w<8>(p, kind, blocks, threads, lds, stream);
 }

@@ -7,11 +7,10 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
     const int W_ = (int)q.L.W;                             // as large as the residency aimed at allows
     // lean variants: random and external agents let h grow long — reducer tails collect in an LDS accumulator and h is
     // rewritten only when it is full (LAZY); the ordering strategies keep h short — plain eager merges without the
-    // accumulator's bookkeeping.  BBX_WIDE_EAGER=1 / =0 force one or the other (experiments).
+    // accumulator's bookkeeping
     const bool strategy = q.agent == BBX_AGENT_DEGREE || q.agent == BBX_AGENT_FIRST || q.agent == BBX_AGENT_NORMAL || q.agent == BBX_AGENT_SUGAR ||
                           q.agent == BBX_AGENT_LAST || q.agent == BBX_AGENT_CODEGREE || q.agent == BBX_AGENT_STRANGE || q.agent == BBX_AGENT_SPICE;
     bool lazy = !q.accounting && !strategy;
-    if (const char* ev = getenv("BBX_WIDE_EAGER")) lazy = !q.accounting && ev[0] == '0';
     if (W_ == 8) lazy = false;                             // (32-byte monomials have no sort key: the accumulator holds keys)
     const bool acct = q.accounting != 0;
     bool one_per_cu = false;
@@ -36,33 +35,18 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
     p = &q;
     const size_t wl = wide_lds_bytes(W_, q.wide_hc, q.wide_fc, q.wide_rc, q.wide_sc);
     const bool tr = p->trace != nullptr;
-#define BBX_WIDE_LAUNCH(WW, TT, LL) do { \
-      hipError_t err_ = hipFuncSetAttribute((const void*)bbx_wide_kernel<WW, TT, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
-      if (err_ != hipSuccess) return (int)err_; \
-      hipLaunchKernelGGL((bbx_wide_kernel<WW, TT, LL>), dim3(p->B), dim3(nw * WAVE), wl, stream, *p); } while (0)
-#define BBX_WIDE_LAUNCH1(WW, LL, AA) do { \
-      hipError_t err_ = hipFuncSetAttribute((const void*)bbx_wide_kernel_1cu<WW, LL, AA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
-      if (err_ != hipSuccess) return (int)err_; \
-      hipLaunchKernelGGL((bbx_wide_kernel_1cu<WW, LL, AA>), dim3(p->B), dim3(nw * WAVE), wl, stream, *p); } while (0)
-#define BBX_WIDE_LAUNCHE(WW) do { \
-      hipError_t err_ = hipFuncSetAttribute((const void*)bbx_wide_eager_kernel<WW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wl); \
-      if (err_ != hipSuccess) return (int)err_; \
-      hipLaunchKernelGGL((bbx_wide_eager_kernel<WW>), dim3(p->B), dim3(nw * WAVE), wl, stream, *p); } while (0)
-    if (W_ == 8) { if (tr) BBX_WIDE_LAUNCH(8, true, false); else BBX_WIDE_LAUNCH(8, false, false); }   // one variant: tier 3 throughout
-    else if (!tr && one_per_cu && !getenv("BBX_WIDE_NO1CU")) {
-      if (W_ == 2) { if (lazy) BBX_WIDE_LAUNCH1(2, true, false); else if (acct) BBX_WIDE_LAUNCH1(2, false, true); else BBX_WIDE_LAUNCH1(2, false, false); }
-      else { if (lazy) BBX_WIDE_LAUNCH1(4, true, false); else if (acct) BBX_WIDE_LAUNCH1(4, false, true); else BBX_WIDE_LAUNCH1(4, false, false); }
-    } else if (!tr && !lazy && !acct) {
-      if (W_ == 2) BBX_WIDE_LAUNCHE(2); else BBX_WIDE_LAUNCHE(4);
-    } else
-    if (W_ == 2) { if (tr) { if (lazy) BBX_WIDE_LAUNCH(2, true, true); else BBX_WIDE_LAUNCH(2, true, false); }
-                   else { if (lazy) BBX_WIDE_LAUNCH(2, false, true); else BBX_WIDE_LAUNCH(2, false, false); } }
-    else { if (tr) { if (lazy) BBX_WIDE_LAUNCH(4, true, true); else BBX_WIDE_LAUNCH(4, true, false); }
-           else { if (lazy) BBX_WIDE_LAUNCH(4, false, true); else BBX_WIDE_LAUNCH(4, false, false); } }
-#undef BBX_WIDE_LAUNCH
-#undef BBX_WIDE_LAUNCH1
-#undef BBX_WIDE_LAUNCHE
-    return (int)hipGetLastError();
+    auto go = [&](void (*kern)(BbxParams)) { return launch_lds(kern, p->B, nw * WAVE, wl, stream, q); };
+    int rc;
+    if (W_ == 8) rc = tr ? go(bbx_wide_kernel<8, true, false>) : go(bbx_wide_kernel<8, false, false>);   // one variant: tier 3 throughout
+    else if (!tr && one_per_cu) {
+      if (W_ == 2) rc = lazy ? go(bbx_wide_kernel_1cu<2, true, false>) : acct ? go(bbx_wide_kernel_1cu<2, false, true>) : go(bbx_wide_kernel_1cu<2, false, false>);
+      else rc = lazy ? go(bbx_wide_kernel_1cu<4, true, false>) : acct ? go(bbx_wide_kernel_1cu<4, false, true>) : go(bbx_wide_kernel_1cu<4, false, false>);
+    } else if (!tr && !lazy && !acct) rc = W_ == 2 ? go(bbx_wide_eager_kernel<2>) : go(bbx_wide_eager_kernel<4>);
+    else if (W_ == 2) rc = tr ? (lazy ? go(bbx_wide_kernel<2, true, true>) : go(bbx_wide_kernel<2, true, false>))
+                              : (lazy ? go(bbx_wide_kernel<2, false, true>) : go(bbx_wide_kernel<2, false, false>));
+    else rc = tr ? (lazy ? go(bbx_wide_kernel<4, true, true>) : go(bbx_wide_kernel<4, true, false>))
+                 : (lazy ? go(bbx_wide_kernel<4, false, true>) : go(bbx_wide_kernel<4, false, false>));
+    return rc ? rc : (int)hipGetLastError();
 }
 #ifdef BBX_PROF_BUILD
 extern "C" int bbx_wide_prof_read(unsigned long long* out, int reset) {   // diagnostic build only

@@ -862,6 +862,11 @@ def test_kernels_per_call():
     gen.seed(np.arange(64))
     assert cost(gen, gen.reset) == 2
     assert cost(gen, lambda: gen.rollout("random", 8, auto_reset=True)) == 2            # general class + wide class behind it
+    for kw in ({"elimination": "none"}, {"caps": {"general_class": 1}}):                # binomial / general LDS-staged class
+        stg = VecLeadMonomialsEnv("3-20-10-weighted", batch=64, k=2, **kw)
+        stg.seed(np.arange(64)); stg.accounting(False)
+        assert cost(stg, stg.reset) == 2
+        assert cost(stg, lambda: stg.rollout("random", 16, auto_reset=True)) == 2, kw   # ... + HBM-resident continuation
 
 
 def test_wide_class_two_kernel_launch_for_more_workgroups_than_cus():
