@@ -294,6 +294,18 @@ class VecLeadMonomialsEnv:
         _ffi.check(_ffi.lib().bbx_policy_rollout_device(self._h, dp(prepared), int(hidden), int(nsteps), dp(u), dp(actions), dp(logprobs), dp(rewards),
                                                        dp(dones), dp(rows), dp(obs), int(obs_rows), int(obs_step_stride), C.c_void_p(int(stream))))
 
+    def policy2_rollout_device(self, prepared, hidden1, hidden2, nsteps, u, actions, logprobs, rewards=None, dones=None, rows=None, obs=None,
+                               obs_rows=0, obs_step_stride=0, stream=0):
+        """policy_rollout_device with a two-hidden-layer PMLP inside the step kernel (bbx_policy2_rollout_device): `prepared`
+        as bbx_pmlp2_prepare left it; the same arrays and layout.  Raises BbxError(BBX_E_UNSUPPORTED) where the batch's kernel
+        class has no built-in policy of this shape."""
+        def dp(x):
+            if x is None or isinstance(x, C.c_void_p):
+                return x
+            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        _ffi.check(_ffi.lib().bbx_policy2_rollout_device(self._h, dp(prepared), int(hidden1), int(hidden2), int(nsteps), dp(u), dp(actions), dp(logprobs),
+                                                        dp(rewards), dp(dones), dp(rows), dp(obs), int(obs_rows), int(obs_step_stride), C.c_void_p(int(stream))))
+
     def sync(self):
         _ffi.check(_ffi.lib().bbx_sync(self._h))
 

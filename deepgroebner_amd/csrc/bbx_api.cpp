@@ -255,7 +255,10 @@ LaunchPlan plan_launch(const bbx_batch* b, const BbxParams& p0, bool resume, boo
     if (p.policy && !(p.policy->rollout ? (!resume && (pl.kind[i] == BBX_K_FAST || pl.kind[i] == BBX_K_HBM))
                                         : (!resume && i == 0 && pl.kind[i] == BBX_K_FAST))) p.policy = nullptr;
     pl.pass[i] = p;
-    pl.waves[i] = pl.kind[i] == BBX_K_WIDE ? b->wide_waves : b->envs_per_block;
+    // (a two-layer policy rollout in the register/LDS class: workgroups of BBX_POL2_WAVES waves, one per CU, that share one LDS
+    // copy of the second layer — fast_body POL2, bbx_fast.h)
+    pl.waves[i] = pl.kind[i] == BBX_K_WIDE ? b->wide_waves
+                : (pl.kind[i] == BBX_K_FAST && p.policy && p.policy->hidden2 > 0) ? (int)BBX_POL2_WAVES : b->envs_per_block;
   }
   return pl;
 }
@@ -1293,6 +1296,36 @@ int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden,
   // HBM-resident binomial kernel from the start
   pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;
   return launch(b, p, (hipStream_t)stream, true, true);   // (rows the policy could not score — more than the block or the kernel holds — are an error)
+}
+
+// two hidden layers inside the step loop (ParallelMultilayerPerceptron([h1, h2]), networks.py:562-571): the same call with the
+// weights bbx_pmlp2_prepare leaves; the same admission as the one-layer call, for the k-step counts the kernels are built for
+static int pmlp2_ks(int cols) { const int ks = (cols + 3) / 4; return ks <= 3 ? 3 : ks <= 8 ? 8 : 16; }
+int bbx_policy2_rollout_device(bbx_batch* b, const float* d_prepared, int hidden1, int hidden2, int nsteps, const float* d_u, int32_t* d_actions,
+                               float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
+                               long long obs_step_stride, void* stream) {
+  if (!b || !d_prepared || !d_u || !d_actions || !d_logprobs) return fail(BBX_E_ARG, "null argument");
+  if (nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0) return fail(BBX_E_ARG, "bad rollout arguments");
+  if (d_obs && obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
+  const int cols = 2 * b->nvars * b->k;
+  if (bbx_pmlp2_prepared_floats(cols, hidden1, hidden2) < 0) return BBX_E_UNSUPPORTED;
+  // built into the binomial kernel classes: 8-byte monomials with <= 12 columns (3 k-steps of four), 16-byte ones with <= 32
+  const int ks = pmlp2_ks(cols);
+  if (!b->binom || !((b->W == 2 && ks == 3) || (b->W == 4 && (ks == 3 || ks == 8))))
+    return fail(BBX_E_UNSUPPORTED, "two-layer policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 32 with "
+                                   "more than 3 variables; <= 128 units per layer); drive this batch with bbx_pmlp2_act and bbx_step_device_autoreset");
+  if (b->accounting) return fail(BBX_E_UNSUPPORTED, "policy rollouts run the lean kernel: call bbx_accounting(b, 0) first");
+  if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
+  if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  BbxPolicy pol{d_prepared, hidden1, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0, hidden2};
+  BbxParams p; fill_params(b, &p);
+  p.nsteps = nsteps; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
+  p.obs = d_obs; p.obs_rows = d_obs ? obs_rows : 0; p.obs_fill = 0;
+  p.trace = nullptr;
+  p.policy = &pol;
+  pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;   // (as bbx_policy_rollout_device)
+  return launch(b, p, (hipStream_t)stream, true, true);
 }
 
 int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, double* d_rewards, uint8_t* d_dones,

@@ -436,7 +436,10 @@ template <int W> __host__ __device__ constexpr size_t binom_scratch_bytes(int ob
 // outgrew the register/LDS-resident class or as the rollout kernel of a batch that is not in that class.  POL = unit
 // blocks of 32 of the hidden layer, PKS = the k-steps of the prepared weights (pmlp_ks_for(2 n k)).
 // AUX: the instantiation without LDS (smem == nullptr).
-template <int W, bool STAGED, bool TRACE, int POL = 0, int PKS = 6, bool AUX = false>
+// POL2 > 0: a policy with TWO hidden layers (bbx_policy2_rollout_device): POL = the first layer's blocks of 16 units, POL2 = the
+// second's, PKS = pmlp2_ks_for(2 n k); tiles of 16 rows through the stand-alone kernel's code (pmlp2_tile, bbx_pmlp.h), every
+// weight read from memory (the second layer's 64 KB stay in L2: this kernel keeps its LDS for the update's scratch).
+template <int W, bool STAGED, bool TRACE, int POL = 0, int PKS = 6, bool AUX = false, int POL2 = 0>
 __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem, const BbxPolicy* pol = nullptr) {
   const BbxParams& p = bbx_kparams();                      // (set-up; the step loop and the write-back behind it take their own)
   (void)p_entry;
@@ -550,6 +553,40 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
       int n = nP < PMLP_MAXROWS ? nP : PMLP_MAXROWS;            // (rows beyond what the policy can score: reported, like rows
       obs_trunc |= nP > PMLP_MAXROWS ? 1 : 0;                    // beyond the caller's block — bbx_sync returns BBX_E_CAPACITY)
       if (p.obs) n = n < p.obs_rows ? n : p.obs_rows;
+      if constexpr (POL2 > 0) {
+        // two hidden layers: column c = 4 s + (lane >> 4) of row (lane & 15), decoded as below
+        const float* W1p = pol->wp;
+        const float* a2l = W1p + (4 * PKS + 1) * 16 * POL;
+        const float* b2l = a2l + 256 * POL * POL2;
+        const float* w3l = b2l + 16 * POL2;
+        const int lr = lane & 15, lg4 = lane >> 4;
+        float* lg = (float*)peel_lds;                        // (the update's scratch is idle here: PMLP_MAXROWS floats)
+        const int pn_ = p.nvars, pk_ = p.k;
+        for (int r0 = 0; r0 < n; r0 += 16) {
+          const int r = r0 + lr;
+          const uint32_t prw = r < n ? e.pairs[r] : 0u;
+          const Mono<W> a0 = e.lm[prw & 0xffffu], a1 = e.tm[prw & 0xffffu], c0 = e.lm[prw >> 16], c1 = e.tm[prw >> 16];
+          // (the column decode is redone per tile — behind an opaque copy of the lane group, so that it is not hoisted into PKS
+          // registers live across the tile, which is what the 128-register budget does not have at 128 units)
+          int g4 = lg4;
+          asm volatile("" : "+v"(g4));
+          float xa[PKS];
+#pragma unroll
+          for (int s = 0; s < PKS; s++) {
+            const int c = 4 * s + g4;
+            const int t = c / pn_, v = c - t * pn_, member = t / pk_, which = t - member * pk_;
+            const int cs = (c < 2 * pn_ * pk_ && which < 2) ? (v | (which << 8) | (member << 9)) : -1;
+            Mono<W> mm;
+#pragma unroll
+            for (int q = 0; q < W; q++) { const uint32_t wi = (cs & 256) ? a1.w[q] : a0.w[q], wj = (cs & 256) ? c1.w[q] : c0.w[q]; mm.w[q] = (cs & 512) ? wj : wi; }
+            xa[s] = cs < 0 ? 0.f : (float)m_exp(mm, cs & 255);
+          }
+          const float part = pmlp2_tile<POL, 0, POL2, PKS, POL>(xa, W1p, W1p + 4 * PKS * 16 * POL, nullptr, nullptr, a2l, b2l, w3l, lane, lr, lg4);
+          if (lg4 == 0 && r < n) lg[r] = part + w3l[16 * POL2];   // (+ the deciding bias, read per tile: one register fewer across it)
+        }
+        wave_sync();
+        action = pmlp_sample(lg, n, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      } else {
       const float* wp = pol->wp;
       const int plr = lane & 31, plk = lane >> 5;
       float* lg = (float*)peel_lds;                          // (the update's scratch is idle here: PMLP_MAXROWS floats)
@@ -582,6 +619,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
       }
       wave_sync();
       action = pmlp_sample(lg, n, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      }
     } else
     if (p.agent == BBX_AGENT_EXTERNAL) action = p.actions[env];
     else if (p.agent == BBX_AGENT_HASH) action = (int)bbx_agent_action32(agent_seed, (uint32_t)t_agent, (uint32_t)nP);
@@ -798,6 +836,12 @@ template <int W, int NB, int KS>
 __global__ __launch_bounds__(256, 4) void bbx_binom_policy_kernel(BbxParams p, BbxPolicy pol) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   binom_body<W, false, false, NB, KS>(p, smem, &pol);
+}
+// the same with a two-hidden-layer policy (binom_body POL2): H1 / H2 = the layers padded to 64 or 128 units, KS = pmlp2_ks_for(2 n k)
+template <int W, int H1, int H2, int KS>
+__global__ __launch_bounds__(256, 4) void bbx_binom_policy2_kernel(BbxParams p, BbxPolicy pol) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  binom_body<W, false, false, H1 / 16, KS, false, H2 / 16>(p, smem, &pol);
 }
 template <int W>
 __global__ __launch_bounds__(256) void bbx_binom_aux_kernel(BbxParams p) {

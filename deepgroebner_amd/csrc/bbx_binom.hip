@@ -16,6 +16,18 @@ static int launch_binom_w(const BbxParams* p, BbxKernel kind, int blocks, int th
       BbxParams q = *p; q.policy = nullptr; q.actions = nullptr; q.rewards = nullptr; q.dones = nullptr; q.rows = nullptr; q.obs_every_step = 0;
       const int nb = pmlp_nb_for(p->policy->hidden), ks = pmlp_ks_for(2 * p->nvars * p->k);
       const size_t lds_pol = (size_t)(threads / WAVE) * binom_scratch_bytes<W>(q.obs_rows);
+      if (p->policy->hidden2 > 0) {                        // two hidden layers (bbx_api.cpp admits k-steps 3, or 8 with 16-byte monomials)
+        const int h1 = pmlp2_hp_for(p->policy->hidden), h2 = pmlp2_hp_for(p->policy->hidden2), k2 = pmlp2_ks_for(2 * p->nvars * p->k);
+#define BBX_BPOL2(A, C, KSV) hipLaunchKernelGGL((bbx_binom_policy2_kernel<W, A, C, KSV>), dim3(blocks), dim3(threads), lds_pol, stream, q, *p->policy)
+#define BBX_BPOL2_H(KSV) do { if (h1 == 64 && h2 == 64) BBX_BPOL2(64, 64, KSV); else if (h1 == 64) BBX_BPOL2(64, 128, KSV); \
+                              else if (h2 == 64) BBX_BPOL2(128, 64, KSV); else BBX_BPOL2(128, 128, KSV); } while (0)
+        if (k2 == 3) BBX_BPOL2_H(3);
+        else if constexpr (W == 4) { if (k2 == 8) BBX_BPOL2_H(8); else return (int)hipErrorInvalidValue; }
+        else return (int)hipErrorInvalidValue;
+#undef BBX_BPOL2_H
+#undef BBX_BPOL2
+        return 0;
+      }
 #define BBX_BPOL(NBV, KSV) hipLaunchKernelGGL((bbx_binom_policy_kernel<W, NBV, KSV>), dim3(blocks), dim3(threads), lds_pol, stream, q, *p->policy)
       if (ks == 6) { if (nb == 2) BBX_BPOL(2, 6); else BBX_BPOL(4, 6); }
       else if (W == 4 && ks == 10) { if (nb == 2) BBX_BPOL(2, 10); else BBX_BPOL(4, 10); }

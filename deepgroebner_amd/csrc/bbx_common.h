@@ -139,7 +139,13 @@ struct BbxPolicy {
   // array is the [B] array of the calls, rewritten at each step (stride_out = 0), and the observation block and row
   // counts describe the state AFTER the step, as that call leaves them (post_obs = 1).  Rollouts: stride_out = B, post_obs = 0.
   int32_t stride_out, post_obs;
+  // 0: the network above.  > 0: two hidden layers (bbx_policy2_rollout_device, networks.py:562-571) of `hidden` and `hidden2`
+  // units, wp as bbx_pmlp2_prepare leaves it; rollouts only
+  int32_t hidden2;
 };
+// workgroup of the register/LDS-resident kernel of a two-layer policy rollout: 16 waves, one workgroup per CU, sharing one
+// LDS copy of the layers behind the first (fast_body POL2, bbx_fast.h)
+enum { BBX_POL2_WAVES = 16 };
 struct BbxParams {
   char* recs;
   BbxLayout L;              // layout of the records in HBM

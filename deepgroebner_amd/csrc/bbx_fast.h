@@ -164,7 +164,11 @@ __device__ __attribute__((noinline)) int f_select_ordered(const uint32_t* pairs,
 // VAL: value() rollouts (buchberger.cpp:248-252, 332-351): the discounted return of the steps taken is accumulated in
 // double, without fusing multiply and add, and written to values[] when the wave leaves.
 // NBK: capacity in units of 64 basis elements (FLay): 2 = registers only, 4 = with the overflow order in LDS.
-template <bool TRACE, bool ACCT, bool PROF = false, bool HL = false, int POL = 0, bool PERSIST = false, bool VAL = false, int NBK = (POL > 0 ? FNBK_POL : FNBK_WIDE)>
+// POL2 > 0: the policy of a POL rollout has TWO hidden layers (bbx_policy2_rollout_device): POL = the first layer's blocks of
+// 16 units, POL2 = the second's; tiles of 16 rows through the stand-alone kernel's code (pmlp2_tile, bbx_pmlp.h), the layers
+// behind the first staged in LDS once per workgroup (the launcher gives the kernel workgroups of BBX_POL2_WAVES waves).
+template <bool TRACE, bool ACCT, bool PROF = false, bool HL = false, int POL = 0, bool PERSIST = false, bool VAL = false, int NBK = (POL > 0 ? FNBK_POL : FNBK_WIDE),
+          int POL2 = 0>
 __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, int ext_action = -1) {
   typedef FLay<NBK> LY;
   constexpr int FG = LY::G, FP = LY::P, FLDS_BYTES = LY::BYTES;
@@ -179,7 +183,16 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   // per-wave regions), every tile then reads them with ds_read instead of going to L1 / L2
   typedef const __attribute__((address_space(3))) float* PolW;
   PolW pol_w = nullptr;
-  if constexpr (POL > 0) {
+  if constexpr (POL > 0 && POL2 > 0) {
+    // (two hidden layers: the permuted second-layer matrix, its biases, the deciding weights and bias — 16 POL x 16 POL2 + 32 POL2
+    // + 4 floats behind the first layer's (4 x 3 + 1) x 16 POL, 16-byte aligned; the first layer stays in memory, L1 hits)
+    constexpr int off = (4 * 3 + 1) * 16 * POL, nfl = 256 * POL * POL2 + 32 * POL2 + 4;
+    __attribute__((address_space(3))) bbx_f32x4* wl_ = (__attribute__((address_space(3))) bbx_f32x4*)(smem + (blockDim.x / WAVE) * (FLDS_BYTES + 4 * FP));
+    const bbx_f32x4* wg = (const bbx_f32x4*)(f_cold_policy()->wp + off);
+    for (int i = (int)threadIdx.x; i < nfl / 4; i += (int)blockDim.x) wl_[i] = wg[i];
+    __syncthreads();                                     // (before any wave may leave)
+    pol_w = (PolW)wl_;
+  } else if constexpr (POL > 0) {
     const int nfl = (2 * 6 + 2) * 32 * POL + 4;
     __attribute__((address_space(3))) float* wl_ = (__attribute__((address_space(3))) float*)(smem + (blockDim.x / WAVE) * (FLDS_BYTES + 4 * FP));
     const float* wg = f_cold_policy()->wp;
@@ -764,6 +777,34 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       const bool pre_obs = pol->post_obs == 0;
       if (p.obs && pre_obs) { o3_toff = (size_t)pol_tt * (size_t)pol->obs_tstride; write_obs32(); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
       if (lane == 0 && pol->rows_t && pre_obs) pol->rows_t[tb] = nP;
+      if constexpr (POL2 > 0) {
+        // two hidden layers: lane l supplies column 4 s + (l >> 4) of row l & 15 — [lm_i | tm_i | lm_j | tm_j] x (e0, e1, e2) —,
+        // the tile is the stand-alone kernel's (bbx_pmlp.h), the layers behind the first read from the workgroup's LDS copy
+        const float* W1p = pol->wp;
+        const float* a2l = (const float*)pol_w;
+        const float* b2l = a2l + 256 * POL * POL2;
+        const float* w3l = b2l + 16 * POL2;
+        const float b3 = w3l[16 * POL2];
+        const int lr = lane & 15, lg4 = lane >> 4;
+        float* lg = (float*)(lbase + FLDS_BYTES);
+        const int pn = (p.obs && nP > p.obs_rows) ? p.obs_rows : nP;   // the rows the policy sees = the rows of the block
+        for (int r0 = 0; r0 < pn; r0 += 16) {
+          const int r = r0 + lr;
+          const uint32_t prw = r < pn ? pairs[r] : 0u;
+          const M2 a0 = lm[prw & 0xffffu], a1 = tm[prw & 0xffffu], c0 = lm[prw >> 16], c1 = tm[prw >> 16];
+          float xa[3];
+#pragma unroll
+          for (int s = 0; s < 3; s++) {
+            const int c = 4 * s + lg4, m = c / 3, v = c - 3 * m;      // monomial m of the row, exponent v
+            const M2 mm = m == 0 ? a0 : m == 1 ? a1 : m == 2 ? c0 : c1;
+            xa[s] = (float)(v == 0 ? (mm.w[0] & 0xffffu) : v == 1 ? (mm.w[0] >> 16) : (mm.w[1] & 0xffffu));
+          }
+          const float part = pmlp2_tile<POL, 0, POL2, 3, POL>(xa, W1p, W1p + 4 * 3 * 16 * POL, nullptr, nullptr, a2l, b2l, w3l, lane, lr, lg4);
+          if (lg4 == 0 && r < pn) lg[r] = part + b3;
+        }
+        wave_sync();
+        action = pmlp_sample(lg, pn, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      } else {
       const PolW wp = pol_w;
       const int plr = lane & 31, plk = lane >> 5;
       float* lg = (float*)(lbase + FLDS_BYTES);
@@ -785,6 +826,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       }
       wave_sync();
       action = pmlp_sample(lg, pn, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      }
     } else
     if (agent == BBX_AGENT_HASH) action = (int)(((uint64_t)f_readlane(hv, t_agent & 63) * (uint32_t)nP) >> 32);   // bbx_agent_action32
     else if (agent == BBX_AGENT_EXTERNAL) {
@@ -1303,6 +1345,14 @@ template <int NB>
 __global__ __launch_bounds__(256, 4) void bbx_fast_policy_rollout_kernel(BbxFastPolicyParams q) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   fast_body<false, false, false, false, NB>(q.f, smem);
+}
+// policy rollout with a two-hidden-layer policy (fast_body POL2): H1 / H2 = the layers padded to 64 or 128 units.  Workgroups
+// of BBX_POL2_WAVES = 16 waves, one per CU (four per SIMD, as the one-layer kernel): one LDS copy of the second layer (64 KB
+// at 128 x 128) serves 16 environments.
+template <int H1, int H2>
+__global__ __launch_bounds__(1024, 4) void bbx_fast_policy2_rollout_kernel(BbxFastPolicyParams q) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  fast_body<false, false, false, false, H1 / 16, false, false, FNBK_POL, H2 / 16>(q.f, smem);
 }
 #ifdef BBX_PROF_BUILD
 // diagnostic build with s_memtime stamps between the phases of a step (never timed, never shipped as a result)

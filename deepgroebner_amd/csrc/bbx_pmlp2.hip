@@ -29,14 +29,8 @@
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 
-// prepared weights (floats): W1p [4 KS][HP1] | b1p [HP1] | [AM [HPM / 16][HP1 / 16][64][4]] | A2 [HP2 / 16][HPI / 16][64][4] | [bMp [HPM]] |
-// b2p [HP2] | wdp [HP2] | bd, pad          (bracketed: the optional middle hidden layer; HPI = HPM if there is one, else HP1)
-// HP = the layer padded to 64 or 128 units, KS = k-steps of four columns built in
-__host__ __device__ constexpr int pmlp2_hp_for(int hidden) { return hidden <= 64 ? 64 : 128; }
-__host__ __device__ constexpr int pmlp2_ks_for(int cols) { const int ks = (cols + 3) / 4; return ks <= 3 ? 3 : ks <= 8 ? 8 : 16; }
-__host__ __device__ constexpr int pmlp2_prepared_floats(int cols, int hp1, int hpm, int hp2) {   // (padded sizes; hpm = 0: two hidden layers)
-  return (4 * pmlp2_ks_for(cols) + 1) * hp1 + hp1 * hpm + (hpm ? hpm : hp1) * hp2 + hpm + 2 * hp2 + 4;
-}
+// (the prepared layout, pmlp2_hidden and the scoring of a tile, pmlp2_tile, live in bbx_pmlp.h: the policy rollouts inside
+// the step kernels run the same code)
 constexpr int PMLP2_WAVES = 8;
 
 // one permuted second-/third-layer matrix: element t of A[HPO / 16][HPI / 16][64][4]
@@ -66,54 +60,6 @@ __global__ void bbx_pmlp2_prepare_kernel(const float* __restrict__ w1, const flo
     else v = i == o_bd ? bd[0] : 0.f;
     out[i] = v;
   }
-}
-
-// one hidden layer behind the first: hout = relu(b + A hin) (LAST = false) or the deciding layer's dot over it (LAST = true:
-// returns this lane's share of the logit).  Two blocks of 16 units in flight, their A operands requested half a block pair ahead.
-template <int NKI, int NKO, bool LAST>
-__device__ __forceinline__ float pmlp2_hidden(const bbx_f32x4 (&hin)[NKI], bbx_f32x4* hout, const float* A, const float* bl, const float* wl,
-                                              int lane, int lg4) {
-  constexpr int HS = NKI / 2;
-  float part = 0.f;
-  auto pair = [&](int b2i) __attribute__((always_inline)) {
-    bbx_f32x4 acc0 = *(const bbx_f32x4*)(bl + 16 * b2i + 4 * lg4), acc1 = *(const bbx_f32x4*)(bl + 16 * b2i + 16 + 4 * lg4);
-    const bbx_f32x4* ap = (const bbx_f32x4*)A + (size_t)b2i * NKI * 64 + lane;
-#pragma unroll
-    for (int hf = 0; hf < 2; hf++) {
-      bbx_f32x4 av0[HS], av1[HS];
-#pragma unroll
-      for (int q = 0; q < HS; q++) { av0[q] = ap[(hf * HS + q) * 64]; av1[q] = ap[(NKI + hf * HS + q) * 64]; }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int q = 0; q < HS; q++) {
-        const bbx_f32x4 hb = hin[hf * HS + q];
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[q].x, hb.x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[q].x, hb.x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[q].y, hb.y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[q].y, hb.y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[q].z, hb.z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[q].z, hb.z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av0[q].w, hb.w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av1[q].w, hb.w, acc1, 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    acc0.x = acc0.x > 0.f ? acc0.x : 0.f; acc0.y = acc0.y > 0.f ? acc0.y : 0.f; acc0.z = acc0.z > 0.f ? acc0.z : 0.f; acc0.w = acc0.w > 0.f ? acc0.w : 0.f;
-    acc1.x = acc1.x > 0.f ? acc1.x : 0.f; acc1.y = acc1.y > 0.f ? acc1.y : 0.f; acc1.z = acc1.z > 0.f ? acc1.z : 0.f; acc1.w = acc1.w > 0.f ? acc1.w : 0.f;
-    if constexpr (LAST) {
-      const bbx_f32x4 w0 = *(const bbx_f32x4*)(wl + 16 * b2i + 4 * lg4), w1v = *(const bbx_f32x4*)(wl + 16 * b2i + 16 + 4 * lg4);
-      part = fmaf(acc0.x, w0.x, part); part = fmaf(acc0.y, w0.y, part); part = fmaf(acc0.z, w0.z, part); part = fmaf(acc0.w, w0.w, part);
-      part = fmaf(acc1.x, w1v.x, part); part = fmaf(acc1.y, w1v.y, part); part = fmaf(acc1.z, w1v.z, part); part = fmaf(acc1.w, w1v.w, part);
-    } else { hout[b2i] = acc0; hout[b2i + 1] = acc1; }
-  };
-  if constexpr (LAST) {
-#pragma clang loop unroll(disable)
-    for (int b2i = 0; b2i < NKO; b2i += 2) pair(b2i);
-  } else {
-#pragma unroll
-    for (int b2i = 0; b2i < NKO; b2i += 2) pair(b2i);
-  }
-  return part;
 }
 
 template <int HP1, int HPM, int HP2, int KS, int NWAVES>
@@ -217,34 +163,8 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
           xa[s] = k < cols ? (float)xi : 0.f;
         }
       }
-      // ---- layer 1: h[blk][v] = relu(b1 + sum_k W1[k][unit] x[row][k]), unit = 16 blk + 4 (lane >> 4) + v
-      // (the first-layer weights stay in memory: L1 hits; the base pointer is opaque per tile so that the optimiser does not
-      // hoist KS x NK1 loads out of the loops into registers the 128-register budget does not have)
-      bbx_f32x4 h[NK1];
-#pragma unroll
-      for (int j = 0; j < NK1; j++) h[j] = *(const bbx_f32x4*)(b1p + 16 * j + 4 * lg4);
-      const float* W1q = W1p + lg4 * HP1 + lr;
-      asm volatile("" : "+v"(W1q));
-#pragma unroll
-      for (int s = 0; s < KS; s++) {
-#pragma unroll
-        for (int j = 0; j < NK1; j++) h[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(W1q[4 * s * HP1 + 16 * j], xa[s], h[j], 0, 0, 0);
-        if (KS > 3 && (s & 1)) __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int j = 0; j < NK1; j++) {
-        h[j].x = h[j].x > 0.f ? h[j].x : 0.f; h[j].y = h[j].y > 0.f ? h[j].y : 0.f;
-        h[j].z = h[j].z > 0.f ? h[j].z : 0.f; h[j].w = h[j].w > 0.f ? h[j].w : 0.f;
-      }
-      // ---- the hidden layers behind the first, then the deciding layer's dot
-      float part;
-      if constexpr (HPM != 0) {
-        bbx_f32x4 hm[NKM];
-        pmlp2_hidden<NK1, NKM, false>(h, hm, aml, bml, nullptr, lane, lg4);
-        part = pmlp2_hidden<NKM, NK2, true>(hm, nullptr, a2l, b2l, w3l, lane, lg4);
-      } else part = pmlp2_hidden<NK1, NK2, true>(h, nullptr, a2l, b2l, w3l, lane, lg4);
-      part += __shfl_xor(part, 16, WAVE);                                     // the other lane groups hold the row's other units
-      part += __shfl_xor(part, 32, WAVE);
+      // ---- layer 1, the hidden layers behind it, the deciding layer's dot (bbx_pmlp.h)
+      const float part = pmlp2_tile<NK1, NKM, NK2, KS>(xa, W1p, b1p, aml, bml, a2l, b2l, w3l, lane, lr, lg4);
       if (lg4 == 0 && r0 + lr < tn) lgt[r0 + lr] = part + b3;
     }
     }

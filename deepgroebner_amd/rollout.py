@@ -10,7 +10,9 @@ device, replacing the per-step host round trip of the reference's agents.
 PyTorch is the plumbing here (device memory, autograd for training); the policy evaluation + sampling of the default
 one-hidden-layer network runs in hand-written HIP: on the matrix cores, either as a kernel of its own fed by the padded
 observation block (bbx_pmlp_act), in front of the step in the same launch (bbx_policy_step_device), or inside the step
-loop (bbx_policy_rollout_device); deeper networks take the torch path.  Actions never visit the host.
+loop (bbx_policy_rollout_device).  Two hidden layers of at most 128 units run inside the step loop too
+(bbx_policy2_rollout_device) or as a kernel of their own (bbx_pmlp2_act), three as a kernel of their own (bbx_pmlp3_act); deeper
+or wider networks take the torch path.  Actions never visit the host.
 """
 import contextlib
 import ctypes as C
@@ -151,7 +153,9 @@ class PMLPPolicy(torch.nn.Module):
     def _fused_weights(self):
         """The kernels' view of the weights (bbx_pmlp_prepare: transposed, zero-padded to the tile sizes), rebuilt only when
         a parameter changed (an optimiser step bumps the tensors' version counters): no per-step transposes, no per-step
-        host read of b2."""
+        host read of b2.  One hidden layer only: the layout has no room for a second."""
+        if len(self.embedding) != 1:
+            raise ValueError("_fused_weights: the one-layer kernels' weights of a policy with %d hidden layers (two: _deep_weights)" % len(self.embedding))
         lin = self.embedding[0]
         key = tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
         c = self.__dict__.get("_fused_cache")
@@ -280,16 +284,28 @@ class DeviceTrajectoryBuffer:
 @_with_gc_paused
 @torch.no_grad()
 def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256):
-    """run_rollout with the policy INSIDE the step kernel (bbx_policy_rollout_device): `chunk` vector steps per launch,
-    environments never wait for each other between steps.  Per-step outputs land in the trajectory buffer's own arrays
-    (no copies).  Raises BbxError (BBX_E_UNSUPPORTED) where the batch's kernel class has no built-in policy — callers
-    fall back to run_rollout.  Returns (total reward per environment, finished episodes) like run_rollout.
-    The rollout kernels are the lean ones (no algorithmic-byte accounting): the handle's accounting is switched off here."""
-    env.accounting(False)
+    """run_rollout with the policy INSIDE the step kernel: `chunk` vector steps per launch, environments never wait for each
+    other between steps.  One hidden layer: bbx_policy_rollout_device; two hidden layers of at most 128 units:
+    bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
+    depth or width raises BbxError (BBX_E_UNSUPPORTED) before anything is prepared or queued.  Per-step outputs land in the
+    trajectory buffer's own arrays (no copies).  Raises BbxError (BBX_E_UNSUPPORTED) where the batch's kernel class has no
+    built-in policy — callers fall back to run_rollout.  Returns (total reward per environment, finished episodes) like
+    run_rollout.  The rollout kernels are the lean ones (no algorithmic-byte accounting): the handle's accounting is switched
+    off here."""
     B, cols = env.batch, env.cols
+    depth = len(policy.embedding)
+    if not (depth == 1 or (depth == 2 and policy.deep_ok(cols))):
+        raise _ffi.BbxError(-5, "run_rollout_fused: policies with one hidden layer, or two of at most 128 units, run inside the step kernels "
+                                "(this one: %s); use run_rollout" % [l.out_features for l in policy.embedding])
+    env.accounting(False)
     dev = torch.device("cuda", torch.cuda.current_device())
     stream = torch.cuda.current_stream()
-    w = policy._fused_weights()
+    if depth == 1:
+        w = policy._fused_weights()
+        rollout = lambda *a: env.policy_rollout_device(w["prepared"], w["hidden"], *a)
+    else:
+        w = policy._deep_weights()
+        rollout = lambda *a: env.policy2_rollout_device(w["prepared"], w["hidden"][0], w["hidden"][1], *a)
     keep_states = buffer is not None and buffer.states is not None
     if keep_states:
         obs_rows = buffer.states.shape[2]
@@ -311,12 +327,11 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
             obs = buffer.states[t:t + n] if keep_states else obs1
             if keep_states:
                 obs.fill_(-1)                           # the kernel writes the live rows only; the rest is the reference's padding
-            env.policy_rollout_device(w["prepared"], w["hidden"], n, u, buffer.actions[t:t + n], buffer.logprobs[t:t + n], buffer.rewards[t:t + n],
-                                      buffer.dones[t:t + n], buffer.rows[t:t + n], obs, obs_rows, B * obs_rows * cols if keep_states else 0,
-                                      stream.cuda_stream)
+            rollout(n, u, buffer.actions[t:t + n], buffer.logprobs[t:t + n], buffer.rewards[t:t + n], buffer.dones[t:t + n], buffer.rows[t:t + n],
+                    obs, obs_rows, B * obs_rows * cols if keep_states else 0, stream.cuda_stream)
             buffer.t += n
         else:
-            env.policy_rollout_device(w["prepared"], w["hidden"], n, u, act, logp, None, None, None, obs1, obs_rows, 0, stream.cuda_stream)
+            rollout(n, u, act, logp, None, None, None, obs1, obs_rows, 0, stream.cuda_stream)
         env.sync()
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)

@@ -204,7 +204,8 @@ int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs
  * rows per environment.  d_w1 [cols][hidden1], d_b1 [hidden1], d_w2 [hidden1][hidden2], d_b2 [hidden2], d_w3 [hidden2],
  * d_b3 [1] (the transposed layouts of torch.nn.Linear weights; every argument on the device: preparing never reads back).
  * Stands alone in front of bbx_step_device_autoreset (two launches per vector step, both recordable into a HIP graph);
- * the fused per-step / rollout / session forms exist for one hidden layer only. */
+ * the fused per-step and session forms exist for one hidden layer only, the rollout form also for two
+ * (bbx_policy2_rollout_device). */
 int bbx_pmlp2_prepared_floats(int cols, int hidden1, int hidden2);   /* < 0: shape not supported */
 int bbx_pmlp2_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
                       int cols, int hidden1, int hidden2, float* d_prepared, void* stream);
@@ -243,6 +244,16 @@ int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, co
 int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden, int nsteps, const float* d_u, int32_t* d_actions,
                               float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
                               long long obs_step_stride, void* stream);
+/* The same with ParallelMultilayerPerceptron(hidden_layers=[hidden1, hidden2]) (networks.py:562-571: two dense layers in the
+ * embedding) choosing every action: d_prepared as bbx_pmlp2_prepare leaves it; arguments and outputs exactly those of
+ * bbx_policy_rollout_device, and the draws those of bbx_pmlp2_act in front of bbx_step_device_autoreset (the logits come from the
+ * same tile code).  Built into the binomial kernel classes (8-byte monomials with 2nk <= 12 columns, 16-byte ones with 2nk <= 32;
+ * at most 128 units per layer); other shapes and classes, accounting on, traced handles or obs_rows > BBX_POLICY_MAX_ROWS:
+ * BBX_E_UNSUPPORTED.  3 variables with k = 2 run in the register/LDS-resident kernel (workgroups of 16 waves sharing one LDS
+ * copy of the second layer), continued by the HBM-resident kernel as for one layer.  Asynchronous like bbx_rollout_device. */
+int bbx_policy2_rollout_device(bbx_batch* b, const float* d_prepared, int hidden1, int hidden2, int nsteps, const float* d_u, int32_t* d_actions,
+                               float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
+                               long long obs_step_stride, void* stream);
 /* obs_every_step != 0 materialises the observation in d_obs after every step (what a device-side policy
  * would consume), otherwise only the state at the end of the rollout is written */
 int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, double* d_rewards, uint8_t* d_dones,
