@@ -98,6 +98,8 @@ SIGNATURES = {
     "bbx_alg_sizes": (C.c_int, [_vp, _vp, _vp]),
     "bbx_alg_get": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "bbx_values_seeded": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp]),
+    "bbx_values_device": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp, _vp]),
+    "bbx_gae_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "bbx_persistent": (C.c_int, [_vp, C.c_int]),
     "bbx_join": (C.c_int, [_vp, _vp]),
     "bbx_graph_replayed": (C.c_int, [_vp, _vp]),

@@ -214,6 +214,15 @@ class VecLeadMonomialsEnv:
             _ffi.check(_ffi.lib().bbx_values_seeded(self._h, strategy.encode(), float(gamma), _ffi.ptr(s), _ffi.ptr(out)))
         return out
 
+    def values_device(self, values, strategy="degree", gamma=0.99, seeds=None, stream=0):
+        """values() without the host in the loop (bbx_values_device): float64 [batch] on the device (a tensor or an address),
+        valid after the next sync().  The states valued are those of the call's place in `stream` order; the rollouts overlap
+        whatever is queued behind it.  seeds: int64 [batch] on the device, needed by "random" only; "sample" raises
+        BbxError (BBX_E_UNSUPPORTED): use values()."""
+        def dp(x):
+            return None if x is None else C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+        _ffi.check(_ffi.lib().bbx_values_device(self._h, strategy.encode(), float(gamma), dp(seeds), dp(values), C.c_void_p(int(stream))))
+
     def copy(self):
         h = C.c_void_p()
         _ffi.check(_ffi.lib().bbx_copy(self._h, C.byref(h)))

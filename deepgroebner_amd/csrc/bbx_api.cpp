@@ -54,6 +54,10 @@ bbx_batch::~bbx_batch() {
   if (ps_stream) (void)hipStreamDestroy(ps_stream);
   if (ps_ctl_stream) (void)hipStreamDestroy(ps_ctl_stream);
   if (d_clone_idx) (void)hipFree(d_clone_idx);
+  bbx_host::value_ring_free(this);
+  if (v_stream) (void)hipStreamDestroy(v_stream);
+  if (d_vident) (void)hipFree(d_vident);
+  if (d_vwords) (void)hipFree(d_vwords);
   void* dev[] = {d_recs, d_q, d_tail, d_out, d_actions, d_mask, d_seeds, d_obs, d_trace, d_hdr,
                  d_vrecs, d_vhdr, d_vsrc, d_vseeds, d_vvals, d_stage, d_obs_off, d_obs_packed};
   for (void* q : dev) if (q) (void)hipFree(q);
@@ -398,6 +402,8 @@ int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream) {
   const size_t bytes = (size_t)b->B * NL.rec_bytes;
   size_t freeb = 0, totalb = 0;
   HIPCHK(hipStreamSynchronize(stream));
+  if (int rc = value_wait(b)) return rc;                    // (clones of queued bbx_values_device calls still read the old records;
+                                                            // their ring slots are not this scratch and stay: value_resolve needs them)
   if (b->d_vrecs) {                                         // value() scratch is sized by the old layout: rebuilt on demand
     void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};
     for (void* q : old) (void)hipFree(q);
@@ -557,7 +563,17 @@ int finish(bbx_batch* b, hipStream_t stream) {
 // error here.  quiesce() (stats, env_status, state_sizes, state_get, copy: calls that only read the records): close a running
 // session unsliced and wait for the device, but do NOT finish — the call stays in flight, and an error of it is still reported
 // by the next call that finishes it, not by a read.
-int settle(bbx_batch* b) { return b->flight.active ? finish(b, b->flight.stream) : BBX_OK; }
+// Calls queued by bbx_values_device are part of what is in flight: the host waits for them before anything that may move
+// records (finish -> grow_records), and resolves them (values of clones that waited for room, errors) behind the flight.
+int settle(bbx_batch* b) {
+  if (b->v_jobs.empty()) return b->flight.active ? finish(b, b->flight.stream) : BBX_OK;
+  if (int rc = value_wait(b)) return rc;
+  const int rc = b->flight.active ? finish(b, b->flight.stream) : BBX_OK;
+  const std::string first = rc ? g_err : std::string();
+  const int vrc = value_resolve(b);
+  if (rc) g_err = first;                                    // (the flight's error is the one reported)
+  return rc ? rc : vrc;
+}
 
 int quiesce(bbx_batch* b) {
   if (b->ps_active) { int rc = session_close(b, false, nullptr, false); if (rc) return rc; }
@@ -1344,7 +1360,7 @@ int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, doub
 int bbx_sync(bbx_batch* b) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (!b->flight.active) { HIPCHK(hipDeviceSynchronize()); return BBX_OK; }
+  if (!b->flight.active && b->v_jobs.empty()) { HIPCHK(hipDeviceSynchronize()); return BBX_OK; }
   return settle(b);
 }
 

@@ -1,7 +1,9 @@
 // libbbx.so — LeadMonomialsEnv::value (buchberger.cpp:332-351): discounted returns of full Buchberger rollouts from clones of
 // the current states (bbx_value, bbx_values, bbx_values_seeded of include/bbx.h).
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "bbx_batch.h"
@@ -111,7 +113,199 @@ int values_for(bbx_batch* b, const std::vector<int32_t>& envs, const char* strat
   return value_rollouts(b, envs, agent, nullptr, gamma, out);
 }
 
+// ---- bbx_values_device: the same rollouts without the host in the loop -------------------------------------------------
+// The clone is ordered in the caller's stream; resort, rollouts and collect run on a stream of the library's own, into one
+// of v_depth clone arrays, so that the tail of a value launch (as long as its longest remaining episode) overlaps the
+// steps queued behind the call and the next value launch.  Nothing here waits on the host side.
+
+int value_ring_ensure(bbx_batch* b) {
+  if (!b->v_stream) HIPCHK(hipStreamCreateWithFlags(&b->v_stream, hipStreamNonBlocking));   // (non-blocking: the NULL stream of the synchronous value calls does not serialise it)
+  if (!b->d_vident) {
+    HIPCHK(hipMalloc((void**)&b->d_vident, (size_t)b->B * sizeof(int32_t)));
+    HIPCHK(hipMalloc((void**)&b->d_vwords, (size_t)BBX_VALUE_MAX_JOBS * 2 * sizeof(uint32_t)));
+    HIPCHK(hipMemsetAsync(b->d_vwords, 0, (size_t)BBX_VALUE_MAX_JOBS * 2 * sizeof(uint32_t), b->v_stream));
+    int lrc = bbx_launch_value_iota(b->d_vident, b->B, b->v_stream);
+    if (lrc) return fail(BBX_E_DEVICE, "index launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  }
+  // the records were enlarged since the slots were made (no call is queued then: settle() resolved them all): made again
+  if (!b->v_ring.empty() && memcmp(&b->v_L, &b->L, sizeof(BbxLayout)) != 0 && b->v_jobs.empty()) {
+    HIPCHK(hipStreamSynchronize(b->v_stream));
+    value_ring_free(b);
+  }
+  if (b->v_ring.empty()) {
+    b->v_ring.resize((size_t)b->v_depth);
+    b->v_L = b->L;
+    for (bbx_vslot& s : b->v_ring) {
+      HIPCHK(hipMalloc((void**)&s.recs, (size_t)b->B * b->L.rec_bytes));
+      HIPCHK(hipMalloc((void**)&s.flags, (size_t)b->B));
+      HIPCHK(hipMalloc((void**)&s.seeds, (size_t)b->B * sizeof(uint32_t)));
+      HIPCHK(hipEventCreateWithFlags(&s.cloned, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+    }
+  }
+  return BBX_OK;
+}
+
+// the rollout kernels of value() on `recs` (resume: clones carried over to enlarged records continue where they stopped)
+int value_launch_rollouts(bbx_batch* b, char* recs, int n, int agent, double gamma, bool resume, hipStream_t stream) {
+  BbxParams p; fill_params(b, &p);
+  p.recs = recs; p.B = n; p.nsteps = 1 << 30; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
+  p.value_mode = 1; p.gamma = gamma; p.values = nullptr; p.trace = nullptr; p.accounting = 0;
+  p.lite = nullptr;                                           // the clones are not the batch's environments
+  const LaunchPlan pl = plan_launch(b, p, resume, true);
+  int lrc = 0;
+  for (int i = 0; i < pl.n && !lrc; i++) lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], stream);
+  if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  return BBX_OK;
+}
+
+int values_device(bbx_batch* b, int agent, double gamma, const int64_t* d_seeds, double* d_values, hipStream_t stream) {
+  if ((int)b->v_jobs.size() >= BBX_VALUE_MAX_JOBS)
+    return fail(BBX_E_UNSUPPORTED, "%d bbx_values_device calls are queued on this handle: call bbx_sync before queueing more", BBX_VALUE_MAX_JOBS);
+  // a running session owns the records on its own stream: closed first, `stream` ordered behind it (a mailbox session is
+  // host-stepped, its flight is finished the usual way)
+  if (b->ps_active) {
+    int rc = b->ps_mbox ? settle(b) : session_close(b, true, stream, false);
+    if (rc) return rc;
+  }
+  if (int rc = value_ring_ensure(b)) return rc;
+  const int n = b->B;
+  const int slot = (int)(b->v_calls % b->v_depth);
+  bbx_vslot& s = b->v_ring[(size_t)slot];
+  if (s.used) HIPCHK(hipStreamWaitEvent(stream, s.done, 0));   // the slot's previous rollouts: a device-side wait
+  else {                                                       // (first use: behind the index array and the cleared words)
+    HIPCHK(hipEventRecord(s.done, b->v_stream));
+    HIPCHK(hipStreamWaitEvent(stream, s.done, 0));
+  }
+  int lrc = 0;
+  if (d_seeds) {
+    lrc = bbx_launch_value_seeds(d_seeds, s.seeds, n, stream);
+    if (lrc) return fail(BBX_E_DEVICE, "seed launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  }
+  const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
+  lrc = bbx_launch_clone(b->d_recs, s.recs, &b->L, b->d_vident, nullptr, n, d_seeds ? s.seeds : nullptr, 0, 1, ngen, s.flags, stream);
+  if (lrc) return fail(BBX_E_DEVICE, "clone launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  HIPCHK(hipEventRecord(s.cloned, stream));
+  HIPCHK(hipStreamWaitEvent(b->v_stream, s.cloned, 0));
+  lrc = bbx_launch_value_resort(s.recs, &b->L, n, s.flags, b->v_stream);
+  if (lrc) return fail(BBX_E_DEVICE, "resort launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (int rc = value_launch_rollouts(b, s.recs, n, agent, gamma, false, b->v_stream)) return rc;
+  uint32_t* word = b->d_vwords + 2 * b->v_jobs.size();
+  lrc = bbx_launch_value_collect_device(s.recs, b->L.rec_bytes, n, d_values, word, 0, b->v_stream);
+  if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  HIPCHK(hipEventRecord(s.done, b->v_stream));
+  s.used = true;
+  b->v_jobs.push_back(bbx_vjob{slot, d_values, b->L, agent, gamma});
+  b->v_calls++;
+  return BBX_OK;
+}
+
+// One queued call whose clones did not all finish (word: what its collect folded).  Clones that wait for room are carried over
+// to records of the enlarged layout (bbx_relayout_kernel), finish there and fill the entries the collect left NaN.
+int value_carry_over(bbx_batch* b, const bbx_vjob& j, size_t jix, const uint32_t* word) {
+  const unsigned capmask = (1u << BBX_ST_G_FULL) | (1u << BBX_ST_P_FULL) | (1u << BBX_ST_ARENA_FULL) | (1u << BBX_ST_POLY_TOO_LONG);
+  unsigned bits = word[0]; int env = (int)word[1] - 1;
+  bool owner = true;                                        // a later call has reused the slot: the waiting clones are gone
+  for (size_t i = jix + 1; i < b->v_jobs.size(); i++) owner = owner && b->v_jobs[i].slot != j.slot;
+  if ((bits & ~capmask) || b->no_growth)
+    return fail(BBX_E_CAPACITY, "value rollout of environment %d did not finish: %s", env,
+                (bits & capmask) ? status_name(__builtin_ctz(bits & capmask)) : "pairs left or an environment in an error state");
+  const int n = b->B;
+  char* src = b->v_ring[(size_t)j.slot].recs; char* tmp = nullptr;
+  BbxLayout Ls = j.L;
+  uint32_t* dw = b->d_vwords + 2 * jix;
+  int rc = BBX_OK;
+  for (int attempt = 0; attempt < 40 && rc == BBX_OK; attempt++) {
+    if (Ls.rec_bytes == b->L.rec_bytes) rc = grow_records(b, bits & capmask, env, 0);   // (else: an earlier call of this wait enlarged them already)
+    if (rc) break;
+    if (!owner) {
+      rc = fail(BBX_E_CAPACITY, "value rollout of environment %d outgrew its records (%s) and %d later bbx_values_device calls reused its clone "
+                                "before the wait; the records have been enlarged, later calls have room", env,
+                status_name(__builtin_ctz(bits & capmask)), b->v_depth);
+      break;
+    }
+    char* next = nullptr;
+    if (hipMalloc((void**)&next, (size_t)n * b->L.rec_bytes) != hipSuccess) { (void)hipGetLastError(); rc = fail(BBX_E_CAPACITY, "no room for the clones of enlarged records"); break; }
+    int lrc = bbx_launch_relayout(src, next, &Ls, &b->L, n, 0);
+    if (tmp) { (void)hipStreamSynchronize(0); (void)hipFree(tmp); }
+    tmp = next; src = next; Ls = b->L;
+    if (lrc) { rc = fail(BBX_E_DEVICE, "relayout launch failed: %s", hipGetErrorString((hipError_t)lrc)); break; }
+    if ((rc = value_launch_rollouts(b, tmp, n, j.agent, j.gamma, true, 0))) break;
+    uint32_t w[2] = {0, 0};
+    if (hipMemsetAsync(dw, 0, sizeof w, 0) != hipSuccess ||
+        bbx_launch_value_collect_device(tmp, b->L.rec_bytes, n, j.d_values, dw, 1, 0) != 0 ||
+        hipMemcpy(w, dw, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(BBX_E_DEVICE, "collect of carried-over clones failed"); break; }
+    bits = w[0]; env = (int)w[1] - 1;
+    if (!bits) break;
+    if (bits & ~capmask) rc = fail(BBX_E_CAPACITY, "value rollout of environment %d did not finish: pairs left", env);
+    else if (attempt == 39) rc = fail(BBX_E_CAPACITY, "value rollouts kept outgrowing the records");
+  }
+  if (tmp) { (void)hipStreamSynchronize(0); (void)hipFree(tmp); }
+  return rc;
+}
+
 }  // namespace
+
+int bbx_value_ring_from_env() {
+  const char* s = getenv("BBX_VALUE_RING");
+  const int d = s && *s ? atoi(s) : BBX_VALUE_RING_DEFAULT;
+  return d < 1 ? 1 : (d > 16 ? 16 : d);
+}
+
+namespace bbx_host {
+int value_wait(bbx_batch* b) {
+  if (!b->v_jobs.empty()) HIPCHK(hipStreamSynchronize(b->v_stream));   // (it waited for every clone: the caller's streams are done with the records too)
+  return BBX_OK;
+}
+
+int value_resolve(bbx_batch* b) {
+  if (b->v_jobs.empty()) return BBX_OK;
+  const size_t nj = b->v_jobs.size();
+  std::vector<uint32_t> w(2 * nj);
+  int err = BBX_OK; std::string msg;
+  if (hipMemcpy(w.data(), b->d_vwords, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) err = fail(BBX_E_DEVICE, "reading the value words failed");
+  else for (size_t i = 0; i < nj; i++) {
+    if (!w[2 * i]) continue;
+    const int rc = value_carry_over(b, b->v_jobs[i], i, &w[2 * i]);   // (every call is served; the first error is the one reported)
+    if (rc && !err) { err = rc; msg = bbx_last_error(); }
+  }
+  b->v_jobs.clear();
+  (void)hipMemsetAsync(b->d_vwords, 0, 2 * nj * sizeof(uint32_t), b->v_stream);
+  if (err && !msg.empty()) return fail(err, "%s", msg.c_str());
+  return err;
+}
+
+void value_ring_free(bbx_batch* b) {
+  for (bbx_vslot& s : b->v_ring) {
+    void* dev[] = {s.recs, s.flags, s.seeds};
+    for (void* q : dev) if (q) (void)hipFree(q);
+    if (s.cloned) (void)hipEventDestroy(s.cloned);
+    if (s.done) (void)hipEventDestroy(s.done);
+  }
+  b->v_ring.clear();
+}
+}  // namespace bbx_host
+
+extern "C" int bbx_values_device(bbx_batch* b, const char* strategy, double gamma, const int64_t* d_seeds, double* d_values, void* stream) {
+  if (!b || !strategy || !d_values) return fail(BBX_E_ARG, "bad arguments");
+  if (!strcmp(strategy, "sample")) return fail(BBX_E_UNSUPPORTED, "\"sample\" (101 rollouts per environment) has no asynchronous form: use bbx_values");
+  const int agent = agent_of_strategy(strategy);
+  if (agent == BBX_AGENT_STDRANDOM && !d_seeds) return fail(BBX_E_ARG, "\"random\" needs d_seeds (the handle's own seed stream lives on the host: bbx_values)");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (stream != nullptr && hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+  if (cap != hipStreamCaptureStatusNone) return fail(BBX_E_UNSUPPORTED, "bbx_values_device cannot be captured into a graph (its clone ring is host bookkeeping)");
+  return values_device(b, agent, gamma, agent == BBX_AGENT_STDRANDOM ? d_seeds : nullptr, d_values, (hipStream_t)stream);
+}
+
+extern "C" int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
+                              double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream) {
+  if (!d_rewards || !d_values || !d_dones || !d_returns || !d_advantages || !d_complete || nsteps < 0 || batch < 0) return fail(BBX_E_ARG, "bad arguments");
+  if (nsteps == 0 || batch == 0) return BBX_OK;
+  const int lrc = bbx_launch_gae(d_rewards, d_values, d_dones, nsteps, batch, gam, gam * lam, d_returns, d_advantages, d_complete, (hipStream_t)stream);
+  if (lrc) return fail(BBX_E_DEVICE, "GAE launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  return BBX_OK;
+}
 
 extern "C" int bbx_value(bbx_batch* b, int idx, const char* strategy, double gamma, double* out) {
   if (!b || !strategy || !out || idx < 0 || idx >= b->B) return fail(BBX_E_ARG, "bad arguments");

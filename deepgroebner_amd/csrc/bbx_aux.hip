@@ -192,6 +192,80 @@ extern "C" int bbx_launch_value_collect(const char* recs, uint32_t rec_bytes, in
   return (int)hipGetLastError();
 }
 
+// ---- bbx_values_device: the asynchronous form (bbx_api_value.cpp) -------------------------------------------------------
+// slot k of a clone array <- environment k (the identity source indices of the clone kernel)
+__global__ void bbx_value_iota_kernel(int32_t* idx, int n) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) idx[k] = k;
+}
+extern "C" int bbx_launch_value_iota(int32_t* idx, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_value_iota_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, idx, n);
+  return (int)hipGetLastError();
+}
+// "random": seed -> engine state of std::default_random_engine::seed(s), minstd_state_of_seed of bbx_api_value.cpp on the
+// device (the int seed converts to the unsigned result type first; x = s mod 2^31 - 1, and 0 becomes 1)
+__global__ void bbx_value_seeds_kernel(const int64_t* seeds, uint32_t* states, int n) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t x = (uint32_t)((uint64_t)seeds[k] % 2147483647ull);
+  states[k] = x ? x : 1u;
+}
+extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_value_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, seeds, states, n);
+  return (int)hipGetLastError();
+}
+// per clone: its discounted return into the caller's array, NaN where the rollout did not run to the end; "did not finish"
+// is folded into the job's word pair the host reads at the next wait: word[0] |= 1 << status for a clone that waits for
+// room (bbx_st_capacity), bit 31 for anything else; word[1] = 1 + the largest such environment index.
+// only_nan != 0 (the carry-over of waiting clones after the records were enlarged): entries that already hold a value stay.
+__global__ void bbx_value_collect_device_kernel(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  if (only_nan && values[k] == values[k]) return;
+  const BbxHdr* h = (const BbxHdr*)(recs + (size_t)k * rec_bytes);
+  const int st = h->status;
+  const bool finished = st == BBX_ST_OK && h->nP == 0;
+  values[k] = finished ? h->vret : __builtin_nan("");
+  if (!finished) {
+    atomicOr(&word[0], bbx_st_capacity(st) ? 1u << st : 1u << 31);
+    atomicMax(&word[1], (uint32_t)k + 1u);
+  }
+}
+extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_value_collect_device_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, values, word, only_nan);
+  return (int)hipGetLastError();
+}
+
+// ---- GAE over a [T][B] trajectory block (DeviceTrajectoryBuffer.finish(), pg.py:20-76 per trajectory) -------------------
+// One thread per environment, reverse scan over t; consecutive threads read consecutive elements of every row.  The
+// arithmetic is the torch loop's, operation for operation: every product is rounded before it is added (no fused
+// multiply-add: contraction is off in the kernel body), gl = gam * lam was formed once in double by the caller.
+__global__ void bbx_gae_kernel(const double* __restrict__ rewards, const double* __restrict__ values, const uint8_t* __restrict__ dones,
+                               int T, int B, double gam, double gl, double* __restrict__ returns, double* __restrict__ advantages,
+                               uint8_t* __restrict__ complete) {
+#pragma clang fp contract(off)                              // (the default contracts a * b + c into one rounding; __dmul_rn / __dadd_rn are
+                                                            // inline * and + that carry the default with them, so plain operators under this)
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B) return;
+  double nret = 0.0, nadv = 0.0, nval = 0.0;
+  uint8_t comp = 0;
+#pragma unroll 8                                            // (the loads of a row do not depend on the row above: issued ahead of the chain)
+  for (int t = T - 1; t >= 0; t--) {
+    const size_t i = (size_t)t * B + e;
+    if (dones[i]) { nret = 0.0; nadv = 0.0; nval = 0.0; comp = 1; }   // step t ends its episode: nothing follows it
+    const double r = rewards[i], v = values[i];
+    const double ret = r + gam * nret;
+    const double adv = ((r - v) + gam * nval) + gl * nadv;
+    returns[i] = ret; advantages[i] = adv; complete[i] = comp;
+    nret = ret; nadv = adv; nval = v;
+  }
+}
+extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
+                              double* returns, double* advantages, uint8_t* complete, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_gae_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, returns, advantages, complete);
+  return (int)hipGetLastError();
+}
+
 // enlarged records (bbx_api.cpp grow_records): every environment's live state moves from its record in the old layout to
 // its record in the new one; an environment that was waiting for room (bbx_st_capacity) is released
 template <int W>

@@ -18,6 +18,11 @@ extern "C" int bbx_launch_clone(const char* src_recs, char* dst_recs, const BbxL
                                 const uint32_t* seeds, int keep_counters, int seed_std, int ngen, uint8_t* flags, hipStream_t stream);
 extern "C" int bbx_launch_value_resort(char* recs, const BbxLayout* L, int n, const uint8_t* flags, hipStream_t stream);
 extern "C" int bbx_launch_value_collect(const char* recs, uint32_t rec_bytes, int n, double* out2, hipStream_t stream);
+extern "C" int bbx_launch_value_iota(int32_t* idx, int n, hipStream_t stream);
+extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, int n, hipStream_t stream);
+extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream);
+extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
+                              double* returns, double* advantages, uint8_t* complete, hipStream_t stream);
 extern "C" int bbx_launch_relayout(const char* src_recs, char* dst_recs, const BbxLayout* Ls, const BbxLayout* Ld, int B, hipStream_t stream);
 extern "C" int bbx_launch_ctl(unsigned long long* ctl, unsigned long long value, hipStream_t stream);
 extern "C" int bbx_launch_gather_lite(const char* recs, uint32_t rec_bytes, int B, void* out, hipStream_t stream);
@@ -45,6 +50,24 @@ struct bbx_flight {
   bool poll = false;                  // its kernel signals completion through the pinned status words (enqueue -> read_lite)
   int async_chain = 0;                // asynchronous steps with caller-supplied actions queued since the last wait
 };
+
+// bbx_values_device (bbx_api_value.cpp): a ring of clone arrays, so that the rollouts of consecutive calls overlap each other
+// and the steps that follow; a slot is reused behind a device-side wait for `done`.
+struct bbx_vslot {
+  char* recs = nullptr;               // [B] records in the layout of the batch when the slot was made
+  uint8_t* flags = nullptr;           // clone flags (bbx_clone_kernel)
+  uint32_t* seeds = nullptr;          // engine states of "random" rollouts
+  hipEvent_t cloned = nullptr;        // the clone has run (the caller's stream) — what the rollouts wait for
+  hipEvent_t done = nullptr;          // the collect has run (the library's stream) — what the next clone into the slot waits for
+  bool used = false;                  // `done` has been recorded at least once
+};
+// One queued call: resolved by the next settle() (value_resolve)
+struct bbx_vjob {
+  int slot; double* d_values; BbxLayout L; int agent; double gamma;
+};
+constexpr int BBX_VALUE_RING_DEFAULT = 2;   // measured: 2, 4 and 8 are equal, 1 is 8 % slower
+constexpr int BBX_VALUE_MAX_JOBS = 8192;    // calls between two waits (a word pair each)
+int bbx_value_ring_from_env();        // BBX_VALUE_RING, clamped to 1..16
 
 struct bbx_gen {
   std::unique_ptr<bbx::IdealGen> g;
@@ -114,6 +137,14 @@ struct bbx_batch : bbx_config {
   // scratch for value(): cloned records, their headers, source indices, agent seeds, results
   char* d_vrecs = nullptr; BbxHdr* d_vhdr = nullptr; int32_t* d_vsrc = nullptr; uint32_t* d_vseeds = nullptr; double* d_vvals = nullptr;
   int vcap = 0;
+  // bbx_values_device: the ring (depth read from BBX_VALUE_RING when the handle is made), the stream its rollouts run on,
+  // the identity source indices, a word pair per queued call, and the calls queued since the last wait
+  int v_depth = bbx_value_ring_from_env();
+  std::vector<bbx_vslot> v_ring; BbxLayout v_L{};
+  hipStream_t v_stream = nullptr;
+  int32_t* d_vident = nullptr; uint32_t* d_vwords = nullptr;
+  std::vector<bbx_vjob> v_jobs;
+  long long v_calls = 0;              // calls so far (slot = v_calls % v_depth)
   // HIP-event timing of the step-kernel launches (bbx_timing)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_open;
@@ -192,6 +223,12 @@ const char* status_name(int s);
 // bbx_api.cpp
 int fill_queues(bbx_batch* b, int min_avail = 1, hipStream_t stream = 0);
 int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream);   // the kernels of one logical launch
+// bbx_api_value.cpp: the calls bbx_values_device queued — value_wait: the host waits for their device work (before anything
+// moves or frees records); value_resolve: after that, read their words, carry waiting clones over to enlarged records,
+// report; value_ring_free: the ring's memory (the device must be idle)
+int value_wait(bbx_batch* b);
+int value_resolve(bbx_batch* b);
+void value_ring_free(bbx_batch* b);
 // bbx_api_session.cpp
 int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external = false, bool device_async = false);
 void start_flight(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external, bool device_async);

@@ -6,6 +6,8 @@ device, replacing the per-step host round trip of the reference's agents.
     DeviceTrajectoryBuffer     TrajectoryBuffer (store/finish/get)    pg.py:79-240
     run_rollout                PGAgent.run_episode(s)                 pg.py:451-503   (one library call per vector step)
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
+    run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
+                               (bbx_values_device: written on the device beside the steps); finish(): one GAE kernel
 
 PyTorch is the plumbing here (device memory, autograd for training); the policy evaluation + sampling of the default
 one-hidden-layer network runs in hand-written HIP: on the matrix cores, either as a kernel of its own fed by the padded
@@ -224,7 +226,23 @@ class DeviceTrajectoryBuffer:
 
     def finish(self):
         """Reverse scan over time with episode boundaries: ret_t = r_t + gam ret_{t+1}; delta_t = r_t - v_t + gam v_{t+1};
-        adv_t = delta_t + gam lam adv_{t+1}; nothing crosses a done flag (pg.py:20-76 per trajectory)."""
+        adv_t = delta_t + gam lam adv_{t+1}; nothing crosses a done flag (pg.py:20-76 per trajectory).  Tensors on the GPU:
+        one kernel (bbx_gae_device, one thread per environment); on the CPU: the torch loop (_finish_torch), whose results
+        the kernel reproduces bit for bit."""
+        T = self.t
+        r, v, d = self.rewards[:T], self.values[:T], self.dones[:T]
+        if not r.is_cuda:
+            return self._finish_torch()
+        ret = torch.empty_like(r); adv = torch.empty_like(r); comp = torch.empty_like(d)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(r.device):
+            _ffi.check(_ffi.lib().bbx_gae_device(p(r), p(v), p(d), T, self.B, float(self.gam), float(self.lam), p(ret), p(adv), p(comp),
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.returns, self.advantages, self.complete = ret, adv, comp
+        return ret, adv, comp
+
+    def _finish_torch(self):
+        """finish() with torch ops, about ten launches per step: CPU tensors, and the reference of the kernel."""
         T = self.t
         r, v, d = self.rewards[:T], self.values[:T], self.dones[:T]
         ret = torch.zeros_like(r); adv = torch.zeros_like(r); comp = torch.zeros_like(d)
@@ -289,7 +307,9 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
     bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
     depth or width raises BbxError (BBX_E_UNSUPPORTED) before anything is prepared or queued.  Per-step outputs land in the
     trajectory buffer's own arrays (no copies).  Raises BbxError (BBX_E_UNSUPPORTED) where the batch's kernel class has no
-    built-in policy — callers fall back to run_rollout.  Returns (total reward per environment, finished episodes) like
+    built-in policy — callers fall back to run_rollout.  There is no value_strategy here (run_rollout has it): baseline
+    values inside the T-step policy kernels would need a rollout to completion nested in the kernels' step loop — a different
+    piece of work.  Returns (total reward per environment, finished episodes) like
     run_rollout.  The rollout kernels are the lean ones (no algorithmic-byte accounting): the handle's accounting is switched
     off here."""
     B, cols = env.batch, env.cols
@@ -341,7 +361,8 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
 
 @_with_gc_paused
 @torch.no_grad()
-def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, sync_every=64, graph=False):
+def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, sync_every=64, graph=False,
+                value_strategy=None, value_gamma=None):
     """nsteps vector steps of `env` (a VecLeadMonomialsEnv already reset) under `policy`, everything on the device
     (obs_rows: rows of the observation block per environment — a pair set with more rows makes env.sync() raise
     BBX_E_CAPACITY, it is never cut silently; 256 is what the register/LDS-resident class holds):
@@ -351,7 +372,18 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     finished episodes int64 [B]).
     graph=True (policies without a fused kernel, i.e. more than one hidden layer; no buffer): the vector step — the
     policy's torch ops and the step kernels — is recorded once into a HIP graph (kept on `env`) and replayed, one graph
-    launch per step instead of ~25 kernel launches from Python; same draws, same results."""
+    launch per step instead of ~25 kernel launches from Python; same draws, same results.
+    value_strategy (with a buffer): buffer.values[t] receives env.value(value_strategy, value_gamma) of the state the policy is
+    about to see at step t (pg.py:451-475 with --value_model: value, then action, then step; after an auto-reset it is the
+    new episode's first state), written on the device by env.values_device straight into the buffer's row, its rollouts
+    overlapping the steps that follow; value_gamma defaults to buffer.gam.  No extra host wait.  None: no values, call for call
+    what it was.  With graph=True: ValueError."""
+    if value_strategy is not None and graph:
+        raise ValueError("run_rollout: value_strategy cannot be recorded into a graph (bbx_values_device keeps host bookkeeping)")
+    if value_strategy is not None and buffer is None:
+        raise ValueError("run_rollout: value_strategy needs a buffer to write the values to")
+    if value_strategy is not None and value_gamma is None:
+        value_gamma = buffer.gam
     B, cols = env.batch, env.cols
     dev = torch.device("cuda", torch.cuda.current_device())
     one_call = len(policy.embedding) == 1 and policy.fused_ok(cols, policy.embedding[0].out_features) and hasattr(env, "policy_step_device")
@@ -378,6 +410,8 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
                 if keep_states:
                     buffer.states[t].copy_(obs)
                 buffer.rows[t].copy_(rows)
+                if value_strategy is not None:          # value, then action, then step (pg.py:461-465)
+                    env.values_device(buffer.values[t], value_strategy, value_gamma, None, stream.cuda_stream)
             if one_call:                                # policy + step: one library call (one kernel where the class has it)
                 env.policy_step_device(w["prepared"], w["hidden"], u_all[i], act, logp, rew, done, rows, obs, obs_rows, 2, stream.cuda_stream)   # (2: incremental padding)
             else:

@@ -254,6 +254,34 @@ int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden,
 int bbx_policy2_rollout_device(bbx_batch* b, const float* d_prepared, int hidden1, int hidden2, int nsteps, const float* d_u, int32_t* d_actions,
                                float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
                                long long obs_step_stride, void* stream);
+/* value() of every environment (bbx_values) on caller-owned device memory, asynchronous: d_values[batch]
+ * (double) is valid after the next bbx_sync.  d_seeds: int64 [batch] on the device, needed by "random" only.
+ * The baseline of the reference's training loop (pg.py:451-475 with --value_model degree: env.value('degree', gamma) before every
+ * step; buchberger.cpp:332-351) without the host in the loop.  The doubles are those of bbx_values_seeded for the same states,
+ * bit for bit ("random": seed -> engine state on the device, as std::default_random_engine::seed; d_seeds == NULL with "random":
+ * BBX_E_ARG; "sample": BBX_E_UNSUPPORTED, use bbx_values; unknown names select First).
+ * The states valued are those of this call's place in `stream` order: behind every *_device call queued before it on that
+ * stream, before any queued after it; environments, generator streams, bbx_stats and bbx_kernels_launched are untouched.
+ * Only the clone is ordered in `stream`: the rollouts run on a stream of the library's own, in one of BBX_VALUE_RING clone
+ * arrays (default 2, read when the handle is created; each costs batch x record bytes of device memory; 1 = no overlap), so
+ * they overlap the steps queued behind the call and each other.  A slot is reused behind a device-side wait; the host never
+ * waits here.  Any number of calls (at most 8192) may be queued between two bbx_sync, interleaved with the other *_device calls.
+ * An environment that sits out a chain of asynchronous steps (bbx_step_device above) is valued in the state it stopped in:
+ * bbx_sync returns that chain's error, and its values of the chain are not to be used.
+ * A clone that runs out of room stops with its partial return; bbx_sync (or any call that settles the handle) enlarges the
+ * records, carries the waiting clones over, finishes them and writes their values — nothing to see, same doubles — as long as
+ * no later call has reused its slot (more than BBX_VALUE_RING calls behind it before the wait: BBX_E_CAPACITY naming the
+ * environment, NaN in its entry, records enlarged for later calls).  With bbx_caps.no_growth: BBX_E_CAPACITY and NaN.  Never a
+ * silently wrong value.  A running persistent session is closed first (device-side); a mailbox session is finished.  While
+ * `stream` is capturing: BBX_E_UNSUPPORTED (the ring is host bookkeeping). */
+int bbx_values_device(bbx_batch* b, const char* strategy, double gamma, const int64_t* d_seeds,
+                      double* d_values, void* stream);
+/* GAE over a [nsteps][batch] trajectory block: what DeviceTrajectoryBuffer.finish() computes (pg.py:20-76 per trajectory, episodes
+ * end where d_dones is set).  ret = r + gam*nret; adv = ((r - v) + gam*nval) + (gam*lam)*nadv, every product rounded before it
+ * is added; d_complete[t] = an episode ends at or after t.  One kernel, one thread per environment; needs no handle;
+ * asynchronous on `stream`. */
+int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
+                   double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream);
 /* obs_every_step != 0 materialises the observation in d_obs after every step (what a device-side policy
  * would consume), otherwise only the state at the end of the rollout is written */
 int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, double* d_rewards, uint8_t* d_dones,

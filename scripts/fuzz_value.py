@@ -1,10 +1,12 @@
 """Randomised parity sweep of value() and copy() (test infrastructure, GPU box): environments stepped to a random point of
 an episode with random actions; value(strategy, gamma) of every environment (device rollouts from clones) equals the CPU
-restatement's double for the deterministic strategies; a copy taken there and the original then continue identically, and
+restatement's double for the deterministic strategies, and the asynchronous call (values_device + sync) returns the same
+doubles as the host one; a copy taken there and the original then continue identically, and
 in-batch clones behave like their sources.      python scripts/fuzz_value.py [ROUNDS] [SEED]"""
 import os, sys, random, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+import torch
 from deepgroebner_amd import VecLeadMonomialsEnv
 from oracle import ffi
 
@@ -46,6 +48,11 @@ for it in range(rounds):
         for strategy in rng.sample(["first", "degree", "normal", "sugar"], 2):
             gamma = rng.choice([0.99, 0.9, 1.0, 0.5])
             got = env.values(strategy, gamma)
+            dev = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")   # the asynchronous call next to the host one
+            env.values_device(dev, strategy, gamma, None, torch.cuda.current_stream().cuda_stream)
+            env.sync()
+            if dev.cpu().numpy().tolist() != got.tolist():
+                print("MISMATCH %s: values_device(%s, %s) %r values %r" % (tag, strategy, gamma, dev.cpu().numpy().tolist(), got.tolist())); sys.exit(1)
             for e in range(B):
                 want = oracles[e].value(strategy, gamma)
                 if got[e] != want:
