@@ -509,13 +509,13 @@ class PolyLists:
         npolys = np.array([len(L) for L in lists], dtype=np.int32)
         nterms = np.array([len(f) for L in lists for f in L], dtype=np.int32)
         coefs = np.array([int(c) for L in lists for f in L for c, _ in f], dtype=np.int32)
-        exps = np.zeros((max(len(coefs), 1), NV), dtype=np.int32)
-        r = 0
-        for L in lists:
-            for f in L:
-                for _, e in f:
-                    exps[r, :len(e)] = e
-                    r += 1
+        rows = [e for L in lists for f in L for _, e in f]
+        if rows and all(len(e) == NV for e in rows):
+            exps = np.asarray(rows, dtype=np.int32).reshape(len(rows), NV)
+        else:
+            exps = np.zeros((max(len(coefs), 1), NV), dtype=np.int32)
+            for r, e in enumerate(rows):
+                exps[r, :len(e)] = e
         _ffi.check(_ffi.lib().bbx_alg_create(int(device), self.n, _ffi.ptr(npolys), _ffi.ptr(nterms), _ffi.ptr(coefs), _ffi.ptr(exps), C.byref(self._h)))
 
     @classmethod
@@ -569,18 +569,31 @@ class PolyLists:
     def interreduce(self):
         _ffi.check(_ffi.lib().bbx_alg_interreduce(self._h))
 
-    def get(self, k):
-        """List k as term lists (exponent tuples of all 8 slots)."""
+    def sizes(self):
+        """(number of polynomials, terms held) of every list: two int32 [n] arrays."""
         sizes = np.zeros(self.n, dtype=np.int32); tot = np.zeros(self.n, dtype=np.int32)
         _ffi.check(_ffi.lib().bbx_alg_sizes(self._h, _ffi.ptr(sizes), _ffi.ptr(tot)))
+        return sizes, tot
+
+    def get(self, k):
+        """List k as term lists (exponent tuples of all 8 slots)."""
+        sizes, tot = self.sizes()
         nterms = np.zeros(max(int(sizes[k]), 1), dtype=np.int32)
         coefs = np.zeros(max(int(tot[k]), 1), dtype=np.int32); exps = np.zeros((max(int(tot[k]), 1), NV), dtype=np.int32)
         _ffi.check(_ffi.lib().bbx_alg_get(self._h, int(k), _ffi.ptr(nterms), _ffi.ptr(coefs), _ffi.ptr(exps), None))
         out, at = [], 0
+        cl, el = coefs.tolist(), exps.tolist()
         for g in range(int(sizes[k])):
-            out.append([(int(coefs[at + t]), tuple(int(x) for x in exps[at + t])) for t in range(int(nterms[g]))])
+            out.append([(cl[at + t], tuple(el[at + t])) for t in range(int(nterms[g]))])
             at += int(nterms[g])
         return out
+
+    def sugars(self, k):
+        """The sugar degree of every polynomial of list k (Polynomial::sugar())."""
+        sizes, _ = self.sizes()
+        sug = np.zeros(max(int(sizes[k]), 1), dtype=np.int32)
+        _ffi.check(_ffi.lib().bbx_alg_get(self._h, int(k), None, None, None, _ffi.ptr(sug)))
+        return [int(s) for s in sug[:int(sizes[k])]]
 
 
 def _nv(*polys):

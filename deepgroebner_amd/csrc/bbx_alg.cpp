@@ -105,6 +105,9 @@ int run(bbx_alg* a, int op, int elim, const int32_t* args4, int32_t* steps) {
       const int st = out[(size_t)k * 4];
       if (st == 0) continue;
       if (bbx_st_capacity(st)) { need |= 1u << st; continue; }
+      // the other lists of this launch (and of the attempts before it) have appended their results on the device: the mirror
+      // follows them, or sizes / get / the index checks of the next call would describe the lists as they were before
+      (void)refresh_headers(a);
       return fail(st == BBX_ST_BAD_ACTION ? BBX_E_ARG : BBX_E_CAPACITY, "list %d: the operation failed (status %d)", k, st);
     }
     if (!need) {
@@ -113,12 +116,13 @@ int run(bbx_alg* a, int op, int elim, const int32_t* args4, int32_t* steps) {
       return refresh_headers(a);
     }
     int rc = grow(a, need);
-    if (rc) return rc;
+    if (rc) { (void)refresh_headers(a); return rc; }      // (lists that had room have their results: see above)
     if (rebuilds) {                                      // (the new lists of the others went with the old second array: all again)
       std::fill(out.begin(), out.end(), -1);
       HIPCHK(hipMemcpy(a->d_out, out.data(), out.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   }
+  (void)refresh_headers(a);
   return fail(BBX_E_CAPACITY, "the operation kept outgrowing the records");
 }
 

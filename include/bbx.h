@@ -392,7 +392,10 @@ int bbx_format_ideal(int npolys, const int32_t* nterms, const int32_t* coefs, co
  *   - binop / reduce APPEND their result to every list (G.push_back): read it back with bbx_alg_sizes + bbx_alg_get;
  *   - update treats the LAST element of every list as f and the elements before it as G, and rewrites the pair sets;
  *   - minimalize / interreduce REPLACE every list by the result.
- * Records grow on demand.  GF(32003), grevlex, up to 8 variables, polynomials of at most 65535 terms. */
+ * Records grow on demand.  GF(32003), grevlex, up to 8 variables, polynomials of at most 65535 terms, degrees and sugars of at
+ * most 65535.  A call that one list makes fail (a result beyond those limits: BBX_E_CAPACITY) leaves THAT list as it was;
+ * the other lists of a binop / reduce may already hold their results — bbx_alg_sizes / bbx_alg_get report every list as it
+ * is on the device, and the handle stays usable. */
 typedef struct bbx_alg bbx_alg;
 int bbx_alg_create(int device, int nlists, const int32_t* npolys, const int32_t* nterms, const int32_t* coefs, const int32_t* exps, bbx_alg** out);
 void bbx_alg_destroy(bbx_alg* a);

@@ -1136,6 +1136,7 @@ void bo_pl_add(void* pl, int nterms, const int* coef, const int* exps) {
 int bo_pl_nterms(void* pl, int i) { return PL(pl)->p[i].n; }
 int bo_pl_sugar(void* pl, int i) { return PL(pl)->p[i].sug; }
 void bo_pl_get(void* pl, int i, int* coef, int* exps) { poly_to_flat(&PL(pl)->p[i], coef, exps); }
+void bo_pl_copy(void* pl, int i, void* out) { pv_push(PL(out), poly_clone(&PL(pl)->p[i])); }
 
 int bo_coef_norm(int a) { return coef_norm(a); }
 int bo_coef_add(int a, int b) { return coef_add(coef_norm(a), coef_norm(b)); }

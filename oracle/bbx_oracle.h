@@ -30,6 +30,7 @@ void  bo_pl_add(void* pl, int nterms, const int* coef, const int* exps); /* Poly
 int   bo_pl_nterms(void* pl, int i);
 int   bo_pl_sugar(void* pl, int i);
 void  bo_pl_get(void* pl, int i, int* coef, int* exps);
+void  bo_pl_copy(void* pl, int i, void* out);                            /* out.push_back(pl[i]): terms and sugar as they are */
 
 /* ---- GF(32003) and monomials ------------------------------------------- */
 int bo_coef_norm(int a);

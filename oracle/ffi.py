@@ -76,6 +76,7 @@ def _sig(lib, pre):
     f("bench_random", C.c_double, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
       C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong))
     if pre == "bo":
+        f("pl_copy", None, _vp, C.c_int, _vp)
         f("env_last_step_bytes", C.c_longlong, _vp)
         f("stat_max_terms", C.c_int, C.c_int)
         f("run_random", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
@@ -93,6 +94,8 @@ def _ia(a):
 
 def pad_exps(exps):
     """[[e0,e1,..],..] with <=8 entries per monomial -> int32 [n, 8]."""
+    if len(exps) and all(len(e) == NV for e in exps):
+        return np.asarray(exps, dtype=np.int32).reshape(len(exps), NV)
     out = np.zeros((len(exps), NV), dtype=np.int32)
     for r, e in enumerate(exps):
         out[r, :len(e)] = e
@@ -130,7 +133,7 @@ class PolyList:
         coef = np.zeros(max(n, 1), dtype=np.int32)
         exps = np.zeros((max(n, 1), NV), dtype=np.int32)
         self.lib.fn("pl_get")(self.h, i, coef.ctypes.data_as(_ip), exps.ctypes.data_as(_ip))
-        return [(int(coef[k]), tuple(int(x) for x in exps[k])) for k in range(n)]
+        return [(c, tuple(e)) for c, e in zip(coef[:n].tolist(), exps[:n].tolist())]
 
     def all(self):
         return [self.get(i) for i in range(len(self))]

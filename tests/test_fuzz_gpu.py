@@ -22,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ("fuzz_policy.py", 60, 307, {}),
     ("fuzz_strategies.py", 150, 308, {}),
     ("fuzz_sessions.py", 300, 309, {}),                        # persistent sessions against a twin without them
+    ("fuzz_algebra.py", 150, 310, {}),                         # PolyLists (bbx_alg_*) against a mirrored oracle list
 ])
 def test_fuzz_slice(script, rounds, seed, env):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", script), str(rounds), str(seed)], cwd=ROOT,
