@@ -292,12 +292,11 @@ extern "C" int bbx_launch_alg_from_envs(const char* src_recs, const BbxLayout* L
 
 extern "C" int bbx_launch_alg(const AlgParams* p, hipStream_t stream) {
   const int waves = 4, blocks = (p->n + waves - 1) / waves;
-#define BBX_ALG_LAUNCH(WW) do { \
-    const size_t lds = (size_t)waves * merge_lds_bytes<WW>(); \
-    hipError_t err_ = hipFuncSetAttribute((const void*)bbx_alg_kernel<WW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (err_ != hipSuccess) return (int)err_; \
-    hipLaunchKernelGGL((bbx_alg_kernel<WW>), dim3(blocks), dim3(waves * WAVE), lds, stream, *p); } while (0)
-  if (p->L.W == 2) BBX_ALG_LAUNCH(2); else if (p->L.W == 4) BBX_ALG_LAUNCH(4); else BBX_ALG_LAUNCH(8);
-#undef BBX_ALG_LAUNCH
+  const int W = (int)p->L.W;
+  const size_t lds = (size_t)waves * (W == 2 ? merge_lds_bytes<2>() : W == 4 ? merge_lds_bytes<4>() : merge_lds_bytes<8>());
+  const int rc = W == 2 ? launch_lds<bbx_alg_kernel<2>>(blocks, waves * WAVE, lds, stream, *p)
+               : W == 4 ? launch_lds<bbx_alg_kernel<4>>(blocks, waves * WAVE, lds, stream, *p)
+                        : launch_lds<bbx_alg_kernel<8>>(blocks, waves * WAVE, lds, stream, *p);
+  if (rc) return rc;
   return (int)hipGetLastError();
 }

@@ -9,8 +9,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <unordered_map>
 #include <random>
 #include <string>
 #include <vector>
@@ -34,12 +32,6 @@ int bbx_host::fail(int code, const char* fmt, ...) {
 }
 namespace {
 using bbx_host::fail; using bbx_host::make_layout; using bbx_host::make_layout_binom;
-
-struct OutBuf {            // one contiguous device block so a step needs a single D2H copy
-  double* rewards; int32_t* rows; uint8_t* dones;
-  size_t bytes;
-};
-
 }  // namespace
 
 bbx_batch::~bbx_batch() {
@@ -247,7 +239,8 @@ LaunchPlan plan_launch(const bbx_batch* b, const BbxParams& p0, bool resume, boo
   pl.poll = !value && !resume && pl.n == 1 && pl.kind[0] == BBX_K_FAST && outputs_pinned(b) && !b->timing && b->poll_misses < 3;
   BbxParams p = p0;
   p.done_seq = 0;
-  if (pl.wide_tail) { p.wide_done = b->d_wide_done; p.wide_ncu = b->ncu; }
+  p.wide_ncu = b->ncu;                                      // (the wide launcher's one-workgroup-per-CU decision; the kernels read it in a tail launch only)
+  if (pl.wide_tail) p.wide_done = b->d_wide_done;
   for (int i = 0; i < pl.n; i++) {
     if (resume || i > 0) { p.set_budget = 0; p.pass = 1; }
     p.spill_terms = b->cls == BbxClass::GENERAL_TO_WIDE && pl.kind[i] == BBX_K_HBM ? 384 : 0;   // (hand long polynomials to the wide kernel)
@@ -330,7 +323,6 @@ int alloc_io(bbx_batch* b, int batch) {
   }
   memset(b->h_io, 0, b->io_bytes);
   HIPCHK(hipHostMalloc((void**)&b->h_act, (size_t)batch * sizeof(int32_t), hipHostMallocDefault));
-  memset(b->h_io, 0, b->io_bytes);
   // (host-stepped batches of up to 64 environments: B = 16 / 32 / 64 step in 24 / 28 / 32 us this way, 49 / 59 / 63 us with device
   // buffers and copy calls — scripts/exp_small_batch.py)
   b->zero_copy = batch <= 64;
@@ -624,7 +616,7 @@ int create_common(std::unique_ptr<bbx::IdealGen> proto, int nvars_obs, int elimi
 
   auto b = std::make_unique<bbx_batch>();
   b->B = batch; b->device = device; b->k = k;
-  { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) b->ncu = cus; }
+  { DeviceInfo di{}; if (device_info(device, &di) == hipSuccess) b->ncu = di.cus; }
   b->elim = elimination; b->rewards = rewards; b->sort_input = sort_input ? 1 : 0; b->sort_reducers = sort_reducers ? 1 : 0;
   b->fixed = proto->fixed();
   b->listed = list != nullptr;
@@ -747,6 +739,19 @@ int create_common(std::unique_ptr<bbx::IdealGen> proto, int nvars_obs, int elimi
   HIPCHK(hipDeviceSynchronize());
   *out = b.release();
   return BBX_OK;
+}
+
+// one asynchronous step on caller buffers (bbx_step_device[_autoreset]; the second launch of an unfused bbx_policy_step_device)
+int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
+                int32_t* d_obs, int obs_rows, int obs_fill, void* stream, int auto_reset) {
+  if (!b || !d_actions) return fail(BBX_E_ARG, "null argument");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  if (d_obs && obs_rows < 1) return fail(BBX_E_ARG, "obs_rows must be positive");
+  BbxParams p; fill_params(b, &p);
+  p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset; p.actions = d_actions;
+  p.rewards = d_rewards; p.dones = d_dones; p.rows = d_rows; p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill;
+  if (!traced(b)) p.trace = nullptr;
+  return launch(b, p, (hipStream_t)stream, d_obs != nullptr, true);
 }
 
 }  // namespace bbx_host
@@ -1121,18 +1126,6 @@ int bbx_rollout(bbx_batch* b, int agent, int nsteps, int auto_reset, double* rew
   return copy_out(b, rewards, dones, rows);
 }
 
-static int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
-                       int32_t* d_obs, int obs_rows, int obs_fill, void* stream, int auto_reset) {
-  if (!b || !d_actions) return fail(BBX_E_ARG, "null argument");
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (d_obs && obs_rows < 1) return fail(BBX_E_ARG, "obs_rows must be positive");
-  BbxParams p; fill_params(b, &p);
-  p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset; p.actions = d_actions;
-  p.rewards = d_rewards; p.dones = d_dones; p.rows = d_rows; p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill;
-  if (!traced(b)) p.trace = nullptr;
-  return launch(b, p, (hipStream_t)stream, d_obs != nullptr, true);
-}
-
 int bbx_step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
                     int32_t* d_obs, int obs_rows, int obs_fill, void* stream) {
   return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 0);
@@ -1140,208 +1133,6 @@ int bbx_step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, u
 int bbx_step_device_autoreset(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
                               int32_t* d_obs, int obs_rows, int obs_fill, void* stream) {
   return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 1);
-}
-
-// prepared-weights geometry: the same constexpr rules as bbx_pmlp.h (k-steps 3 / 6 / 10 / 16 / 32, unit blocks 1 / 2 / 4 / 8)
-static int pmlp_ks(int cols) { const int ks = (cols + 1) / 2; return ks <= 3 ? 3 : ks <= 6 ? 6 : ks <= 10 ? 10 : ks <= 16 ? 16 : 32; }
-static int pmlp_nb(int hidden) { const int nb = (hidden + 31) / 32; return nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8; }
-
-int bbx_pmlp_prepared_floats(int cols, int hidden) {
-  if (cols < 1 || cols > 64 || hidden < 1 || hidden > 256) return fail(BBX_E_UNSUPPORTED, "policy shape %d x %d is not built into the policy kernel", cols, hidden);
-  return (2 * pmlp_ks(cols) + 2) * 32 * pmlp_nb(hidden) + 4;
-}
-
-int bbx_pmlp_prepare(const float* d_w1, const float* d_b1, const float* d_w2, float b2, int cols, int hidden, float* d_prepared, void* stream) {
-  if (!d_w1 || !d_b1 || !d_w2 || !d_prepared) return fail(BBX_E_ARG, "null argument");
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  int lrc = bbx_launch_pmlp_prepare(d_w1, d_b1, d_w2, b2, cols, hidden, d_prepared, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
-int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
-                 const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  if (!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs) return fail(BBX_E_ARG, "null argument");
-  if (batch < 1 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
-  if (obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  int lrc = bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
-// ---- two and three hidden layers (bbx_pmlp2.hip; hm = 0: no middle layer)
-extern "C" int bbx_pmlp2_floats(int cols, int h1, int hm, int h2);
-extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
-                                        const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
-extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
-                                    const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream);
-
-static int pmlp_deep_floats(int cols, int h1, int hm, int h2, bool three) {
-  if (cols < 1 || cols > 64 || h1 < 1 || h1 > 128 || h2 < 1 || h2 > 128 || (three && (hm < 1 || hm > 128)))
-    return three ? fail(BBX_E_UNSUPPORTED, "policy shape %d x %d x %d x %d is not built into the three-layer policy kernel", cols, h1, hm, h2)
-                 : fail(BBX_E_UNSUPPORTED, "policy shape %d x %d x %d is not built into the two-layer policy kernel", cols, h1, h2);
-  return bbx_pmlp2_floats(cols, h1, three ? hm : 0, h2);
-}
-static int pmlp_deep_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int h1, int hm, int h2,
-                         bool three, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  if (!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs) return fail(BBX_E_ARG, "null argument");
-  if (batch < 1 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
-  if (obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
-  if (pmlp_deep_floats(cols, h1, hm, h2, three) < 0) return BBX_E_UNSUPPORTED;
-  int dev = 0, cus = 0, max_lds = 0;
-  HIPCHK(hipGetDevice(&dev));
-  {
-    // per device, asked once (this sits on the per-step path of a policy rollout).  gfx950 has 160 KB of LDS per workgroup, whatever
-    // hipDeviceAttributeMaxSharedMemoryPerBlock says (64 KB: the limit without the per-function attribute); the library is built
-    // for that part only, so that figure is the floor for it and for nothing else
-    static std::mutex mu; static int c_cus[64], c_lds[64]; static bool c_have[64];
-    std::lock_guard<std::mutex> g(mu);
-    const int d = dev & 63;
-    if (!c_have[d]) {
-      HIPCHK(hipDeviceGetAttribute(&c_cus[d], hipDeviceAttributeMultiprocessorCount, dev));
-      HIPCHK(hipDeviceGetAttribute(&c_lds[d], hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, dev));
-      if (strncmp(prop.gcnArchName, "gfx950", 6) == 0 && c_lds[d] < 163840) c_lds[d] = 163840;
-      c_have[d] = true;
-    }
-    cus = c_cus[d]; max_lds = c_lds[d];
-  }
-  int lrc = bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, cus, max_lds,
-                                 (hipStream_t)stream);
-  if (lrc == (int)hipErrorInvalidValue)
-    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, max_lds);
-  if (lrc) return fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
-int bbx_pmlp2_prepared_floats(int cols, int hidden1, int hidden2) { return pmlp_deep_floats(cols, hidden1, 0, hidden2, false); }
-
-int bbx_pmlp2_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
-                      int cols, int hidden1, int hidden2, float* d_prepared, void* stream) {
-  if (!d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_w3 || !d_b3 || !d_prepared) return fail(BBX_E_ARG, "null argument");
-  if (bbx_pmlp2_prepared_floats(cols, hidden1, hidden2) < 0) return BBX_E_UNSUPPORTED;
-  int lrc = bbx_launch_pmlp2_prepare(d_w1, d_b1, nullptr, nullptr, d_w2, d_b2, d_w3, d_b3, cols, hidden1, 0, hidden2, d_prepared, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
-int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
-                  const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, d_u, d_actions, d_logprobs, stream);
-}
-
-int bbx_pmlp3_prepared_floats(int cols, int hidden1, int hidden2, int hidden3) { return pmlp_deep_floats(cols, hidden1, hidden2, hidden3, true); }
-
-int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
-                      const float* d_w4, const float* d_b4, int cols, int hidden1, int hidden2, int hidden3, float* d_prepared, void* stream) {
-  if (!d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_w3 || !d_b3 || !d_w4 || !d_b4 || !d_prepared) return fail(BBX_E_ARG, "null argument");
-  if (bbx_pmlp3_prepared_floats(cols, hidden1, hidden2, hidden3) < 0) return BBX_E_UNSUPPORTED;
-  int lrc = bbx_launch_pmlp2_prepare(d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_w4, d_b4, cols, hidden1, hidden2, hidden3, d_prepared, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
-int bbx_pmlp3_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
-                  int hidden3, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, hidden2, hidden3, true, d_u, d_actions, d_logprobs, stream);
-}
-
-int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, const float* d_u, int32_t* d_actions, float* d_logprobs,
-                           double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows, int obs_fill, void* stream) {
-  if (!b || !d_prepared || !d_u || !d_actions || !d_logprobs || !d_rows || !d_obs) return fail(BBX_E_ARG, "null argument");
-  if (obs_rows < 1) return fail(BBX_E_ARG, "obs_rows must be positive");
-  if (obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  const int cols = 2 * b->nvars * b->k;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  // one launch for policy + step where the step kernel has the policy built in (the register/LDS-resident class, lean
-  // variant, 33..128 hidden units, at most 12 columns); everywhere else the two launches it replaces
-  if (!(lean_fast(b) && (pmlp_nb(hidden) == 2 || pmlp_nb(hidden) == 4) && cols <= 12)) {
-    int rc = bbx_pmlp_act(d_obs, d_rows, b->B, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream);
-    if (rc) return rc;
-    return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 1);
-  }
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  if (b->ps_enabled && b->nvars == 3 && b->k == 2 && b->device_gen) {
-    // persistent sessions: the call joins (or begins) a session whose kernel has the policy inside its step loop — the
-    // uniforms of consecutive calls must then be consecutive [B] slices of one array (what a rollout loop that draws its
-    // random numbers a chunk of steps at a time passes), every other argument the same from call to call
-    BbxPolicy spol{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, 0, 0, 1};
-    BbxParams sp; fill_params(b, &sp);
-    sp.nsteps = 1; sp.set_budget = 1; sp.agent = BBX_AGENT_EXTERNAL; sp.auto_reset = 1;
-    sp.obs = d_obs; sp.obs_rows = obs_rows; sp.obs_fill = obs_fill; sp.trace = nullptr;
-    sp.policy = &spol;
-    return launch(b, sp, (hipStream_t)stream, true, true);
-  }
-  BbxPolicy pol{d_prepared, hidden, d_u, d_actions, d_logprobs, 0, nullptr, nullptr, nullptr, 0, 0, 0};
-  BbxParams p; fill_params(b, &p);
-  p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1; p.actions = d_actions;   // (the follow-up pass reads them)
-  p.rewards = d_rewards; p.dones = d_dones; p.rows = d_rows; p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill;
-  p.trace = nullptr;
-  p.policy = &pol;
-  return launch(b, p, (hipStream_t)stream, true, true);
-}
-
-int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden, int nsteps, const float* d_u, int32_t* d_actions,
-                              float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
-                              long long obs_step_stride, void* stream) {
-  if (!b || !d_prepared || !d_u || !d_actions || !d_logprobs) return fail(BBX_E_ARG, "null argument");
-  if (nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0) return fail(BBX_E_ARG, "bad rollout arguments");
-  if (d_obs && obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
-  const int cols = 2 * b->nvars * b->k;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  // where the policy is built into the step kernels: binomial classes with 8- or 16-byte monomials, 33..128 hidden units,
-  // observation widths whose prepared weights have 6 k-steps (or 10 with 16-byte monomials)
-  const int ks = pmlp_ks(cols);
-  if (!b->binom || (b->W != 2 && b->W != 4) || (pmlp_nb(hidden) != 2 && pmlp_nb(hidden) != 4) || !(ks == 6 || (b->W == 4 && ks == 10)))
-    return fail(BBX_E_UNSUPPORTED, "policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 20 with "
-                                   "more than 3 variables; 33..128 hidden units); drive this batch with bbx_policy_step_device");
-  if (b->accounting) return fail(BBX_E_UNSUPPORTED, "policy rollouts run the lean kernel: call bbx_accounting(b, 0) first");
-  if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
-  if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  BbxPolicy pol{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0};
-  BbxParams p; fill_params(b, &p);
-  p.nsteps = nsteps; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
-  p.obs = d_obs; p.obs_rows = d_obs ? obs_rows : 0; p.obs_fill = 0;   // (no block: the kernels size their logits for every row they score)
-  p.trace = nullptr;
-  p.policy = &pol;
-  // the register/LDS-resident kernel has the policy for 3 variables and k = 2; every other admitted shape runs in the
-  // HBM-resident binomial kernel from the start
-  pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;
-  return launch(b, p, (hipStream_t)stream, true, true);   // (rows the policy could not score — more than the block or the kernel holds — are an error)
-}
-
-// two hidden layers inside the step loop (ParallelMultilayerPerceptron([h1, h2]), networks.py:562-571): the same call with the
-// weights bbx_pmlp2_prepare leaves; the same admission as the one-layer call, for the k-step counts the kernels are built for
-static int pmlp2_ks(int cols) { const int ks = (cols + 3) / 4; return ks <= 3 ? 3 : ks <= 8 ? 8 : 16; }
-int bbx_policy2_rollout_device(bbx_batch* b, const float* d_prepared, int hidden1, int hidden2, int nsteps, const float* d_u, int32_t* d_actions,
-                               float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
-                               long long obs_step_stride, void* stream) {
-  if (!b || !d_prepared || !d_u || !d_actions || !d_logprobs) return fail(BBX_E_ARG, "null argument");
-  if (nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0) return fail(BBX_E_ARG, "bad rollout arguments");
-  if (d_obs && obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
-  const int cols = 2 * b->nvars * b->k;
-  if (bbx_pmlp2_prepared_floats(cols, hidden1, hidden2) < 0) return BBX_E_UNSUPPORTED;
-  // built into the binomial kernel classes: 8-byte monomials with <= 12 columns (3 k-steps of four), 16-byte ones with <= 32
-  const int ks = pmlp2_ks(cols);
-  if (!b->binom || !((b->W == 2 && ks == 3) || (b->W == 4 && (ks == 3 || ks == 8))))
-    return fail(BBX_E_UNSUPPORTED, "two-layer policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 32 with "
-                                   "more than 3 variables; <= 128 units per layer); drive this batch with bbx_pmlp2_act and bbx_step_device_autoreset");
-  if (b->accounting) return fail(BBX_E_UNSUPPORTED, "policy rollouts run the lean kernel: call bbx_accounting(b, 0) first");
-  if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
-  if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  BbxPolicy pol{d_prepared, hidden1, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0, hidden2};
-  BbxParams p; fill_params(b, &p);
-  p.nsteps = nsteps; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
-  p.obs = d_obs; p.obs_rows = d_obs ? obs_rows : 0; p.obs_fill = 0;
-  p.trace = nullptr;
-  p.policy = &pol;
-  pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;   // (as bbx_policy_rollout_device)
-  return launch(b, p, (hipStream_t)stream, true, true);
 }
 
 int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, double* d_rewards, uint8_t* d_dones,

@@ -1,0 +1,175 @@
+// libbbx.so — the PMLP policy calls of include/bbx.h: prepared weights, the stand-alone act kernels (one, two and three hidden
+// layers), policy + step in one call, and policy rollouts inside the step kernels.  Which shapes the kernels are built for is
+// stated once, in bbx_pmlp_shape.h: a call is admitted here by the predicates the launchers pick an instantiation with.
+#include "bbx_batch.h"
+#include "bbx_pmlp_shape.h"
+
+using namespace bbx_host;
+
+namespace {
+
+// what every policy call refuses first: a null argument, arguments out of range (the call's own text), a block taller than
+// the kernels score (obs_rows: 0 where the call has none)
+int refuse_args(bool null_arg, bool bad, const char* bad_text, int obs_rows) {
+  if (null_arg) return fail(BBX_E_ARG, "null argument");
+  if (bad) return fail(BBX_E_ARG, "%s", bad_text);
+  if (obs_rows > BBX_POLICY_MAX_ROWS) return fail(BBX_E_UNSUPPORTED, "the policy kernels score at most %d rows per environment (obs_rows = %d)", BBX_POLICY_MAX_ROWS, obs_rows);
+  return BBX_OK;
+}
+
+int launched(int lrc) { return lrc ? fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc)) : BBX_OK; }
+
+int pmlp_deep_floats(int cols, int h1, int hm, int h2, bool three) {
+  if (cols < 1 || cols > 64 || h1 < 1 || h1 > 128 || h2 < 1 || h2 > 128 || (three && (hm < 1 || hm > 128)))
+    return three ? fail(BBX_E_UNSUPPORTED, "policy shape %d x %d x %d x %d is not built into the three-layer policy kernel", cols, h1, hm, h2)
+                 : fail(BBX_E_UNSUPPORTED, "policy shape %d x %d x %d is not built into the two-layer policy kernel", cols, h1, h2);
+  const Pmlp2Pads pd = pmlp2_pads(h1, three ? hm : 0, h2);
+  return pmlp2_prepared_floats(cols, pd.hp1, pd.hpm, pd.hp2);
+}
+
+int pmlp_deep_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int h1, int hm, int h2,
+                  bool three, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
+  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (pmlp_deep_floats(cols, h1, hm, h2, three) < 0) return BBX_E_UNSUPPORTED;
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));   // (cached: this sits on the per-step path of a policy rollout)
+  int lrc = bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, di.cus, di.max_lds, (hipStream_t)stream);
+  if (lrc == (int)hipErrorInvalidValue)
+    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, di.max_lds);
+  return launched(lrc);
+}
+
+// A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
+int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
+                   int nsteps, const float* d_u, int32_t* d_actions, float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
+                   int32_t* d_obs, int obs_rows, long long obs_step_stride, void* stream) {
+  if (int rc = refuse_args(!b || !d_prepared || !d_u || !d_actions || !d_logprobs, nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0,
+                           "bad rollout arguments", d_obs ? obs_rows : 0)) return rc;
+  const int cols = 2 * b->nvars * b->k;
+  if (int rc = admit(b, cols, hidden, hidden2)) return rc;
+  if (b->accounting) return fail(BBX_E_UNSUPPORTED, "policy rollouts run the lean kernel: call bbx_accounting(b, 0) first");
+  if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
+  if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  BbxPolicy pol{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0, hidden2};
+  BbxParams p; fill_params(b, &p);
+  p.nsteps = nsteps; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
+  p.obs = d_obs; p.obs_rows = d_obs ? obs_rows : 0; p.obs_fill = 0;   // (no block: the kernels size their logits for every row they score)
+  p.trace = nullptr; p.policy = &pol;
+  // the register/LDS-resident kernel has the policy for 3 variables and k = 2; every other admitted shape runs in the
+  // HBM-resident binomial kernel from the start
+  pol.rollout = (lean_fast(b) && b->nvars == 3 && b->k == 2) ? 1 : 2;
+  return launch(b, p, (hipStream_t)stream, true, true);   // (rows the policy could not score — more than the block or the kernel holds — are an error)
+}
+
+// the shape tests: the prepared-weights range, then whether the step kernels of this batch have the policy (bbx_pmlp_shape.h)
+int admit_rollout(const bbx_batch* b, int cols, int hidden, int) {
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  if (!b->binom || !pmlp_step_has(b->W, cols, hidden))
+    return fail(BBX_E_UNSUPPORTED, "policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 20 with "
+                                   "more than 3 variables; 33..128 hidden units); drive this batch with bbx_policy_step_device");
+  return BBX_OK;
+}
+int admit_rollout2(const bbx_batch* b, int cols, int hidden1, int hidden2) {
+  if (bbx_pmlp2_prepared_floats(cols, hidden1, hidden2) < 0) return BBX_E_UNSUPPORTED;
+  if (!b->binom || !pmlp2_step_has(b->W, cols, hidden1, hidden2))
+    return fail(BBX_E_UNSUPPORTED, "two-layer policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 32 with "
+                                   "more than 3 variables; <= 128 units per layer); drive this batch with bbx_pmlp2_act and bbx_step_device_autoreset");
+  return BBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bbx_pmlp_prepared_floats(int cols, int hidden) {
+  if (cols < 1 || cols > 64 || hidden < 1 || hidden > 256) return fail(BBX_E_UNSUPPORTED, "policy shape %d x %d is not built into the policy kernel", cols, hidden);
+  return pmlp_prepared_floats(cols, hidden);
+}
+
+int bbx_pmlp_prepare(const float* d_w1, const float* d_b1, const float* d_w2, float b2, int cols, int hidden, float* d_prepared, void* stream) {
+  if (!d_w1 || !d_b1 || !d_w2 || !d_prepared) return fail(BBX_E_ARG, "null argument");
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_prepare(d_w1, d_b1, d_w2, b2, cols, hidden, d_prepared, (hipStream_t)stream));
+}
+
+int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
+                 const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
+  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, (hipStream_t)stream));
+}
+
+// ---- two and three hidden layers (bbx_pmlp2.hip)
+int bbx_pmlp2_prepared_floats(int cols, int hidden1, int hidden2) { return pmlp_deep_floats(cols, hidden1, 0, hidden2, false); }
+int bbx_pmlp3_prepared_floats(int cols, int hidden1, int hidden2, int hidden3) { return pmlp_deep_floats(cols, hidden1, hidden2, hidden3, true); }
+
+int bbx_pmlp2_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
+                      int cols, int hidden1, int hidden2, float* d_prepared, void* stream) {
+  if (!d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_w3 || !d_b3 || !d_prepared) return fail(BBX_E_ARG, "null argument");
+  if (bbx_pmlp2_prepared_floats(cols, hidden1, hidden2) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp2_prepare(d_w1, d_b1, nullptr, nullptr, d_w2, d_b2, d_w3, d_b3, cols, hidden1, 0, hidden2, d_prepared, (hipStream_t)stream));
+}
+
+int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                  const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
+  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, d_u, d_actions, d_logprobs, stream);
+}
+
+int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,
+                      const float* d_w4, const float* d_b4, int cols, int hidden1, int hidden2, int hidden3, float* d_prepared, void* stream) {
+  if (!d_w1 || !d_b1 || !d_w2 || !d_b2 || !d_w3 || !d_b3 || !d_w4 || !d_b4 || !d_prepared) return fail(BBX_E_ARG, "null argument");
+  if (bbx_pmlp3_prepared_floats(cols, hidden1, hidden2, hidden3) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp2_prepare(d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_w4, d_b4, cols, hidden1, hidden2, hidden3, d_prepared, (hipStream_t)stream));
+}
+
+int bbx_pmlp3_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                  int hidden3, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
+  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, hidden2, hidden3, true, d_u, d_actions, d_logprobs, stream);
+}
+
+int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, const float* d_u, int32_t* d_actions, float* d_logprobs,
+                           double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows, int obs_fill, void* stream) {
+  if (int rc = refuse_args(!b || !d_prepared || !d_u || !d_actions || !d_logprobs || !d_rows || !d_obs, obs_rows < 1, "obs_rows must be positive", obs_rows)) return rc;
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  const int cols = 2 * b->nvars * b->k;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  // one launch for policy + step where the step kernel has the policy built in (the register/LDS-resident class, lean
+  // variant, 33..128 hidden units, at most 12 columns); everywhere else the two launches it replaces
+  if (!(lean_fast(b) && pmlp_fused_step_has(cols, hidden))) {
+    int rc = bbx_pmlp_act(d_obs, d_rows, b->B, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream);
+    if (rc) return rc;
+    return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 1);
+  }
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  // persistent sessions: the call joins (or begins) a session whose kernel has the policy inside its step loop — the
+  // uniforms of consecutive calls must then be consecutive [B] slices of one array (what a rollout loop that draws its
+  // random numbers a chunk of steps at a time passes), every other argument the same from call to call
+  const bool session = b->ps_enabled && b->nvars == 3 && b->k == 2 && b->device_gen;
+  BbxPolicy pol = session ? BbxPolicy{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, 0, 0, 1}
+                          : BbxPolicy{d_prepared, hidden, d_u, d_actions, d_logprobs, 0, nullptr, nullptr, nullptr, 0, 0, 0};
+  BbxParams p; fill_params(b, &p);
+  p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
+  p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill; p.trace = nullptr;
+  if (!session) { p.actions = d_actions; p.rewards = d_rewards; p.dones = d_dones; p.rows = d_rows; }   // (actions: the follow-up pass reads them)
+  p.policy = &pol;
+  return launch(b, p, (hipStream_t)stream, true, true);
+}
+
+int bbx_policy_rollout_device(bbx_batch* b, const float* d_prepared, int hidden, int nsteps, const float* d_u, int32_t* d_actions,
+                              float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
+                              long long obs_step_stride, void* stream) {
+  return policy_rollout(b, d_prepared, hidden, 0, admit_rollout, nsteps, d_u, d_actions, d_logprobs, d_rewards, d_dones, d_rows, d_obs, obs_rows,
+                        obs_step_stride, stream);
+}
+
+// two hidden layers inside the step loop (ParallelMultilayerPerceptron([h1, h2]), networks.py:562-571): the same call with the
+// weights bbx_pmlp2_prepare leaves
+int bbx_policy2_rollout_device(bbx_batch* b, const float* d_prepared, int hidden1, int hidden2, int nsteps, const float* d_u, int32_t* d_actions,
+                               float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
+                               long long obs_step_stride, void* stream) {
+  return policy_rollout(b, d_prepared, hidden1, hidden2, admit_rollout2, nsteps, d_u, d_actions, d_logprobs, d_rewards, d_dones, d_rows, d_obs, obs_rows,
+                        obs_step_stride, stream);
+}
+
+}  // extern "C"

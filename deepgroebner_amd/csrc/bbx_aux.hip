@@ -360,7 +360,7 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
 extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_block, hipStream_t stream) {
   const int threads = envs_per_block * WAVE;
   const int blocks = (p->B + envs_per_block - 1) / envs_per_block;
-  if (kind == BBX_K_FAST) { bbx_launch_fast(p, blocks, threads, envs_per_block, stream); return (int)hipGetLastError(); }
+  if (kind == BBX_K_FAST) { const int rc = bbx_launch_fast(p, blocks, threads, envs_per_block, stream); return rc ? rc : (int)hipGetLastError(); }
   if (kind == BBX_K_WIDE) {
     if (p->L.W != 2 && p->L.W != 4 && p->L.W != 8) return (int)hipErrorInvalidValue;
     return bbx_launch_wide(p, envs_per_block, stream);

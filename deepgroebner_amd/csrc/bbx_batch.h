@@ -1,6 +1,7 @@
 // The batch handle of libbbx's C ABI and the internals its translation units share (bbx_api.cpp: creation, kernels of a
 // launch, waits, stepping; bbx_api_session.cpp: what a call becomes — persistent / mailbox sessions, recorded steps;
-// bbx_api_value.cpp: value(); bbx_api_state.cpp: introspection, generators, text format).
+// bbx_api_value.cpp: value(); bbx_api_policy.cpp: the PMLP policy calls — prepare, act, policy step, policy rollouts;
+// bbx_api_state.cpp: introspection, generators, text format).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,6 +35,10 @@ extern "C" int bbx_launch_mark_reset(char* recs, uint32_t rec_bytes, int B, cons
 extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const float* w2, float b2, int cols, int hidden, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
+                                        const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
+                                    const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
 
 
 // The call in flight: what finish() waits for, continues and reports on.  Formed in two places only — start_flight() (a
@@ -223,6 +228,8 @@ const char* status_name(int s);
 // bbx_api.cpp
 int fill_queues(bbx_batch* b, int min_avail = 1, hipStream_t stream = 0);
 int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream);   // the kernels of one logical launch
+int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,
+                int obs_fill, void* stream, int auto_reset);   // bbx_step_device[_autoreset]
 // bbx_api_value.cpp: the calls bbx_values_device queued — value_wait: the host waits for their device work (before anything
 // moves or frees records); value_resolve: after that, read their words, carry waiting clones over to enlarged records,
 // report; value_ring_free: the ring's memory (the device must be idle)

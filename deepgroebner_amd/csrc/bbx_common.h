@@ -31,6 +31,11 @@
 #define BBX_P 32003u
 #define BBX_POLICY_MAX_ROWS 2048    /* rows (pairs) per environment the policy kernels score: their logits live in LDS */
 #define BBX_MAXVARS 8
+#ifdef __HIPCC__                    /* functions the host side and the kernels share */
+#define BBX_HD __host__ __device__
+#else
+#define BBX_HD
+#endif
 
 // per-environment status (sticky except STARVED)
 enum {
@@ -56,11 +61,7 @@ enum {
 // started: nothing persistent is modified before its last capacity check), the host enlarges the record layout
 // (bbx_api.cpp grow_records) and the environment continues.  A launch that finds an environment waiting like that adds
 // its steps to the environment's budget instead of replacing it, so no step is lost across asynchronous launches.
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-int bbx_st_capacity(int st) { return st == BBX_ST_G_FULL || st == BBX_ST_P_FULL || st == BBX_ST_ARENA_FULL || st == BBX_ST_POLY_TOO_LONG; }
+static inline BBX_HD int bbx_st_capacity(int st) { return st == BBX_ST_G_FULL || st == BBX_ST_P_FULL || st == BBX_ST_ARENA_FULL || st == BBX_ST_POLY_TOO_LONG; }
 
 // the status word of the `lite` block ({status, q_head, budget, |P|} per environment, polled by the host after a
 // launch) carries this flag on top of the status code: BbxHdr.obs_trunc != 0
@@ -224,29 +225,17 @@ enum BbxKernel { BBX_K_HBM = 0, BBX_K_STAGED = 1, BBX_K_AUX = 2, BBX_K_FAST = 3,
 #define BBX_GEN_MAXDEG 63
 
 // position-keyed commutative hash used for parity traces (same definition in oracle/trace.py)
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-uint64_t bbx_mix64(uint64_t idx, uint32_t word) {
+static inline BBX_HD uint64_t bbx_mix64(uint64_t idx, uint32_t word) {
   uint64_t z = ((idx << 32) | (uint64_t)word) + 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
 // counter-based action hash of the built-in random agent (same in oracle/ffi.py, oracle/*.c*)
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-uint32_t bbx_agent_hash32(uint32_t seed, uint32_t t) {
+static inline BBX_HD uint32_t bbx_agent_hash32(uint32_t seed, uint32_t t) {
   return (uint32_t)(bbx_mix64((uint64_t)seed, t) >> 32);
 }
 // the row the built-in random agent picks among `rows`: multiply-shift range reduction (one mul_hi on the device)
-static inline
-#ifdef __HIPCC__
-__host__ __device__
-#endif
-uint32_t bbx_agent_action32(uint32_t seed, uint32_t t, uint32_t rows) {
+static inline BBX_HD uint32_t bbx_agent_action32(uint32_t seed, uint32_t t, uint32_t rows) {
   return (uint32_t)(((uint64_t)bbx_agent_hash32(seed, t) * rows) >> 32);
 }

@@ -1,5 +1,4 @@
 // Hand-tuned register/LDS-resident kernel of the headline class (bbx_fast.h): launcher.
-#include <atomic>
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 #include "bbx_binom.h"
@@ -47,8 +46,11 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
     return 0;
   }
 #endif
-  if (p->policy) {                                         // policy + step in one launch (bbx_api.cpp checked the shapes)
+  if (p->policy) {                                         // policy + step in one launch
     BbxFastPolicyParams q; q.f = f; q.pol = *p->policy;
+    const int cols = 2 * f.k * f.nvars;                    // (the shapes built in: the predicates bbx_api_policy.cpp admits a call by)
+    if (!(!q.pol.rollout ? pmlp_fused_step_has(cols, q.pol.hidden) : q.pol.hidden2 > 0 ? pmlp2_step_has(2, cols, q.pol.hidden, q.pol.hidden2)
+                                                                                       : pmlp_step_has(2, cols, q.pol.hidden))) return (int)hipErrorInvalidValue;
     q.f.agent = BBX_AGENT_EXTERNAL; q.f.actions = q.pol.actions;
     if (q.pol.rollout) {                                   // nsteps steps, the policy inside the step loop (3 variables, k = 2)
       q.f.actions = nullptr; q.f.rewards = nullptr; q.f.dones = nullptr; q.f.rows = q.pol.post_obs ? q.pol.rows_t : nullptr; q.f.obs_every_step = 0; q.f.auto_reset = 1;
@@ -57,18 +59,9 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
         // per wave its state and the logits of up to 256 rows (5 KB), per workgroup the layers behind the first (65 KB at 128 x 128):
         // 16 waves = 145 KB of the CU's 160
         const size_t rl2 = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)h1 * h2 + 2 * h2 + 4) * sizeof(float);
-        int dev_ = 0; (void)hipGetDevice(&dev_); dev_ &= 63;
-#define BBX_FP2(A, C) do { \
-          static std::atomic<size_t> set_[64];   /* per device, the largest size asked for so far: > 64 KB of dynamic LDS needs the attribute */ \
-          if (set_[dev_].load(std::memory_order_acquire) < rl2) { \
-            hipError_t err_ = hipFuncSetAttribute((const void*)bbx_fast_policy2_rollout_kernel<A, C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl2); \
-            if (err_ != hipSuccess) return (int)err_; \
-            size_t old_ = set_[dev_].load(std::memory_order_relaxed); \
-            while (old_ < rl2 && !set_[dev_].compare_exchange_weak(old_, rl2, std::memory_order_release)) {} } \
-          hipLaunchKernelGGL((bbx_fast_policy2_rollout_kernel<A, C>), dim3(blocks), dim3(threads), rl2, stream, q); } while (0)
-        if (h1 == 64 && h2 == 64) BBX_FP2(64, 64); else if (h1 == 64) BBX_FP2(64, 128); else if (h2 == 64) BBX_FP2(128, 64); else BBX_FP2(128, 128);
+#define BBX_FP2(A, C) launch_lds<bbx_fast_policy2_rollout_kernel<A, C>>(blocks, threads, rl2, stream, q)
+        return h1 == 64 && h2 == 64 ? BBX_FP2(64, 64) : h1 == 64 ? BBX_FP2(64, 128) : h2 == 64 ? BBX_FP2(128, 64) : BBX_FP2(128, 128);
 #undef BBX_FP2
-        return 0;
       }
       const size_t rl = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)(2 * 6 + 2) * 32 * pmlp_nb_for(q.pol.hidden) + 4) * sizeof(float);
       if (p->ctl) {                                        // per-step calls served by a persistent session
@@ -80,7 +73,7 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
       else hipLaunchKernelGGL((bbx_fast_policy_rollout_kernel<4>), dim3(blocks), dim3(threads), rl, stream, q);
       return 0;
     }
-    const int nb = pmlp_nb_for(q.pol.hidden), ks = pmlp_ks_for(2 * f.k * f.nvars);
+    const int nb = pmlp_nb_for(q.pol.hidden), ks = pmlp_ks_for(cols);
     const size_t pl = pmlp_lds_bytes(envs_per_block, f.obs_rows), ll = pl > lds_pol ? pl : lds_pol;
     if (ks == 3) { if (nb == 2) hipLaunchKernelGGL((bbx_fast_policy_kernel<2, 3>), dim3(blocks), dim3(threads), ll, stream, q);
                    else hipLaunchKernelGGL((bbx_fast_policy_kernel<4, 3>), dim3(blocks), dim3(threads), ll, stream, q); }

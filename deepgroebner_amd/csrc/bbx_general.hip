@@ -278,13 +278,13 @@ static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int 
   const bool trace = p->trace != nullptr;
   if (kind == BBX_K_AUX) { hipLaunchKernelGGL(bbx_aux_kernel<W>, dim3(blocks), dim3(threads), lds, stream, *p); return 0; }
   if (kind == BBX_K_STAGED)
-    return launch_lds(trace ? bbx_step_kernel<W, true, true> : bbx_step_kernel<W, true, false>, blocks, threads, lds, stream, *p);
+    return trace ? launch_lds<bbx_step_kernel<W, true, true>>(blocks, threads, lds, stream, *p) : launch_lds<bbx_step_kernel<W, true, false>>(blocks, threads, lds, stream, *p);
 #ifdef BBX_PROF_BUILD   // diagnostic build only (-DBBX_PROF_BUILD): per-phase s_memtime sums, never in the product library
   if (!trace && getenv("BBX_PROF")) {
     static unsigned long long* d_prof = nullptr;
     if (!d_prof) (void)hipMalloc((void**)&d_prof, (size_t)p->B * 10 * sizeof(unsigned long long));
     lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();
-    (void)launch_lds(bbx_step_prof_kernel<W>, blocks, threads, lds, stream, *p, d_prof);
+    (void)launch_lds<bbx_step_prof_kernel<W>>(blocks, threads, lds, stream, *p, d_prof);
     (void)hipStreamSynchronize(stream);
     std::vector<unsigned long long> h((size_t)p->B * 10);
     (void)hipMemcpy(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost);
@@ -298,7 +298,7 @@ static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int 
   }
 #endif
   lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();          // merge-path tile scratch, one per wave
-  return launch_lds(trace ? bbx_step_kernel<W, false, true> : bbx_step_kernel<W, false, false>, blocks, threads, lds, stream, *p);
+  return trace ? launch_lds<bbx_step_kernel<W, false, true>>(blocks, threads, lds, stream, *p) : launch_lds<bbx_step_kernel<W, false, false>>(blocks, threads, lds, stream, *p);
 }
 extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
   return p->L.W == 2 ? launch_general_w<2>(p, kind, blocks, threads, lds, stream)

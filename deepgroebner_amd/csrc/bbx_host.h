@@ -52,6 +52,9 @@ hipError_t pool_host_malloc(void** p, size_t n, unsigned flags);
 hipError_t pool_host_free(void* p);
 uint16_t* inv_table(int device);                      // GF(32003) inverses on the device (one table per device and process)
 void pool_synced(bool on);                          // the calling thread has synchronised the device: frees need not
+// What the host side asks a device for, once per device and process: its compute units and the dynamic LDS a workgroup can have
+struct DeviceInfo { int cus, max_lds; };
+hipError_t device_info(int device, DeviceInfo* out);
 }  // namespace bbx_host
 #ifndef BBX_NO_POOL_MACROS
 #define hipMalloc(p, n) bbx_host::pool_malloc((void**)(p), (n))

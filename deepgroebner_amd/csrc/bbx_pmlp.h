@@ -1,6 +1,7 @@
 // PMLP policy on the observation block (included by the binomial / fast / aux translation units: the step kernels of
 // the binomial classes have the policy built in).
 #pragma once
+#include "bbx_pmlp_shape.h"
 
 // ------------------------------------------------------------------ the consumer of the observation block: PMLP policy
 // The reference's default policy (ParallelMultilayerPerceptron, networks.py:522-571 = ParallelEmbeddingLayer :49-95 with
@@ -72,15 +73,7 @@ __device__ __forceinline__ int pmlp_sample(const float* lg, int n, int env, floa
 // KS = k-steps built in (>= ceil(cols / 2)), NB = unit blocks (>= ceil(hidden / 32), a power of two).
 typedef float bbx_f32x16 __attribute__((ext_vector_type(16)));
 typedef float bbx_f32x4 __attribute__((ext_vector_type(4)));
-__host__ __device__ constexpr int pmlp_ks_for(int cols) {   // the built-in k-step counts
-  const int ks = (cols + 1) / 2;
-  return ks <= 3 ? 3 : ks <= 6 ? 6 : ks <= 10 ? 10 : ks <= 16 ? 16 : 32;
-}
-__host__ __device__ constexpr int pmlp_nb_for(int hidden) { const int nb = (hidden + 31) / 32; return nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8; }
-// prepared weights (floats): W1p [2 KS][32 NB] | b1p [32 NB] | w2p [32 NB] | b2 | pad to a multiple of 4
-__host__ __device__ constexpr int pmlp_prepared_floats(int cols, int hidden) {
-  return (2 * pmlp_ks_for(cols) + 2) * 32 * pmlp_nb_for(hidden) + 4;
-}
+// (the built-in k-step and unit-block counts and the prepared layout: bbx_pmlp_shape.h)
 // one tile: the logit (without b2) of row (lane & 31) from the lane's B operands xa[]; G unit blocks in flight together
 // (registers: 32 G + G KS)
 // (WP: where the prepared weights live — `const float*` in memory, or an LDS pointer when a rollout kernel has staged them
@@ -176,14 +169,7 @@ __host__ __device__ constexpr size_t pmlp_lds_bytes(int waves, int obs_rows) { r
 // operand mapping and weight layout: bbx_pmlp2.hip), shared by the stand-alone kernel (bbx_pmlp2_act_kernel) and the policy
 // rollouts inside the step kernels (fast_body POL2, bbx_fast.h; binom_body POL2, bbx_binom.h): one code for all of them, so
 // that a logit computed inside a step kernel is bit-identical to the stand-alone kernel's.
-// prepared weights (floats): W1p [4 KS][HP1] | b1p [HP1] | [AM [HPM / 16][HP1 / 16][64][4]] | A2 [HP2 / 16][HPI / 16][64][4] | [bMp [HPM]] |
-// b2p [HP2] | wdp [HP2] | bd, pad          (bracketed: the optional middle hidden layer; HPI = HPM if there is one, else HP1)
-// HP = the layer padded to 64 or 128 units, KS = k-steps of four columns built in
-__host__ __device__ constexpr int pmlp2_hp_for(int hidden) { return hidden <= 64 ? 64 : 128; }
-__host__ __device__ constexpr int pmlp2_ks_for(int cols) { const int ks = (cols + 3) / 4; return ks <= 3 ? 3 : ks <= 8 ? 8 : 16; }
-__host__ __device__ constexpr int pmlp2_prepared_floats(int cols, int hp1, int hpm, int hp2) {   // (padded sizes; hpm = 0: two hidden layers)
-  return (4 * pmlp2_ks_for(cols) + 1) * hp1 + hp1 * hpm + (hpm ? hpm : hp1) * hp2 + hpm + 2 * hp2 + 4;
-}
+// The prepared weights and the padding of the layers (HP = 64 or 128 units, KS = k-steps of four columns): bbx_pmlp_shape.h.
 
 // one hidden layer behind the first: hout = relu(b + A hin) (LAST = false) or the deciding layer's dot over it (LAST = true:
 // returns this lane's share of the logit).  Two blocks of 16 units in flight, their A operands requested half a block pair ahead

@@ -25,7 +25,6 @@
 // launch with two waves per SIMD (SQ_VALU_MFMA_BUSY_CYCLES: 25 us of 64) — more waves are what fills them, not a better
 // distribution of the environments: sorting them by tile count (even loads per wave) and handing them out through a ticket
 // counter (dynamic) were both built; the first changed nothing, the second was slower (same-address atomics from eight XCDs).
-#include <atomic>
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 
@@ -177,29 +176,16 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
   }
 }
 
-// padded layer sizes: two hidden layers are padded one by one; with a middle layer all three take the size of the widest
-// (one kernel per size instead of eight)
-static void pmlp2_pads(int h1, int hm, int h2, int* hp1, int* hpm, int* hp2) {
-  if (hm == 0) { *hp1 = pmlp2_hp_for(h1); *hpm = 0; *hp2 = pmlp2_hp_for(h2); return; }
-  const int mx = h1 > hm ? (h1 > h2 ? h1 : h2) : (hm > h2 ? hm : h2);
-  *hp1 = *hpm = *hp2 = pmlp2_hp_for(mx);
-}
-
-extern "C" int bbx_pmlp2_floats(int cols, int h1, int hm, int h2) {
-  int hp1, hpm, hp2; pmlp2_pads(h1, hm, h2, &hp1, &hpm, &hp2);
-  return pmlp2_prepared_floats(cols, hp1, hpm, hp2);
-}
-
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream) {
-  int hp1, hpm, hp2; pmlp2_pads(h1, hm, h2, &hp1, &hpm, &hp2);
+  const auto [hp1, hpm, hp2] = pmlp2_pads(h1, hm, h2);
   hipLaunchKernelGGL(bbx_pmlp2_prepare_kernel, dim3(64), dim3(256), 0, stream, w1, b1, wm, bm, w2, b2, wd, bd, cols, h1, hm, h2, hp1, hpm, hp2, out);
   return (int)hipGetLastError();
 }
 
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
                                     const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream) {
-  int hp1, hpm, hp2; pmlp2_pads(h1, hm, h2, &hp1, &hpm, &hp2);
+  const auto [hp1, hpm, hp2] = pmlp2_pads(h1, hm, h2);
   const int ks = pmlp2_ks_for(cols);
   // 64 KB of second-layer weights: two workgroups of 8 waves per CU; with a middle layer of that size (128 KB): one workgroup
   // of 16 waves — or of 8 or 4 where tall observation blocks (4 bytes of logits per row and wave) leave less room
@@ -213,18 +199,11 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
     if (ml <= (size_t)max_lds || hpm != 128 || waves == 4) break;
   }
   if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  int dev_ = 0; (void)hipGetDevice(&dev_); dev_ &= 63;
   const int max_blocks = (hpm == 128 ? 1 : 2) * (cus > 0 ? cus : 256);
   int blocks = (B + waves - 1) / waves;
   blocks = blocks < max_blocks ? blocks : max_blocks;
-#define BBX_P2(N1, NM, N2, K, NW) do { \
-    static std::atomic<size_t> set_[64];   /* per device, once per size: the call is not free (the attribute belongs to the current device's code object) */ \
-    if (set_[dev_].load(std::memory_order_acquire) < ml) { \
-      hipError_t err_ = hipFuncSetAttribute((const void*)bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ml); \
-      if (err_ != hipSuccess) return (int)err_; \
-      size_t old_ = set_[dev_].load(std::memory_order_relaxed); \
-      while (old_ < ml && !set_[dev_].compare_exchange_weak(old_, ml, std::memory_order_release)) {} } \
-    hipLaunchKernelGGL((bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>), dim3(blocks), dim3(NW * WAVE), ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions, logprobs, lgcap); } while (0)
+  int rc = 0;
+#define BBX_P2(N1, NM, N2, K, NW) rc = launch_lds<bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>>(blocks, NW * WAVE, ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions, logprobs, lgcap)
 #define BBX_P2_K(N1, NM, N2, NW) do { if (ks == 3) BBX_P2(N1, NM, N2, 3, NW); else if (ks == 8) BBX_P2(N1, NM, N2, 8, NW); else BBX_P2(N1, NM, N2, 16, NW); } while (0)
   if (hpm == 128 && waves == 16) BBX_P2_K(128, 128, 128, 16);
   else if (hpm == 128 && waves == 8) BBX_P2_K(128, 128, 128, 8);
@@ -234,5 +213,5 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
   else if (hp2 == 64) BBX_P2_K(128, 0, 64, 8); else BBX_P2_K(128, 0, 128, 8);
 #undef BBX_P2_K
 #undef BBX_P2
-  return (int)hipGetLastError();
+  return rc ? rc : (int)hipGetLastError();
 }

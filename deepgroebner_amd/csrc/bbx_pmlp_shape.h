@@ -1,0 +1,43 @@
+// Shapes of the PMLP policy kernels, stated once: the prepared-weight geometry, and which (columns, hidden units) the step kernels
+// have a policy built in for.  Plain C++: the host API (bbx_api_policy.cpp) admits a call by the functions the launchers
+// (bbx_fast.hip, bbx_binom.hip, bbx_aux.hip, bbx_pmlp2.hip) dispatch behind and the kernels (bbx_pmlp.h) are sized with.
+#pragma once
+#include "bbx_common.h"
+
+// ---- one hidden layer (bbx_pmlp.h: pmlp_tile).  KS = k-steps of two columns built in (>= ceil(cols / 2)), NB = blocks of 32
+// hidden units (>= ceil(hidden / 32), a power of two)
+BBX_HD constexpr int pmlp_ks_for(int cols) { const int ks = (cols + 1) / 2; return ks <= 3 ? 3 : ks <= 6 ? 6 : ks <= 10 ? 10 : ks <= 16 ? 16 : 32; }
+BBX_HD constexpr int pmlp_nb_for(int hidden) { const int nb = (hidden + 31) / 32; return nb <= 1 ? 1 : nb <= 2 ? 2 : nb <= 4 ? 4 : 8; }
+// prepared weights (floats): W1p [2 KS][32 NB] | b1p [32 NB] | w2p [32 NB] | b2 | pad to a multiple of 4
+BBX_HD constexpr int pmlp_prepared_floats(int cols, int hidden) { return (2 * pmlp_ks_for(cols) + 2) * 32 * pmlp_nb_for(hidden) + 4; }
+
+// ---- two and three hidden layers (bbx_pmlp.h: pmlp2_tile; bbx_pmlp2.hip)
+// prepared weights (floats): W1p [4 KS][HP1] | b1p [HP1] | [AM [HPM / 16][HP1 / 16][64][4]] | A2 [HP2 / 16][HPI / 16][64][4] | [bMp [HPM]] |
+// b2p [HP2] | wdp [HP2] | bd, pad          (bracketed: the optional middle hidden layer; HPI = HPM if there is one, else HP1)
+// HP = the layer padded to 64 or 128 units, KS = k-steps of four columns built in
+BBX_HD constexpr int pmlp2_hp_for(int hidden) { return hidden <= 64 ? 64 : 128; }
+BBX_HD constexpr int pmlp2_ks_for(int cols) { const int ks = (cols + 3) / 4; return ks <= 3 ? 3 : ks <= 8 ? 8 : 16; }
+BBX_HD constexpr int pmlp2_prepared_floats(int cols, int hp1, int hpm, int hp2) {   // (padded sizes; hpm = 0: two hidden layers)
+  return (4 * pmlp2_ks_for(cols) + 1) * hp1 + hp1 * hpm + (hpm ? hpm : hp1) * hp2 + hpm + 2 * hp2 + 4;
+}
+// padded layer sizes: two hidden layers are padded one by one; with a middle layer all three take the size of the widest
+// (one kernel per size instead of eight)
+struct Pmlp2Pads { int hp1, hpm, hp2; };
+BBX_HD constexpr Pmlp2Pads pmlp2_pads(int h1, int hm, int h2) {
+  if (hm == 0) return {pmlp2_hp_for(h1), 0, pmlp2_hp_for(h2)};
+  const int hp = pmlp2_hp_for(h1 > hm ? (h1 > h2 ? h1 : h2) : (hm > h2 ? hm : h2));
+  return {hp, hp, hp};
+}
+
+// ---- the policies built into the step kernels
+// a rollout with one hidden layer, step kernels of W-word monomials (bbx_binom_policy_kernel; 8-byte monomials with 3 variables
+// and k = 2 also bbx_fast_policy_rollout_kernel): 33..128 hidden units, 6 k-steps, or 10 with 16-byte monomials
+BBX_HD constexpr bool pmlp_step_has(int W, int cols, int hidden) {
+  return (W == 2 || W == 4) && (pmlp_nb_for(hidden) == 2 || pmlp_nb_for(hidden) == 4) && (pmlp_ks_for(cols) == 6 || (W == 4 && pmlp_ks_for(cols) == 10));
+}
+// ... with two (bbx_binom_policy2_kernel, bbx_fast_policy2_rollout_kernel): <= 128 units per layer, 3 k-steps, or 8 with 16-byte monomials
+BBX_HD constexpr bool pmlp2_step_has(int W, int cols, int h1, int h2) {
+  return h1 >= 1 && h1 <= 128 && h2 >= 1 && h2 <= 128 && (((W == 2 || W == 4) && pmlp2_ks_for(cols) == 3) || (W == 4 && pmlp2_ks_for(cols) == 8));
+}
+// policy + one step in one launch, the register/LDS-resident class (bbx_fast_policy_kernel): 33..128 hidden units, <= 12 columns
+BBX_HD constexpr bool pmlp_fused_step_has(int cols, int hidden) { return (pmlp_nb_for(hidden) == 2 || pmlp_nb_for(hidden) == 4) && cols >= 1 && cols <= 12; }

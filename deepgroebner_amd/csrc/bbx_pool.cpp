@@ -1,8 +1,9 @@
-// Buffers of destroyed handles kept for the next handle, and the per-device inverse table (declared in bbx_host.h): the one
+// Buffers of destroyed handles kept for the next handle, the per-device inverse table and device record (bbx_host.h): the one
 // translation unit of libbbx's host side that calls hipMalloc / hipFree / hipHostMalloc / hipHostFree themselves.
 #define BBX_NO_POOL_MACROS
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -120,4 +121,21 @@ uint16_t* inv_table(int device) {
   return tab[device];
 }
 
+hipError_t device_info(int device, DeviceInfo* out) {
+  static std::mutex mu; static DeviceInfo info[64]; static bool have[64];
+  if (device < 0 || device >= 64) return hipErrorInvalidDevice;
+  std::lock_guard<std::mutex> g(mu);
+  if (!have[device]) {
+    DeviceInfo d{}; hipDeviceProp_t prop;
+    hipError_t e = hipDeviceGetAttribute(&d.cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&d.max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device);
+    if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+    if (e != hipSuccess) return e;
+    // gfx950 has 160 KB of LDS per workgroup, whatever hipDeviceAttributeMaxSharedMemoryPerBlock says (64 KB: the limit without
+    // the per-function attribute); the library is built for that part only, so that figure is the floor for it and for nothing else
+    if (strncmp(prop.gcnArchName, "gfx950", 6) == 0 && d.max_lds < 163840) d.max_lds = 163840;
+    info[device] = d; have[device] = true;
+  }
+  *out = info[device]; return hipSuccess;
+}
 }  // namespace bbx_host

@@ -20,8 +20,7 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
       q.wide_fc = q.wide_hc; q.wide_rc = q.wide_hc; q.wide_sc = lazy ? q.wide_hc : 0;
     }
     else {
-      static int ncu = 0;
-      if (!ncu) { int dev = 0; hipDeviceProp_t pr; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ncu = pr.multiProcessorCount; if (ncu <= 0) ncu = 256; }
+      const int ncu = q.wide_ncu > 0 ? q.wide_ncu : 256;   // (plan_launch: the device's CUs; unknown: as many as the largest part has)
       // one workgroup per CU while the batch fits that way (160 KB each), otherwise two per CU (80 KB each)
       const bool one = q.B <= ncu || q.wide_tail == 2;     // (the tail kernel: the workgroups with work left fit one per CU)
       one_per_cu = one;
@@ -35,17 +34,18 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
     p = &q;
     const size_t wl = wide_lds_bytes(W_, q.wide_hc, q.wide_fc, q.wide_rc, q.wide_sc);
     const bool tr = p->trace != nullptr;
-    auto go = [&](void (*kern)(BbxParams)) { return launch_lds(kern, p->B, nw * WAVE, wl, stream, q); };
+#define GO(...) launch_lds<__VA_ARGS__>(p->B, nw * WAVE, wl, stream, q)
     int rc;
-    if (W_ == 8) rc = tr ? go(bbx_wide_kernel<8, true, false>) : go(bbx_wide_kernel<8, false, false>);   // one variant: tier 3 throughout
+    if (W_ == 8) rc = tr ? GO(bbx_wide_kernel<8, true, false>) : GO(bbx_wide_kernel<8, false, false>);   // one variant: tier 3 throughout
     else if (!tr && one_per_cu) {
-      if (W_ == 2) rc = lazy ? go(bbx_wide_kernel_1cu<2, true, false>) : acct ? go(bbx_wide_kernel_1cu<2, false, true>) : go(bbx_wide_kernel_1cu<2, false, false>);
-      else rc = lazy ? go(bbx_wide_kernel_1cu<4, true, false>) : acct ? go(bbx_wide_kernel_1cu<4, false, true>) : go(bbx_wide_kernel_1cu<4, false, false>);
-    } else if (!tr && !lazy && !acct) rc = W_ == 2 ? go(bbx_wide_eager_kernel<2>) : go(bbx_wide_eager_kernel<4>);
-    else if (W_ == 2) rc = tr ? (lazy ? go(bbx_wide_kernel<2, true, true>) : go(bbx_wide_kernel<2, true, false>))
-                              : (lazy ? go(bbx_wide_kernel<2, false, true>) : go(bbx_wide_kernel<2, false, false>));
-    else rc = tr ? (lazy ? go(bbx_wide_kernel<4, true, true>) : go(bbx_wide_kernel<4, true, false>))
-                 : (lazy ? go(bbx_wide_kernel<4, false, true>) : go(bbx_wide_kernel<4, false, false>));
+      if (W_ == 2) rc = lazy ? GO(bbx_wide_kernel_1cu<2, true, false>) : acct ? GO(bbx_wide_kernel_1cu<2, false, true>) : GO(bbx_wide_kernel_1cu<2, false, false>);
+      else rc = lazy ? GO(bbx_wide_kernel_1cu<4, true, false>) : acct ? GO(bbx_wide_kernel_1cu<4, false, true>) : GO(bbx_wide_kernel_1cu<4, false, false>);
+    } else if (!tr && !lazy && !acct) rc = W_ == 2 ? GO(bbx_wide_eager_kernel<2>) : GO(bbx_wide_eager_kernel<4>);
+    else if (W_ == 2) rc = tr ? (lazy ? GO(bbx_wide_kernel<2, true, true>) : GO(bbx_wide_kernel<2, true, false>))
+                              : (lazy ? GO(bbx_wide_kernel<2, false, true>) : GO(bbx_wide_kernel<2, false, false>));
+    else rc = tr ? (lazy ? GO(bbx_wide_kernel<4, true, true>) : GO(bbx_wide_kernel<4, true, false>))
+                 : (lazy ? GO(bbx_wide_kernel<4, false, true>) : GO(bbx_wide_kernel<4, false, false>));
+#undef GO
     return rc ? rc : (int)hipGetLastError();
 }
 #ifdef BBX_PROF_BUILD

@@ -139,3 +139,40 @@ def test_policy_shapes_are_checked_on_the_host(ffi_):
     assert dll.bbx_pmlp3_prepared_floats(12, 40, 100, 17) == (4 * 3 + 1) * 128 + 2 * 128 * 128 + 3 * 128 + 4   # (all three padded to the widest)
     assert dll.bbx_pmlp3_prepared_floats(12, 40, 129, 17) == -5 and b"three-layer" in dll.bbx_last_error()
     assert dll.bbx_graph_replayed(None, None) == -1                                                   # BBX_E_ARG
+
+
+def _built_in(need, sizes):
+    return next(s for s in sizes if s >= need)
+
+
+def test_prepared_sizes_follow_the_documented_layout(ffi_):
+    """The prepared-buffer sizes against the layouts written out in bbx_pmlp_shape.h — the formulas are restated here, not
+    taken from the library — over the whole admitted range, and -5 just outside each end of it.
+    One hidden layer: W1p [2 KS][32 NB] | b1p [32 NB] | w2p [32 NB] | b2, padded to four floats; KS = the built-in count of
+    two-column k-steps (3, 6, 10, 16, 32), NB = the built-in count of 32-unit blocks (1, 2, 4, 8).
+    Two / three: W1p [4 KS][HP1] | b1p [HP1] | [AM [HPM][HP1]] | A2 [HP2][HPI] | [bMp [HPM]] | b2p [HP2] | wdp [HP2] | bd, padded
+    to four floats; KS = four-column k-steps (3, 8, 16), HP = a layer padded to 64 or 128 units — two layers one by one, three
+    layers all to the widest."""
+    dll = ffi_.lib()
+    for cols in range(1, 65):
+        ks = _built_in((cols + 1) // 2, (3, 6, 10, 16, 32))
+        for hidden in range(1, 257):
+            hp = 32 * _built_in((hidden + 31) // 32, (1, 2, 4, 8))
+            assert dll.bbx_pmlp_prepared_floats(cols, hidden) == 2 * ks * hp + hp + hp + 4, (cols, hidden)
+    for bad in ((0, 128), (65, 128), (12, 0), (12, 257)):
+        assert dll.bbx_pmlp_prepared_floats(*bad) == -5, bad
+    sizes = (1, 64, 65, 128)
+    pad = lambda h: 64 if h <= 64 else 128                  # noqa: E731
+    for cols in range(1, 65):
+        k1 = 4 * _built_in((cols + 3) // 4, (3, 8, 16))
+        for h1 in sizes:
+            for h2 in sizes:
+                p1, p2 = pad(h1), pad(h2)
+                assert dll.bbx_pmlp2_prepared_floats(cols, h1, h2) == k1 * p1 + p1 + p2 * p1 + p2 + p2 + 4, (cols, h1, h2)
+                for hm in sizes:
+                    p = pad(max(h1, hm, h2))
+                    assert dll.bbx_pmlp3_prepared_floats(cols, h1, hm, h2) == k1 * p + p + p * p + p * p + p + p + p + 4, (cols, h1, hm, h2)
+    for bad in ((0, 64, 64), (65, 64, 64), (12, 0, 64), (12, 129, 64), (12, 64, 0), (12, 64, 129)):
+        assert dll.bbx_pmlp2_prepared_floats(*bad) == -5, bad
+    for bad in ((0, 64, 64, 64), (65, 64, 64, 64), (12, 0, 64, 64), (12, 129, 64, 64), (12, 64, 0, 64), (12, 64, 129, 64), (12, 64, 64, 0), (12, 64, 64, 129)):
+        assert dll.bbx_pmlp3_prepared_floats(*bad) == -5, bad

@@ -755,6 +755,33 @@ def test_long_polynomials_cyclic7_all_merge_paths(wide, lds_terms, lean):
         assert np.array_equal(_state_words(basis, pairs, order), want), e
 
 
+def test_wide_class_handles_with_a_larger_lds_window_in_between():
+    """Three handles over cyclic-7 in one process, LDS windows forced to 64, 1024 and 64 terms: the same kernel is launched
+    with little dynamic LDS, then with more than the 64 KB a kernel gets without its attribute raised (accounting off: the
+    variant with the LDS accumulator, 10 more bytes per term of window), then with little again — the launch helper raises
+    the limit only when a launch asks for more than any before it on that device.  8 traced steps each: every trace equals the
+    oracle's, field for field, and so each other."""
+    from deepgroebner_amd import VecLeadMonomialsEnv
+    bo = ffi.load("bo")
+    B, T, k = 4, 8, 2
+    want = []
+    for e in range(B):
+        o = bo.env("cyclic-7")
+        want.append(run_trace(o, k, T, "hash", agent_seed=e))
+    envs, got = [], []
+    for lds_terms in (64, 1024, 64):
+        env = VecLeadMonomialsEnv("cyclic-7", batch=B, k=k, caps={"wide_lds_terms": lds_terms})
+        env.accounting(False)
+        env.seed_agent(np.arange(B)); env.trace_enable(T); env.reset()
+        env.rollout("random", T, auto_reset=True)
+        envs.append(env)
+        got.append([env.trace_read(e, 0, T) for e in range(B)])
+        for e in range(B):
+            compare_with_trace(env, e, want[e], T, "wide_lds_terms %d" % lds_terms)
+    for e in range(B):
+        assert got[0][e].tobytes() == got[1][e].tobytes() == got[2][e].tobytes(), e
+
+
 @pytest.mark.parametrize("waves", [3, 5, 8])
 @pytest.mark.parametrize("lean", [0, 1])
 def test_wide_class_lockstep_stress(waves, lean):

@@ -195,11 +195,12 @@ def test_two_layer_rollout_refusals():
         return (torch.rand((T, B), device="cuda"), torch.zeros((T, B), dtype=torch.int32, device="cuda"), torch.zeros((T, B), device="cuda"),
                 torch.zeros((T, B, R, cols), dtype=torch.int32, device="cuda"))
 
-    def refused(env, w, h1, h2, R):
+    def refused(env, w, h1, h2, R, text=None):
         u, A, L, O = outs(R, env.cols)
         with pytest.raises(_ffi.BbxError) as ex:
             env.policy2_rollout_device(w["prepared"], h1, h2, T, u, A, L, None, None, None, O, R, 0, s)
         assert ex.value.code == -5, str(ex.value)
+        assert text is None or str(ex.value).endswith(text), str(ex.value)
 
     cyc = VecLeadMonomialsEnv("cyclic-4", batch=B, k=2); cyc.reset(); cyc.accounting(False)
     w = _policy(cyc.cols, (64, 64), 1)._deep_weights()
@@ -208,7 +209,7 @@ def test_two_layer_rollout_refusals():
     w = _policy(env.cols, (128, 128), 1)._deep_weights()
     refused(env, w, 256, 128, 64)
     refused(env, w, 128, 256, 64)
-    refused(env, w, 128, 128, 2049)
+    refused(env, w, 128, 128, 2049, "the policy kernels score at most 2048 rows per environment (obs_rows = 2049)")
     env.accounting(True)
     refused(env, w, 128, 128, 64)
     env.accounting(False)

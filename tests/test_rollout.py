@@ -238,6 +238,38 @@ def test_deep_policy_kernels_on_tall_observation_blocks(hidden, R):
 
 
 @pytest.mark.gpu
+def test_deep_policy_kernel_after_a_taller_block_in_the_same_process():
+    """One three-layer policy of 128 units scored on blocks of 64, 1024 and 64 rows again: every launch sizes its dynamic LDS
+    (128 KB of weights + the logits of its waves) anew and the launch helper raises a kernel's limit only when a launch asks
+    for more than any before it.  64 and 1024 rows pick different workgroup widths (16 and 4 waves), so a block of 256 rows
+    follows: the 16-wave kernel of the 64-row launches again, with 12 KB more.  Against act_torch: equal draws,
+    log-probabilities within the tolerance of test_deep_policy_kernels_on_tall_observation_blocks."""
+    import torch
+    from deepgroebner_amd.rollout import PMLPPolicy
+    torch.manual_seed(13)
+    B, cols = 8, 20
+    policy = PMLPPolicy(cols, [128, 128, 128]).cuda()
+    with torch.no_grad():
+        for lin in list(policy.embedding) + [policy.deciding]:
+            lin.weight.mul_(0.3)
+    blocks = {}
+    for R in (64, 1024, 256):
+        obs = torch.randint(0, 9, (B, R, cols), dtype=torch.int32, device="cuda")
+        rows = torch.randint(1, R + 1, (B,), dtype=torch.int32, device="cuda")
+        rows[0] = R; rows[1] = 1
+        obs[torch.arange(R, device="cuda")[None, :] >= rows[:, None]] = -1
+        blocks[R] = (obs, rows, torch.rand(B, device="cuda"))
+    for R in (64, 1024, 64, 256):
+        obs, rows, u = blocks[R]
+        a_k, l_k = policy.act(obs, rows, u)
+        a_t, l_t = policy.act_torch(obs, rows, u)
+        torch.cuda.synchronize()
+        print("R = %d: %d draws differ, max |dlogp| = %.3g" % (R, int((a_k != a_t).sum()), float((l_k - l_t).abs().max())))
+        assert torch.equal(a_k.long(), a_t.long()), R
+        assert torch.allclose(l_k, l_t, atol=5e-4, rtol=1e-4), R
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("hidden", [(128,), (64,), (128, 128), (64, 64, 64), (128, 128, 128)])
 def test_policy_kernels_score_up_to_2048_rows(hidden):
     """5-10-5-uniform pair sets pass a thousand rows: the policy kernels keep an environment's logits in LDS, 2048 of them
@@ -540,6 +572,8 @@ def test_policy_rollout_rejects_what_the_kernel_class_cannot_do():
     with pytest.raises(_ffi.BbxError) as ei:
         env.policy_rollout_device(w["prepared"], w["hidden"], 4, z, z.int(), z.clone(), stream=torch.cuda.current_stream().cuda_stream)
     assert ei.value.code == -5                               # BBX_E_UNSUPPORTED (include/bbx.h)
+    assert str(ei.value).endswith("policy rollouts are built into the binomial kernel classes only (<= 7 variables, 2nk <= 12 columns, or <= 20 with "
+                                  "more than 3 variables; 33..128 hidden units); drive this batch with bbx_policy_step_device")
 
 
 @pytest.mark.gpu
