@@ -189,7 +189,9 @@ int bbx_step_device_autoreset(bbx_batch* b, const int32_t* d_actions, double* d_
  * the host every step.  fp32, the hidden layer on the matrix cores (exact f32 MFMA); cols <= 64, hidden <= 256, at most
  * 2048 rows per environment (obs_rows > 2048: BBX_E_UNSUPPORTED; a policy rollout without an observation block whose pair
  * set outgrows 2048 rows: BBX_E_CAPACITY from bbx_sync — never a silent cut).  exp / log of the softmax are the
- * hardware's fast forms (__expf / __logf): log-probabilities agree with an IEEE evaluation to ~2e-4 (tests/test_rollout.py).
+ * hardware's fast forms (__expf / __logf).  Against a float64 evaluation a log-probability is held to
+ * |error| <= C_L 2^-24 (S + |logZ| + 1), S the network evaluated with |W|, |b|, |x| (tests/policy_cases.py, tests/test_policy_parity.py;
+ * C_L = 64 is a ceiling, not yet a measurement: about 4e-6 (S + |logZ| + 1)).
  * The weights are handed over PREPARED: bbx_pmlp_prepare copies d_w1 [cols][hidden] (the layout of
  * torch.nn.Linear(...).weight.t()), d_b1 [hidden], d_w2 [hidden], b2 into d_prepared (bbx_pmlp_prepared_floats(cols,
  * hidden) floats, 16-byte aligned) zero-padded to the kernels' tile sizes; call it again whenever the weights change.

@@ -1,8 +1,9 @@
 """Randomised self-consistency sweep of the policy paths (test infrastructure, GPU box): for random binomial distributions,
 observation widths, hidden sizes, batch sizes and kernel capacities, bbx_policy_rollout_device (policy inside the step
 kernels, T steps per launch, split at a random point) must reproduce T calls of bbx_policy_step_device on a copy of the batch
-— actions, log-probabilities, rewards, dones, row counts, observations — and the torch module must agree with the sampled
-log-probabilities; the two- / three-layer policy kernels (random layer sizes) must agree with the torch module on the
+— actions, log-probabilities, rewards, dones, row counts, observations — and its first step's draws must pass the float64
+reference's check (tests/policy_cases.py: check_draws — every action admissible for its uniform number, every log-probability
+within the measured tolerance); so must the draws of the two- / three-layer policy kernels (random layer sizes) on the
 rollout's final block.     python scripts/fuzz_policy.py [ROUNDS] [SEED]"""
 import os, sys, random, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,6 +11,7 @@ import numpy as np
 import torch
 from deepgroebner_amd import VecLeadMonomialsEnv, _ffi
 from deepgroebner_amd.rollout import PMLPPolicy
+from tests import policy_cases as pc
 
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -44,11 +46,13 @@ for it in range(rounds):
         want = {key: [] for key in ("obs", "rows", "act", "logp", "rew", "done")}
         for t in range(T):
             want["obs"].append(obs.clone()); want["rows"].append(rows.clone())
-            if t == 0:                                       # the torch module on the same block
-                lp = policy(obs)
             env.policy_step_device(w["prepared"], w["hidden"], u[t], act, logp, rew, done, rows, obs, R, 1, s); env.sync()
-            if t == 0 and not torch.allclose(logp, lp.gather(1, act.long()[:, None]).squeeze(1), atol=3e-4, rtol=1e-4):
-                print("MISMATCH %s: kernel log-probabilities vs the torch module" % tag); sys.exit(1)
+            if t == 0:                                       # the float64 reference on the same block
+                try:
+                    pc.check_draws(pc.weights_of(policy), want["obs"][0].cpu().numpy(), want["rows"][0].cpu().numpy(), u[0].cpu().numpy(),
+                                   act.cpu().numpy(), logp.cpu().numpy(), what=tag)
+                except AssertionError as ex:
+                    print("MISMATCH %s: kernel draws vs the float64 reference: %s" % (tag, str(ex)[:300])); sys.exit(1)
             for key, v in (("act", act), ("logp", logp), ("rew", rew), ("done", done)):
                 want[key].append(v.clone())
         A = torch.zeros((T, B), dtype=torch.int32, device="cuda"); L = torch.zeros((T, B), dtype=torch.float32, device="cuda")
@@ -78,7 +82,7 @@ for it in range(rounds):
     if not np.array_equal(env.stats()[:, :5], twin.stats()[:, :5]):
         print("MISMATCH %s: counters" % tag); sys.exit(1)
     # the deeper kernels (bbx_pmlp2_act / bbx_pmlp3_act) on the final block of this rollout: random layer sizes against the
-    # torch module — log-probability of the drawn row, and the draw itself up to round-off ties
+    # float64 reference — the draw admissible for its uniform number, the log-probability of the drawn row
     deep = [rng.randint(1, 128) for _ in range(rng.choice([2, 3]))]
     pol2 = PMLPPolicy(env.cols, deep).cuda()
     with torch.no_grad():
@@ -87,20 +91,14 @@ for it in range(rounds):
     live_rows = torch.clamp(rows, min=1)
     uu = torch.rand(B, device="cuda")
     a_k, l_k = pol2.act(obs, live_rows, uu)
-    a_t, _ = pol2.act_torch(obs, live_rows, uu)
     torch.cuda.synchronize()
-    lp2 = pol2(obs)
-    n_eff = torch.clamp(live_rows, max=R)
     if pol2.deep_ok(env.cols) and R <= 1024:
-        # (the reference masks by the -1 padding, the kernel by the row count: compare on the rows both see)
-        validm = torch.arange(R, device="cuda")[None, :] < n_eff[:, None]
-        lpm = torch.log_softmax(torch.where(validm, lp2, torch.full_like(lp2, -1e30)), dim=1)
-        if not ((a_k >= 0).all() and (a_k < n_eff).all()):
-            print("MISMATCH %s: deep policy %s drew outside the rows" % (tag, deep)); sys.exit(1)
-        if not torch.allclose(l_k, lpm.gather(1, a_k.long()[:, None]).squeeze(1), atol=5e-4, rtol=1e-4):
-            print("MISMATCH %s: deep policy %s log-probabilities vs the torch module" % (tag, deep)); sys.exit(1)
-        if (a_k == a_t).float().mean() < 0.98:
-            print("MISMATCH %s: deep policy %s draws" % (tag, deep)); sys.exit(1)
+        # (the reference masks by the row count, like the kernel)
+        try:
+            pc.check_draws(pc.weights_of(pol2), obs.cpu().numpy(), live_rows.cpu().numpy(), uu.cpu().numpy(), a_k.cpu().numpy(), l_k.cpu().numpy(),
+                           what=tag)
+        except AssertionError as ex:
+            print("MISMATCH %s: deep policy %s vs the float64 reference: %s" % (tag, deep, str(ex)[:300])); sys.exit(1)
         tag += " deep=%s" % deep
     print("ok " + tag)
     del env, twin, O
