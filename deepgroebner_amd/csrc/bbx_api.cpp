@@ -266,10 +266,10 @@ int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) 
   if (pl.wide_tail) HIPCHK(hipMemsetAsync(b->d_wide_done, 0, 256, stream));
   b->flight.poll = pl.poll;
   if (pl.poll) {
-    b->poll_seq = (b->poll_seq % 16000) + 1; pl.pass[0].done_seq = b->poll_seq;
+    b->poll_seq = bbx_lite_seq_of(b->poll_seq); pl.pass[0].done_seq = b->poll_seq;
     // the words the host is going to watch start out cleared: pinned memory is handed out uninitialised and may still hold
     // the status words — sequence numbers included — of a handle that was destroyed
-    for (int e = 0; e < b->B; e++) ((volatile int32_t*)b->h_io)[(size_t)e * 4] = 0;
+    clear_pinned_seq(b);
     std::atomic_thread_fence(std::memory_order_release);
   }
   for (int i = 0; i < pl.n; i++) {
@@ -308,13 +308,14 @@ int write_gen_states(bbx_batch* b, const std::vector<long long>& seeds) {
 }
 
 int alloc_io(bbx_batch* b, int batch) {
-  b->io_bytes = (size_t)batch * 29;
+  const BbxOutLayout o = bbx_out_layout(batch);
+  b->io_bytes = o.bytes;
   HIPCHK(hipMalloc((void**)&b->d_out, b->io_bytes));
   HIPCHK(hipMemset(b->d_out, 0, b->io_bytes));
-  b->d_lite = (int32_t*)b->d_out;
-  b->d_rewards = (double*)(b->d_out + (size_t)batch * 16);
-  b->d_rows = (int32_t*)(b->d_out + (size_t)batch * 24);
-  b->d_dones = (uint8_t*)(b->d_out + (size_t)batch * 28);
+  b->d_lite = (int32_t*)(b->d_out + o.lite);
+  b->d_rewards = (double*)(b->d_out + o.rewards);
+  b->d_rows = (int32_t*)(b->d_out + o.rows);
+  b->d_dones = (uint8_t*)(b->d_out + o.dones);
   // (the block the step kernels write their outputs and status words to in zero-copy launches, and the host may spin on:
   // fine-grained, so that device writes are visible while the kernel is still running)
   if (hipHostMalloc((void**)&b->h_io, b->io_bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
@@ -333,26 +334,37 @@ int alloc_io(bbx_batch* b, int batch) {
   return BBX_OK;
 }
 
+// The one way the pinned block's status records become h_lite.  The gone mark of a mailbox session is not part of the
+// budget; h_head is what fill_queues tops the rings up from (handles that draw their ideals on the device ignore it).
+void take_lite(bbx_batch* b) {
+  const BbxLite* src = (const BbxLite*)b->h_io;
+  b->h_lite.assign(src, src + b->B);
+  for (int e = 0; e < b->B; e++) { b->h_lite[e].budget &= ~BBX_LITE_GONE; b->h_head[e] = b->h_lite[e].q_head; }
+}
+
+// spin until ready() holds (true) or 2 ms have passed (false); the acquire side of the kernels' release stores
+template <class F> static bool spin_2ms(F ready) {
+  const auto t0 = std::chrono::steady_clock::now();
+  bool ok = false;
+  for (unsigned spins = 0; !(ok = ready()); spins++)
+    if ((spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return ok;
+}
+
 // fetch the block the kernels of the last launch left behind (status words and the host-API outputs) in one copy;
 // `pinned`: they wrote it into the pinned block themselves (outputs_pinned() of the call in flight)
 int read_lite(bbx_batch* b, hipStream_t stream, bool pinned) {
-  b->h_lite.resize((size_t)b->B * 4);
   if (!pinned) HIPCHK(hipMemcpyAsync(b->h_io, b->d_out, b->io_bytes, hipMemcpyDeviceToHost, stream));
   bool seen = false;
   if (pinned && b->flight.poll) {                    // spin on the status words the kernel writes last (a few microseconds
-    const auto t0 = std::chrono::steady_clock::now();   // earlier than the runtime's signal); 2 ms, then the normal wait
-    for (int spins = 0;; spins++) {
-      if (scan_seq(b, (uint32_t)b->poll_seq, 0).all) { seen = true; b->poll_misses = 0; break; }
-      if ((spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) b->poll_misses++;                  // (three in a row: the writes do not arrive early on this system; stop spinning)
+    seen = spin_2ms([b] { return scan_seq(b, b->poll_seq, 0).all; });   // earlier than the runtime's signal), then the normal wait
+    b->poll_misses = seen ? 0 : b->poll_misses + 1;  // (three in a row: the writes do not arrive early on this system; stop spinning)
     b->flight.poll = false;
   }
   // (every so often the runtime gets its wait as well, so that it can retire the commands it queued)
   if (!seen || (++b->polled_launches & 63) == 0) HIPCHK(hipStreamSynchronize(stream));   // (zero-copy launches wrote h_io themselves)
-  memcpy(b->h_lite.data(), b->h_io, (size_t)b->B * 16);
-  for (int e = 0; e < b->B; e++) b->h_head[e] = b->h_lite[(size_t)e * 4 + 1];
+  take_lite(b);
   return BBX_OK;
 }
 
@@ -425,123 +437,141 @@ int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream) {
   return BBX_OK;
 }
 
+// ---- finish() in its parts ------------------------------------------------------------------------------------------------
+// A mailbox session with nothing owed (the host waited for every step it issued and every status word says OK — the
+// observation-cut bit is not asked, unlike in mbox_step's scan: bbx_step_obs re-checks the rows itself): tell the waves to go,
+// wait for them, done — no closing kernel.  *handled = false: something is owed or to report; the session closes the usual way.
+static int mbox_fast_close(bbx_batch* b, bool* handled) {
+  const SeqScan s = scan_seq(b, bbx_lite_seq_of((int)b->ps_target), 0);
+  *handled = s.all && !s.trouble;
+  if (!*handled) return BBX_OK;
+  b->ps_active = false;
+  if (int rc = ps_write_ctl(b, true)) return rc;
+  b->ps_mbox = false;
+  // every wave marks its status block when it has stored its environment and left (BBX_LITE_GONE): a spin of a few
+  // microseconds instead of the runtime's wait for the kernel (hundreds, once per episode of a gym loop)
+  const bool gone = spin_2ms([b] {
+    for (int e = 0; e < b->B; e++) if (!(pinned_lite(b)[e].budget & BBX_LITE_GONE)) return false;
+    return true;
+  });
+  if (!gone) HIPCHK(hipStreamSynchronize(b->ps_stream));
+  continue_session(b);
+  take_lite(b);
+  return BBX_OK;                                          // (every status word said OK: nothing to serve, nothing to report)
+}
+
+// A persistent session: stop it; its kernels run in slices (on ps_stream) until nothing is owed
+static int drain_session(bbx_batch* b) {
+  if (int rc = session_close(b, false, nullptr, true)) return rc;
+  for (int guard = 0;; guard++) {
+    if (int rc = read_lite(b, b->ps_stream, outputs_pinned(b))) return rc;
+    bool owed = false;
+    for (int e = 0; e < b->B && !owed; e++) owed = bbx_lite_status(b->h_lite[e].word0) == BBX_ST_TIMESLICE;
+    if (!owed) return BBX_OK;
+    if (guard >= 100000) return fail(BBX_E_DEVICE, "a persistent session still owes steps after 100000 time slices");
+    if (int rc = session_kernel(b, false, nullptr, true)) return rc;
+  }
+}
+
+// What one round found: environments that wait for service (STARVED / SPILL: refill, relaunch), and those whose records
+// were full (bit s of grow: some environment reported capacity status s; grow_env: the first of them)
+struct ServeRound { bool again = false; unsigned grow = 0; int grow_env = -1; };
+
+// One round: fetch the status block and classify every environment.  The first error goes to *err and stays there (of
+// several, the first is the one reported); what needs service is noted whatever else there is to report.
+static int serve_round(bbx_batch* b, hipStream_t stream, int* err, ServeRound* r) {
+  if (int rc = read_lite(b, stream, outputs_pinned(b))) return rc;
+  if (int rc = collect_events(b)) return rc;
+  for (int e = 0; e < b->B; e++) {
+    const int st = bbx_lite_status(b->h_lite[e].word0);
+    if (st == BBX_ST_STARVED && !b->gen_error.empty() && !b->gen_error[e].empty() && b->h_tail[e] - b->h_head[e] <= 0) {
+      if (*err == BBX_OK) {
+        const std::string msg = b->gen_error[e];       // the draw this environment is waiting for is the one that failed
+        b->gen_error[e].clear();
+        *err = fail(BBX_E_GENERATOR, "%s", msg.c_str());
+      }
+      continue;
+    }
+    if (st == BBX_ST_GEN_ZERO) { if (*err == BBX_OK) *err = fail(BBX_E_GENERATOR, "random polynomial cancelled to zero (undefined in the reference)"); }
+    else if (st == BBX_ST_GEN_FAIL) { if (*err == BBX_OK) *err = fail(BBX_E_GENERATOR, "failed to generate two distinct random monomials after 1000 trials"); }
+    else if ((st == BBX_ST_STARVED || st == BBX_ST_SPILL) && b->flight.policy_rollout) {
+      // (the continuation pass runs right behind the first one; what is still unfinished here cannot be resumed: the
+      // policy arguments belonged to the caller's frame)
+      if (*err == BBX_OK) *err = fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s)", e, status_name(st));
+    }
+    else if (st == BBX_ST_STARVED || st == BBX_ST_SPILL) r->again = true;
+    else if (st == BBX_ST_BAD_ACTION) { if (*err == BBX_OK) *err = fail(BBX_E_ACTION, "environment %d: %s", e, status_name(st)); }
+    else if (bbx_st_capacity(st) && !b->no_growth) { r->grow |= 1u << st; if (r->grow_env < 0) r->grow_env = e; }
+    else if (st != BBX_ST_OK && *err == BBX_OK) {
+      if (int rc = read_headers(b, stream)) return rc;
+      *err = fail(BBX_E_CAPACITY, "environment %d: %s (|G|=%d |P|=%d terms=%d)", e, status_name(st),
+                  b->h_hdr[e].nG, b->h_hdr[e].nP, b->h_hdr[e].arena_used);
+    }
+  }
+  return BBX_OK;
+}
+
+// Enlarge what was full.  true: the environments then take the step they stopped at (the launch is resumed); false: the
+// call ends here, with *err saying why
+static bool grow_and_resume(bbx_batch* b, const ServeRound& r, hipStream_t stream, int* err) {
+  const bbx_flight& f = b->flight;
+  auto note = [err](int code) { if (*err == BBX_OK) *err = code; };
+  const int rc = grow_records(b, r.grow, r.grow_env, stream);
+  if (rc) { note(rc); return false; }
+  if (f.policy_rollout) {                           // (its per-step arrays belonged to the caller's frame: cannot be resumed)
+    note(fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s); the records have been enlarged, later rollouts have room",
+              r.grow_env, status_name(__builtin_ctz(r.grow))));
+    return false;
+  }
+  if (f.device_async && f.p.agent == BBX_AGENT_EXTERNAL && f.async_chain > 1) {
+    // several asynchronous steps with caller-supplied actions were queued behind each other (or replayed from a graph):
+    // the environment stopped at one of them and sat out the rest; the action buffer now holds a later step's actions,
+    // so the step it stopped at cannot be taken for it
+    note(fail(BBX_E_CAPACITY, "environment %d outgrew its records (%s) inside a chain of asynchronous steps with caller-supplied actions and took "
+                              "none of the chain's later steps; the records have been enlarged, later calls have room", r.grow_env,
+              status_name(__builtin_ctz(r.grow))));
+    return false;
+  }
+  return true;
+}
+
+// rows an observation lost for lack of space in a caller-owned block: an error the caller must hear about
+static int report_obs_trunc(const bbx_batch* b) {
+  for (int e = 0; e < b->B; e++)
+    if (b->h_lite[e].word0 & BBX_LITE_OBS_TRUNC)
+      return fail(BBX_E_CAPACITY, "environment %d: an observation had more rows than the caller's block holds (obs_rows = %d) or, in a policy "
+                                  "rollout, than the policy kernels score (%d); the extra rows were not written / scored", e, b->flight.p.obs_rows, BBX_POLICY_MAX_ROWS);
+  return BBX_OK;
+}
+
 // wait for the launch in flight; serve environments that ran out of queued ideals or outgrew the LDS class; surface
 // errors.  Whatever happens, the handle is left with nothing in flight: an error is reported once, not re-raised by
 // every later call, and environments that only needed service (STARVED / SPILL) have been served before the first
 // error of another environment is returned (finish() ends the flight).
 int finish_impl(bbx_batch* b, hipStream_t stream) {
-  bbx_flight& f = b->flight;
   if (b->ps_active && b->ps_mbox) {
-    // nothing owed (the host waited for every step it issued and every status word says OK — the observation-cut bit is not
-    // asked, unlike in mbox_step's scan: bbx_step_obs re-checks the rows itself): tell the waves to go, wait for the kernel,
-    // done — no closing kernel
-    const SeqScan s = scan_seq(b, (uint32_t)(b->ps_target % 16000) + 1u, 0);
-    if (s.all && !s.trouble) {
-      b->ps_active = false;
-      if (int rc = ps_write_ctl(b, true)) return rc;
-      b->ps_mbox = false;
-      // every wave marks its status block when it has stored its environment and left (bbx_fast.h): a spin of a few
-      // microseconds instead of the runtime's wait for the kernel (hundreds, once per episode of a gym loop)
-      const volatile int32_t* w = (const volatile int32_t*)b->h_io;
-      bool gone = false;
-      const auto t0 = std::chrono::steady_clock::now();
-      for (unsigned spins = 0; !gone; spins++) {
-        gone = true;
-        for (int e = 0; e < b->B; e++) gone = gone && (w[(size_t)e * 4 + 2] & 0x40000000);
-        if (!gone && (spins & 255) == 255 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (!gone) HIPCHK(hipStreamSynchronize(b->ps_stream));
-      continue_session(b);
-      b->h_lite.resize((size_t)b->B * 4);
-      memcpy(b->h_lite.data(), b->h_io, (size_t)b->B * 16);
-      for (int e = 0; e < b->B; e++) { b->h_lite[(size_t)e * 4 + 2] &= 0x3fffffff; b->h_head[e] = b->h_lite[(size_t)e * 4 + 1]; }
-      return BBX_OK;                                      // (every status word said OK: nothing to serve, nothing to report)
-    }
+    bool handled = false;
+    if (int rc = mbox_fast_close(b, &handled)) return rc;
+    if (handled) return BBX_OK;
+  }
+  if (b->ps_active) {
+    if (int rc = drain_session(b)) return rc;
+    stream = b->ps_stream;
   }
   int err = BBX_OK;
-  auto note = [&err](int code) { if (err == BBX_OK) err = code; };
-  if (b->ps_active) {                                // a persistent session: stop it; its kernels run in slices until nothing is owed
-    int rc = session_close(b, false, nullptr, true);
-    if (rc) return rc;
-    stream = b->ps_stream;
-    for (int guard = 0;; guard++) {
-      rc = read_lite(b, stream, outputs_pinned(b));
-      if (rc) return rc;
-      bool owed = false;
-      for (int e = 0; e < b->B && !owed; e++) owed = (b->h_lite[(size_t)e * 4] & 0xffff) == BBX_ST_TIMESLICE;
-      if (!owed) break;
-      if (guard >= 100000) return fail(BBX_E_DEVICE, "a persistent session still owes steps after 100000 time slices");
-      rc = session_kernel(b, false, nullptr, true);
-      if (rc) return rc;
-    }
-  }
   for (int round = 0;; round++) {
-    int rc = read_lite(b, stream, outputs_pinned(b));
+    ServeRound r;
+    int rc = serve_round(b, stream, &err, &r);
     if (rc) return rc;
-    rc = collect_events(b);
-    if (rc) return rc;
-    bool again = false;
-    unsigned grow = 0; int grow_env = -1;
-    for (int e = 0; e < b->B; e++) {
-      const int st = b->h_lite[(size_t)e * 4] & 0xffff;
-      if (st == BBX_ST_STARVED && !b->gen_error.empty() && !b->gen_error[e].empty() && b->h_tail[e] - b->h_head[e] <= 0) {
-        if (err == BBX_OK) {
-          const std::string msg = b->gen_error[e];       // the draw this environment is waiting for is the one that failed
-          b->gen_error[e].clear();
-          note(fail(BBX_E_GENERATOR, "%s", msg.c_str()));
-        }
-        continue;
-      }
-      if (st == BBX_ST_GEN_ZERO) { if (err == BBX_OK) note(fail(BBX_E_GENERATOR, "random polynomial cancelled to zero (undefined in the reference)")); }
-      else if (st == BBX_ST_GEN_FAIL) { if (err == BBX_OK) note(fail(BBX_E_GENERATOR, "failed to generate two distinct random monomials after 1000 trials")); }
-      else if ((st == BBX_ST_STARVED || st == BBX_ST_SPILL) && f.policy_rollout) {
-        // (the continuation pass runs right behind the first one; what is still unfinished here cannot be resumed: the
-        // policy arguments belonged to the caller's frame)
-        if (err == BBX_OK) note(fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s)", e, status_name(st)));
-      }
-      else if (st == BBX_ST_STARVED || st == BBX_ST_SPILL) again = true;
-      else if (st == BBX_ST_BAD_ACTION) { if (err == BBX_OK) note(fail(BBX_E_ACTION, "environment %d: %s", e, status_name(st))); }
-      else if (bbx_st_capacity(st) && !b->no_growth) { grow |= 1u << st; if (grow_env < 0) grow_env = e; }
-      else if (st != BBX_ST_OK && err == BBX_OK) {
-        rc = read_headers(b, stream);
-        if (rc) return rc;
-        note(fail(BBX_E_CAPACITY, "environment %d: %s (|G|=%d |P|=%d terms=%d)", e, status_name(st),
-                  b->h_hdr[e].nG, b->h_hdr[e].nP, b->h_hdr[e].arena_used));
-      }
-    }
-    if (grow) {                                       // enlarge what was full; the environments then take the step they stopped at
-      rc = grow_records(b, grow, grow_env, stream);
-      if (rc) { note(rc); break; }
-      if (f.policy_rollout) {                         // (its per-step arrays belonged to the caller's frame: cannot be resumed)
-        note(fail(BBX_E_CAPACITY, "environment %d could not finish its policy rollout (%s); the records have been enlarged, later rollouts have room",
-                  grow_env, status_name(__builtin_ctz(grow))));
-        break;
-      }
-      if (f.device_async && f.p.agent == BBX_AGENT_EXTERNAL && f.async_chain > 1) {
-        // several asynchronous steps with caller-supplied actions were queued behind each other (or replayed from a graph):
-        // the environment stopped at one of them and sat out the rest; the action buffer now holds a later step's actions,
-        // so the step it stopped at cannot be taken for it
-        note(fail(BBX_E_CAPACITY, "environment %d outgrew its records (%s) inside a chain of asynchronous steps with caller-supplied actions and took "
-                                  "none of the chain's later steps; the records have been enlarged, later calls have room", grow_env,
-                  status_name(__builtin_ctz(grow))));
-        break;
-      }
-      again = true;
-    }
-    if (!again) break;
-    if (round > 100000) { note(fail(BBX_E_GENERATOR, "ideal queue starvation did not resolve")); break; }
+    if (r.grow && !grow_and_resume(b, r, stream, &err)) break;
+    if (!r.again && !r.grow) break;
+    if (round > 100000) { rc = fail(BBX_E_GENERATOR, "ideal queue starvation did not resolve"); if (err == BBX_OK) err = rc; break; }
     rc = fill_queues(b, 1, stream);
     if (rc) return rc;
-    rc = enqueue(b, f.p, true, stream);       // continue the rollout where each environment stopped
+    rc = enqueue(b, b->flight.p, true, stream);       // continue the rollout where each environment stopped
     if (rc) return rc;
   }
-  if (err == BBX_OK && f.obs_external)
-    for (int e = 0; e < b->B; e++)
-      if (b->h_lite[(size_t)e * 4] & BBX_LITE_OBS_TRUNC)
-        return fail(BBX_E_CAPACITY, "environment %d: an observation had more rows than the caller's block holds (obs_rows = %d) or, in a policy "
-                                    "rollout, than the policy kernels score (%d); the extra rows were not written / scored", e, f.p.obs_rows, BBX_POLICY_MAX_ROWS);
-  return err;
+  return err == BBX_OK && b->flight.obs_external ? report_obs_trunc(b) : err;
 }
 
 int finish(bbx_batch* b, hipStream_t stream) {
@@ -575,17 +605,19 @@ int quiesce(bbx_batch* b) {
 
 // zero-copy launches: outputs and status words go straight to the pinned host block
 void zc_outputs(bbx_batch* b, BbxParams* p) {
-  p->lite = (int32_t*)b->zc_io_dev;
-  p->rewards = (double*)(b->zc_io_dev + (size_t)b->B * 16);
-  p->rows = (int32_t*)(b->zc_io_dev + (size_t)b->B * 24);
-  p->dones = (uint8_t*)(b->zc_io_dev + (size_t)b->B * 28);
+  const BbxOutLayout o = bbx_out_layout(b->B);
+  p->lite = (int32_t*)(b->zc_io_dev + o.lite);
+  p->rewards = (double*)(b->zc_io_dev + o.rewards);
+  p->rows = (int32_t*)(b->zc_io_dev + o.rows);
+  p->dones = (uint8_t*)(b->zc_io_dev + o.dones);
 }
 
 // the outputs of a host-API launch: already on the host (finish() fetched the whole block)
 int copy_out(bbx_batch* b, double* rewards, uint8_t* dones, int32_t* rows) {
-  if (rewards) memcpy(rewards, b->h_io + (size_t)b->B * 16, (size_t)b->B * 8);
-  if (rows) memcpy(rows, b->h_io + (size_t)b->B * 24, (size_t)b->B * 4);
-  if (dones) memcpy(dones, b->h_io + (size_t)b->B * 28, (size_t)b->B);
+  const BbxOutLayout o = bbx_out_layout(b->B);
+  if (rewards) memcpy(rewards, b->h_io + o.rewards, (size_t)b->B * sizeof(double));
+  if (rows) memcpy(rows, b->h_io + o.rows, (size_t)b->B * sizeof(int32_t));
+  if (dones) memcpy(dones, b->h_io + o.dones, (size_t)b->B);
   return BBX_OK;
 }
 
@@ -969,33 +1001,32 @@ int bbx_reset(bbx_batch* b, const uint8_t* mask, int32_t* rows) {
   if (rc) return rc;
   rc = finish(b, 0);
   if (rc) return rc;
-  if (rows) for (int e = 0; e < b->B; e++) rows[e] = b->h_lite[(size_t)e * 4 + 3];
+  if (rows) for (int e = 0; e < b->B; e++) rows[e] = b->h_lite[e].nP;
   return BBX_OK;
+}
+
+// The parameters of a host step (nsteps = 1) or of an observation of the current state (nsteps = 0): external agent, a new
+// budget, actions and outputs in the pinned block of a zero-copy handle, in the device block otherwise
+static void host_step_params(bbx_batch* b, BbxParams* p, int nsteps, int auto_reset) {
+  fill_params(b, p);
+  p->nsteps = nsteps; p->set_budget = 1; p->agent = BBX_AGENT_EXTERNAL; p->auto_reset = auto_reset;
+  if (b->zero_copy) zc_outputs(b, p); else { p->rewards = b->d_rewards; p->dones = b->d_dones; p->rows = b->d_rows; }
+  if (nsteps) p->actions = b->zero_copy ? b->zc_act_dev : b->d_actions;
 }
 
 static int step_host(bbx_batch* b, const int32_t* actions, double* rewards, uint8_t* dones, int32_t* rows, int auto_reset) {
   if (!b || !actions) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   memcpy(b->h_act, actions, (size_t)b->B * sizeof(int32_t));
-  if (mbox_eligible(b)) {
-    BbxParams p; fill_params(b, &p);
-    p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset;
-    p.actions = b->zc_act_dev; zc_outputs(b, &p);
-    bool used = false;
-    int rc = mbox_step(b, p, &used);
+  BbxParams p; host_step_params(b, &p, 1, auto_reset);
+  bool used = false;                                          // taken through a mailbox session
+  if (mbox_eligible(b)) { if (int rc = mbox_step(b, p, &used)) return rc; }
+  if (!used) {
+    if (!b->zero_copy) HIPCHK(hipMemcpyAsync(b->d_actions, b->h_act, (size_t)b->B * sizeof(int32_t), hipMemcpyHostToDevice, 0));
+    int rc = launch(b, p, 0);
+    if (!rc) rc = finish(b, 0);
     if (rc) return rc;
-    if (used) { b->mbox_epoch = b->api_epoch; return copy_out(b, rewards, dones, rows); }
   }
-  BbxParams p; fill_params(b, &p);
-  p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset;
-  if (b->zero_copy) { p.actions = b->zc_act_dev; zc_outputs(b, &p); }
-  else {
-    HIPCHK(hipMemcpyAsync(b->d_actions, b->h_act, (size_t)b->B * sizeof(int32_t), hipMemcpyHostToDevice, 0));
-    p.actions = b->d_actions; p.rewards = b->d_rewards; p.dones = b->d_dones; p.rows = b->d_rows;
-  }
-  int rc = launch(b, p, 0);
-  if (!rc) rc = finish(b, 0);
-  if (rc) return rc;
   b->mbox_epoch = b->api_epoch;
   return copy_out(b, rewards, dones, rows);
 }
@@ -1007,14 +1038,37 @@ int bbx_step_autoreset(bbx_batch* b, const int32_t* actions, double* rewards, ui
   return step_host(b, actions, rewards, dones, rows, 1);
 }
 
-// (re)size the padded device observation block
-static int ensure_obs_block(bbx_batch* b, int rows_cap) {
-  if (b->obs_rows_cap >= (size_t)rows_cap) return BBX_OK;
-  const size_t cols = (size_t)2 * b->nvars * b->k;
-  if (b->d_obs) HIPCHK(hipFree(b->d_obs));
-  b->d_obs = nullptr; b->obs_rows_cap = 0;
-  HIPCHK(hipMalloc((void**)&b->d_obs, (size_t)b->B * rows_cap * cols * sizeof(int32_t)));
-  b->obs_rows_cap = rows_cap;
+// (re)size the padded observation block to rows_cap rows per environment, first use and growth alike.  pinned: the block of
+// zero-copy handles, which the kernels write through its device address (h_zobs / zc_obs_dev); otherwise device memory (d_obs)
+static int ensure_obs_block(bbx_batch* b, bool pinned, size_t rows_cap) {
+  size_t& cap = pinned ? b->zobs_rows_cap : b->obs_rows_cap;
+  if (cap >= rows_cap) return BBX_OK;
+  const size_t bytes = (size_t)b->B * rows_cap * 2 * b->nvars * b->k * sizeof(int32_t);
+  cap = 0;
+  if (pinned) {
+    if (b->h_zobs) (void)hipHostFree(b->h_zobs);
+    b->h_zobs = nullptr;
+    HIPCHK(hipHostMalloc((void**)&b->h_zobs, bytes, hipHostMallocCoherent | hipHostMallocMapped));
+    HIPCHK(hipHostGetDevicePointer((void**)&b->zc_obs_dev, b->h_zobs, 0));
+  } else {
+    if (b->d_obs) HIPCHK(hipFree(b->d_obs));
+    b->d_obs = nullptr;
+    HIPCHK(hipMalloc((void**)&b->d_obs, bytes));
+  }
+  cap = rows_cap;
+  return BBX_OK;
+}
+
+// (re)size the ragged block bbx_step_obs hands to the caller, h_obs (pinned: [B + 1 offsets][values]), to `need` words and
+// more; device: also the pack kernel's output, d_obs_packed
+static int ensure_obs_packed(bbx_batch* b, bool device, size_t need) {
+  if (need <= b->obs_packed_cap) return BBX_OK;
+  if (b->d_obs_packed) (void)hipFree(b->d_obs_packed);
+  if (b->h_obs) (void)hipHostFree(b->h_obs);
+  b->d_obs_packed = nullptr; b->h_obs = nullptr; b->obs_packed_cap = 0;
+  if (device) HIPCHK(hipMalloc((void**)&b->d_obs_packed, need * 2 * sizeof(int32_t)));
+  HIPCHK(hipHostMalloc((void**)&b->h_obs, need * 2 * sizeof(int32_t), hipHostMallocDefault));
+  b->obs_packed_cap = need * 2;
   return BBX_OK;
 }
 
@@ -1024,18 +1078,10 @@ int bbx_step_obs(bbx_batch* b, const int32_t* actions, int auto_reset, double* r
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   const int cols = 2 * b->nvars * b->k;
   const bool zc = b->zero_copy;
-  int rc;
-  if (zc) {
-    if (!b->h_zobs) {
-      b->zobs_rows_cap = 128;
-      HIPCHK(hipHostMalloc((void**)&b->h_zobs, (size_t)b->B * b->zobs_rows_cap * cols * sizeof(int32_t), hipHostMallocCoherent | hipHostMallocMapped));
-      HIPCHK(hipHostGetDevicePointer((void**)&b->zc_obs_dev, b->h_zobs, 0));
-    }
-  } else {
-    rc = ensure_obs_block(b, b->obs_rows_cap ? (int)b->obs_rows_cap : 128);
-    if (rc) return rc;
-    if (!b->d_obs_off) HIPCHK(hipMalloc((void**)&b->d_obs_off, ((size_t)b->B + 1) * sizeof(int32_t)));
-  }
+  size_t& cap = zc ? b->zobs_rows_cap : b->obs_rows_cap;    // rows per environment of the padded block
+  int rc = ensure_obs_block(b, zc, cap ? cap : 128);
+  if (rc) return rc;
+  if (!zc && !b->d_obs_off) HIPCHK(hipMalloc((void**)&b->d_obs_off, ((size_t)b->B + 1) * sizeof(int32_t)));
   if (actions) {
     memcpy(b->h_act, actions, (size_t)b->B * sizeof(int32_t));
     if (!zc) HIPCHK(hipMemcpyAsync(b->d_actions, b->h_act, (size_t)b->B * sizeof(int32_t), hipMemcpyHostToDevice, 0));
@@ -1043,12 +1089,8 @@ int bbx_step_obs(bbx_batch* b, const int32_t* actions, int auto_reset, double* r
   for (int attempt = 0;; attempt++) {
     // (the parameters are formed per attempt: the first one may have enlarged the records — another array, another layout —
     // and a second attempt with the first one's parameters stepped the freed copy: found by scripts/fuzz_gym.py, round 4)
-    BbxParams p; fill_params(b, &p);
-    p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = auto_reset ? 1 : 0;
-    if (zc) zc_outputs(b, &p); else { p.rewards = b->d_rewards; p.dones = b->d_dones; p.rows = b->d_rows; }
-    if (actions && !attempt) { p.actions = zc ? b->zc_act_dev : b->d_actions; p.nsteps = 1; }
-    else { p.nsteps = 0; p.actions = nullptr; }             // observation of the current state only / the step is done: only rewrite the observation
-    const size_t cap = zc ? b->zobs_rows_cap : b->obs_rows_cap;
+    // a later attempt, like a call without actions: the step is done, only (re)write the observation
+    BbxParams p; host_step_params(b, &p, actions && !attempt ? 1 : 0, auto_reset ? 1 : 0);
     p.obs = zc ? b->zc_obs_dev : b->d_obs; p.obs_rows = (int)cap; p.obs_fill = 0; p.obs_every_step = 0;
     bool used = false;
     if (!attempt && actions && zc && mbox_eligible(b)) {    // a step of a loop: through the resident kernel's mailbox
@@ -1064,34 +1106,20 @@ int bbx_step_obs(bbx_batch* b, const int32_t* actions, int auto_reset, double* r
     }
     if (!attempt) copy_out(b, rewards, dones, rows);
     int maxr = 0; size_t total = 0;
-    for (int e = 0; e < b->B; e++) { const int r = b->h_lite[(size_t)e * 4 + 3]; maxr = r > maxr ? r : maxr; total += (size_t)r; }
+    for (int e = 0; e < b->B; e++) { const int r = b->h_lite[e].nP; maxr = r > maxr ? r : maxr; total += (size_t)r; }
     if ((size_t)maxr > cap) {                               // some pair set outgrew the block: enlarge it and write again
       size_t ncap = cap;
       while (ncap < (size_t)maxr) ncap *= 2;
-      if (zc) {
-        (void)hipHostFree(b->h_zobs); b->h_zobs = nullptr;
-        HIPCHK(hipHostMalloc((void**)&b->h_zobs, (size_t)b->B * ncap * cols * sizeof(int32_t), hipHostMallocCoherent | hipHostMallocMapped));
-        HIPCHK(hipHostGetDevicePointer((void**)&b->zc_obs_dev, b->h_zobs, 0));
-        b->zobs_rows_cap = ncap;
-      } else {
-        rc = ensure_obs_block(b, (int)ncap);
-        if (rc) return rc;
-      }
+      rc = ensure_obs_block(b, zc, ncap);
+      if (rc) return rc;
       continue;
     }
-    const size_t need = (total ? total : 1) * (size_t)cols + (size_t)b->B + 1;
-    if (need > b->obs_packed_cap) {
-      if (b->d_obs_packed) (void)hipFree(b->d_obs_packed);
-      if (b->h_obs) (void)hipHostFree(b->h_obs);
-      b->d_obs_packed = nullptr; b->h_obs = nullptr; b->obs_packed_cap = 0;
-      if (!zc) HIPCHK(hipMalloc((void**)&b->d_obs_packed, need * 2 * sizeof(int32_t)));
-      HIPCHK(hipHostMalloc((void**)&b->h_obs, need * 2 * sizeof(int32_t), hipHostMallocDefault));
-      b->obs_packed_cap = need * 2;
-    }
+    rc = ensure_obs_packed(b, !zc, (total ? total : 1) * (size_t)cols + (size_t)b->B + 1);
+    if (rc) return rc;
     // pinned layout: [B + 1 offsets (rows)] [total * cols values]; the offsets are a host-side prefix sum of the rows
     // just fetched (the device computes the same ones for its pack kernel)
     b->h_obs[0] = 0;
-    for (int e = 0; e < b->B; e++) b->h_obs[e + 1] = b->h_obs[e] + b->h_lite[(size_t)e * 4 + 3];
+    for (int e = 0; e < b->B; e++) b->h_obs[e + 1] = b->h_obs[e] + b->h_lite[e].nP;
     if (total && zc) {                                      // the padded block is already in host memory: squeeze it here
       for (int e = 0; e < b->B; e++)
         memcpy(b->h_obs + b->B + 1 + (size_t)b->h_obs[e] * cols, b->h_zobs + (size_t)e * cap * cols,
@@ -1182,12 +1210,7 @@ int bbx_obs(bbx_batch* b, int32_t* out, int max_rows, int fill) {
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   const size_t cols = (size_t)2 * b->nvars * b->k;
   const size_t need = (size_t)b->B * max_rows * cols;
-  if (b->obs_rows_cap < (size_t)max_rows) {
-    if (b->d_obs) HIPCHK(hipFree(b->d_obs));
-    b->d_obs = nullptr;
-    HIPCHK(hipMalloc((void**)&b->d_obs, need * sizeof(int32_t)));
-    b->obs_rows_cap = max_rows;
-  }
+  if (int rc = ensure_obs_block(b, false, (size_t)max_rows)) return rc;
   BbxParams p; fill_params(b, &p);
   p.nsteps = 0; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 0;
   p.obs = b->d_obs; p.obs_rows = max_rows; p.obs_fill = fill; p.trace = nullptr;

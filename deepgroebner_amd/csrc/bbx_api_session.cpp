@@ -214,7 +214,7 @@ int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external, bo
   const bool admits = !capturing && session_admits(b, p, device_async);
   LaunchKind kind = capturing ? L_CAPTURE : L_PLAIN;
   if (b->ps_active) {
-    if (admits && !b->ps_mbox && session_same_policy(b, p) && session_same_call(b->ps_p, p) && b->ps_target + p.nsteps < (1ll << 30)) kind = L_SESSION_JOIN;
+    if (admits && !b->ps_mbox && session_same_policy(b, p) && session_same_call(b->ps_p, p) && b->ps_target + p.nsteps < BBX_LITE_BUDGET_BOUND) kind = L_SESSION_JOIN;
     else {                                  // something else: the session ends; what follows is ordered behind it
       rc = session_close(b, !admits, stream, false);
       if (rc) return rc;
@@ -246,7 +246,7 @@ bool mbox_eligible(const bbx_batch* b) {
 int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
   *used = false;
   int rc;
-  const bool join = b->ps_active && b->ps_mbox && session_same_call(b->ps_p, p) && b->ps_target < (1ll << 30);
+  const bool join = b->ps_active && b->ps_mbox && session_same_call(b->ps_p, p) && b->ps_target < BBX_LITE_BUDGET_BOUND;
   if (!join) {
     // a session pays when the steps come in a row (a loop); a caller that does something else on the handle between steps
     // (value() per step, pg.py:461-465) is served by one launch per step as before: four steps in a row start a session
@@ -260,7 +260,7 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
     if (!rc) rc = settle(b);
     if (!rc) rc = fill_queues(b, 1, nullptr);
     if (rc) return rc;
-    for (int e = 0; e < b->B; e++) ((volatile int32_t*)b->h_io)[(size_t)e * 4] = 0;
+    clear_pinned_seq(b);
     b->ps_p = p; b->ps_p.ctl = nullptr; b->ps_p.policy = nullptr;
     b->ps_mbox = true; b->ps_active = true; b->ps_target = 1; b->ps_sessions++;
     b->ps_recent.clear();
@@ -278,8 +278,7 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
   }
   // the step's sequence number on every environment's status word — or something else to look at (here an observation cut
   // for lack of rows is trouble too: finish() then reports it)
-  const uint32_t want = (uint32_t)(b->ps_target % 16000) + 1u;
-  const volatile int32_t* w = (const volatile int32_t*)b->h_io;
+  const int want = bbx_lite_seq_of((int)b->ps_target);
   const auto t0 = std::chrono::steady_clock::now();
   SeqScan s{false, false}; bool timed_out = false;
   for (unsigned spins = 0;; spins++) {
@@ -291,7 +290,7 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
       if (hipStreamQuery(b->ps_stream) == hipSuccess) {
         if (scan_seq(b, want, 0).all) { s.all = true; break; }
         bool stopped = false;                                // an environment that left with something to report ends the mailbox
-        for (int e = 0; e < b->B; e++) { const uint32_t st = (uint32_t)w[(size_t)e * 4] & 0xffffu; stopped = stopped || (st != BBX_ST_OK && st != BBX_ST_TIMESLICE); }
+        for (int e = 0; e < b->B; e++) { const int st = bbx_lite_status(pinned_lite(b)[e].word0); stopped = stopped || (st != BBX_ST_OK && st != BBX_ST_TIMESLICE); }
         if (stopped) break;
         rc = session_kernel(b, false, nullptr, true);
         if (rc) return rc;
@@ -302,8 +301,7 @@ int mbox_step(bbx_batch* b, BbxParams& p, bool* used) {
   *used = true;
   if (s.all && !s.trouble) {
     b->mbox_misses = 0;
-    b->h_lite.resize((size_t)b->B * 4);
-    memcpy(b->h_lite.data(), b->h_io, (size_t)b->B * 16);
+    take_lite(b);                                           // (h_head too: device-drawn ideals, nobody consumes it — fill_queues)
     return BBX_OK;
   }
   // not through the mailbox (an error status, rows beyond the caller's block, an environment that left the class, no answer):

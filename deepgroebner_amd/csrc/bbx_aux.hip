@@ -310,7 +310,7 @@ __global__ void bbx_gather_lite_kernel(const char* recs, uint32_t rec_bytes, int
   int env = blockIdx.x * blockDim.x + threadIdx.x;
   if (env >= B) return;
   const BbxHdr* h = (const BbxHdr*)(recs + (size_t)env * rec_bytes);
-  out[env] = make_int4(h->status, h->q_head, h->budget, h->nP);
+  out[env] = make_int4(bbx_lite_word0(h->status, 0, 0), h->q_head, h->budget, h->nP);
 }
 extern "C" int bbx_launch_gather_lite(const char* recs, uint32_t rec_bytes, int B, void* out, hipStream_t stream) {
   hipLaunchKernelGGL(bbx_gather_lite_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, B, (int4*)out);

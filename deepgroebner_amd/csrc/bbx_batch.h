@@ -108,7 +108,7 @@ struct bbx_batch : bbx_config {
   std::vector<uint32_t> h_q;          // host mirror of the ideal queue
   std::vector<int32_t> h_tail, h_head;
   std::vector<BbxHdr> h_hdr;
-  std::vector<int32_t> h_lite;        // per environment {status, q_head, budget, nP}: what is polled after every launch
+  std::vector<BbxLite> h_lite;        // the status block (bbx_common.h) as the last launch left it: take_lite
   bool q_dirty = true;
   std::vector<uint8_t> q_dirty_env;
   // ideals drawn on the device (binomial distributions): the table the kernels read, the per-environment engine state
@@ -120,8 +120,8 @@ struct bbx_batch : bbx_config {
   char* d_recs = nullptr;
   uint32_t* d_q = nullptr;
   int32_t* d_tail = nullptr;
-  // one device block polled after every launch: lite[B][4] {status, q_head, budget, |P|} | rewards f64[B] | rows i32[B] |
-  // dones u8[B]; the kernels write it themselves, the host fetches it with ONE copy into pinned memory
+  // one device block polled after every launch (bbx_out_layout, bbx_common.h: status block | rewards | rows | dones); the
+  // kernels write it themselves, the host fetches it with ONE copy into pinned memory
   char* d_out = nullptr; int32_t* d_lite = nullptr; double* d_rewards = nullptr; int32_t* d_rows = nullptr; uint8_t* d_dones = nullptr;
   char* h_io = nullptr; size_t io_bytes = 0;      // pinned mirror of d_out
   int32_t* h_act = nullptr;                       // pinned staging of host actions
@@ -195,19 +195,23 @@ int settle(bbx_batch* b);            // finish() whatever is in flight (the entr
 int quiesce(bbx_batch* b);           // the read-only introspection calls: close a session and wait, WITHOUT finishing
 // the outputs and status words of the call in flight are in the pinned block (zero-copy host steps, a mailbox session)
 inline bool outputs_pinned(const bbx_batch* b) { return b->zero_copy && b->flight.p.lite == (int32_t*)b->zc_io_dev; }
-// The status words of the pinned block (the first of every environment's four) against sequence number `want` (bits 17..):
-// all — every one carries it; trouble — one that carries it reports a status other than OK, or one of the bits `flags`.
+// The status block in pinned memory (bbx_common.h BbxLite), as the host watches it while a kernel may still be writing
+inline volatile BbxLite* pinned_lite(const bbx_batch* b) { return (volatile BbxLite*)b->h_io; }
+// Its status words against sequence number `want`: all — every one carries it; trouble — one that carries it reports a
+// status other than OK, or one of the bits `flags`.
 struct SeqScan { bool all, trouble; };
-inline SeqScan scan_seq(const bbx_batch* b, uint32_t want, uint32_t flags) {
-  const volatile int32_t* w = (const volatile int32_t*)b->h_io;
+inline SeqScan scan_seq(const bbx_batch* b, int want, int32_t flags) {
+  const volatile BbxLite* w = pinned_lite(b);
   SeqScan s{true, false};
   for (int e = 0; e < b->B; e++) {
-    const uint32_t v = (uint32_t)w[(size_t)e * 4];
-    if ((v >> 17) != want) s.all = false;
-    else if ((v & 0xffffu) != BBX_ST_OK || (v & flags)) s.trouble = true;
+    const int32_t v = w[e].word0;
+    if (bbx_lite_seq(v) != want) s.all = false;
+    else if (bbx_lite_status(v) != BBX_ST_OK || (v & flags)) s.trouble = true;
   }
   return s;
 }
+// the words the host is going to watch start out cleared (no step has sequence number 0)
+inline void clear_pinned_seq(const bbx_batch* b) { for (int e = 0; e < b->B; e++) pinned_lite(b)[e].word0 = 0; }
 inline bool traced(const bbx_batch* b) { return b->d_trace && b->trace_cap >= 1; }
 // the register/LDS-resident class, lean and untraced: what sessions, mailboxes and the fused policy step run on
 inline bool lean_fast(const bbx_batch* b) { return b->cls == BbxClass::FAST && !b->accounting && !traced(b); }
@@ -226,6 +230,7 @@ void fill_params(bbx_batch* b, BbxParams* p);
 int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream);
 const char* status_name(int s);
 // bbx_api.cpp
+void take_lite(bbx_batch* b);         // the pinned block's status records -> h_lite, the queue heads they report -> h_head
 int fill_queues(bbx_batch* b, int min_avail = 1, hipStream_t stream = 0);
 int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream);   // the kernels of one logical launch
 int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows,

@@ -476,7 +476,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     // keep resuming an environment that has no step left
     if (was_transient && status == BBX_ST_OK && lane == 0) {
       ghdr->status = BBX_ST_OK;
-      if (p.lite) p.lite[4 * (size_t)env] &= ~0xffff;
+      if (p.lite) p.lite[4 * (size_t)env] &= ~BBX_LITE_STATUS_MASK;
     }
     return;
   }
@@ -817,7 +817,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     h->budget = budget; h->rollout_pos = rollout_pos; h->done_last = done_last; h->alg_bytes = alg_bytes;
     h->vret = vret; h->vdisc = vdisc; h->obs_trunc = obs_trunc;
     if (pz.sess_target) h->sess_done = pz.sess_target - budget;
-    if (pz.lite) *(int4*)(pz.lite + 4 * (size_t)env) = make_int4(status | (obs_trunc ? BBX_LITE_OBS_TRUNC : 0), q_head, budget, nP);
+    if (pz.lite) *(int4*)(pz.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(status, obs_trunc, 0), q_head, budget, nP);
     if (pz.value_mode && pz.values) pz.values[env] = vret;
     if (!handoff) {
       if (pz.rewards && (steps_done > 0 || pz.pass == 0)) pz.rewards[env] = last_reward;

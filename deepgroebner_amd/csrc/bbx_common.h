@@ -26,6 +26,7 @@
 // operate on it directly): slot s (= variable s) lives in word s/2, half s%2; the LAST slot holds
 // the total degree.  W=2 serves n<=3 variables (8 B / monomial), W=4 serves n<=7 (16 B).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define BBX_P 32003u
@@ -52,7 +53,8 @@ enum {
   BBX_ST_GEN_ZERO = 11,     // a random polynomial cancelled to zero (undefined in the reference)
   BBX_ST_POLY_LIMIT = 12,   // a basis element would have more than 65535 terms (plen[] is 16 bits): a hard limit
   BBX_ST_TIMESLICE = 14,    // transient: a kernel of a persistent session ended its time slice with steps still owed (a kernel
-                            // that runs longer than ~100 ms is clocked down to half speed; sessions run in slices of 40 ms)
+                            // that runs longer than ~100 ms is clocked down to half speed; sessions run in slices of 10 ms:
+                            // PS_SLICE_TICKS, bbx_api_session.cpp)
   BBX_ST_SPILL = 8,         // transient: the state outgrew the LDS-resident class; the HBM-resident pass of the
                             // same launch sequence continues this environment
 };
@@ -63,9 +65,39 @@ enum {
 // its steps to the environment's budget instead of replacing it, so no step is lost across asynchronous launches.
 static inline BBX_HD int bbx_st_capacity(int st) { return st == BBX_ST_G_FULL || st == BBX_ST_P_FULL || st == BBX_ST_ARENA_FULL || st == BBX_ST_POLY_TOO_LONG; }
 
-// the status word of the `lite` block ({status, q_head, budget, |P|} per environment, polled by the host after a
-// launch) carries this flag on top of the status code: BbxHdr.obs_trunc != 0
+// The status block ("lite"): what every step kernel leaves per environment and the host reads after every launch.
+//   word0   bits 0..15 the status (BBX_ST_*), bit 16 BBX_LITE_OBS_TRUNC (BbxHdr.obs_trunc != 0), bits 17.. a sequence number
+//   budget  the steps still owed; BBX_LITE_GONE on top of it once a mailbox session's wave has left
+// No sequence number (the host waits through the runtime): ONE 16-byte store.  With one (BbxParams::done_seq, mailbox sessions:
+// the block is pinned host memory the host spins on) word0 goes LAST: the other three words and every output (rewards, dones,
+// rows, observation) as plain stores, __threadfence_system(), then word0 as a system-scope release store.  Step or launch n
+// carries bbx_lite_seq_of(n): never 0, which is what the host clears the words to before it watches them.
+// The gone mark says "this wave has stored its environment and left": what the host waits for when it closes a mailbox session,
+// instead of the runtime's completion signal.  A release store of its own, the wave's last, behind word0: the host, seeing it,
+// may begin the next session at once, and a word0 arriving behind the mark carried this session's last sequence number into
+// the next one (whose first step then returned the OLD step's outputs: found by scripts/fuzz_gym.py, round 4).
+struct BbxLite { int32_t word0, q_head, budget, nP; };
+static_assert(sizeof(BbxLite) == 16, "the kernels store a BbxLite as one int4");
+#define BBX_LITE_STATUS_MASK 0xffff
 #define BBX_LITE_OBS_TRUNC 0x10000
+#define BBX_LITE_SEQ_SHIFT 17
+#define BBX_LITE_SEQ_MOD 16000       /* sequence numbers are 1..16000: (16000 + 1) << 17 must stay below 2^31 (a round number under 16383) */
+#define BBX_LITE_GONE 0x40000000     /* on the budget word */
+#define BBX_LITE_BUDGET_BOUND (1 << 30)   /* a session issues fewer steps than this in all (launch_kind, mbox_step) */
+static_assert(((long long)(BBX_LITE_SEQ_MOD + 1) << BBX_LITE_SEQ_SHIFT) <= 0x7fffffffll, "word0 stays a positive int32_t");
+static_assert(BBX_LITE_GONE >= BBX_LITE_BUDGET_BOUND && BBX_LITE_GONE > 0, "the gone mark lies above every session budget");
+static inline BBX_HD int32_t bbx_lite_word0(int status, int trunc, int seq) { return status | (trunc ? BBX_LITE_OBS_TRUNC : 0) | (seq << BBX_LITE_SEQ_SHIFT); }
+static inline BBX_HD int bbx_lite_status(int32_t w) { return w & BBX_LITE_STATUS_MASK; }
+static inline BBX_HD int bbx_lite_seq(int32_t w) { return (int)((uint32_t)w >> BBX_LITE_SEQ_SHIFT); }
+static inline BBX_HD int bbx_lite_seq_of(int n) { return (n % BBX_LITE_SEQ_MOD) + 1; }   // n >= 0
+
+// The host API's output block, on the device and in its pinned mirror: BbxLite[B] | rewards f64[B] | rows i32[B] | dones u8[B]
+// (16 | 8 | 4 | 1 bytes per environment: every array aligned to its element for any B); byte offsets and the total
+struct BbxOutLayout { size_t lite, rewards, rows, dones, bytes; };
+static inline BBX_HD BbxOutLayout bbx_out_layout(size_t B) {
+  const size_t rw = B * sizeof(BbxLite), ro = rw + B * sizeof(double), dn = ro + B * sizeof(int32_t);
+  return {0, rw, ro, dn, dn + B};
+}
 
 struct BbxHdr {             // 128 bytes
   int32_t nG, nP, arena_used, status;
@@ -178,9 +210,8 @@ struct BbxParams {
   int32_t pass;             // 0: primary launch; 1: follow-up launch serving only environments with work left
   const uint16_t* inv_table; // [32003] inverses in GF(32003) (L2-resident), binomial class
   const uint32_t* gen;      // device-side generator table (BBX_GEN_* layout below) or null: ideals come from the queue
-  int32_t* lite;            // [B][4] {status, q_head, budget, |P|}: what the host polls after a launch, or null
-  int32_t done_seq;         // != 0: lite lives in host memory and the host spins on it — the status word carries this
-                            // number in bits 17.., written behind a system-scope fence after every other output
+  int32_t* lite;            // BbxLite[B] (above), as words: what the host polls after a launch, or null
+  int32_t done_seq;         // != 0: lite lives in host memory and the host spins on it — word0 carries this sequence number
   BbxTraceRec* trace;       // [B, trace_stride] or null
   int32_t trace_stride;
   // persistent sessions (bbx_persistent; register/LDS-resident class): asynchronous rollouts queued behind each other do not

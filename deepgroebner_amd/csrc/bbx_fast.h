@@ -729,7 +729,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
           int32_t* lw = cm->lite + 4 * (size_t)env;
           lw[1] = q_head; lw[2] = budget; lw[3] = nP;
           __threadfence_system();
-          __hip_atomic_store(lw, BBX_ST_OK | (obs_trunc ? BBX_LITE_OBS_TRUNC : 0) | (((taken % 16000) + 1) << 17), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+          __hip_atomic_store(lw, bbx_lite_word0(BBX_ST_OK, obs_trunc, bbx_lite_seq_of(taken)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
       }
     }
@@ -1275,23 +1275,16 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       if (rws) rws[env] = nP;
     }
     if (cz->lite) {
-      // the host may be spinning on this word (done_seq): everything else this wave wrote — rewards, rows, the observation
-      // block in host memory — has to be visible first
       // (a mailbox session: the sequence number of the last step this environment took, as its per-step publication left it)
-      const int seq = (PERSIST && cz->mbox) ? (h->sess_done % 16000) + 1 : cz->done_seq;
+      const int seq = (PERSIST && cz->mbox) ? bbx_lite_seq_of(h->sess_done) : cz->done_seq;
       int32_t* lw = cz->lite + 4 * (size_t)env;
-      const int word0 = status | (trunc_all ? BBX_LITE_OBS_TRUNC : 0) | (seq << 17);
-      if (seq) {                                       // the word the host watches goes last and alone, behind a system-scope fence
-        // (a mailbox session: bit 30 of the budget word says "this wave has left and stored its environment" — what the host
-        // waits for when it closes the session, instead of the runtime's completion signal)
+      const int word0 = bbx_lite_word0(status, trunc_all, seq);
+      if (seq) {                                       // the host may be spinning on word0: the store forms of bbx_common.h, BbxLite
         lw[1] = q_head; lw[2] = budget; lw[3] = nP;
         __threadfence_system();
         __hip_atomic_store(lw, word0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        // (the mark is this wave's LAST store: the host, seeing it, clears the status words and may begin the next session at once —
-        // a status word arriving behind the mark carried this session's last sequence number into the next one, where a session of
-        // one step has the number the next session's first step waits for: the host then returned the OLD step's outputs.  Found
-        // by scripts/fuzz_gym.py mixing bbx_step_obs and bbx_step calls.)
-        if (PERSIST && cz->mbox) __hip_atomic_store(lw + 2, budget | 0x40000000, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        // (the gone mark, this wave's LAST store)
+        if (PERSIST && cz->mbox) __hip_atomic_store(lw + 2, budget | BBX_LITE_GONE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       } else *(int4*)lw = make_int4(word0, q_head, budget, nP);
     }
   }

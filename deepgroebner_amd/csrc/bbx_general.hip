@@ -242,7 +242,7 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
     h->total_additions = total_adds; h->episodes = episodes; h->zero_reductions = zero_red; h->steps_done = steps_done;
     h->budget = budget; h->rollout_pos = rollout_pos; h->done_last = done_last; h->alg_bytes = alg_bytes;
     h->vret = vret; h->vdisc = vdisc; h->obs_trunc = obs_trunc;
-    if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(status | (obs_trunc ? BBX_LITE_OBS_TRUNC : 0), q_head, budget, nP);
+    if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(status, obs_trunc, 0), q_head, budget, nP);
     if (p.value_mode && p.values) p.values[env] = vret;
     if (!handoff) {
       if (p.rewards && (steps_done > 0 || p.pass == 0)) p.rewards[env] = last_reward;

@@ -1133,7 +1133,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
       h->total_steps = st->total_steps; h->total_additions = st->total_adds; h->episodes = st->episodes; h->zero_reductions = st->zero_red;
       h->steps_done = steps_done; h->budget = budget; h->rollout_pos = st->rollout_pos; h->done_last = done_last; h->alg_bytes = st->alg_bytes;
       h->vret = st->vret; h->vdisc = st->vdisc; h->obs_trunc = obs_trunc;
-      if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(status | (obs_trunc ? BBX_LITE_OBS_TRUNC : 0), q_head, budget, nP);
+      if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(status, obs_trunc, 0), q_head, budget, nP);
       if (p.value_mode && p.values) p.values[env] = st->vret;
       if (p.rewards && (steps_done > 0 || p.pass == 0)) p.rewards[env] = st->last_reward;
       if (p.dones) p.dones[env] = (uint8_t)((done_last || (nP == 0 && !need_reset)) ? 1 : 0);

@@ -176,3 +176,29 @@ def test_prepared_sizes_follow_the_documented_layout(ffi_):
         assert dll.bbx_pmlp2_prepared_floats(*bad) == -5, bad
     for bad in ((0, 64, 64, 64), (65, 64, 64, 64), (12, 0, 64, 64), (12, 129, 64, 64), (12, 64, 0, 64), (12, 64, 129, 64), (12, 64, 64, 0), (12, 64, 64, 129)):
         assert dll.bbx_pmlp3_prepared_floats(*bad) == -5, bad
+
+
+def test_status_block_definition(tmp_path):
+    """The status block every kernel class and the host API share (bbx_common.h: BbxLite, bbx_lite_*, bbx_out_layout), through
+    a stand-alone host program that includes that header only.  The output block against the documented layout, restated
+    here — status block 16 B | rewards 8 B | rows 4 B | dones 1 B per environment; the status word round-tripped over every
+    status, both truncation values and the sequence numbers on either side of the wrap, against status | trunc << 16 | seq << 17."""
+    import subprocess
+    exe = str(tmp_path / "lite_block_check")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "deepgroebner_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "lite_block_check.cpp"), "-o", exe])
+    p = subprocess.run([exe], stdout=subprocess.PIPE, text=True)
+    assert p.returncode == 0, p.stdout[-400:]
+    lines = [ln.split() for ln in p.stdout.splitlines()]
+    layouts = {int(ln[1]): [int(v) for v in ln[2:]] for ln in lines if ln[0] == "layout"}
+    assert sorted(layouts) == [1, 8, 64, 4096]
+    for B, got in layouts.items():
+        assert got == [0, 16 * B, 24 * B, 28 * B, 29 * B], (B, got)
+    assert ["seq_of", "1", "16000", "1", str(((1 << 30) - 1) % 16000 + 1)] in lines
+    words = [[int(v) for v in ln[1:]] for ln in lines if ln[0] == "word0"]
+    assert {w[0] for w in words} == set(range(15)) and {w[1] for w in words} == {0, 1} and {w[2] for w in words} == {1, 16000}
+    assert len(words) == 15 * 2 * 4                          # (1, 16000, seq_of(15999) = 16000, seq_of(16000) = 1)
+    for status, trunc, seq, w, status2, trunc2, seq2 in words:
+        assert w == status | (trunc << 16) | (seq << 17) and 0 <= w < 2 ** 31
+        assert (status2, trunc2, seq2) == (status, trunc, seq)
+    assert ["gone", "1", str((1 << 30) - 1)] in lines and ["bad", "0"] in lines

@@ -359,3 +359,98 @@ def test_policy_step_session_leaves_the_new_episodes_block():
         live = torch.arange(R, device="cuda")[None, :] < rows2[:, None]
         assert torch.equal(obs[live], obs2[live]), t
     assert ended > 50                                           # (episodes did end inside the calls)
+
+
+# ---- the status block's sequence number across its wrap ------------------------------------------------------------------
+# A host step is recognised by the sequence number in its status word (bbx_common.h: bbx_lite_seq_of), which starts over
+# after BBX_LITE_SEQ_MOD steps.  The two tests below step across that point, where a number is met for the second time.
+# Wall time: the oracle's side and the loop around it are 0.4 s (B = 1), 0.7 s (B = 3; 1.2 s with observations) and 2.6 s
+# (B = 16) on a host core; the device's side (16 k steps of 10-30 us) has not been measured yet — no MI355X could be had when
+# the tests were written; profiles/ holds the figure once it is.
+SEQ_MOD = 16000                                              # BBX_LITE_SEQ_MOD
+WRAP_STEPS = SEQ_MOD + 50
+
+
+def _hash_actions(B, T):
+    """ffi.agent_hash(e + 1, t) for every t < T, e < B (the action choice of the mailbox test above), in one numpy pass."""
+    z = ((np.arange(B, dtype=np.uint64)[None, :] + np.uint64(1)) << np.uint64(32)) | np.arange(T, dtype=np.uint64)[:, None]
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(32)).astype(np.int64)
+
+
+def _steps_across_the_wrap(B, with_obs, one_session):
+    """Auto-reset host steps in a row, every step's reward, done flag and row count against the oracle; with_obs: through
+    bbx_step_obs (env.step), the observation compared as well; otherwise through bbx_step_autoreset.  WRAP_STEPS of them —
+    one_session: as many as it takes (WRAP_STEPS + 24 as a rule) until ONE session has taken more than SEQ_MOD in a row, so
+    that its count did cross the wrap wherever it began (a host thread that loses the CPU for 3 ms ends a mailbox session, and
+    the next one counts from 1 again: mbox_step)."""
+    from deepgroebner_amd import VecLeadMonomialsEnv, _ffi
+    bo = ffi.load("bo")
+    k = 2
+    env = VecLeadMonomialsEnv(DIST, batch=B, k=k)
+    env.seed(np.arange(B) + 77); env.accounting(False)
+    env.reset()
+    oracles = []
+    for e in range(B):
+        o = bo.env(DIST); o.seed(77 + e); o.reset(); oracles.append(o)
+    hashes = _hash_actions(B, 3 * WRAP_STEPS)
+    assert hashes[5, B - 1] == ffi.agent_hash(B, 5)
+    o_step, o_nP, o_reset = bo.fn("env_step"), bo.fn("env_nP"), bo.fn("env_reset")
+    handles = [o.h for o in oracles]
+    nP = [o.nP for o in oracles]
+    acts = np.zeros(B, dtype=np.int32); rew = np.zeros(B, dtype=np.float64)
+    done = np.zeros(B, dtype=np.uint8); rows = np.zeros(B, dtype=np.int32)
+    fn, args = _ffi.lib().bbx_step_autoreset, (env._h, _ffi.ptr(acts), _ffi.ptr(rew), _ffi.ptr(done), _ffi.ptr(rows))
+    want_rew = [0.0] * B; want_done = [0] * B
+    t = in_a_row = sessions = 0
+    while in_a_row < SEQ_MOD + 10 if one_session else t < WRAP_STEPS:
+        assert t < 3 * WRAP_STEPS, "no session lasted"
+        for e in range(B):
+            acts[e] = hashes[t, e] % max(nP[e], 1)
+        if with_obs:
+            states, rew, done, _ = env.step(acts, auto_reset=True)
+            rows = env.rows
+        else:
+            rc = fn(*args)
+            if rc:
+                _ffi.check(rc)
+        for e, h in enumerate(handles):
+            want_rew[e] = o_step(h, int(acts[e]))
+            n = o_nP(h)
+            want_done[e] = int(n == 0)
+            if n == 0:
+                o_reset(h); n = o_nP(h)
+            nP[e] = n
+        assert rew.tolist() == want_rew and [int(d) for d in done] == want_done and rows.tolist() == nP, (t, rew, done, rows, want_rew, want_done, nP)
+        if with_obs:
+            for e, o in enumerate(oracles):
+                assert np.array_equal(states[e], o.obs(k)), (t, e)
+        t += 1; in_a_row += 1
+        if one_session and t % 64 == 0:                      # (a session begins with the fifth step in a row: well inside 64)
+            now = env.session_stats()["sessions"]
+            if now != sessions:
+                sessions, in_a_row = now, 0
+    return env, t
+
+
+@pytest.mark.parametrize("with_obs", [False, True])
+@pytest.mark.parametrize("B", [1, 3])
+def test_mailbox_session_across_the_sequence_wrap(B, with_obs):
+    """A host mailbox session whose step count passes BBX_LITE_SEQ_MOD: the step after the wrap carries a sequence number the
+    session has used before (16 000 steps earlier), and every step's outputs — with_obs: the observation too — must still be
+    that step's.  The statistics say that the steps did join sessions, one launch per step would pass otherwise: all but the
+    four that precede each session and the one that begins it (and four more where the helper's look at the statistics fell
+    among those and the count of steps in a row began again: under ten per session)."""
+    env, steps = _steps_across_the_wrap(B, with_obs, True)
+    ss = env.session_stats()
+    assert ss["sessions"] >= 1 and ss["joined"] > steps - 10 * ss["sessions"], (ss, steps)
+
+
+def test_zero_copy_polled_steps_across_the_sequence_wrap():
+    """B = 16: above the mailbox limit, inside zero-copy — one launch per step, the host spinning on the launch's sequence
+    number in the pinned status words (bbx_flight::poll); 16 050 launches take that number past its wrap."""
+    env, _ = _steps_across_the_wrap(16, False, False)
+    assert env.session_stats()["sessions"] == 0
