@@ -249,11 +249,95 @@ enum BbxKernel { BBX_K_HBM = 0, BBX_K_STAGED = 1, BBX_K_AUX = 2, BBX_K_FAST = 3,
 //   [BBX_GEN_CP + 2 i]      cumulative probability i of the degree distribution (double, 64 entries, padded with +inf)
 //   [BBX_GEN_DEG + 8 i]     per degree i: offset of its monomials (in monomials), their number, the two constants of
 //                           libstdc++'s uniform_int_distribution(0, number - 1) — scaling, past — and floor(2^32 / scaling)
+//   [BBX_GEN_JUMP + k]      16807^(k + 1) mod (2^31 - 1), k < BBX_GEN_BATCH: the engine's jump-ahead multipliers (lane-parallel draw)
 //   [BBX_GEN_MONO + W j]    monomial j, packed (with degree slot), in the reference's enumeration order (ideals.cpp:39-64)
 #define BBX_GEN_CP 8
 #define BBX_GEN_DEG (BBX_GEN_CP + 128)
-#define BBX_GEN_MONO (BBX_GEN_DEG + 512)
+#define BBX_GEN_JUMP (BBX_GEN_DEG + 512)
+#define BBX_GEN_BATCH 128
+#define BBX_GEN_MONO (BBX_GEN_JUMP + BBX_GEN_BATCH)
 #define BBX_GEN_MAXDEG 63
+
+#ifdef __cplusplus
+// ------------------------------------------------------------------ one generator of a binomial ideal from a batch of raws
+// The lane-parallel draw of the fast class (gen_ideal_lanes, bbx_device.h) computes the engine's next BBX_GEN_BATCH outputs
+// at once (x_k = 16807^k x_0 mod (2^31 - 1)) and lets lane f decode generator f from the raws a sequential draw WITHOUT
+// rejections and retrials would have given it: bbx_gen_stride of them.  The decode is stated once, here, for the kernel and
+// for the host check (tests/reset_draw_check.cpp): the operations of gen_binomial (bbx_device.h) / BinomialGen
+// (bbx_ideals.cpp) in their order.  A generator whose sequential draw would have used another number of raws — a uniform draw
+// at or past `past`, or two equal monomials — reports `deviated`; the caller then drops the whole batch and draws one by one.
+// Acc supplies the data, each its own way (registers and cross-lane reads on the device, plain arrays on the host):
+//   uint32_t raw(int i)         raw i of this generator's window          double cp(int i)          cumulative probability i
+//   BbxGenRow row(int d)        the per-degree row of degree d            void mono(j, uint32_t w[2])   monomial j (W = 2)
+static inline BBX_HD uint32_t bbx_gen_mulmod(uint32_t a, uint32_t x) {      // a x mod (2^31 - 1); a, x in [1, 2^31 - 1)
+  const uint64_t pr = (uint64_t)a * x;
+  uint32_t s = (uint32_t)(pr & 0x7fffffffu) + (uint32_t)(pr >> 31);        // 2^31 = 1 (mod 2^31 - 1); below 2 (2^31 - 1)
+  if (s >= 2147483647u) s -= 2147483647u;
+  return s;
+}
+// ret / scaling for ret < 2^31 with magic = floor(2^32 / scaling): the estimate is at most one too small
+static inline BBX_HD uint32_t bbx_gen_div(uint32_t ret, uint32_t scaling, uint32_t magic) {
+  uint32_t q = (uint32_t)(((uint64_t)ret * magic) >> 32);
+  if (ret - q * scaling >= scaling) q++;
+  return q;
+}
+static inline BBX_HD double bbx_gen_canonical(uint32_t r1, uint32_t r2) {   // random.tcc generate_canonical, k = 2
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+  const double R = 2147483646.0;
+  double sum = (double)(r1 - 1u);
+  sum = sum + (double)(r2 - 1u) * R;
+  double ret = sum / (R * R);
+  if (ret >= 1.0) ret = 0x1.fffffffffffffp-1;                               // nextafter(1, 0)
+  return ret;
+}
+static inline BBX_HD int bbx_gen_stride(uint32_t flags, int ncp) {          // raws of one generator: [c] [degrees] m1 m2
+  return ((flags & 2u) ? 0 : 1) + (ncp == 0 ? 0 : ((flags & 1u) ? 2 : 4)) + 2;
+}
+#define BBX_GEN_BATCH_MAXPOLY 11                                            /* 11 generators x 7 raws <= BBX_GEN_BATCH */
+struct BbxGenRow { uint32_t off, scaling, past, magic; };
+struct BbxGenDraw { uint32_t lead[2], tail[2], c; bool deviated; };
+template <class Acc>
+static inline BBX_HD BbxGenDraw bbx_gen_decode(const Acc& acc, uint32_t flags, int ncp) {
+  BbxGenDraw r;
+  bool dev = false;
+  int at = 0;
+  // (a rejected draw decodes as 0: whatever follows is dropped with the batch, but stays inside the table)
+  auto uniform = [&](uint32_t scaling, uint32_t past, uint32_t magic) {
+    uint32_t ret = acc.raw(at++) - 1u;
+    if (ret >= past) { dev = true; ret = 0; }
+    return bbx_gen_div(ret, scaling, magic);
+  };
+  auto degree = [&]() {                                                     // std::lower_bound(cp, cp + ncp, pr) - cp
+    const uint32_t r1 = acc.raw(at), r2 = acc.raw(at + 1);
+    at += 2;
+    const double pr = bbx_gen_canonical(r1, r2);
+    int d = 0;
+    for (int i = 0; i < ncp; i++) d += acc.cp(i) < pr ? 1 : 0;
+    return d;
+  };
+  r.c = (flags & 2u) ? BBX_P - 1u : 1u + uniform(67104u, 2147462208u, 64004u);
+  int d1 = 0, d2 = 0;
+  if (ncp != 0) {
+    d1 = degree();
+    d2 = (flags & 1u) ? d1 : degree();
+  }
+  const BbxGenRow row1 = acc.row(d1), row2 = acc.row(d2);
+  const uint32_t j1 = row1.off + uniform(row1.scaling, row1.past, row1.magic);
+  const uint32_t j2 = row2.off + uniform(row2.scaling, row2.past, row2.magic);
+  uint32_t m1[2], m2[2];
+  acc.mono(j1, m1); acc.mono(j2, m2);                                       // (both loads in flight)
+  // grevlex as one unsigned compare: m_gt for W = 2 (bbx_device.h)
+  const uint64_t k1 = (((uint64_t)m1[1] << 32) | m1[0]) ^ 0x0000FFFFFFFFFFFFull;
+  const uint64_t k2 = (((uint64_t)m2[1] << 32) | m2[0]) ^ 0x0000FFFFFFFFFFFFull;
+  const bool second = k2 > k1;
+  r.lead[0] = second ? m2[0] : m1[0]; r.lead[1] = second ? m2[1] : m1[1];
+  r.tail[0] = second ? m1[0] : m2[0]; r.tail[1] = second ? m1[1] : m2[1];
+  r.deviated = dev || k1 == k2;                                             // equal: the trial loop would go round
+  return r;
+}
+#endif
 
 // position-keyed commutative hash used for parity traces (same definition in oracle/trace.py)
 static inline BBX_HD uint64_t bbx_mix64(uint64_t idx, uint32_t word) {

@@ -505,32 +505,21 @@ __device__ int wave_merge_tiled(const PView<W>& A, const PView<W>& B, char* lds,
 // from the same published algorithms as the host generators (bbx_ideals.cpp), operation for operation, so that a
 // seeded environment sees the same ideals wherever they are drawn.  Everything is wave-uniform: scalar registers, scalar
 // loads from the immutable table.  Doubles: plain IEEE operations, no contraction.
+// (the arithmetic itself — the engine's step, the division, generate_canonical — is stated once, in bbx_common.h, for this
+// sequential draw, the lane-parallel one below and the host check)
 __device__ __forceinline__ uint32_t gen_next(uint32_t& x) {                 // x <- 16807 x mod (2^31 - 1)
-  const uint64_t pr = (uint64_t)x * 16807u;
-  uint32_t s = (uint32_t)(pr & 0x7fffffffu) + (uint32_t)(pr >> 31);        // 2^31 = 1 (mod 2^31 - 1)
-  if (s >= 2147483647u) s -= 2147483647u;
-  x = s;
-  return s;
+  x = bbx_gen_mulmod(16807u, x);
+  return x;
 }
-// ret / scaling for ret < 2^31 with magic = floor(2^32 / scaling): the estimate is at most one too small
-__device__ __forceinline__ uint32_t gen_div(uint32_t ret, uint32_t scaling, uint32_t magic) {
-  uint32_t q = (uint32_t)(((uint64_t)ret * magic) >> 32);
-  if (ret - q * scaling >= scaling) q++;
-  return q;
-}
+__device__ __forceinline__ uint32_t gen_div(uint32_t ret, uint32_t scaling, uint32_t magic) { return bbx_gen_div(ret, scaling, magic); }
 __device__ __forceinline__ uint32_t gen_uniform(uint32_t& x, uint32_t scaling, uint32_t past, uint32_t magic) {   // uniform_int_dist.h, downscaling
   uint32_t ret;
   do ret = gen_next(x) - 1u; while (ret >= past);
   return gen_div(ret, scaling, magic);
 }
 __device__ __forceinline__ double gen_canonical(uint32_t& x) {             // random.tcc generate_canonical, k = 2
-#pragma clang fp contract(off)
-  const double R = 2147483646.0;
-  double sum = (double)(gen_next(x) - 1u);
-  sum = sum + (double)(gen_next(x) - 1u) * R;
-  double ret = sum / (R * R);
-  if (ret >= 1.0) ret = 0x1.fffffffffffffp-1;                               // nextafter(1, 0)
-  return ret;
+  const uint32_t r1 = gen_next(x), r2 = gen_next(x);
+  return bbx_gen_canonical(r1, r2);
 }
 // The small tables live one entry per lane for the duration of a reset (two coalesced loads): the cumulative
 // probabilities, so that std::lower_bound is a compare + ballot + popcount, and the per-degree rows, fetched with
@@ -573,6 +562,56 @@ __device__ __forceinline__ bool gen_binomial(uint32_t& x, const uint32_t* g, con
     if (m_gt(m1, m2)) { lead = m1; tail = m2; return true; }
   }
   return false;
+}
+
+// A whole ideal of at most BBX_GEN_BATCH_MAXPOLY generators at once (W = 2): the engine's next 128 outputs in one vector step
+// (lane l: x_{l+1} and x_{l+65}, jump-ahead multipliers from the table), then lane f < npoly decodes generator f from the raws
+// [f S, f S + S) a draw without rejections would have given it (bbx_gen_decode, bbx_common.h: gen_binomial's operations in
+// their order).  False — and nothing changed — if any generator deviates from that stride: the caller then draws one by one
+// from the same x.  True: lane f holds generator f, x has advanced by npoly S.  Lanes >= npoly decode generator 0 again
+// (every lane takes part in the cross-lane reads; their result is not a generator).
+struct GenBatchAcc {
+  uint32_t lo, hi; int base; bool two; const GenLanes& L; const uint32_t* g;
+  __device__ __forceinline__ uint32_t raw(int i) const {
+    const int k = base + i;
+    const uint32_t a = (uint32_t)__builtin_amdgcn_ds_bpermute((k & 63) << 2, (int)lo);
+    if (!two) return a;                                                     // (wave-uniform: the whole ideal within 64 raws)
+    const uint32_t b = (uint32_t)__builtin_amdgcn_ds_bpermute((k & 63) << 2, (int)hi);
+    return k < 64 ? a : b;
+  }
+  __device__ __forceinline__ double cp(int i) const {
+    const long long v = __double_as_longlong(L.cp);
+    const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i), h = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), i);
+    return __longlong_as_double((long long)(((uint64_t)h << 32) | l));
+  }
+  __device__ __forceinline__ BbxGenRow row(int d) const {
+    BbxGenRow r;
+    r.off = (uint32_t)__builtin_amdgcn_ds_bpermute(d << 2, (int)L.off); r.scaling = (uint32_t)__builtin_amdgcn_ds_bpermute(d << 2, (int)L.scaling);
+    r.past = (uint32_t)__builtin_amdgcn_ds_bpermute(d << 2, (int)L.past); r.magic = (uint32_t)__builtin_amdgcn_ds_bpermute(d << 2, (int)L.magic);
+    return r;
+  }
+  __device__ __forceinline__ void mono(uint32_t j, uint32_t w[2]) const {
+    const uint2 v = *(const uint2*)(g + BBX_GEN_MONO + 2 * (size_t)j);
+    w[0] = v.x; w[1] = v.y;
+  }
+};
+__device__ __forceinline__ bool gen_ideal_lanes(uint32_t& x, const uint32_t* g, const GenLanes& L, uint32_t flags, int ncp, int npoly,
+                                                Mono<2>& lead, Mono<2>& tail, uint32_t& c) {
+  static_assert(BBX_GEN_BATCH_MAXPOLY * 7 <= BBX_GEN_BATCH && BBX_GEN_BATCH == 2 * WAVE, "an ideal's raws fit the batch");
+  // (a degree is at most ncp - 1 <= BBX_GEN_MAXDEG: the last cumulative probability is 1.0 and a canonical draw is below 1)
+  static_assert(BBX_GEN_MAXDEG < WAVE, "every degree's row sits in a lane: ds_bpermute wraps beyond the wave where v_readlane would not");
+  // (everything that depends on the lane alone would otherwise be hoisted out of the step loop and held in vector
+  // registers across all of it: the lane number goes through an opaque copy)
+  int ln = lane_id(); asm volatile("" : "+v"(ln));
+  // (npoly >= 1, as every distribution has a generator: `used - 1` below is a lane index)
+  const int S = bbx_gen_stride(flags, ncp), used = npoly * S;
+  const GenBatchAcc acc = {bbx_gen_mulmod(g[BBX_GEN_JUMP + ln], x), bbx_gen_mulmod(g[BBX_GEN_JUMP + WAVE + ln], x),
+                           (ln < npoly ? ln : 0) * S, used > WAVE, L, g};
+  const BbxGenDraw d = bbx_gen_decode(acc, flags, ncp);
+  if (ballot64(ln < npoly && d.deviated) != 0) return false;
+  lead.w[0] = d.lead[0]; lead.w[1] = d.lead[1]; tail.w[0] = d.tail[0]; tail.w[1] = d.tail[1]; c = d.c;
+  x = (uint32_t)(used <= WAVE ? __builtin_amdgcn_readlane((int)acc.lo, used - 1) : __builtin_amdgcn_readlane((int)acc.hi, used - 1 - WAVE));
+  return true;
 }
 
 // sort_input (buchberger.cpp:299-303: std::sort of the drawn generators by lead monomial, ascending).  For at most 16

@@ -621,8 +621,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
           const bool sorted = cq->sort_input != 0;
           const bool one_pass = npoly <= 11 && limG >= npoly && limP >= npoly + ((npoly * (npoly - 1)) >> 1);
           M2 tabL = m_zero<2>(), tabT = m_zero<2>(); uint32_t tabC = 0; int rank = 0;
+          // one_pass ideals are drawn across the lanes (gen_ideal_lanes: lane f gets generator f at once) unless a generator
+          // would take a rejection or a retrial: then, and on every other path, the generators are drawn one after another
+          const bool batch = one_pass && gen_ideal_lanes(x, gtab, GL, gflags, ncp, npoly, tabL, tabT, tabC);
           if (sorted) {
-            for (int fidx = 0; fidx < npoly && ok; fidx++) {
+            for (int fidx = 0; fidx < npoly && ok && !batch; fidx++) {
               M2 lead, tail; uint32_t c;
               if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, lead, tail, c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
               if (lane == fidx) { tabL = lead; tabT = tail; tabC = c; }
@@ -631,7 +634,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
             FSTAMP(6);                                     // 6: reset: drawing the ideal
             if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
           }
-          for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted); fidx++) {
+          if (batch && !sorted) {                          // (already in basis order: lane f writes generator f)
+            if (lane < npoly) { lm[lane] = tabL; tm[lane] = tabT; gi[lane] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+            FSTAMP(6);
+          }
+          for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted) && !batch; fidx++) {
             if (!one_pass && (nG + 1 > limG || nP + nG > limP)) { status = BBX_ST_SPILL; ok = false; x = x_start; break; }   // redone from the same draw
             BTerm<2> t0, t1;
             t0.c = 1;

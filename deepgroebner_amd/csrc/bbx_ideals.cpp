@@ -380,6 +380,8 @@ class RandomBase : public IdealGen {
       const double v = i < degree_.cp.size() ? degree_.cp[i] : HUGE_VAL;
       memcpy(&t[BBX_GEN_CP + 2 * i], &v, 8);
     }
+    MinStd0 jump; jump.seed(1);                            // x_0 = 1: output k is 16807^k
+    for (size_t k = 0; k < BBX_GEN_BATCH; k++) t[BBX_GEN_JUMP + k] = (uint32_t)jump.next();
     size_t at = 0;
     for (int i = 0; i <= d; i++) {
       const auto& B = (*bases_)[i];
