@@ -159,17 +159,40 @@ template <int W> __device__ __forceinline__ Mono<W> m_div(const Mono<W>& a, cons
   for (int i = 0; i < W; i++) r.w[i] = pk_sub(a.w[i], b.w[i]);
   return r;
 }
+// the total degree summed from the exponent slots, in 32 bits (the degree slot is not read): v_sad_u16 against zero adds both
+// halves of a word to the accumulator
+template <int W> __device__ __forceinline__ uint32_t m_tdeg(const Mono<W>& a) {
+  uint32_t d = a.w[W - 1] & 0xffffu;
+#pragma unroll
+  for (int i = 0; i < W - 1; i++) d = __builtin_amdgcn_sad_u16(a.w[i], 0u, d);
+  return d;
+}
 template <int W> __device__ __forceinline__ Mono<W> m_lcm(const Mono<W>& a, const Mono<W>& b) {  // cpp:111-118
   Mono<W> r;
 #pragma unroll
   for (int i = 0; i < W; i++) r.w[i] = pk_max(a.w[i], b.w[i]);
-  // recompute the degree slot = sum of the exponent slots
-  uint32_t t = 0;
-#pragma unroll
-  for (int i = 0; i < W - 1; i++) t += r.w[i];            // halves add independently (sums < 65536)
-  uint32_t d = (t & 0xffffu) + (t >> 16) + (r.w[W - 1] & 0xffffu);
-  r.w[W - 1] = (r.w[W - 1] & 0xffffu) | (d << 16);
+  // recompute the degree slot = sum of the exponent slots MODULO 65 536: two lead monomials within the limits can have an lcm
+  // of a larger degree (x^40000 and y^40000).  The slot is then the true degree's low 16 bits — so that the degree of a
+  // quotient lcm / a, which divides b and is exact, comes out of m_div right — and nothing may order, or test divisibility
+  // of, lcms by it: the pair-set update uses m_tdeg / m_divides_x below, the S-polynomial's sugar check reports the pair
+  // when it is selected.
+  if constexpr (W == 2) {
+    const uint32_t d = (r.w[0] & 0xffffu) + (r.w[0] >> 16) + (r.w[1] & 0xffffu);
+    r.w[1] = (r.w[1] & 0xffffu) | (d << 16);
+  } else {
+    const uint32_t d = m_tdeg(r);                         // (the halves of several words summed in one register would carry
+    r.w[W - 1] = (r.w[W - 1] & 0xffffu) | (d << 16);      // into each other beyond 65 535)
+  }
   return r;
+}
+// a | b on the exponent slots alone: what m_divides is for monomials whose degree slot holds the degree, and the only valid
+// form for lcms whose degree passes 65 535 (a divisor's wrapped degree can be the larger one)
+template <int W> __device__ __forceinline__ bool m_divides_x(const Mono<W>& a, const Mono<W>& b) {
+  uint32_t x = 0;
+#pragma unroll
+  for (int i = 0; i < W - 1; i++) x |= pk_subsat(a.w[i], b.w[i]);
+  x |= pk_subsat(a.w[W - 1], b.w[W - 1]) & 0xffffu;
+  return x == 0;
 }
 template <int W> __device__ __forceinline__ bool m_eq(const Mono<W>& a, const Mono<W>& b) {  // cpp:77-81
   uint32_t x = 0;
@@ -779,7 +802,7 @@ __device__ bool wave_update(EnvT& e, const BbxLayout& L, int& nG, int& nP, const
       for (int u = 0; u < UF; u++) {
         if (base + u * WAVE < nP) {
           const Mono<W> l = m_lcm(li[u], lj[u]);
-          const bool drop = m_divides(lmf, l) && !m_eq(l, m_lcm(li[u], lmf)) && !m_eq(l, m_lcm(lj[u], lmf));
+          const bool drop = m_divides_x(lmf, l) && !m_eq(l, m_lcm(li[u], lmf)) && !m_eq(l, m_lcm(lj[u], lmf));
           const bool keep = in[u] && !drop;
           const uint64_t mask = ballot64(keep);
           if (first_drop) {
@@ -829,12 +852,12 @@ __device__ bool wave_update(EnvT& e, const BbxLayout& L, int& nG, int& nP, const
       };
       for (;;) {
         uint32_t dm = 0xFFFFFFFFu;
-        for (int u = 0; u < nch; u++) { const uint32_t d = m_deg(ldsL(u * WAVE + lane)); dm = ((candb >> u) & 1u) && d < dm ? d : dm; }
+        for (int u = 0; u < nch; u++) { const uint32_t d = m_tdeg(ldsL(u * WAVE + lane)); dm = ((candb >> u) & 1u) && d < dm ? d : dm; }
         const uint32_t dmin = wave_min32(dm);
         if (dmin == 0xFFFFFFFFu) break;
         for (int u = 0; u < nch; u++) {
           const Mono<W> Lu = ldsL(u * WAVE + lane);
-          uint64_t surv = ballot64(((candb >> u) & 1u) && m_deg(Lu) == dmin);
+          uint64_t surv = ballot64(((candb >> u) & 1u) && m_tdeg(Lu) == dmin);
           while (surv) {
             const int sl = __builtin_ctzll(surv);
             Mono<W> Ls;
@@ -844,7 +867,7 @@ __device__ bool wave_update(EnvT& e, const BbxLayout& L, int& nG, int& nP, const
             for (int v = 0; v < nch; v++) {
               const Mono<W> Lv = ldsL(v * WAVE + lane);
               const bool eq = m_eq(Lv, Ls);
-              if (m_divides(Ls, Lv)) candb &= ~(1u << v);
+              if (m_divides_x(Ls, Lv)) candb &= ~(1u << v);
               any_cp |= ballot64(eq && ((cpb >> v) & 1u));
               if (v == u) surv &= ~ballot64(eq);
             }
@@ -878,16 +901,19 @@ __device__ bool wave_update(EnvT& e, const BbxLayout& L, int& nG, int& nP, const
     // degree: every candidate of minimal degree is minimal; its bucket of equal lcms emits (smallest index, m)
     // unless a member is coprime to f (88-89), and all multiples of it stop being candidates.  Every lane only
     // ever reads and writes the flags of its own indices (i = lane mod 64), the bucket's lcm travels by readlane.
+    // The degree is the TRUE one, summed from the exponent slots (m_tdeg), and divisibility is tested on the exponent slots
+    // (m_divides_x): an lcm's degree can pass 65 535, its degree slot then holds the low 16 bits only.  Here and in the
+    // on-chip form above; the filter of the old pairs likewise.
     for (;;) {
       uint32_t dm = 0xFFFFFFFFu;
-      for (int i = lane; i < m; i += WAVE) if (e.cp[i] & 2) { uint32_t d = m_deg(e.lcm[i]); dm = d < dm ? d : dm; }
+      for (int i = lane; i < m; i += WAVE) if (e.cp[i] & 2) { uint32_t d = m_tdeg((Mono<W>)e.lcm[i]); dm = d < dm ? d : dm; }
       const uint32_t dmin = wave_min32(dm);
       if (dmin == 0xFFFFFFFFu) break;
       for (int base = 0; base < m; base += WAVE) {
         const int i = base + lane;
         Mono<W> Li = m_zero<W>();
         bool sv = false;
-        if (i < m) { Li = e.lcm[i]; sv = (e.cp[i] & 2) && m_deg(Li) == dmin; }
+        if (i < m) { Li = e.lcm[i]; sv = (e.cp[i] & 2) && m_tdeg(Li) == dmin; }
         uint64_t surv = ballot64(sv);
         while (surv) {
           const int sl = __builtin_ctzll(surv);
@@ -902,7 +928,7 @@ __device__ bool wave_update(EnvT& e, const BbxLayout& L, int& nG, int& nP, const
               const Mono<W> Lj = e.lcm[j];
               const uint8_t fj = e.cp[j];
               eq = m_eq(Lj, Ls);
-              if (m_divides(Ls, Lj)) e.cp[j] = (uint8_t)(fj & ~2);
+              if (m_divides_x(Ls, Lj)) e.cp[j] = (uint8_t)(fj & ~2);
               any_cp |= eq && (fj & 1);
             }
             if (b2 == base) surv &= ~ballot64(eq);

@@ -414,3 +414,51 @@ def interreduce_case(nv, n=280):
         idx = rng.choice(len(cand), size=min(len(cand), int(rng.integers(24, 60))), replace=False)
         G.append(normalise(bo, [(int(rng.integers(1, P)), lead)] + list(zip(coefs(rng, len(idx)), (cand[int(i)] for i in idx)))))
     return bo.minimalize(G)
+
+
+# ---- pair lcms whose degree passes 65 535 (the degree slot of a packed monomial has 16 bits) ----------------------------
+
+def _mono(nv, **slots):
+    e = [0] * nv
+    for name, x in slots.items():
+        e[int(name[1:])] = x
+    return tuple(e)
+
+
+def degree_limit_ideals():
+    """{label: (nv, F)}: three generators within the limits (every exponent and degree at most 65 535) such that
+    lcm(LM f0, LM f2) has a degree beyond 65 535 and is a proper multiple of lcm(LM f1, LM f2), which has not: Gebauer-Moeller
+    drops the pair (0, 2).  An update that orders or compares the lcms by a 16-bit degree takes the large one for a small one,
+    emits it first and keeps it.
+      3 variables (8-byte monomials): degree 70 000 against 60 020.
+      4 and 8 variables (16- and 32-byte monomials): degree 66 100 against 35 120, the two large exponents in the LOW halves of
+      different 32-bit words (x0: word 0; x2 resp. x6: word 1 resp. 3), 35 000 + 31 000 > 65 535 — a sum of whole words
+      carries into the high halves there."""
+    out = {3: (3, [[(1, _mono(3, x0=1, x2=10000)), (1, _mono(3))],
+                   [(1, _mono(3, x0=1, x2=20)), (1, _mono(3, x1=1))],
+                   [(1, _mono(3, x0=30000, x1=30000)), (1, _mono(3, x2=1))]])}
+    for nv, c, d in ((4, "x2", "x3"), (8, "x6", "x7")):
+        out[nv] = (nv, [[(1, _mono(nv, x0=1, **{c: 31000})), (1, _mono(nv))],
+                        [(1, _mono(nv, x0=1, **{c: 20})), (1, _mono(nv, x1=1))],
+                        [(1, _mono(nv, x0=35000, **{d: 100})), (1, _mono(nv, **{c: 1}))]])
+    return out
+
+
+def hard_limit_ideal():
+    """[x^40000 z + 1, y^40000 z + 1]: one pair, whose lcm has degree 80 001 — selecting it cannot be done in 16 bits."""
+    return [[(1, (40000, 0, 1)), (1, (0, 0, 0))], [(1, (0, 40000, 1)), (1, (0, 0, 0))]]
+
+
+def padded(F):
+    return [[(c, pad(e)) for c, e in f] for f in F]
+
+
+def lcm_degree(a, b):
+    return sum(max(x, y) for x, y in zip(a, b))
+
+
+def pair_sugar(o, i, j):
+    """Sugar of the S-polynomial of the oracle environment's pair (i, j), from its basis (buchberger.cpp:18-21)."""
+    li, lj = [int(x) for x in o.poly(int(i))[1][0]], [int(x) for x in o.poly(int(j))[1][0]]
+    d = lcm_degree(li, lj)
+    return max(o.poly_sugar(int(i)) + d - sum(li), o.poly_sugar(int(j)) + d - sum(lj))

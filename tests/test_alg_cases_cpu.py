@@ -92,6 +92,49 @@ def test_update_cases_drop_emit_and_share_buckets(bo, nv):
         assert cp_buckets >= 1, label
 
 
+@pytest.mark.parametrize("nv", (3, 4, 8))
+def test_degree_limit_ideals_are_within_the_limits_and_their_lcms_are_not(bo, nv):
+    """Generators within the documented limits; lcm(0, 2) beyond 65 535, a proper multiple of lcm(1, 2), which is not; for 4
+    and 8 variables the low halves of two different words of the packed lcm sum past 65 535.  The reference's update drops
+    the pair (0, 2) — under Gebauer-Moeller only — and an environment's first six steps under the first-pair rule select no
+    pair whose sugar passes the limit while the basis keeps meeting lcms that do."""
+    n, F = ac.degree_limit_ideals()[nv]
+    assert n == nv and all(max(e) <= 65535 and sum(e) <= 65535 for f in F for _, e in f)
+    assert [bo.polylist([f]).get(0) for f in ac.padded(F)] == ac.padded(F)           # (terms in descending order as written)
+    lm = [f[0][1] for f in F]
+    big, small = ac.lcm_degree(lm[0], lm[2]), ac.lcm_degree(lm[1], lm[2])
+    assert big > 65535 >= small and ac.lcm_degree(lm[0], lm[1]) <= 65535
+    l02, l12 = [max(x, y) for x, y in zip(lm[0], lm[2])], [max(x, y) for x, y in zip(lm[1], lm[2])]
+    assert l02 != l12 and all(x <= y for x, y in zip(l12, l02))
+    assert (big & 0xffff) < small                                                      # a 16-bit degree would order them the other way
+    if nv > 3:
+        words = [ac.pad(l02)[2 * w] for w in range(4)]                                 # the low halves of the words
+        assert sum(1 for x in words if x >= 30000) == 2 and sum(words[:-1] if nv == 4 else words) > 65535
+    G = ac.padded(F)
+    assert bo.update(G[:2], [(0, 1)], G[2], "gebauermoeller")[1] == [(0, 1), (1, 2)]
+    for elim in ("lcm", "none"):
+        assert bo.update(G[:2], [(0, 1)], G[2], elim)[1] == [(0, 1), (0, 2), (1, 2)]
+    o = bo.env(fixed=F); o.reset()
+    assert o.nG == 3 and o.pairs().tolist() == [[0, 1], [1, 2]]
+    beyond = 0
+    for t in range(6):
+        assert o.nP > 0
+        i, j = o.pairs()[0]
+        assert ac.pair_sugar(o, i, j) <= 65535, t
+        nG = o.nG
+        o.step(0)
+        if o.nG > nG:
+            new = [int(x) for x in o.poly(nG)[1][0]]
+            beyond += sum(1 for g in range(nG) if ac.lcm_degree([int(x) for x in o.poly(g)[1][0]], new) > 65535)
+    assert beyond >= 3
+
+
+def test_hard_limit_ideal_has_one_pair_beyond_the_limit(bo):
+    F = ac.hard_limit_ideal()
+    o = bo.env(fixed=F); o.reset()
+    assert o.pairs().tolist() == [[0, 1]] and ac.lcm_degree(F[0][0][1], F[1][0][1]) == 80001 and ac.pair_sugar(o, 0, 1) == 80001
+
+
 @pytest.mark.parametrize("nv", NVS)
 def test_reduce_and_interreduce_cases_do_work(bo, nv):
     """Several divisors divide the dividend's lead term; the growing case's intermediate results are many times its length;

@@ -229,6 +229,22 @@ def test_degree_and_sugar_limit(bo, var):
             refused(L, mirrors, lambda: L.reduce([(5, 5), (5, 5)]), lambda m: m.reduce(5, 5), 0, [("add", 0, 1), ("add", 0, 1)])
 
 
+@pytest.mark.parametrize("elimination", ("gebauermoeller", "lcm", "none"))
+@pytest.mark.parametrize("nv", (3, 4, 8))
+def test_update_with_lcms_beyond_the_degree_limit(bo, nv, elimination):
+    """Generators within the limits whose lcm(0, 2) has degree 70 000 (3 variables) or 66 100 (4 and 8 variables: the low halves
+    of two words of the packed lcm sum past 65 535) and is a proper multiple of lcm(1, 2): the reference's pair list in order
+    — (0, 2) leaves under Gebauer-Moeller and stays under the other two —, beside a small list in the same batch."""
+    F = ac.padded(ac.degree_limit_ideals()[nv][1])
+    small = [[(2, mono(nv - 1, 2)), (1, ac.pad(()))], [(7, mono(0, 1))], [(1, mono(0, 1)), (3, mono(nv - 1, 1))]]
+    L, mirrors = handle(bo, [F, small])
+    got = L.update([[(0, 1)], [(0, 1)]], elimination)
+    want = [m.update([(0, 1)], elimination) for m in mirrors]
+    assert want[0] == ([(0, 1), (1, 2)] if elimination == "gebauermoeller" else [(0, 1), (0, 2), (1, 2)])
+    assert got == want, (nv, elimination, got)
+    check(L, mirrors, "update leaves the lists as they are")
+
+
 # ---- reduce ------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("nv", NVS)
