@@ -451,6 +451,8 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
   BbxHdr* ghdr = (BbxHdr*)grec;
   const BbxLayout& L = STAGED ? p.LL : p.L;
 
+  // (entry, per-step bookkeeping and exit of the step protocol, bbx_device.h / DESIGN 4.0, written out: with the shared StepState
+  // this class measured 0.6 % slower on 5-10-5-uniform, profiles/r08_step_protocol_ab.txt)
   int nG = uni(ghdr->nG), nP = uni(ghdr->nP);
   int status = uni(ghdr->status), need_reset = uni(ghdr->need_reset), q_head = uni(ghdr->q_head);
   int t_agent = uni(ghdr->t), episode_steps = uni(ghdr->episode_steps);
@@ -464,13 +466,13 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
   // behind a kernel of a persistent session this class only serves what that kernel handed over (an environment whose
   // slice was over waits for the session's next kernel)
   if (p.sess_target && status != BBX_ST_SPILL) return;
-  const bool was_transient = status == BBX_ST_STARVED || status == BBX_ST_SPILL || status == BBX_ST_TIMESLICE;
+  const bool was_transient = bbx_st_transient(status);
   if (was_transient) status = BBX_ST_OK;
   double vret = ghdr->vret, vdisc = ghdr->vdisc;
   int obs_trunc = uni(ghdr->obs_trunc);
   if (p.set_budget) { budget = bbx_st_capacity(status) ? budget + p.nsteps : p.nsteps; rollout_pos = 0; done_last = 0; vret = 0.0; vdisc = 1.0; obs_trunc = 0; }   // (bbx_common.h: bbx_st_capacity)
   if (p.sess_target) budget = p.sess_target - uni(ghdr->sess_done);   // closing launch of a persistent session: what is still owed
-  if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget > 0 && nP > 0)))) {
+  if (p.pass == 1 && !bbx_pass_has_work(status, need_reset, budget, nP)) {
     // nothing to do here.  If the kernel in front could not hold the environment (it is too large for the register/LDS
     // class) although there was nothing to take either, its hand-over mark must not outlive the launch: the host would
     // keep resuming an environment that has no step left
@@ -750,7 +752,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     } else zero_red++;
     bytes += nP * obs_term_bytes;
     alg_bytes += bytes;
-    const double reward = (p.rewards_mode == BBX_REW_ADDITIONS) ? (-1.0 - (double)nsteps_red) : -1.0;
+    const double reward = step_reward(p.rewards_mode, nsteps_red);
     last_reward = reward;
     if (p.value_mode) value_accumulate(vret, vdisc, reward, p.gamma);
     total_steps++; total_adds += 1 + nsteps_red; t_agent++; episode_steps++; steps_done++;
@@ -780,11 +782,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
       uint64_t oh = bin_obs<W, true>(e, p, env, nP, false, true);
       uint64_t ph = wave_pairs_hash<W, EnvB>(e, nP);
       uint64_t nh = nG > nG_before ? bin_poly_hash<W>(e, nG - 1) : 0;
-      if (lane == 0) {
-        BbxTraceRec& tr = p.trace[(size_t)env * p.trace_stride + rollout_pos];
-        tr.action = action; tr.nP = nP; tr.nG = nG; tr.done = done ? 1 : 0; tr.reward = reward;
-        tr.obs_hash = oh; tr.pairs_hash = ph; tr.newpoly_hash = nh;
-      }
+      if (lane == 0) trace_put(p, env, rollout_pos, action, nP, nG, done, reward, oh, ph, nh);
     }
     budget--; rollout_pos++;
     done_last = done ? 1 : 0;
@@ -821,7 +819,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     if (pz.value_mode && pz.values) pz.values[env] = vret;
     if (!handoff) {
       if (pz.rewards && (steps_done > 0 || pz.pass == 0)) pz.rewards[env] = last_reward;
-      if (pz.dones) pz.dones[env] = (uint8_t)((done_last || (nP == 0 && !need_reset)) ? 1 : 0);
+      if (pz.dones) pz.dones[env] = (uint8_t)bbx_done_flag(done_last, nP, need_reset);
       if (pz.rows) pz.rows[env] = nP;
     }
   }

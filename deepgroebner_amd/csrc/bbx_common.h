@@ -26,6 +26,7 @@
 // operate on it directly): slot s (= variable s) lives in word s/2, half s%2; the LAST slot holds
 // the total degree.  W=2 serves n<=3 variables (8 B / monomial), W=4 serves n<=7 (16 B).
 #pragma once
+#include <stdbool.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -64,6 +65,14 @@ enum {
 // (bbx_api.cpp grow_records) and the environment continues.  A launch that finds an environment waiting like that adds
 // its steps to the environment's budget instead of replacing it, so no step is lost across asynchronous launches.
 static inline BBX_HD int bbx_st_capacity(int st) { return st == BBX_ST_G_FULL || st == BBX_ST_P_FULL || st == BBX_ST_ARENA_FULL || st == BBX_ST_POLY_TOO_LONG; }
+// Transient statuses say "steps are still owed, somebody else (the host's refill, the follow-up pass, the session's next
+// kernel) has to act first": every step kernel clears them on entry and tries again.
+static inline BBX_HD int bbx_st_transient(int st) { return st == BBX_ST_STARVED || st == BBX_ST_SPILL || st == BBX_ST_TIMESLICE; }
+// A follow-up pass (BbxParams::pass == 1) serves an environment only when it has something to do: a pending reset or owed steps
+static inline BBX_HD bool bbx_pass_has_work(int st, int need_reset, int budget, int nP) { return st == BBX_ST_OK && (need_reset || (budget > 0 && nP > 0)); }
+// The `dones` output: the last step taken ended an episode, or the episode is over and no reset is pending (a finished
+// environment stepped without auto-reset stays done)
+static inline BBX_HD int bbx_done_flag(int done_last, int nP, int need_reset) { return (done_last || (nP == 0 && !need_reset)) ? 1 : 0; }
 
 // The status block ("lite"): what every step kernel leaves per environment and the host reads after every launch.
 //   word0   bits 0..15 the status (BBX_ST_*), bit 16 BBX_LITE_OBS_TRUNC (BbxHdr.obs_trunc != 0), bits 17.. a sequence number

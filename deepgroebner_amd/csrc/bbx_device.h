@@ -1288,3 +1288,86 @@ __device__ void stage_copy(const Env<W>& dst, const Env<W>& src, int nG, int nP,
   for (int i = lane; i < nP; i += WAVE) dst.pairs[i] = src.pairs[i];
   for (int i = lane; i < nT; i += WAVE) { dst.am[i] = src.am[i]; dst.ac[i] = src.ac[i]; }
 }
+
+// ------------------------------------------------------------------ the step protocol
+// What every step kernel does around its algebra, stated once.  The general class runs it; the binomial class follows it over
+// locals of its own and shares its pure helpers (step_reward, trace_put, bbx_common.h's predicates); the wide class and the
+// hand-scheduled fast class restate it: binomial and wide measured slower on this struct.  Entry: hdr_load, step_budget, bbx_pass_has_work.  Per step:
+// the agent's action (table_agent_action or select_pair), step_reward, trace_put, step_account.  Exit: hdr_store.
+struct StepState {
+  int nG, nP, arena_used, status, need_reset, q_head, t_agent, episode_steps, episodes, zero_red;
+  long long total_steps, total_adds, alg_bytes;
+  uint32_t agent_seed, std_rng, gen_state;
+  uint32_t rng_mark;        // std_rng before the step in progress: what hdr_store writes when that step has to be taken again
+  int budget, rollout_pos, done_last, obs_trunc;
+  int steps_done, status_in;   // steps of this launch; the status it found, before the transient ones were cleared
+  double vret, vdisc, last_reward;
+};
+// the header as the launch finds it, the transient statuses cleared (bbx_common.h); by value: the fields are registers
+__device__ __forceinline__ StepState hdr_load(const BbxHdr* h) {
+  StepState s;
+  s.nG = uni(h->nG); s.nP = uni(h->nP); s.arena_used = uni(h->arena_used);
+  s.status = uni(h->status); s.need_reset = uni(h->need_reset); s.q_head = uni(h->q_head);
+  s.t_agent = uni(h->t); s.episode_steps = uni(h->episode_steps); s.episodes = uni(h->episodes); s.zero_red = uni(h->zero_reductions);
+  s.total_steps = h->total_steps; s.total_adds = h->total_additions; s.alg_bytes = h->alg_bytes;
+  s.agent_seed = (uint32_t)uni((int)h->agent_seed); s.std_rng = (uint32_t)uni((int)h->std_rng); s.gen_state = h->gen_rng;
+  s.budget = uni(h->budget); s.rollout_pos = uni(h->rollout_pos); s.done_last = uni(h->done_last);
+  s.status_in = s.status;
+  if (bbx_st_transient(s.status)) s.status = BBX_ST_OK;
+  s.vret = h->vret; s.vdisc = h->vdisc; s.obs_trunc = uni(h->obs_trunc);
+  s.rng_mark = s.std_rng; s.steps_done = 0; s.last_reward = 0.0;
+  return s;
+}
+// a launch that starts a rollout: its steps, and the per-rollout fields anew.  An environment waiting for the host to enlarge
+// its record keeps the steps it still owes (bbx_common.h, bbx_st_capacity)
+__device__ __forceinline__ void step_budget(StepState& s, const BbxParams& p) {
+  if (!p.set_budget) return;
+  s.budget = bbx_st_capacity(s.status) ? s.budget + p.nsteps : p.nsteps;
+  s.rollout_pos = 0; s.done_last = 0; s.vret = 0.0; s.vdisc = 1.0; s.obs_trunc = 0;
+}
+// The agents that choose a row without looking at a polynomial; false: an ordering strategy (select_pair: its sugar accessor
+// differs per class, so it stays with the caller).  The caller range-checks the action either way (BBX_ST_BAD_ACTION).
+__device__ __forceinline__ bool table_agent_action(const BbxParams& p, int env, uint32_t agent_seed, int t_agent, int nP, uint32_t& std_rng, int& action) {
+  if (p.agent == BBX_AGENT_EXTERNAL) action = p.actions[env];
+  else if (p.agent == BBX_AGENT_HASH) action = (int)bbx_agent_action32(agent_seed, (uint32_t)t_agent, (uint32_t)nP);
+  else if (p.agent == BBX_AGENT_FIRST) action = 0;
+  else if (p.agent == BBX_AGENT_LAST) action = nP - 1;
+  else if (p.agent == BBX_AGENT_STDRANDOM) action = std_choice(std_rng, nP);
+  else return false;
+  return true;
+}
+__device__ __forceinline__ double step_reward(int rewards_mode, int nsteps_red) {   // buchberger.cpp:328
+  return rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)nsteps_red) : -1.0;
+}
+// parity trace (tests): one record per environment and step of the rollout; one lane
+__device__ __forceinline__ void trace_put(const BbxParams& p, int env, int pos, int action, int nP, int nG, bool done, double reward, uint64_t obs_hash, uint64_t pairs_hash, uint64_t newpoly_hash) {
+  BbxTraceRec& tr = p.trace[(size_t)env * p.trace_stride + pos];
+  tr.action = action; tr.nP = nP; tr.nG = nG; tr.done = done ? 1 : 0; tr.reward = reward;
+  tr.obs_hash = obs_hash; tr.pairs_hash = pairs_hash; tr.newpoly_hash = newpoly_hash;
+}
+// the bookkeeping of a step that has happened (the state is the one after it; done: its pair set is empty)
+__device__ __forceinline__ void step_account(StepState& s, const BbxParams& p, double reward, int nsteps_red, bool done) {
+  s.last_reward = reward;
+  if (p.value_mode) value_accumulate(s.vret, s.vdisc, reward, p.gamma);
+  s.total_steps++; s.total_adds += 1 + nsteps_red; s.t_agent++; s.episode_steps++; s.steps_done++;
+  s.budget--; s.rollout_pos++;
+  s.done_last = done ? 1 : 0;
+  if (done) { s.episodes++; if (p.auto_reset) s.need_reset = 1; }
+}
+// Exit (one lane): the header back, then what the caller reads.  rewind_rng: the step in progress did not happen and its draw
+// is taken again.  handoff: the environment continues in the follow-up pass of this launch, which reports in its place —
+// the status block and the value are written either way, rewards / dones / rows are not; a pass that took no step leaves
+// the reward of the pass in front.
+__device__ __forceinline__ void hdr_store(BbxHdr* h, const BbxParams& p, int env, const StepState& s, bool rewind_rng, bool handoff) {
+  h->nG = s.nG; h->nP = s.nP; h->arena_used = s.arena_used; h->status = s.status; h->need_reset = s.need_reset;
+  h->q_head = s.q_head; h->t = s.t_agent; h->std_rng = rewind_rng ? s.rng_mark : s.std_rng; h->gen_rng = s.gen_state;
+  h->episode_steps = s.episode_steps; h->total_steps = s.total_steps; h->total_additions = s.total_adds; h->episodes = s.episodes;
+  h->zero_reductions = s.zero_red; h->steps_done = s.steps_done; h->budget = s.budget; h->rollout_pos = s.rollout_pos;
+  h->done_last = s.done_last; h->alg_bytes = s.alg_bytes; h->vret = s.vret; h->vdisc = s.vdisc; h->obs_trunc = s.obs_trunc;
+  if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(s.status, s.obs_trunc, 0), s.q_head, s.budget, s.nP);
+  if (p.value_mode && p.values) p.values[env] = s.vret;
+  if (handoff) return;
+  if (p.rewards && (s.steps_done > 0 || p.pass == 0)) p.rewards[env] = s.last_reward;
+  if (p.dones) p.dones[env] = (uint8_t)bbx_done_flag(s.done_last, s.nP, s.need_reset);
+  if (p.rows) p.rows[env] = s.nP;
+}

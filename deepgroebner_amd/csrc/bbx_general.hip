@@ -17,22 +17,14 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
   BbxHdr* ghdr = (BbxHdr*)grec;
   const BbxLayout& L = STAGED ? p.LL : p.L;      // the layout this kernel works in
 
-  int nG = uni(ghdr->nG), nP = uni(ghdr->nP), arena_used = uni(ghdr->arena_used);
-  int status = uni(ghdr->status), need_reset = uni(ghdr->need_reset), q_head = uni(ghdr->q_head);
-  int t_agent = uni(ghdr->t), episode_steps = uni(ghdr->episode_steps);
-  int episodes = uni(ghdr->episodes), zero_red = uni(ghdr->zero_reductions);
-  long long total_steps = ghdr->total_steps, total_adds = ghdr->total_additions, alg_bytes = ghdr->alg_bytes;
-  const uint32_t agent_seed = uni((int)ghdr->agent_seed);
-  uint32_t std_rng = (uint32_t)uni((int)ghdr->std_rng);
-  uint32_t gen_state = ghdr->gen_rng;
-  int budget = uni(ghdr->budget), rollout_pos = uni(ghdr->rollout_pos);
-  int done_last = uni(ghdr->done_last);
-  if (status == BBX_ST_STARVED || status == BBX_ST_SPILL || status == BBX_ST_TIMESLICE) status = BBX_ST_OK;   // transient states: try again
-  double vret = ghdr->vret, vdisc = ghdr->vdisc;
-  int obs_trunc = uni(ghdr->obs_trunc);
-  // (an environment waiting for the host to enlarge its record keeps the steps it still owes: bbx_common.h)
-  if (p.set_budget) { budget = bbx_st_capacity(status) ? budget + p.nsteps : p.nsteps; rollout_pos = 0; done_last = 0; vret = 0.0; vdisc = 1.0; obs_trunc = 0; }
-  if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget > 0 && nP > 0)))) return;  // nothing left to do here
+  StepState s = hdr_load(ghdr);                 // the protocol around the algebra: bbx_device.h
+  step_budget(s, p);
+  if (p.pass == 1 && !bbx_pass_has_work(s.status, s.need_reset, s.budget, s.nP)) return;  // nothing left to do here
+
+  // What the algebra's functions take by reference lives in locals of its own from here to the exit: a struct of which one
+  // member's address goes into a call that is not inlined (32-byte monomials) would stay in memory as a whole.
+  int nG = s.nG, nP = s.nP, arena_used = s.arena_used, status = s.status, q_head = s.q_head;
+  uint32_t gen_state = s.gen_state;
 
   Env<W> ge = env_view<W>(grec, p.L);
   // In the staged instantiation the working view is ALWAYS the LDS copy (never a select between an LDS and
@@ -40,7 +32,7 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
   Env<W> e = STAGED ? env_view<W>(smem + (size_t)wave_in_block * L.rec_bytes, L) : ge;
   bool staged_in = false;
   if (STAGED) {
-    if (status == BBX_ST_OK && !(!need_reset && nP == 0)) {   // (an idle environment is not staged: bbx_fast.h, idle0)
+    if (status == BBX_ST_OK && !(!s.need_reset && nP == 0)) {   // (an idle environment is not staged: bbx_fast.h, idle0)
       if (nG > (int)L.maxG || nP > (int)L.maxP || arena_used > (int)L.arena) status = BBX_ST_SPILL;
       else {
         stage_copy<W>(e, ge, nG, nP, arena_used);
@@ -49,8 +41,6 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
       }
     }
   }
-  int steps_done = 0;
-  double last_reward = 0.0;
   const bool tracing = TRACE && p.trace != nullptr;   // hashing code exists only in the TRACE instantiations
   // per-wave LDS tile scratch of the merge-path merge (HBM-resident class only; the launcher provides it)
   char* mlds = (!STAGED && smem != nullptr) ? smem + (size_t)wave_in_block * merge_lds_bytes<W>() : nullptr;
@@ -62,11 +52,10 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
   Mono<W>* rm = e.hm + 2 * maxT;  uint16_t* rc = e.hc + 2 * maxT;
   Mono<W>* tm = e.hm + 3 * maxT;  uint16_t* tc = e.hc + 3 * maxT;   // 2*maxT staging
 
-  uint32_t rng_mark = std_rng;                  // the selection engine's state before the step in progress
   for (;;) {
     if (status != BBX_ST_OK) break;
-    rng_mark = std_rng;
-    if (need_reset) {                           // also serves a reset left pending by the last step
+    s.rng_mark = s.std_rng;                       // the selection engine's state before the step in progress
+    if (s.need_reset) {                           // also serves a reset left pending by the last step
       if (!wave_reset<W>(e, p, L, env, nG, nP, arena_used, q_head, &status, gen_state)) {
         // the reset restarts from the same queued ideal: in the LDS class a capacity miss is only a spill
         if (STAGED && (status == BBX_ST_G_FULL || status == BBX_ST_P_FULL || status == BBX_ST_ARENA_FULL)) {
@@ -74,9 +63,9 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
         }
         break;
       }
-      need_reset = 0; episode_steps = 0;
+      s.need_reset = 0; s.episode_steps = 0;
     }
-    if (budget <= 0) break;
+    if (s.budget <= 0) break;
     if (nP == 0) break;                         // finished episode and no auto-reset: nothing to do
     // headroom for the worst case of this step, checked BEFORE anything is modified so that a miss leaves a
     // consistent state: one new basis element of <= maxT terms and at most |G| new pairs
@@ -87,12 +76,8 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
 
     // ---- choose the pair ------------------------------------------------------------------
     int action;
-    if (p.agent == BBX_AGENT_EXTERNAL) action = p.actions[env];
-    else if (p.agent == BBX_AGENT_HASH) action = (int)bbx_agent_action32(agent_seed, (uint32_t)t_agent, (uint32_t)nP);
-    else if (p.agent == BBX_AGENT_FIRST) action = 0;
-    else if (p.agent == BBX_AGENT_LAST) action = nP - 1;
-    else if (p.agent == BBX_AGENT_STDRANDOM) action = std_choice(std_rng, nP);
-    else action = select_pair<W>(e, nP, p.agent, [&](int g) { return (int)e.psug[g]; });
+    if (!table_agent_action(p, env, s.agent_seed, s.t_agent, nP, s.std_rng, action))
+      action = select_pair<W>(e, nP, p.agent, [&](int g) { return (int)e.psug[g]; });
     action = uni(action);
     if (action < 0 || action >= nP) { status = BBX_ST_BAD_ACTION; break; }
     const uint32_t pr = (uint32_t)uni((int)e.pairs[action]);
@@ -194,62 +179,36 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
     if (rn != 0) {
       if (!wave_add_poly<W>(e, L, nG, nP, arena_used, rm, rc, rn, rsug, p.elim, p.sort_reducers, &status)) break;
       sb += 12LL * rn + 8LL * nG_before + 8LL * (nP_before + nP);
-    } else zero_red++;
+    } else s.zero_red++;
     sb += 4LL * nP * 2 * p.nvars * p.k;             // the observation matrix of the new state
-    alg_bytes += sb;
-    const double reward = (p.rewards_mode == BBX_REW_ADDITIONS) ? (-1.0 - (double)nsteps_red) : -1.0;  // 328
-    last_reward = reward;
-    if (p.value_mode) value_accumulate(vret, vdisc, reward, p.gamma);
-    total_steps++; total_adds += 1 + nsteps_red; t_agent++; episode_steps++; steps_done++;
+    s.alg_bytes += sb;
+    const double reward = step_reward(p.rewards_mode, nsteps_red);
     const bool done = nP == 0;
 
     // ---- the observation a policy would consume after this step ---------------------------------
-    if (p.obs_every_step && p.obs) { wave_obs<W>(e, p, env, nP, true, false); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
+    if (p.obs_every_step && p.obs) { wave_obs<W>(e, p, env, nP, true, false); s.obs_trunc |= nP > p.obs_rows ? 1 : 0; }
     // ---- parity trace (tests): hashes of the post-step observation / pair set / new element ---
     if (TRACE && tracing) {
       uint64_t oh = wave_obs<W, true>(e, p, env, nP, false, true);
       uint64_t ph = wave_pairs_hash<W, Env<W>>(e, nP);
       uint64_t nh = nG > nG_before ? wave_poly_hash<W>(e, nG - 1) : 0;
-      if (lane == 0) {
-        BbxTraceRec& tr = p.trace[(size_t)env * p.trace_stride + rollout_pos];
-        tr.action = action; tr.nP = nP; tr.nG = nG; tr.done = done ? 1 : 0; tr.reward = reward;
-        tr.obs_hash = oh; tr.pairs_hash = ph; tr.newpoly_hash = nh;
-      }
+      if (lane == 0) trace_put(p, env, s.rollout_pos, action, nP, nG, done, reward, oh, ph, nh);
     }
-    budget--; rollout_pos++;
-    done_last = done ? 1 : 0;
-    if (done) {
-      episodes++;
-      if (p.auto_reset) need_reset = 1;
-    }
+    step_account(s, p, reward, nsteps_red, done);
   }
 
-  if (bbx_st_capacity(status) || status == BBX_ST_SPILL) std_rng = rng_mark;   // the step did not happen: its draw is taken again
   if (PROF && prof_out && lane == 0) for (int i = 0; i < 10; i++) prof_out[(size_t)env * 10 + i] = ps[i];
-  // an environment that must continue in the follow-up pass reports nothing yet
-  const bool handoff = status == BBX_ST_SPILL;
   // ---- observation of the state the caller sees next ------------------------------------------
-  if (p.obs && status == BBX_ST_OK) { wave_obs<W>(e, p, env, nP, true, false); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
+  if (p.obs && status == BBX_ST_OK) { wave_obs<W>(e, p, env, nP, true, false); s.obs_trunc |= nP > p.obs_rows ? 1 : 0; }
 
   if (STAGED && staged_in) {
     wave_sync();
     stage_copy<W>(ge, e, nG, nP, arena_used);
   }
-  if (lane == 0) {
-    BbxHdr* h = ghdr;
-    h->nG = nG; h->nP = nP; h->arena_used = arena_used; h->status = status; h->need_reset = need_reset;
-    h->q_head = q_head; h->t = t_agent; h->std_rng = std_rng; h->gen_rng = gen_state; h->episode_steps = episode_steps; h->total_steps = total_steps;
-    h->total_additions = total_adds; h->episodes = episodes; h->zero_reductions = zero_red; h->steps_done = steps_done;
-    h->budget = budget; h->rollout_pos = rollout_pos; h->done_last = done_last; h->alg_bytes = alg_bytes;
-    h->vret = vret; h->vdisc = vdisc; h->obs_trunc = obs_trunc;
-    if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(status, obs_trunc, 0), q_head, budget, nP);
-    if (p.value_mode && p.values) p.values[env] = vret;
-    if (!handoff) {
-      if (p.rewards && (steps_done > 0 || p.pass == 0)) p.rewards[env] = last_reward;
-      if (p.dones) p.dones[env] = (uint8_t)((done_last || (nP == 0 && !need_reset)) ? 1 : 0);
-      if (p.rows) p.rows[env] = nP;
-    }
-  }
+  s.nG = nG; s.nP = nP; s.arena_used = arena_used; s.status = status; s.q_head = q_head; s.gen_state = gen_state;
+  // the engine rewinds when the step did not happen (the draw comes before the merges that can miss max_poly_terms or hand the
+  // step to the wide class); an environment that must continue in the follow-up pass reports nothing yet
+  if (lane == 0) hdr_store(ghdr, p, env, s, bbx_st_capacity(s.status) || s.status == BBX_ST_SPILL, s.status == BBX_ST_SPILL);
 }
 
 template <int W, bool STAGED, bool TRACE>
