@@ -212,16 +212,22 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   double vret = 0.0, vdisc = 1.0;                      // VAL
   if (VAL && !p.set_budget) { vret = ghdr->vret; vdisc = ghdr->vdisc; }
   const uint32_t agent_seed = (uint32_t)uni((int)ghdr->agent_seed);
-  int budget = uni(ghdr->budget), rollout_pos = uni(ghdr->rollout_pos), done_last = uni(ghdr->done_last);
+  int budget_in = uni(ghdr->budget), rollout_pos = uni(ghdr->rollout_pos), done_in = uni(ghdr->done_last);
   if (status == BBX_ST_STARVED || status == BBX_ST_SPILL || status == BBX_ST_TIMESLICE) status = BBX_ST_OK;
-  if (p.set_budget) { budget = bbx_st_capacity(status) ? budget + p.nsteps : p.nsteps; rollout_pos = 0; done_last = 0; }   // (bbx_common.h: bbx_st_capacity)
-  if (p.sess_target) budget = p.sess_target - uni(ghdr->sess_done);   // later kernels of a persistent session: what is still owed
+  if (p.set_budget) { budget_in = bbx_st_capacity(status) ? budget_in + p.nsteps : p.nsteps; rollout_pos = 0; done_in = 0; }   // (bbx_common.h: bbx_st_capacity)
+  if (p.sess_target) budget_in = p.sess_target - uni(ghdr->sess_done);   // later kernels of a persistent session: what is still owed
   const uint32_t t_begin = PERSIST ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
   int mb_action = -1;                                  // mailbox session of ONE environment: the action that came with the control word
   bool mb_pending = false;                             // mailbox session: a step has been taken whose outputs the host is waiting for
   int pol_t0 = 0;                                      // POL + PERSIST: agent step counter minus session step, fixed for the kernel
   if (POL > 0 && PERSIST) { int vz_; asm volatile("v_mov_b32 %0, 0" : "=v"(vz_)); pol_t0 = vz_ + (t_agent - (p.set_budget ? 0 : uni(ghdr->sess_done))); }
-  if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget > 0 && nP > 0)))) return;
+  if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget_in > 0 && nP > 0)))) return;
+  // The steps still owed are not counted down: t_stop is the agent step count at which the issued steps are exhausted (what
+  // is owed = t_stop - t_agent, formed in the loop's slow path and at the write-back), and t_event the count at which the
+  // loop top has something other than a plain step to do: the smaller of t_stop and the next multiple of 64, or t_agent
+  // itself wherever the next loop top is special (the first one, after a step that ends an episode, after a mailbox step).
+  // A plain step tests t_agent == t_event and nothing else about the launch.
+  int t_stop = t_agent + budget_in, t_event = t_agent;
 
   // HBM record arrays (binomial layout: every array 16-B aligned, capacities hbmG / maxP); the addresses are only
   // formed where the record is read or written (launch start / end), never kept live across the step loop
@@ -278,7 +284,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   int trace_pos = rollout_pos;                                        // TRACE only
   long long bytes_total = 0;
   int last_nred = vzero - 1;                           // reward of the last step, kept as its integer reduction count
-  int obs_trunc = vzero;                               // an observation had more rows than the caller's block (rows cut)
+  int obs_rows_max = vzero;                            // largest |P| an observation was written for (more than the caller's block: rows cut)
+  // the agent step count behind the last step that ended an episode (done_last == (t_done == t_agent): nothing to write per
+  // step), and the one this launch began with (the first loop top is no 64th-step boundary the loop has crossed)
+  int t_done = vzero + (done_in ? t_agent : t_agent - 1);
+  const int t_entry = vzero + t_agent;
   const bool tracing = TRACE && p.trace != nullptr;
   const int n = HL ? 3 : p.nvars, kk = HL ? 2 : p.k;
   const int agent = HL ? BBX_AGENT_HASH : p.agent;
@@ -306,6 +316,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   int32_t* const o3_base = obs32 ? p.obs + (size_t)env * p.obs_rows * 12 : nullptr;   // (wave-uniform: the block of this environment)
   typedef int32_t ObsV3 __attribute__((ext_vector_type(3)));
   size_t o3_toff = 0;                                    // POL: the step's slice of a [nsteps][B][rows][12] block
+  auto note_rows = [&]() { obs_rows_max = obs_rows_max > nP ? obs_rows_max : nP; };   // (one v_max: obs_trunc is derived where the wave leaves)
   auto write_obs32 = [&]() {
     const int rows = nP < p.obs_rows ? nP : p.obs_rows;
     // The rows go out through a buffer descriptor whose size is exactly the live part of the block: the hardware drops the
@@ -313,7 +324,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     // was ~16 scalar instructions per 32 rows, on the unit that binds this kernel.  The gathers run for all lanes: a pair
     // index beyond |P| stays inside the pair array (|P| <= FP = its capacity, and a trip covers rows r0 .. r0 + 31 with
     // r0 <= FP - 32), what it reads is a stale pair, and the basis index taken from it is clamped to the arrays' FG entries.
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(o3_base + o3_toff), 0, rows * 48, 0x00020000);
+    // (Only the block's address is kept across steps: the descriptor is formed here, from an address the optimiser cannot see
+    // through — hoisted out of the step loop, its four words lived in spilled lanes and were written back after every use.)
+    int32_t* ob = o3_base + o3_toff;
+    asm volatile("" : "+s"(ob));
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)ob, 0, rows * 48, 0x00020000);
     for (int r0 = 0; r0 < rows; r0 += 32) {
       const int ra = r0 + o3_row, rb = ra + 16;
       const uint32_t pa = pairs[ra], pb = pairs[rb];
@@ -594,181 +609,216 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     PA = pairs[lane];
   };
 
+#ifndef BBX_PRIO_SHIFT
+#define BBX_PRIO_SHIFT 6
+#endif
+  static_assert(BBX_PRIO_SHIFT == 6, "one test serves the hash refill, the priority rotation and the time slice");
   for (;;) {
     // |P| is wave-uniform by construction, but the compiler's uniformity analysis loses that across the loop; pinned
     // here, every branch of the step is a scalar branch (without it the whole body runs under exec masks, with
     // per-lane copies of all state at each join: +40 % instructions)
     nP = uni(nP);
-    if (status != BBX_ST_OK) break;
-    if (need_reset) {                                      // BuchbergerEnv::reset from the next queued ideal(s)
-      bool ok = true;
-      const FColdParams cq = f_cold_params();
-      const uint32_t* gtab = cq->gen;
-      if (gtab) {                                          // draw the ideal here (see gen_binomial): no queue, no host
-        const int npoly = (int)ldc(gtab + 2), ncp = (int)ldc(gtab + 4);
-        const uint32_t gflags = ldc(gtab + 3);
-        const GenLanes GL = gen_lanes(gtab);
-        uint32_t x = (uint32_t)uni((int)gen_state);
-        FSTAMP(0);
+    // Everything rare is behind ONE test: the launch's first loop top, a reset, a mailbox publication, the 64th-step
+    // housekeeping, the issued steps exhausted (t_event above).  A plain step goes straight to the capacity tests.
+    if (__builtin_expect(t_agent == t_event, 0)) {
+      if (status != BBX_ST_OK) break;
+      if (need_reset) {                                      // BuchbergerEnv::reset from the next queued ideal(s)
+        bool ok = true;
+        const FColdParams cq = f_cold_params();
+        const uint32_t* gtab = cq->gen;
+        if (gtab) {                                          // draw the ideal here (see gen_binomial): no queue, no host
+          const int npoly = (int)ldc(gtab + 2), ncp = (int)ldc(gtab + 4);
+          const uint32_t gflags = ldc(gtab + 3);
+          const GenLanes GL = gen_lanes(gtab);
+          uint32_t x = (uint32_t)uni((int)gen_state);
+          FSTAMP(0);
+          for (;;) {
+            const uint32_t x_start = x;
+            nG = 0; nP = 0;
+            clear_reducers();
+            // sort_input: all generators are drawn first (lane f keeps generator f), then enter in sorted order.  one_pass: the
+            // generators only go to the basis-order arrays as they are drawn and install_ideal sets up pairs and reducers at
+            // once (at most 11 generators within the caps: every ideal of the n <= 11 distributions); otherwise add_poly
+            // inserts them one by one (the draw is the same on every path: same calls, same order)
+            const bool sorted = cq->sort_input != 0;
+            const bool one_pass = npoly <= 11 && limG >= npoly && limP >= npoly + ((npoly * (npoly - 1)) >> 1);
+            M2 tabL = m_zero<2>(), tabT = m_zero<2>(); uint32_t tabC = 0; int rank = 0;
+            // one_pass ideals are drawn across the lanes (gen_ideal_lanes: lane f gets generator f at once) unless a generator
+            // would take a rejection or a retrial: then, and on every other path, the generators are drawn one after another
+            const bool batch = one_pass && gen_ideal_lanes(x, gtab, GL, gflags, ncp, npoly, tabL, tabT, tabC);
+            if (sorted) {
+              for (int fidx = 0; fidx < npoly && ok && !batch; fidx++) {
+                M2 lead, tail; uint32_t c;
+                if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, lead, tail, c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
+                if (lane == fidx) { tabL = lead; tabT = tail; tabC = c; }
+              }
+              rank = gen_sorted_rank<2>(tabL, npoly);
+              FSTAMP(6);                                     // 6: reset: drawing the ideal
+              if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+            }
+            if (batch && !sorted) {                          // (already in basis order: lane f writes generator f)
+              if (lane < npoly) { lm[lane] = tabL; tm[lane] = tabT; gi[lane] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+              FSTAMP(6);
+            }
+            for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted) && !batch; fidx++) {
+              if (!one_pass && (nG + 1 > limG || nP + nG > limP)) { status = BBX_ST_SPILL; ok = false; x = x_start; break; }   // redone from the same draw
+              BTerm<2> t0, t1;
+              t0.c = 1;
+              if (sorted) {
+                const int src = __builtin_ctzll(ballot64(lane < npoly && rank == fidx));
+                t0.m = f_readlane(tabL, src); t1.m = f_readlane(tabT, src); t1.c = f_readlane(tabC, src);
+              } else if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, t0.m, t1.m, t1.c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
+              if (!sorted) FSTAMP(6);
+              if (one_pass) {                                // basis-order arrays only: install_ideal does the rest
+                if (lane == 0) { lm[fidx] = t0.m; tm[fidx] = t1.m; gi[fidx] = make_uint2(1u | (t1.c << 16), 1u | (m_deg(t0.m) << 16)); }
+                continue;
+              }
+              if (__builtin_expect(npoly <= 64, 1)) add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, 1>{});
+              else add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, NBK>{});
+              FSTAMP(7);                                     // 7: reset: installing the ideal (basis, pairs, reducers)
+            }
+            if (one_pass && ok) {
+              wave_sync();
+              install_ideal(npoly, sorted);
+              FSTAMP(7);
+            }
+            if (!ok || nP != 0) break;                       // buchberger.cpp:313-314: redraw while the pair set is empty
+          }
+          gen_state = x;
+        } else {
+        const uint32_t q_slot_words = cq->q_slot_words, q_fixed = cq->q_fixed;
         for (;;) {
-          const uint32_t x_start = x;
+          const uint32_t* slot;
+          if (q_fixed) slot = cq->qwords;
+          else {
+            const int tail = uni(cq->qtail[env]);          // (a plain load would count as divergent and drag nG / nP into VGPRs)
+            if (q_head >= tail) { status = BBX_ST_STARVED; ok = false; break; }
+            slot = cq->qwords + (size_t)env * cq->q_env_stride + (size_t)(q_head % (int)cq->q_nslots) * q_slot_words;
+          }
           nG = 0; nP = 0;
           clear_reducers();
-          // sort_input: all generators are drawn first (lane f keeps generator f), then enter in sorted order.  one_pass: the
-          // generators only go to the basis-order arrays as they are drawn and install_ideal sets up pairs and reducers at
-          // once (at most 11 generators within the caps: every ideal of the n <= 11 distributions); otherwise add_poly
-          // inserts them one by one (the draw is the same on every path: same calls, same order)
-          const bool sorted = cq->sort_input != 0;
-          const bool one_pass = npoly <= 11 && limG >= npoly && limP >= npoly + ((npoly * (npoly - 1)) >> 1);
-          M2 tabL = m_zero<2>(), tabT = m_zero<2>(); uint32_t tabC = 0; int rank = 0;
-          // one_pass ideals are drawn across the lanes (gen_ideal_lanes: lane f gets generator f at once) unless a generator
-          // would take a rejection or a retrial: then, and on every other path, the generators are drawn one after another
-          const bool batch = one_pass && gen_ideal_lanes(x, gtab, GL, gflags, ncp, npoly, tabL, tabT, tabC);
-          if (sorted) {
-            for (int fidx = 0; fidx < npoly && ok && !batch; fidx++) {
-              M2 lead, tail; uint32_t c;
-              if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, lead, tail, c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
-              if (lane == fidx) { tabL = lead; tabT = tail; tabC = c; }
-            }
-            rank = gen_sorted_rank<2>(tabL, npoly);
-            FSTAMP(6);                                     // 6: reset: drawing the ideal
-            if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+          // the whole ideal (<= 128 words for up to 15 binomials) comes in with two coalesced loads, one word per
+          // lane; fields are then picked with v_readlane instead of a chain of dependent scalar-address loads
+          const bool small_slot = q_slot_words <= 128;
+          uint32_t qA = 0, qB = 0;
+          if (small_slot) {
+            if (lane < (int)q_slot_words) qA = slot[lane];
+            if (lane + 64 < (int)q_slot_words) qB = slot[lane + 64];
           }
-          if (batch && !sorted) {                          // (already in basis order: lane f writes generator f)
-            if (lane < npoly) { lm[lane] = tabL; tm[lane] = tabT; gi[lane] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
-            FSTAMP(6);
-          }
-          for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted) && !batch; fidx++) {
-            if (!one_pass && (nG + 1 > limG || nP + nG > limP)) { status = BBX_ST_SPILL; ok = false; x = x_start; break; }   // redone from the same draw
+          auto qword = [&](int j) -> uint32_t {
+            if (!small_slot) return (uint32_t)uni((int)slot[j]);
+            return j < 64 ? f_readlane(qA, j) : f_readlane(qB, j - 64);
+          };
+          const int npoly = (int)qword(0);
+          int at = 1;
+          for (int fidx = 0; fidx < npoly; fidx++) {
+            const int nt = (int)qword(at), sugar = (int)qword(at + 1);
+            if (nG + 1 > limG || nP + nG > limP) { status = BBX_ST_SPILL; ok = false; break; }
             BTerm<2> t0, t1;
-            t0.c = 1;
-            if (sorted) {
-              const int src = __builtin_ctzll(ballot64(lane < npoly && rank == fidx));
-              t0.m = f_readlane(tabL, src); t1.m = f_readlane(tabT, src); t1.c = f_readlane(tabC, src);
-            } else if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, t0.m, t1.m, t1.c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
-            if (!sorted) FSTAMP(6);
-            if (one_pass) {                                // basis-order arrays only: install_ideal does the rest
-              if (lane == 0) { lm[fidx] = t0.m; tm[fidx] = t1.m; gi[fidx] = make_uint2(1u | (t1.c << 16), 1u | (m_deg(t0.m) << 16)); }
-              continue;
-            }
-            if (__builtin_expect(npoly <= 64, 1)) add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, 1>{});
-            else add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, NBK>{});
-            FSTAMP(7);                                     // 7: reset: installing the ideal (basis, pairs, reducers)
+            t0.c = qword(at + 2); t0.m.w[0] = qword(at + 3); t0.m.w[1] = qword(at + 4);
+            t1.c = 0; t1.m = m_zero<2>();
+            if (nt == 2) { t1.c = qword(at + 5); t1.m.w[0] = qword(at + 6); t1.m.w[1] = qword(at + 7); }
+            add_poly(t0, t1, sugar, -1, std::integral_constant<int, NBK>{});
+            at += 2 + nt * 3;
           }
-          if (one_pass && ok) {
-            wave_sync();
-            install_ideal(npoly, sorted);
-            FSTAMP(7);
+          if (!ok) break;
+          if (!q_fixed) q_head++;
+          if (nP != 0 || q_fixed) break;                   // buchberger.cpp:313-314: redraw while the pair set is empty
+        }
+        }
+        if (!ok) { if (status != BBX_ST_STARVED) { nG = 0; nP = 0; } break; }
+        need_reset = 0;
+        if constexpr (POL > 0 && PERSIST) {
+          // per-step policy calls served by a session (bbx_policy_step_device): the block and the row count the caller finds when
+          // the session ends are those of the NEW episode, as after a launch per step — the step that ended the episode wrote the
+          // state it left (no rows), and within the session nobody reads the block (found by scripts/fuzz_sessions.py)
+          const FColdPolicy polr = f_cold_policy();
+          if (polr->post_obs) {
+            if (p.obs) { write_obs32(); note_rows(); }
+            if (lane == 0 && polr->rows_t) polr->rows_t[env] = nP;
           }
-          if (!ok || nP != 0) break;                       // buchberger.cpp:313-314: redraw while the pair set is empty
-        }
-        gen_state = x;
-      } else {
-      const uint32_t q_slot_words = cq->q_slot_words, q_fixed = cq->q_fixed;
-      for (;;) {
-        const uint32_t* slot;
-        if (q_fixed) slot = cq->qwords;
-        else {
-          const int tail = uni(cq->qtail[env]);          // (a plain load would count as divergent and drag nG / nP into VGPRs)
-          if (q_head >= tail) { status = BBX_ST_STARVED; ok = false; break; }
-          slot = cq->qwords + (size_t)env * cq->q_env_stride + (size_t)(q_head % (int)cq->q_nslots) * q_slot_words;
-        }
-        nG = 0; nP = 0;
-        clear_reducers();
-        // the whole ideal (<= 128 words for up to 15 binomials) comes in with two coalesced loads, one word per
-        // lane; fields are then picked with v_readlane instead of a chain of dependent scalar-address loads
-        const bool small_slot = q_slot_words <= 128;
-        uint32_t qA = 0, qB = 0;
-        if (small_slot) {
-          if (lane < (int)q_slot_words) qA = slot[lane];
-          if (lane + 64 < (int)q_slot_words) qB = slot[lane + 64];
-        }
-        auto qword = [&](int j) -> uint32_t {
-          if (!small_slot) return (uint32_t)uni((int)slot[j]);
-          return j < 64 ? f_readlane(qA, j) : f_readlane(qB, j - 64);
-        };
-        const int npoly = (int)qword(0);
-        int at = 1;
-        for (int fidx = 0; fidx < npoly; fidx++) {
-          const int nt = (int)qword(at), sugar = (int)qword(at + 1);
-          if (nG + 1 > limG || nP + nG > limP) { status = BBX_ST_SPILL; ok = false; break; }
-          BTerm<2> t0, t1;
-          t0.c = qword(at + 2); t0.m.w[0] = qword(at + 3); t0.m.w[1] = qword(at + 4);
-          t1.c = 0; t1.m = m_zero<2>();
-          if (nt == 2) { t1.c = qword(at + 5); t1.m.w[0] = qword(at + 6); t1.m.w[1] = qword(at + 7); }
-          add_poly(t0, t1, sugar, -1, std::integral_constant<int, NBK>{});
-          at += 2 + nt * 3;
-        }
-        if (!ok) break;
-        if (!q_fixed) q_head++;
-        if (nP != 0 || q_fixed) break;                   // buchberger.cpp:313-314: redraw while the pair set is empty
-      }
-      }
-      if (!ok) { if (status != BBX_ST_STARVED) { nG = 0; nP = 0; } break; }
-      need_reset = 0;
-      if constexpr (POL > 0 && PERSIST) {
-        // per-step policy calls served by a session (bbx_policy_step_device): the block and the row count the caller finds when
-        // the session ends are those of the NEW episode, as after a launch per step — the step that ended the episode wrote the
-        // state it left (no rows), and within the session nobody reads the block (found by scripts/fuzz_sessions.py)
-        const FColdPolicy polr = f_cold_policy();
-        if (polr->post_obs) {
-          if (p.obs) { write_obs32(); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
-          if (lane == 0 && polr->rows_t) polr->rows_t[env] = nP;
         }
       }
+      if constexpr (PERSIST && POL == 0 && !HL) {
+        // A host mailbox session: the host spins on this environment's status word for the step's sequence number.  The step's
+        // outputs reach host memory first — here, behind the reset of an environment whose episode the step ended (auto-reset:
+        // the observation and the row count the call returns are the new episode's, as in a launch per step).
+        if (mb_pending) {
+          mb_pending = false;
+          const FColdParams cm = f_cold_params();
+          if (uni(t_done) == t_agent && auto_reset && cm->obs) { if (obs32) write_obs32(); else write_obs(true, false); note_rows(); }
+          __threadfence_system();
+          if (lane == 0) {
+            const BbxHdr* hh = (const BbxHdr*)(cm->recs + (size_t)env * cm->rec_bytes);
+            const int taken = (cm->set_budget ? 0 : hh->sess_done) + t_agent - hh->t;      // steps of the session's total taken so far
+            if (cm->rewards) cm->rewards[env] = cm->rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)last_nred) : -1.0;
+            if (cm->dones) cm->dones[env] = (uint8_t)(t_done == t_agent ? 1 : 0);
+            if (cm->rows) cm->rows[env] = nP;
+            int32_t* lw = cm->lite + 4 * (size_t)env;
+            lw[1] = q_head; lw[2] = t_stop - t_agent; lw[3] = nP;
+            __threadfence_system();
+            __hip_atomic_store(lw, bbx_lite_word0(BBX_ST_OK, obs_rows_max > cm->obs_rows ? 1 : 0, bbx_lite_seq_of(taken)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+          }
+        }
+      }
+      // every 64th step the loop has taken (not where the launch begins: the entry has filled hv): the three things that need
+      // no finer grain
+      const int owed = t_stop - t_agent;
+      if ((t_agent & 63) == 0 && t_agent != uni(t_entry)) {
+        hv = bbx_agent_hash32(agent_seed, (uint32_t)(t_agent + lane));
+        bool slice_over = false;
+        if constexpr (PERSIST) {                           // the time slice (see BBX_ST_TIMESLICE): 64 steps are ~0.2 ms of a 10 ms slice
+          const uint32_t lim = f_cold_params()->slice_ticks;
+          slice_over = lim && (uint32_t)__builtin_amdgcn_s_memrealtime() - t_begin > lim;
+        }
+#ifndef BBX_NO_PRIO_ROTATION
+        // The instruction arbiter serves the OLDEST wave first, and this kernel is bound by the one scalar unit its waves share:
+        // left alone, the waves of the workgroups dispatched first run at 2.1 us per step and those dispatched last at 3.8,
+        // so every launch ends with a phase in which only the starved quarter is left, too few waves to fill the unit.
+        // Rotating the user priority (which ranks above age) every 2^BBX_PRIO_SHIFT steps, offset by the workgroup's quarter of
+        // the grid, gives every wave of a SIMD the same share over time: all finish together.  (s_setprio takes an immediate.)
+        switch (((t_agent >> BBX_PRIO_SHIFT) + (env >> 10)) & 3) {
+          case 0: __builtin_amdgcn_s_setprio(0); break;
+          case 1: __builtin_amdgcn_s_setprio(1); break;
+          case 2: __builtin_amdgcn_s_setprio(2); break;
+          default: __builtin_amdgcn_s_setprio(3); break;
+        }
+#endif
+        if (PERSIST && slice_over && owed > 0) { status = BBX_ST_TIMESLICE; break; }   // steps are still owed: the next kernel takes them
+      }
+      if (owed <= 0) {
+        if constexpr (PERSIST) {
+          // every step issued so far is taken: have more been issued meanwhile?  (Nothing about the session is kept live
+          // across the step loop: the steps taken are the agent's step counter minus what the record's header — untouched
+          // until this wave leaves — says it was when the session began.)
+          const FColdParams cq = f_cold_params();
+          const unsigned long long* ctl = cq->ctl;
+          const BbxHdr* hh = (const BbxHdr*)(cq->recs + (size_t)env * cq->rec_bytes);
+          const int taken = (cq->set_budget ? 0 : uni(hh->sess_done)) + t_agent - uni(hh->t);   // of the session's total
+          const uint32_t t0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
+          bool more = false;
+          for (;;) {
+            // (a mailbox session's word lives in host memory and is followed by the step's action: acquire, system scope)
+            const unsigned long long w = cq->mbox ? __hip_atomic_load(ctl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM)
+                                                  : __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int tgt = uni((int)(uint32_t)w), stop = uni((int)(uint32_t)(w >> 32));
+            // (a mailbox session of one environment carries the step's action in bits 33.. of the word, + 1: one read over the bus
+            // instead of two; valid for the LAST step issued, i.e. when exactly one step is owed)
+            if (tgt > taken) { t_stop = t_agent + (tgt - taken); more = true; mb_action = (cq->mbox && tgt - taken == 1) ? uni((int)(uint32_t)(w >> 33)) - 1 : -1; break; }
+            if (stop & 1) break;
+            const uint32_t now = (uint32_t)__builtin_amdgcn_s_memrealtime();
+            if (now - t0 > 2000000u) break;                                // 20 ms without news
+            if (cq->slice_ticks && now - t_begin > cq->slice_ticks) break; // the slice is over anyway
+            if (cq->mbox) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(32);   // (a host waits on the other side: short naps)
+          }
+          if (!more) break;
+        } else break;
+      }
+      if (nP == 0) break;
+      const int t_next = (t_agent | 63) + 1;
+      t_event = t_stop < t_next ? t_stop : t_next;
     }
     FSTAMP(0);                                             // 0: loop top / reset (a device-drawn reset's draw and install: 6, 7)
-    if constexpr (PERSIST && POL == 0 && !HL) {
-      // A host mailbox session: the host spins on this environment's status word for the step's sequence number.  The step's
-      // outputs reach host memory first — here, behind the reset of an environment whose episode the step ended (auto-reset:
-      // the observation and the row count the call returns are the new episode's, as in a launch per step).
-      if (mb_pending) {
-        mb_pending = false;
-        const FColdParams cm = f_cold_params();
-        if (done_last && auto_reset && cm->obs) { if (obs32) write_obs32(); else write_obs(true, false); obs_trunc |= nP > cm->obs_rows ? 1 : 0; }
-        __threadfence_system();
-        if (lane == 0) {
-          const BbxHdr* hh = (const BbxHdr*)(cm->recs + (size_t)env * cm->rec_bytes);
-          const int taken = (cm->set_budget ? 0 : hh->sess_done) + t_agent - hh->t;      // steps of the session's total taken so far
-          if (cm->rewards) cm->rewards[env] = cm->rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)last_nred) : -1.0;
-          if (cm->dones) cm->dones[env] = (uint8_t)done_last;
-          if (cm->rows) cm->rows[env] = nP;
-          int32_t* lw = cm->lite + 4 * (size_t)env;
-          lw[1] = q_head; lw[2] = budget; lw[3] = nP;
-          __threadfence_system();
-          __hip_atomic_store(lw, bbx_lite_word0(BBX_ST_OK, obs_trunc, bbx_lite_seq_of(taken)), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-    }
-    if (budget <= 0) {
-      if constexpr (PERSIST) {
-        // every step issued so far is taken: have more been issued meanwhile?  (Nothing about the session is kept live
-        // across the step loop: the steps taken are the agent's step counter minus what the record's header — untouched
-        // until this wave leaves — says it was when the session began.)
-        const FColdParams cq = f_cold_params();
-        const unsigned long long* ctl = cq->ctl;
-        const BbxHdr* hh = (const BbxHdr*)(cq->recs + (size_t)env * cq->rec_bytes);
-        const int taken = (cq->set_budget ? 0 : uni(hh->sess_done)) + t_agent - uni(hh->t);   // of the session's total
-        const uint32_t t0 = (uint32_t)__builtin_amdgcn_s_memrealtime();
-        bool more = false;
-        for (;;) {
-          // (a mailbox session's word lives in host memory and is followed by the step's action: acquire, system scope)
-          const unsigned long long w = cq->mbox ? __hip_atomic_load(ctl, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM)
-                                                : __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const int tgt = uni((int)(uint32_t)w), stop = uni((int)(uint32_t)(w >> 32));
-          // (a mailbox session of one environment carries the step's action in bits 33.. of the word, + 1: one read over the bus
-          // instead of two; valid for the LAST step issued, i.e. when exactly one step is owed)
-          if (tgt > taken) { budget = tgt - taken; more = true; mb_action = (cq->mbox && budget == 1) ? uni((int)(uint32_t)(w >> 33)) - 1 : -1; break; }
-          if (stop & 1) break;
-          const uint32_t now = (uint32_t)__builtin_amdgcn_s_memrealtime();
-          if (now - t0 > 2000000u) break;                                // 20 ms without news
-          if (cq->slice_ticks && now - t_begin > cq->slice_ticks) break; // the slice is over anyway
-          if (cq->mbox) __builtin_amdgcn_s_sleep(4); else __builtin_amdgcn_s_sleep(32);   // (a host waits on the other side: short naps)
-        }
-        if (!more) break;
-      } else break;
-    }
-    if (nP == 0) break;
     if (nG + 1 > limG || nP - 1 + nG > limP) { status = BBX_ST_SPILL; break; }   // before anything is modified
 
     // ---- choose the pair -----------------------------------------------------------------------------------------
@@ -778,11 +828,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       const FColdPolicy pol = f_cold_policy();
       // step of the rollout (the budget was set to nsteps; closing launches of a session: what is owed of its total), or of
       // the session (PERSIST: the agent's step counter against what it was when the session began)
-      pol_tt = PERSIST ? uni(t_agent - pol_t0) : uni((p.sess_target ? p.sess_target : p.nsteps) - budget);
+      pol_tt = PERSIST ? uni(t_agent - pol_t0) : uni((p.sess_target ? p.sess_target : p.nsteps) - (t_stop - t_agent));
       const size_t tb = (size_t)pol_tt * (size_t)p.B + (size_t)env;
       const float uu = pol->u[tb];                           // (requested before the observation goes out)
       const bool pre_obs = pol->post_obs == 0;
-      if (p.obs && pre_obs) { o3_toff = (size_t)pol_tt * (size_t)pol->obs_tstride; write_obs32(); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
+      if (p.obs && pre_obs) { o3_toff = (size_t)pol_tt * (size_t)pol->obs_tstride; write_obs32(); note_rows(); }
       if (lane == 0 && pol->rows_t && pre_obs) pol->rows_t[tb] = nP;
       if constexpr (POL2 > 0) {
         // two hidden layers: lane l supplies column 4 s + (l >> 4) of row l & 15 — [lm_i | tm_i | lm_j | tm_j] x (e0, e1, e2) —,
@@ -1155,34 +1205,9 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     last_nred = vzero + nred;
     if (VAL) value_accumulate(vret, vdisc, p.rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)nred) : -1.0, p.gamma);
     adds += 1 + nred; t_agent++;
-#ifndef BBX_PRIO_SHIFT
-#define BBX_PRIO_SHIFT 6
-#endif
-    static_assert(BBX_PRIO_SHIFT == 6, "one test per step serves the hash refill, the priority rotation and the time slice");
-    bool slice_over = false;
-    if ((t_agent & 63) == 0) {                             // every 64th step: the three things that need no finer grain
-      hv = bbx_agent_hash32(agent_seed, (uint32_t)(t_agent + lane));
-      if constexpr (PERSIST) {                             // the time slice (see BBX_ST_TIMESLICE): 64 steps are ~0.2 ms of a 10 ms slice
-        const uint32_t lim = f_cold_params()->slice_ticks;
-        slice_over = lim && (uint32_t)__builtin_amdgcn_s_memrealtime() - t_begin > lim;
-      }
-#ifndef BBX_NO_PRIO_ROTATION
-      // The instruction arbiter serves the OLDEST wave first, and this kernel is bound by the one scalar unit its waves share:
-      // left alone, the waves of the workgroups dispatched first run at 2.1 us per step and those dispatched last at 3.8,
-      // so every launch ends with a phase in which only the starved quarter is left, too few waves to fill the unit.
-      // Rotating the user priority (which ranks above age) every 2^BBX_PRIO_SHIFT steps, offset by the workgroup's quarter of
-      // the grid, gives every wave of a SIMD the same share over time: all finish together.  (s_setprio takes an immediate.)
-      switch (((t_agent >> BBX_PRIO_SHIFT) + (env >> 10)) & 3) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-      }
-#endif
-    }
     const bool done = nP == 0;
 
-    if (obs_step) { if (obs32) write_obs32(); else write_obs(true, false); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
+    if (obs_step) { if (obs32) write_obs32(); else write_obs(true, false); note_rows(); }
     if (TRACE && tracing) {
       const uint64_t oh = write_obs(false, true);
       uint64_t ph = 0;
@@ -1212,7 +1237,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     }
     if constexpr (POL > 0) {
       const FColdPolicy pol = f_cold_policy();
-      if (pol->post_obs && p.obs) { write_obs32(); obs_trunc |= nP > p.obs_rows ? 1 : 0; }   // (the block a per-step call leaves: the NEW state)
+      if (pol->post_obs && p.obs) { write_obs32(); note_rows(); }   // (the block a per-step call leaves: the NEW state)
       if (lane == 0) {
         const size_t tb = (size_t)pol_tt * (size_t)pol->stride_out + (size_t)env;
         if (pol->rewards_t) pol->rewards_t[tb] = p.rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)nred) : -1.0;
@@ -1220,11 +1245,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         if (pol->post_obs && pol->rows_t) pol->rows_t[env] = nP;
       }
     }
-    if constexpr (PERSIST && POL == 0 && !HL) mb_pending = f_cold_params()->mbox != 0;   // (published at the loop top, behind a reset)
-    budget--; if (TRACE) trace_pos++;
-    done_last = done ? 1 : 0;
-    if (done) { episodes++; if (auto_reset) need_reset = 1; }
-    if (PERSIST && slice_over && budget > 0) { status = BBX_ST_TIMESLICE; FSTAMP(5); break; }   // steps are still owed: the next kernel takes them
+    if constexpr (PERSIST && POL == 0 && !HL) {            // (published at the loop top, behind a reset)
+      if (f_cold_params()->mbox) { mb_pending = true; t_event = t_agent; }
+    }
+    if (TRACE) trace_pos++;
+    if (done) { episodes++; t_done = vzero + t_agent; t_event = t_agent; if (auto_reset) need_reset = 1; }   // (the next loop top: reset, or leave)
     FSTAMP(5);                                             // 5: observation + bookkeeping
   }
   const FColdParams cz = f_cold_params();
@@ -1232,7 +1257,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
 
   const bool handoff = status == BBX_ST_SPILL;
   if (handoff && lane == 0 && cz->ctl_stats) atomicAdd((unsigned long long*)cz->ctl_stats + 1, 1ull);   // statistics: environments that left the class
-  if (POL == 0 && p.obs && status == BBX_ST_OK) { if (obs32) write_obs32(); else write_obs(true, false); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
+  if (POL == 0 && p.obs && status == BBX_ST_OK) { if (obs32) write_obs32(); else write_obs(true, false); note_rows(); }
   if (staged_in) {                                                   // write the live prefixes back to the HBM record
     wave_sync();
     F_HBM_PTRS(cz)
@@ -1255,6 +1280,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   }
   if (lane == 0) {
     BbxHdr* h = (BbxHdr*)(cz->recs + (size_t)env * cz->rec_bytes);
+    const int budget = t_stop - t_agent, done_last = t_done == t_agent ? 1 : 0;   // (derived: the loop counts nothing down)
+    const int obs_trunc = obs_rows_max > cz->obs_rows ? 1 : 0;
     // steps done = the rollout budget this launch started with minus what is left (the header still holds the old one)
     const int budget0 = cz->sess_target ? cz->sess_target - h->sess_done
                                         : (cz->set_budget ? (bbx_st_capacity(status) ? h->budget + cz->nsteps : cz->nsteps) : h->budget);
