@@ -70,6 +70,9 @@ SIGNATURES = {
     "bbx_pmlp_prepared_floats": (C.c_int, [C.c_int, C.c_int]),
     "bbx_pmlp_prepare": (C.c_int, [_vp, _vp, _vp, C.c_float, C.c_int, C.c_int, _vp, _vp]),
     "bbx_pmlp_act": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "bbx_pmlp_logprob": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "bbx_pmlp_grad_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bbx_pmlp_grad": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_pmlp2_prepared_floats": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "bbx_pmlp2_prepare": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "bbx_pmlp2_act": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),

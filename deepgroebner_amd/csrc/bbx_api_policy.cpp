@@ -100,6 +100,31 @@ int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs
   return launched(bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, (hipStream_t)stream));
 }
 
+// ---- the policy as a differentiable function of its weights (bbx_pmlp_grad.h)
+int bbx_pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                     int hidden, float* d_logprobs, float* d_entropy, void* stream) {
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, (hipStream_t)stream));
+}
+
+int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) {
+  if (n < 0 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
+  if (int rc = refuse_args(false, false, "", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return pmlp_grad_workspace_floats(n, cols, hidden);
+}
+
+int bbx_pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                  int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
+                  void* stream) {
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
+                                       d_gw2, d_gb2, (hipStream_t)stream));
+}
+
 // ---- two and three hidden layers (bbx_pmlp2.hip)
 int bbx_pmlp2_prepared_floats(int cols, int hidden1, int hidden2) { return pmlp_deep_floats(cols, hidden1, 0, hidden2, false); }
 int bbx_pmlp3_prepared_floats(int cols, int hidden1, int hidden2, int hidden3) { return pmlp_deep_floats(cols, hidden1, hidden2, hidden3, true); }

@@ -35,6 +35,11 @@ extern "C" int bbx_launch_mark_reset(char* recs, uint32_t rec_bytes, int B, cons
 extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const float* w2, float b2, int cols, int hidden, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
+                                       int hidden, float* logprobs, float* entropy, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
+                                    int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
+                                    hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,

@@ -1,0 +1,267 @@
+// PMLP policy, one hidden layer, as a differentiable function of its weights (bbx_pmlp_logprob, bbx_pmlp_grad of include/bbx.h):
+// the log-probability of a recorded action, the entropy over a state's rows, and the gradient of
+//   L = sum_s glogp[s] logprob_s + gent[s] entropy_s
+// with respect to W1, b1, w2, b2 — what the reference's update (pg.py _fit_policy_model) needs per recorded state.  Nothing of
+// size [n][rows][hidden] ever exists in memory: the backward pass recomputes the hidden tile.
+//
+// Forward (bbx_pmlp_logprob_kernel): one wave per state; the logits go to the wave's LDS array through pmlp_tile exactly as in
+// pmlp_act_wave (same tile code, same G, same max / sum order, same lg[a] - logz: the log-probability of an action bbx_pmlp_act
+// has just sampled from the same block and weights is that call's, bit for bit).  Entropy: with e_r = exp(z_r - max),
+// se = sum e_r:   H = log(se) - (sum_r e_r (z_r - max)) / se   (= logZ - sum_r p_r z_r with the maximum taken out of both terms,
+// so that large logits do not cancel).
+//
+// Backward (bbx_pmlp_grad_kernel + bbx_pmlp_grad_reduce_kernel): a wave takes states p, p + waves, ... (pmlp_grad_waves(n) waves
+// per unit group: bbx_pmlp_shape.h).  Per state: the logits as above, then p_r, H and
+//   g_r = glogp (delta_{r,a} - p_r) - gent p_r (log p_r + H)
+// overwrite the logits in LDS (zero beyond the live rows, up to the next multiple of 32).  Per 32-row tile and unit block the
+// hidden tile is recomputed THE OTHER WAY ROUND, D'[row][unit]: the operands of pmlp_tile swapped —
+//   A operand  lane l: x[row r0 + (l & 31)][2s + (l >> 5)]           B operand  lane l: W1[2s + (l >> 5)][unit 32 ub + (l & 31)]
+//   D'         lane l, register v: row r0 + (v & 3) + 8 (v >> 2) + 4 (l >> 5), unit 32 ub + (l & 31); starts at b1[unit]
+// so a UNIT's 32 rows lie along the registers of lanes l and l + 32: relu, dh = g_r w2[unit] [h > 0], dw2 += g_r relu(h) and
+// db1 += dh are in-lane sums over the registers (g_r: four 16-byte LDS reads per lane, a broadcast per lane half), and register v
+// of dh is directly the B operand of k-step v of   dW1[k][unit] += sum_rows x[row][k] dh[row][unit]   (the step's two k values
+// are the rows of register v in the two lane halves), whose A operand is x[r0 + (v & 3) + 8 (v >> 2) + 4 (l >> 5)][32 cb + (l & 31)]:
+// the same permuted row order.  dW1 comes out as lane l, register v: column 32 cb + (v & 3) + 8 (v >> 2) + 4 (l >> 5), unit on the lane.
+// dW1, db1, dw2 and db2 stay in registers across all states of the wave; at the end the wave writes its partial sums to the
+// caller's workspace, and the second kernel adds the partials of every output in a fixed order: no floating-point atomics,
+// and the partition depends on n and the shape alone, so the same inputs give the same bits on any device.
+// 8 unit blocks x 2 column blocks x 16 accumulators do not fit in a wave: a wave owns PMLP_GRAD_UBW unit blocks (at most 64 dW1
+// accumulators) and the unit groups are spread ACROSS THE GRID (blockIdx.y); every group computes the logits of its states
+// itself (db2 is taken from group 0).
+#pragma once
+#include "bbx_pmlp.h"
+
+// LDS floats per wave of the gradient kernel: the g_r of a state, padded to whole tiles
+__host__ __device__ constexpr int pmlp_grad_lgcap(int obs_rows) { return ((pmlp_lgcap(obs_rows) + 31) / 32) * 32; }
+__host__ __device__ constexpr size_t pmlp_grad_lds_bytes(int waves, int obs_rows) { return (size_t)waves * pmlp_grad_lgcap(obs_rows) * sizeof(float); }
+
+// the logits of one state into lg (pmlp_act_wave's loop, written again: that one stays as it is); returns the live row count
+template <int NB, int KS>
+__device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __restrict__ ob, int nraw, int obs_rows, int cols, const float* __restrict__ wp,
+                                                int lr, int lk) {
+  constexpr int HP = 32 * NB;
+  constexpr int G = (KS <= 10 ? 2 : 1) < NB ? (KS <= 10 ? 2 : 1) : NB;
+  const float b2 = wp[(size_t)(2 * KS + 2) * HP];
+  int n = 0;
+  for (int r0 = 0;; r0 += 32) {
+    int r = r0 + lr; r = r < obs_rows ? r : obs_rows - 1;    // inside the block whatever the row count is
+    const int32_t* xr = ob + (size_t)r * cols;
+    float xa[KS];
+#pragma unroll
+    for (int s2 = 0; s2 < KS; s2++) {
+      const int k = 2 * s2 + lk;
+      const int32_t xi = xr[k < cols ? k : 0];
+      xa[s2] = k < cols ? (float)xi : 0.f;
+    }
+    const float logit = pmlp_tile<NB, KS, G>(xa, wp, lr, lk);
+    if (r0 == 0) { n = uni(nraw); n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS; }
+    if (lk == 0 && r0 + lr < n) lg[r0 + lr] = logit + b2;
+    if (r0 + 32 >= n) break;
+  }
+  return n;
+}
+
+// maximum, sum of exponentials and log-partition of the n > 0 logits in lg: pmlp_sample's reductions in pmlp_sample's order
+struct PmlpSoftmax { float mx, se, logz; };
+__device__ __forceinline__ PmlpSoftmax pmlp_softmax_wave(const float* lg, int n, int lane) {
+  float mx = -3.0e38f;
+  for (int r = lane; r < n; r += WAVE) { const float t = lg[r]; mx = t > mx ? t : mx; }
+  mx = lane63_f32(wave_max_f32(mx));
+  float se = 0.f;
+  for (int r = lane; r < n; r += WAVE) se += __expf(lg[r] - mx);
+  se = lane63_f32(wave_sum_f32(se));
+  const float logz = mx + __logf(se);
+  return {mx, se, logz};
+}
+// H = log(se) - (sum_r e_r (z_r - mx)) / se
+__device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int lane, const PmlpSoftmax& sm) {
+  float sd = 0.f;
+  for (int r = lane; r < n; r += WAVE) { const float d = lg[r] - sm.mx; sd += __expf(d) * d; }
+  sd = lane63_f32(wave_sum_f32(sd));
+  return __logf(sm.se) - sd / sm.se;
+}
+
+template <int NB, int KS>
+__global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
+                                                                  const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
+                                                                  const float* __restrict__ wp, float* __restrict__ logprobs, float* __restrict__ entropy) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
+  const int s = blockIdx.x * ((int)blockDim.x / WAVE) + wave;
+  if (s >= B) return;
+  float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);
+  const int nraw = rows[s];
+  const int a = uni(actions[s]);
+  const int n = pmlp_logits_wave<NB, KS>(lg, obs + (size_t)s * obs_rows * cols, nraw, obs_rows, cols, wp, lane & 31, lane >> 5);
+  if (n <= 0) { if (lane == 0) { logprobs[s] = 0.f; if (entropy) entropy[s] = 0.f; } return; }
+  wave_sync();
+  const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+  const bool ok = a >= 0 && a < n;
+  if (lane == 0) logprobs[s] = ok ? lg[a] - sm.logz : __builtin_nanf("");
+  if (entropy) {
+    const float H = pmlp_entropy_wave(lg, n, lane, sm);
+    if (lane == 0) entropy[s] = H;
+  }
+}
+
+template <int NB, int KS>
+__global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
+                                                               const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
+                                                               const float* __restrict__ wp, const float* __restrict__ glogp,
+                                                               const float* __restrict__ gent, int nwaves, float* __restrict__ ws) {
+  constexpr int HP = 32 * NB;
+  constexpr int CB = KS == 32 ? 2 : 1;                               // pmlp_grad_cb
+  constexpr int UBW = NB < (CB == 2 ? 2 : 4) ? NB : (CB == 2 ? 2 : 4);   // pmlp_grad_ubw
+  constexpr int UW = 32 * UBW, NG = NB / UBW;
+  constexpr int PW = UW * (32 * CB + 2) + 4;                         // pmlp_grad_partial_floats
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
+  const int p = blockIdx.x * ((int)blockDim.x / WAVE) + wave;       // my place among the group's waves
+  const int grp = blockIdx.y;                                        // my unit group: unit blocks grp UBW ...
+  if (p >= nwaves) return;
+  float* lg = (float*)smem + (size_t)wave * pmlp_grad_lgcap(obs_rows);
+  const int lr = lane & 31, lk = lane >> 5;
+  const float* wl = wp + lk * HP + grp * UW + lr;                    // my B-operand column: + 2 s HP + 32 u
+
+  bbx_f32x16 dW[UBW][CB];
+  float db1a[UBW], dw2a[UBW], db2a = 0.f;
+#pragma unroll
+  for (int u = 0; u < UBW; u++) {
+    db1a[u] = 0.f; dw2a[u] = 0.f;
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+      for (int v = 0; v < 16; v++) dW[u][cb][v] = 0.f;
+  }
+
+  for (int s = p; s < B; s += nwaves) {
+    const int nraw = rows[s];
+    const int a = uni(actions[s]);
+    const int32_t* ob = obs + (size_t)s * obs_rows * cols;
+    wave_sync();                                                      // (the previous state's g_r have been read)
+    // (the weights are the same for every state and tile: their base pointers are opaque per use, so that the optimiser does not
+    // hoist hundreds of loads out of the loops into registers the dW1 accumulators need)
+    const float* wq = wp;
+    asm volatile("" : "+s"(wq));
+    const int n = pmlp_logits_wave<NB, KS>(lg, ob, nraw, obs_rows, cols, wq, lr, lk);
+    if (n <= 1 || a < 0 || a >= n) continue;                         // no row, one row (delta - p = 0) or a bad action: nothing
+    wave_sync();
+    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+    const float H = pmlp_entropy_wave(lg, n, lane, sm);
+    const float gl = glogp[s], ge = gent ? gent[s] : 0.f;
+    const float rse = 1.f / sm.se;
+    const int n32 = (n + 31) & ~31;
+    for (int r = lane; r < n32; r += WAVE) {                          // (every lane reads and writes its own entries only)
+      float g = 0.f;
+      if (r < n) {
+        const float t = lg[r];
+        const float pr = __expf(t - sm.mx) * rse;
+        g = gl * ((r == a ? 1.f : 0.f) - pr) - ge * pr * ((t - sm.logz) + H);
+      }
+      lg[r] = g; db2a += g;
+    }
+    wave_sync();
+    for (int r0 = 0; r0 < n; r0 += 32) {
+      // the rows of this tile twice: as the k-step operands of the hidden tile (row on the lane), and in the permuted row
+      // order of the accumulator registers with the column on the lane (dW1's A operands); rows beyond n count as zero
+      float xa[KS];
+      {
+        const bool in = r0 + lr < n;
+        const int32_t* xr = ob + (size_t)(in ? r0 + lr : 0) * cols;
+#pragma unroll
+        for (int s2 = 0; s2 < KS; s2++) {
+          const int k = 2 * s2 + lk;
+          const int32_t xi = xr[k < cols ? k : 0];
+          xa[s2] = (in && k < cols) ? (float)xi : 0.f;
+        }
+      }
+      float xt[CB][16], gv[16];
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const bbx_f32x4 g4 = *(const bbx_f32x4*)(lg + r0 + 8 * q + 4 * lk);
+        gv[4 * q] = g4.x; gv[4 * q + 1] = g4.y; gv[4 * q + 2] = g4.z; gv[4 * q + 3] = g4.w;
+      }
+#pragma unroll
+      for (int v = 0; v < 16; v++) {
+        const int r = r0 + (v & 3) + 8 * (v >> 2) + 4 * lk;
+        const bool in = r < n;
+        const int32_t* xr = ob + (size_t)(in ? r : 0) * cols;
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) {
+          const int k = 32 * cb + lr;
+          const int32_t xi = xr[k < cols ? k : 0];
+          xt[cb][v] = (in && k < cols) ? (float)xi : 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < UBW; u++) {
+        const float* wlq = wl + 32 * u;
+        asm volatile("" : "+v"(wlq));
+        const float bu = wlq[(2 * KS - lk) * HP], wu = wlq[(2 * KS + 1 - lk) * HP];   // b1p / w2p [grp UW + 32 u + lr]
+        bbx_f32x16 D;
+#pragma unroll
+        for (int v = 0; v < 16; v++) D[v] = bu;
+#pragma unroll
+        for (int s2 = 0; s2 < KS; s2++) D = __builtin_amdgcn_mfma_f32_32x32x2f32(xa[s2], wlq[2 * s2 * HP], D, 0, 0, 0);
+        float dw2 = dw2a[u], db1 = db1a[u];
+#pragma unroll
+        for (int v = 0; v < 16; v++) {
+          const float h = D[v];
+          const bool pos = h > 0.f;
+          dw2 = fmaf(gv[v], pos ? h : 0.f, dw2);
+          const float dh = pos ? gv[v] * wu : 0.f;
+          db1 += dh;
+          D[v] = dh;
+        }
+        dw2a[u] = dw2; db1a[u] = db1;
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+          for (int v = 0; v < 16; v++) dW[u][cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(xt[cb][v], D[v], dW[u][cb], 0, 0, 0);
+      }
+    }
+  }
+
+  // the wave's partial sums: dW1 [32 CB][UW] | db1 [UW] | dw2 [UW] | db2
+  float* part = ws + ((size_t)p * NG + grp) * PW;
+#pragma unroll
+  for (int u = 0; u < UBW; u++) {
+#pragma unroll
+    for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+      for (int v = 0; v < 16; v++) part[(32 * cb + (v & 3) + 8 * (v >> 2) + 4 * lk) * UW + 32 * u + lr] = dW[u][cb][v];
+    const float tb = db1a[u] + __shfl_xor(db1a[u], 32, WAVE), tw = dw2a[u] + __shfl_xor(dw2a[u], 32, WAVE);   // the unit's other 16 rows
+    if (lk == 0) { part[32 * CB * UW + 32 * u + lr] = tb; part[32 * CB * UW + UW + 32 * u + lr] = tw; }
+  }
+  const float t2 = wave_sum_f32(db2a);
+  if (lane == WAVE - 1) part[32 * CB * UW + 2 * UW] = t2;
+}
+
+// The second stage: output i of dW1 [cols][hidden] | db1 [hidden] | dw2 [hidden] | db2 is the sum of its nwaves partials —
+// 64 outputs per workgroup, the partials of an output dealt to four threads (partial q, q + 4, ... in order), the four sums
+// added as (s0 + s1) + (s2 + s3).  nwaves = 0: zeros.
+__global__ __launch_bounds__(256) void bbx_pmlp_grad_reduce_kernel(const float* __restrict__ ws, int nwaves, int cols, int hidden,
+                                                                   float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2,
+                                                                   float* __restrict__ gb2) {
+  __shared__ float part[4][64];
+  const int cb = pmlp_grad_cb(cols), ubw = pmlp_grad_ubw(cols, hidden), uw = 32 * ubw;
+  const int ng = pmlp_nb_for(hidden) / ubw, pw = pmlp_grad_partial_floats(cols, hidden);
+  const int total = cols * hidden + 2 * hidden + 1;
+  const int j = threadIdx.x & 63, q = threadIdx.x >> 6;
+  const int i = blockIdx.x * 64 + j;
+  float* out = nullptr;
+  float sum = 0.f;
+  if (i < total) {
+    int k, unit;                                                      // row of the partial block (column of W1, or 32 cb: db1, + 1: dw2), unit
+    if (i < cols * hidden) { k = i / hidden; unit = i - k * hidden; out = gw1 + i; }
+    else if (i < cols * hidden + hidden) { k = 32 * cb; unit = i - cols * hidden; out = gb1 + unit; }
+    else if (i < total - 1) { k = 32 * cb + 1; unit = i - cols * hidden - hidden; out = gw2 + unit; }
+    else { k = 32 * cb + 2; unit = 0; out = gb2; }
+    const int grp = unit / uw;
+    const float* src = ws + (size_t)grp * pw + (size_t)k * uw + (unit - grp * uw);
+    for (int w = q; w < nwaves; w += 4) sum += src[(size_t)w * ng * pw];
+  }
+  part[q][j] = sum;
+  __syncthreads();
+  if (q == 0 && out) *out = (part[0][j] + part[1][j]) + (part[2][j] + part[3][j]);
+}

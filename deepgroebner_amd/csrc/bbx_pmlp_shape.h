@@ -11,6 +11,26 @@ BBX_HD constexpr int pmlp_nb_for(int hidden) { const int nb = (hidden + 31) / 32
 // prepared weights (floats): W1p [2 KS][32 NB] | b1p [32 NB] | w2p [32 NB] | b2 | pad to a multiple of 4
 BBX_HD constexpr int pmlp_prepared_floats(int cols, int hidden) { return (2 * pmlp_ks_for(cols) + 2) * 32 * pmlp_nb_for(hidden) + 4; }
 
+// ---- one hidden layer, gradients (bbx_pmlp_grad.h).  A wave accumulates dW1 for PMLP_GRAD_UBW unit blocks x CB column blocks
+// of 32 (64 accumulator registers at the most); the NB / UBW unit groups are separate waves (blockIdx.y).  The states are
+// dealt to pmlp_grad_waves(n) waves per group, wave p taking states p, p + waves, ...: a function of n alone, never of the device.
+constexpr int PMLP_GRAD_STATES_PER_WAVE = 4;      // a further wave per this many states ...
+constexpr int PMLP_GRAD_MAX_WAVES = 1024;         // ... up to this many per unit group
+BBX_HD constexpr int pmlp_grad_cb(int cols) { return pmlp_ks_for(cols) == 32 ? 2 : 1; }
+BBX_HD constexpr int pmlp_grad_ubw(int cols, int hidden) {
+  const int nb = pmlp_nb_for(hidden), most = pmlp_grad_cb(cols) == 2 ? 2 : 4;
+  return nb < most ? nb : most;
+}
+BBX_HD constexpr int pmlp_grad_waves(int n) {
+  const int w = (n + PMLP_GRAD_STATES_PER_WAVE - 1) / PMLP_GRAD_STATES_PER_WAVE;
+  return w < 1 ? 1 : w > PMLP_GRAD_MAX_WAVES ? PMLP_GRAD_MAX_WAVES : w;
+}
+// one wave's partial sums (floats): dW1 [32 CB][32 UBW] | db1 [32 UBW] | dw2 [32 UBW] | db2, pad to a multiple of 4
+BBX_HD constexpr int pmlp_grad_partial_floats(int cols, int hidden) { return 32 * pmlp_grad_ubw(cols, hidden) * (32 * pmlp_grad_cb(cols) + 2) + 4; }
+BBX_HD constexpr int pmlp_grad_workspace_floats(int n, int cols, int hidden) {
+  return pmlp_grad_waves(n) * (pmlp_nb_for(hidden) / pmlp_grad_ubw(cols, hidden)) * pmlp_grad_partial_floats(cols, hidden);
+}
+
 // ---- two and three hidden layers (bbx_pmlp.h: pmlp2_tile; bbx_pmlp2.hip)
 // prepared weights (floats): W1p [4 KS][HP1] | b1p [HP1] | [AM [HPM / 16][HP1 / 16][64][4]] | A2 [HP2 / 16][HPI / 16][64][4] | [bMp [HPM]] |
 // b2p [HP2] | wdp [HP2] | bd, pad          (bracketed: the optional middle hidden layer; HPI = HPM if there is one, else HP1)

@@ -68,6 +68,44 @@ def compute_advantages(rewards, values, gam, lam):
     return discount_rewards(delta, gam * lam)
 
 
+class _PMLPEvaluate(torch.autograd.Function):
+    """log pi(a | s) and the entropy of pi(. | s) of a one-hidden-layer PMLPPolicy through bbx_pmlp_logprob, differentiable
+    with respect to the four parameter tensors through bbx_pmlp_grad (the hidden activations are recomputed there: nothing of
+    size [N, R, hidden] is kept between forward and backward).  No gradient for states, actions or rows."""
+
+    @staticmethod
+    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2):
+        N, R, cols = states.shape
+        w = policy._fused_weights()
+        logp = torch.empty(N, dtype=torch.float32, device=states.device)
+        ent = torch.empty(N, dtype=torch.float32, device=states.device)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(states.device):
+            _ffi.check(_ffi.lib().bbx_pmlp_logprob(p(states), p(rows), p(actions), N, R, cols, w["prepared"], w["hidden"], p(logp), p(ent),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        ctx.policy, ctx.prep, ctx.hidden = policy, w["keep"], w["hidden"]     # (the prepared weights of THIS forward pass)
+        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2)
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, glogp, gent):
+        states, rows, actions, w1, b1, w2, b2 = ctx.saved_tensors
+        N, R, cols = states.shape
+        hidden = ctx.hidden
+        dev = states.device
+        glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
+        gw1 = torch.empty((cols, hidden), dtype=torch.float32, device=dev)
+        gb1 = torch.empty(hidden, dtype=torch.float32, device=dev)
+        gw2 = torch.empty(hidden, dtype=torch.float32, device=dev)
+        gb2 = torch.empty(1, dtype=torch.float32, device=dev)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            ws = ctx.policy._grad_workspace(N, R, cols, hidden, dev)
+            _ffi.check(_ffi.lib().bbx_pmlp_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), hidden, p(glogp), p(gent), p(ws),
+                                                p(gw1), p(gb1), p(gw2), p(gb2), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype)
+
+
 class PMLPPolicy(torch.nn.Module):
     """ParallelMultilayerPerceptron(hidden_layers) of the reference: every row of the -1-padded [batch, rows, cols] int
     block is embedded by the same MLP (relu), scored by one linear unit, padded rows get -1e9, log-softmax over rows."""
@@ -176,6 +214,63 @@ class PMLPPolicy(torch.nn.Module):
             self.__dict__["_fused_cache"] = c
         return c
 
+    def _grad_workspace(self, N, R, cols, hidden, device):
+        """The workspace of bbx_pmlp_grad, kept between calls (it grows only; calls on one stream run in order)."""
+        nfl = _ffi.lib().bbx_pmlp_grad_workspace_floats(N, R, cols, hidden)
+        _ffi.check(min(nfl, 0))
+        ws = self.__dict__.get("_grad_ws")
+        if ws is None or ws.numel() < nfl or ws.device != device:
+            ws = torch.empty(nfl, dtype=torch.float32, device=device)
+            self.__dict__["_grad_ws"] = ws
+        return ws
+
+    @staticmethod
+    def _row_counts(states, rows):
+        return (states[:, :, -1] != -1).sum(1).to(torch.int32) if rows is None else rows
+
+    def evaluate(self, states, actions, rows=None):
+        """The training-time view of recorded experience (pg.py _fit_policy_model): states int [N, R, cols], actions [N] ->
+        (logprobs float32 [N] of the recorded actions, entropy float32 [N] of the distribution over each state's rows),
+        differentiable with respect to the module's parameters.  rows [N]: the live rows per state (None: those whose last
+        column is not -1, as forward masks).  No live rows: 0.0 and 0.0; an action outside the live rows: NaN.
+        One hidden layer on the GPU: the HIP kernels bbx_pmlp_logprob / bbx_pmlp_grad; otherwise evaluate_torch."""
+        N, R, cols = states.shape
+        lin = self.embedding[0]
+        if (states.is_cuda and len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
+                and self.fused_ok(cols, lin.out_features) and 1 <= R <= 2048):
+            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
+            st = states if states.dtype == torch.int32 else states.to(torch.int32)
+            return _PMLPEvaluate.apply(self, st.contiguous(), rows, actions.to(torch.int32).contiguous(), lin.weight, lin.bias,
+                                       self.deciding.weight, self.deciding.bias)
+        return self.evaluate_torch(states, actions, rows)
+
+    def evaluate_torch(self, states, actions, rows=None):
+        """evaluate with torch ops and autograd (any depth, any device; the baseline of the kernels): forward, gather, and
+        -(exp(lp) lp) summed over the live rows."""
+        N, R, _ = states.shape
+        if rows is None:
+            lp = self.forward(states)
+            live = states[:, :, -1] != -1
+        else:                                                         # (the count masks, whatever the rows beyond it hold)
+            live = torch.arange(R, device=states.device)[None, :] < torch.clamp(rows.to(torch.int64), 0, R)[:, None]
+            lg = self._logits(states)
+            lp = torch.log_softmax(torch.where(live, lg, torch.full_like(lg, -1e9)), dim=-1)
+        n = live.sum(1)
+        a = actions.to(torch.int64)
+        ok = (a >= 0) & (a < n)
+        picked = lp.gather(1, torch.where(ok, a, torch.zeros_like(a))[:, None]).squeeze(1)
+        zero = torch.zeros_like(picked)
+        logp = torch.where(n > 0, torch.where(ok, picked, torch.full_like(picked, float("nan"))), zero)
+        lpl = torch.where(live, lp, torch.zeros_like(lp))
+        ent = torch.where(n > 0, -(torch.exp(lpl) * lpl * live.to(lp.dtype)).sum(dim=1), zero)
+        return logp, ent
+
+    def _logits(self, batch):
+        x = batch.to(self.deciding.weight.dtype)
+        for layer in self.embedding:
+            x = torch.relu(layer(x))
+        return self.deciding(x).squeeze(-1)
+
     def act_torch(self, obs, rows, u, actions=None, logprobs=None):
         """The same draw with torch ops (the reference of the fused kernel; any depth)."""
         lp = self.forward(obs)
@@ -259,14 +354,15 @@ class DeviceTrajectoryBuffer:
         self.returns, self.advantages, self.complete = ret, adv, comp
         return ret, adv, comp
 
-    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False):
+    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
         """Training data of all complete-episode steps whose state had more than one row (pg.py:162-240): (states or None,
         actions, logprobs, advantages, values-to-fit), advantages normalised by their mean and population std over the
         complete steps (pg.py:176-178: before the single-row filter, like the reference), steps ordered trajectory after
         trajectory (environment-major).  batch_size=None: one tuple of whole tensors.  Otherwise the reference's
         padded_batch: a list of such tuples of at most batch_size steps each, the state block of a batch cut to the most
         rows any of its states has (-1 padding beyond a state's own rows, as stored); sort=True orders the steps by their
-        number of rows first (less padding); drop_remainder=True leaves a short last batch out."""
+        number of rows first (less padding); drop_remainder=True leaves a short last batch out.  with_rows=True: every tuple
+        carries the states' row counts (int32) as a sixth element (what PMLPPolicy.evaluate takes as `rows`)."""
         if self.returns is None:
             self.finish()
         T = self.t
@@ -281,13 +377,15 @@ class DeviceTrajectoryBuffer:
         out = [st, em(self.actions)[comp][keep], em(self.logprobs)[comp][keep], adv[keep], em(self.returns)[comp].to(torch.float32)[keep]]
         rows = rows[keep]
         if batch_size is None and not sort:
-            return tuple(out)
+            return tuple(out + [rows]) if with_rows else tuple(out)
         if sort:
             order = torch.argsort(rows, stable=True)
             out = [None if x is None else x[order] for x in out]
             rows = rows[order]
         if batch_size is None:
-            return tuple(out)
+            return tuple(out + [rows]) if with_rows else tuple(out)
+        if with_rows:
+            out = out + [rows]
         n = int(rows.numel())
         batches = []
         for i in range(0, n, batch_size):

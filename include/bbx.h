@@ -200,6 +200,39 @@ int bbx_pmlp_prepared_floats(int cols, int hidden);        /* < 0: shape not sup
 int bbx_pmlp_prepare(const float* d_w1, const float* d_b1, const float* d_w2, float b2, int cols, int hidden, float* d_prepared, void* stream);
 int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
                  const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream);
+/* ---- the same policy as a differentiable function of its weights: what the reference's update (pg.py _fit_policy_model)
+ * needs per recorded state.  No handle: device pointers and a stream; asynchronous on `stream`, recordable into a HIP graph,
+ * no host read-back and no allocation inside the calls.  One hidden layer only.
+ * bbx_pmlp_logprob: d_logprobs[s] = log pi(d_actions[s] | state s) and d_entropy[s] (may be NULL) = the entropy of pi(. | state s)
+ * for n recorded states d_obs [n][obs_rows][cols] under the weights d_prepared (as bbx_pmlp_prepare leaves them).
+ *   Shapes: exactly those of bbx_pmlp_act (cols <= 64, hidden <= 256, obs_rows <= BBX_POLICY_MAX_ROWS); anything else:
+ *     BBX_E_UNSUPPORTED with a message, before anything is queued.  n == 0 is legal (bbx_pmlp_grad then only zeroes its outputs).
+ *   Rows: the row COUNT masks, n_s = clamp(d_rows[s], 0, min(obs_rows, 2048)); what lies beyond the live rows, -1 padding or
+ *     garbage, plays no part.
+ *   n_s <= 0: logprob = 0.0f, entropy = 0.0f, no contribution to any gradient.
+ *   n_s == 1: logprob = 0, entropy = 0, and a gradient contribution that is exactly zero (delta - p = 0).
+ *   An action outside [0, n_s) on a state with n_s > 0: logprob = NaN (never a silently wrong number); its entropy is still
+ *     computed; in bbx_pmlp_grad such a state contributes NOTHING (its d_glogp / d_gent entries are not read into any sum).
+ *   exp / log are the fast forms of bbx_pmlp_act; the logits come from the same tile code, the maximum and the sum in the same
+ *     order: for an action bbx_pmlp_act has just sampled from the same block and weights, d_logprobs equals that call's bit for bit.
+ *   Entropy: log(se) - (sum_r e_r (z_r - m)) / se with m = max_r z_r, e_r = exp(z_r - m), se = sum_r e_r (= logZ - sum_r p_r z_r).
+ *   Against a float64 evaluation (tests/policy_grad_cases.py): the log-probability as for bbx_pmlp_act; the entropy within
+ *     C_H 2^-24 (S + |logZ| + 1)(1 + log n_s).
+ * bbx_pmlp_grad: dL/dW1 -> d_gw1 [cols][hidden], dL/db1 -> d_gb1 [hidden], dL/dw2 -> d_gw2 [hidden], dL/db2 -> d_gb2 [1] of
+ *     L = sum_s d_glogp[s] logprob_s + d_gent[s] entropy_s          (d_gent may be NULL = zeros)
+ *   in the layouts bbx_pmlp_prepare READS (not the padded ones).  The outputs are overwritten, not accumulated into.
+ *   The hidden activations are recomputed, never stored: d_workspace holds bbx_pmlp_grad_workspace_floats(n, obs_rows, cols,
+ *   hidden) floats (16-byte aligned), which does not grow with obs_rows and is bounded in n (at most 1024 partial sums per output).
+ *   Deterministic: no floating-point atomics; every wave's partial sums go to the workspace and a second kernel of the same
+ *   call adds them in a fixed order; the partition depends on (n, cols, hidden) alone, not on the device: two calls on the same
+ *   inputs return the same bits.  Against float64 every entry is held to C_G 2^-24 sum_s K_s A_s (K_s = S + |logZ_s| + 1, A_s the
+ *   state's contribution with every term replaced by its absolute value: tests/policy_grad_cases.py). */
+int bbx_pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                     const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream);
+int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden);   /* < 0: shape not supported */
+int bbx_pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                  const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent, float* d_workspace,
+                  float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
 /* The same for ParallelMultilayerPerceptron(hidden_layers=[hidden1, hidden2]) (networks.py:562-571: two dense layers in the
  * embedding): logit_r = w3 . relu(W2^T relu(W1^T x_r + b1) + b2) + b3, both layers on the matrix cores in exact f32, the
  * second layer's weights staged in LDS once per workgroup (bbx_pmlp2.hip); cols <= 64, hidden1, hidden2 <= 128, at most 2048
