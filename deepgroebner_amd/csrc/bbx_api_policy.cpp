@@ -39,6 +39,21 @@ int pmlp_deep_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int ob
   return launched(lrc);
 }
 
+// the training calls for two hidden layers: the shape first (it needs no device and outranks a null pointer: a caller sizing
+// buffers asks with none), naming the number that is out of range
+bool pmlp2_shape_refused(int cols, int h1, int h2) { return cols < 1 || cols > 64 || h1 < 1 || h1 > 128 || h2 < 1 || h2 > 128; }
+int refuse_pmlp2(int obs_rows, int cols, int h1, int h2) {
+  if (cols < 1 || cols > 64) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..64 columns (cols = %d)", cols);
+  if (h1 < 1 || h1 > 128) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..128 units per layer (hidden1 = %d)", h1);
+  if (h2 < 1 || h2 > 128) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..128 units per layer (hidden2 = %d)", h2);
+  return refuse_args(false, false, "", obs_rows);
+}
+int launched_lds(int lrc, int dev, int max_lds) {
+  if (lrc == (int)hipErrorInvalidValue)
+    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, max_lds);
+  return launched(lrc);
+}
+
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
 int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
                    int nsteps, const float* d_u, int32_t* d_actions, float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
@@ -139,6 +154,37 @@ int bbx_pmlp2_prepare(const float* d_w1, const float* d_b1, const float* d_w2, c
 int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
                   const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
   return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, d_u, d_actions, d_logprobs, stream);
+}
+
+// ---- two hidden layers as a differentiable function of the weights (bbx_pmlp2_grad.h).  Shapes: those of bbx_pmlp2_act,
+// refused before a device is asked for anything
+int bbx_pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                      int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (n == 0) return BBX_OK;
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, di.cus,
+                                               di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+
+int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (n < 0 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
+  return pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
+}
+
+int bbx_pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                   int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+                   float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 ||
+                           (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1,
+                                            d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
 }
 
 int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,

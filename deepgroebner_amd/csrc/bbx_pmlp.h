@@ -58,6 +58,26 @@ __device__ __forceinline__ int pmlp_sample(const float* lg, int n, int env, floa
   return uni(pick);
 }
 
+// maximum, sum of exponentials and log-partition of the n > 0 logits in lg: pmlp_sample's reductions in pmlp_sample's order
+struct PmlpSoftmax { float mx, se, logz; };
+__device__ __forceinline__ PmlpSoftmax pmlp_softmax_wave(const float* lg, int n, int lane) {
+  float mx = -3.0e38f;
+  for (int r = lane; r < n; r += WAVE) { const float t = lg[r]; mx = t > mx ? t : mx; }
+  mx = lane63_f32(wave_max_f32(mx));
+  float se = 0.f;
+  for (int r = lane; r < n; r += WAVE) se += __expf(lg[r] - mx);
+  se = lane63_f32(wave_sum_f32(se));
+  const float logz = mx + __logf(se);
+  return {mx, se, logz};
+}
+// H = log(se) - (sum_r e_r (z_r - mx)) / se
+__device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int lane, const PmlpSoftmax& sm) {
+  float sd = 0.f;
+  for (int r = lane; r < n; r += WAVE) { const float d = lg[r] - sm.mx; sd += __expf(d) * d; }
+  sd = lane63_f32(wave_sum_f32(sd));
+  return __logf(sm.se) - sd / sm.se;
+}
+
 // The hidden layer on the matrix cores, exact f32 (v_mfma_f32_32x32x2_f32 = an fmaf chain), everything in registers: a
 // tile is 32 hidden units x 32 rows of the block, D[unit][row] = sum_k W1[k][unit] x[row][k] + b1[unit]:
 //   A operand  lane l: W1[2s + (l >> 5)][unit = 32 nb + (l & 31)]        (coalesced loads, the same for every wave: L1)

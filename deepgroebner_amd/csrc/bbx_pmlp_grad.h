@@ -61,26 +61,7 @@ __device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __rest
   return n;
 }
 
-// maximum, sum of exponentials and log-partition of the n > 0 logits in lg: pmlp_sample's reductions in pmlp_sample's order
-struct PmlpSoftmax { float mx, se, logz; };
-__device__ __forceinline__ PmlpSoftmax pmlp_softmax_wave(const float* lg, int n, int lane) {
-  float mx = -3.0e38f;
-  for (int r = lane; r < n; r += WAVE) { const float t = lg[r]; mx = t > mx ? t : mx; }
-  mx = lane63_f32(wave_max_f32(mx));
-  float se = 0.f;
-  for (int r = lane; r < n; r += WAVE) se += __expf(lg[r] - mx);
-  se = lane63_f32(wave_sum_f32(se));
-  const float logz = mx + __logf(se);
-  return {mx, se, logz};
-}
-// H = log(se) - (sum_r e_r (z_r - mx)) / se
-__device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int lane, const PmlpSoftmax& sm) {
-  float sd = 0.f;
-  for (int r = lane; r < n; r += WAVE) { const float d = lg[r] - sm.mx; sd += __expf(d) * d; }
-  sd = lane63_f32(wave_sum_f32(sd));
-  return __logf(sm.se) - sd / sm.se;
-}
-
+// (pmlp_softmax_wave / pmlp_entropy_wave: bbx_pmlp.h, beside pmlp_sample, whose order they keep)
 template <int NB, int KS>
 __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                   const int32_t* __restrict__ actions, int B, int obs_rows, int cols,

@@ -49,6 +49,28 @@ BBX_HD constexpr Pmlp2Pads pmlp2_pads(int h1, int hm, int h2) {
   return {hp, hp, hp};
 }
 
+// ---- two hidden layers, gradients (bbx_pmlp2_grad.h).  A workgroup of pmlp2_grad_waves waves accumulates all six gradients for
+// the states p, p + groups, ...; wave w owns units 32 w .. 32 w + 31 of both layers.  pmlp2_grad_groups(n) workgroups, each with
+// one slot of partial sums in the workspace: a function of n alone, never of the device.
+constexpr int PMLP2_GRAD_STATES_PER_GROUP = 4;    // a further workgroup per this many states ...
+constexpr int PMLP2_GRAD_MAX_GROUPS = 512;        // ... up to this many (64 x 128 x 128: 512 slots of 24964 floats, 12.8 M <= 2^24)
+BBX_HD constexpr int pmlp2_grad_cb(int cols) { return pmlp2_ks_for(cols) == 16 ? 2 : 1; }   // blocks of 32 columns
+BBX_HD constexpr int pmlp2_grad_waves(int hp1, int hp2) { return (hp1 > hp2 ? hp1 : hp2) / 32; }
+BBX_HD constexpr int pmlp2_grad_groups(int n) {
+  const int g = (n + PMLP2_GRAD_STATES_PER_GROUP - 1) / PMLP2_GRAD_STATES_PER_GROUP;
+  return g < 1 ? 1 : g > PMLP2_GRAD_MAX_GROUPS ? PMLP2_GRAD_MAX_GROUPS : g;
+}
+// one workgroup's partial sums (float offsets; padded sizes, kp = 32 pmlp2_grad_cb(cols)):
+// dW1 [kp][hp1] | db1 [hp1] | dW2 [hp1][hp2] | db2 [hp2] | dw3 [hp2] | db3 [4: one per wave]
+struct Pmlp2GradLayout { int w1, b1, w2, b2, w3, b3, total; };
+BBX_HD constexpr Pmlp2GradLayout pmlp2_grad_layout(int kp, int hp1, int hp2) {
+  const int b1 = kp * hp1, w2 = b1 + hp1, b2 = w2 + hp1 * hp2, w3 = b2 + hp2, b3 = w3 + hp2;
+  return {0, b1, w2, b2, w3, b3, b3 + 4};
+}
+BBX_HD constexpr int pmlp2_grad_workspace_floats(int n, int cols, int h1, int h2) {
+  return pmlp2_grad_groups(n) * pmlp2_grad_layout(32 * pmlp2_grad_cb(cols), pmlp2_hp_for(h1), pmlp2_hp_for(h2)).total;
+}
+
 // ---- the policies built into the step kernels
 // a rollout with one hidden layer, step kernels of W-word monomials (bbx_binom_policy_kernel; 8-byte monomials with 3 variables
 // and k = 2 also bbx_fast_policy_rollout_kernel): 33..128 hidden units, 6 k-steps, or 10 with 16-byte monomials

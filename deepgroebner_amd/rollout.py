@@ -106,12 +106,53 @@ class _PMLPEvaluate(torch.autograd.Function):
         return None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype)
 
 
+class _PMLP2Evaluate(torch.autograd.Function):
+    """_PMLPEvaluate for two hidden layers: bbx_pmlp2_logprob forward, bbx_pmlp2_grad backward (both hidden tiles are recomputed
+    there), gradients for the six parameter tensors in torch.nn.Linear's own layouts.  No gradient for states, actions or rows."""
+
+    @staticmethod
+    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, w3, b3):
+        N, R, cols = states.shape
+        logp = torch.empty(N, dtype=torch.float32, device=states.device)
+        ent = torch.empty(N, dtype=torch.float32, device=states.device)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(states.device):
+            w = policy._deep_weights()
+            h1, h2 = w["hidden"]
+            # (the prepared buffer is refilled in place when the weights change: backward reads THIS forward pass's weights
+            # from a copy of its own, made on the stream behind the fill)
+            prep = w["keep"][0].clone()
+            _ffi.check(_ffi.lib().bbx_pmlp2_logprob(p(states), p(rows), p(actions), N, R, cols, p(prep), h1, h2, p(logp), p(ent),
+                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        ctx.policy, ctx.prep, ctx.hidden = policy, prep, (h1, h2)
+        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, w3, b3)
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, glogp, gent):
+        states, rows, actions, w1, b1, w2, b2, w3, b3 = ctx.saved_tensors
+        N, R, cols = states.shape
+        h1, h2 = ctx.hidden
+        dev = states.device
+        glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gw1, gb1, gw2, gb2, gw3, gb3 = new(cols, h1), new(h1), new(h1, h2), new(h2), new(h2), new(1)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            ws = ctx.policy._grad2_workspace(N, R, cols, h1, h2, dev)
+            _ffi.check(_ffi.lib().bbx_pmlp2_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), h1, h2, p(glogp), p(gent), p(ws),
+                                                 p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return (None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.t().to(w2.dtype), gb2.to(b2.dtype),
+                gw3.view(1, -1).to(w3.dtype), gb3.to(b3.dtype))
+
+
 class PMLPPolicy(torch.nn.Module):
     """ParallelMultilayerPerceptron(hidden_layers) of the reference: every row of the -1-padded [batch, rows, cols] int
     block is embedded by the same MLP (relu), scored by one linear unit, padded rows get -1e9, log-softmax over rows."""
 
-    def __init__(self, cols, hidden_layers=(128,)):
+    def __init__(self, cols, hidden_layers=(128,), deep_kernels=False):
         super().__init__()
+        self.deep_kernels = deep_kernels                              # two hidden layers: evaluate through bbx_pmlp2_logprob / bbx_pmlp2_grad
         dims = [cols] + list(hidden_layers)
         self.embedding = torch.nn.ModuleList([torch.nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:])])
         self.deciding = torch.nn.Linear(dims[-1], 1)
@@ -224,6 +265,16 @@ class PMLPPolicy(torch.nn.Module):
             self.__dict__["_grad_ws"] = ws
         return ws
 
+    def _grad2_workspace(self, N, R, cols, h1, h2, device):
+        """The workspace of bbx_pmlp2_grad, kept between calls (it grows only; calls on one stream run in order)."""
+        nfl = _ffi.lib().bbx_pmlp2_grad_workspace_floats(N, R, cols, h1, h2)
+        _ffi.check(min(nfl, 0))
+        ws = self.__dict__.get("_grad2_ws")
+        if ws is None or ws.numel() < nfl or ws.device != device:
+            ws = torch.empty(nfl, dtype=torch.float32, device=device)
+            self.__dict__["_grad2_ws"] = ws
+        return ws
+
     @staticmethod
     def _row_counts(states, rows):
         return (states[:, :, -1] != -1).sum(1).to(torch.int32) if rows is None else rows
@@ -233,7 +284,8 @@ class PMLPPolicy(torch.nn.Module):
         (logprobs float32 [N] of the recorded actions, entropy float32 [N] of the distribution over each state's rows),
         differentiable with respect to the module's parameters.  rows [N]: the live rows per state (None: those whose last
         column is not -1, as forward masks).  No live rows: 0.0 and 0.0; an action outside the live rows: NaN.
-        One hidden layer on the GPU: the HIP kernels bbx_pmlp_logprob / bbx_pmlp_grad; otherwise evaluate_torch."""
+        One hidden layer on the GPU: the HIP kernels bbx_pmlp_logprob / bbx_pmlp_grad; two hidden layers of at most 128 units
+        on the GPU with deep_kernels set: bbx_pmlp2_logprob / bbx_pmlp2_grad; otherwise evaluate_torch."""
         N, R, cols = states.shape
         lin = self.embedding[0]
         if (states.is_cuda and len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
@@ -242,6 +294,13 @@ class PMLPPolicy(torch.nn.Module):
             st = states if states.dtype == torch.int32 else states.to(torch.int32)
             return _PMLPEvaluate.apply(self, st.contiguous(), rows, actions.to(torch.int32).contiguous(), lin.weight, lin.bias,
                                        self.deciding.weight, self.deciding.bias)
+        if (self.deep_kernels and states.is_cuda and len(self.embedding) == 2 and self.deep_ok(cols) and 1 <= R <= 2048
+                and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
+            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
+            st = states if states.dtype == torch.int32 else states.to(torch.int32)
+            l2 = self.embedding[1]
+            return _PMLP2Evaluate.apply(self, st.contiguous(), rows, actions.to(torch.int32).contiguous(), lin.weight, lin.bias, l2.weight, l2.bias,
+                                        self.deciding.weight, self.deciding.bias)
         return self.evaluate_torch(states, actions, rows)
 
     def evaluate_torch(self, states, actions, rows=None):

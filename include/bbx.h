@@ -202,7 +202,7 @@ int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs
                  const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream);
 /* ---- the same policy as a differentiable function of its weights: what the reference's update (pg.py _fit_policy_model)
  * needs per recorded state.  No handle: device pointers and a stream; asynchronous on `stream`, recordable into a HIP graph,
- * no host read-back and no allocation inside the calls.  One hidden layer only.
+ * no host read-back and no allocation inside the calls.  One hidden layer here; two: bbx_pmlp2_logprob / bbx_pmlp2_grad below.
  * bbx_pmlp_logprob: d_logprobs[s] = log pi(d_actions[s] | state s) and d_entropy[s] (may be NULL) = the entropy of pi(. | state s)
  * for n recorded states d_obs [n][obs_rows][cols] under the weights d_prepared (as bbx_pmlp_prepare leaves them).
  *   Shapes: exactly those of bbx_pmlp_act (cols <= 64, hidden <= 256, obs_rows <= BBX_POLICY_MAX_ROWS); anything else:
@@ -246,6 +246,33 @@ int bbx_pmlp2_prepare(const float* d_w1, const float* d_b1, const float* d_w2, c
                       int cols, int hidden1, int hidden2, float* d_prepared, void* stream);
 int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
                   const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream);
+/* The two-layer policy as a differentiable function of its weights: bbx_pmlp_logprob / bbx_pmlp_grad for
+ * ParallelMultilayerPerceptron([hidden1, hidden2]), with the same conventions word for word — no handle, asynchronous on `stream`,
+ * no host read-back, no allocation; n == 0 is legal (bbx_pmlp2_grad then only zeroes its outputs); the row count masks,
+ * n_s = clamp(d_rows[s], 0, min(obs_rows, 2048)); n_s <= 0: 0.0f / 0.0f and no gradient; n_s == 1: 0 / 0 and an exactly zero
+ * contribution; an action outside [0, n_s): logprob NaN, the entropy still computed, nothing contributed to any gradient (its
+ * d_glogp / d_gent are not read into any sum); entropy = log(se) - (sum_r e_r (z_r - m)) / se; the relu derivative is
+ * [pre-activation > 0] in both layers; L = sum_s d_glogp[s] logprob_s + d_gent[s] entropy_s (d_gent may be NULL = zeros).
+ *   d_prepared: exactly what bbx_pmlp2_prepare leaves.  Shapes: those of bbx_pmlp2_act (cols <= 64, hidden1, hidden2 <= 128,
+ *     obs_rows <= BBX_POLICY_MAX_ROWS); anything else: BBX_E_UNSUPPORTED naming the number, before anything is queued and
+ *     without a device.  A device with less LDS per workgroup than the staged second layer needs: BBX_E_UNSUPPORTED.
+ *   The logits come from the tile code of bbx_pmlp2_act, maximum and sum in its order: for an action bbx_pmlp2_act has just
+ *     drawn from the same block and prepared weights, d_logprobs equals that call's log-probability bit for bit.
+ *   Outputs in the layouts bbx_pmlp2_prepare READS: d_gw1 [cols][hidden1], d_gb1 [hidden1], d_gw2 [hidden1][hidden2],
+ *     d_gb2 [hidden2], d_gw3 [hidden2], d_gb3 [1]; overwritten, not accumulated into; nothing outside them is written.
+ *   Both hidden tiles are recomputed, never stored: d_workspace holds bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1,
+ *     hidden2) floats (16-byte aligned), which does not depend on obs_rows, stops growing with n (at most 512 partial sums per
+ *     output) and is at most 2^24 floats.  Deterministic: no floating-point atomics; every workgroup's partial sums go to the
+ *     workspace and a second kernel of the same call adds them in a fixed order; the partition depends on (n, cols, hidden1,
+ *     hidden2) alone: two calls on the same inputs return the same bits.  Against float64 (tests/policy2_grad_cases.py): the
+ *     log-probability as for bbx_pmlp2_act, the entropy within C_H2 2^-24 K_s (1 + log n_s), every gradient entry within
+ *     C_G2 2^-24 sum_s K_s A_s. */
+int bbx_pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                      const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream);
+int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2);   /* < 0: not supported */
+int bbx_pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                   const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace,
+                   float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
 /* ... and for three hidden layers (hidden_layers=[hidden1, hidden2, hidden3], each <= 128): the same kernel with a middle layer
  * whose output stays in registers as the next layer's B operands; d_w3 [hidden2][hidden3], d_b3 [hidden3], d_w4 [hidden3],
  * d_b4 [1].  All three layers are padded to the widest one's tile size (64 or 128 units). */

@@ -1,8 +1,9 @@
 """States/s of one policy-gradient evaluation on recorded experience: PMLPPolicy.evaluate + loss.backward() through the HIP
-kernels (bbx_pmlp_logprob / bbx_pmlp_grad: hidden activations recomputed, never stored) and through evaluate_torch (torch ops
+kernels (bbx_pmlp_logprob / bbx_pmlp_grad, or bbx_pmlp2_logprob / bbx_pmlp2_grad for --hidden H1,H2 — PMLPPolicy(deep_kernels=True):
+hidden activations recomputed, never stored) and through evaluate_torch (torch ops
 and autograd over the whole [N, R, cols] block), on identical tensors in the same process.  Prints one JSON line.
 
-    python scripts/bench_policy_grad.py [--states 4096] [--rows 64] [--cols 12] [--hidden 128] [--reps 30]
+    python scripts/bench_policy_grad.py [--states 4096] [--rows 64] [--cols 12] [--hidden 128 | 128,128] [--reps 30]
 
 Each repetition is timed with device events; the rate is states over the MEDIAN repetition; the two paths alternate in blocks
 of --block repetitions so that drift hits both.  Peak memory: torch.cuda.max_memory_allocated over one evaluate + backward of
@@ -23,7 +24,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--states", type=int, default=4096)
 ap.add_argument("--rows", type=int, default=64, help="rows per state block (R); the live rows of a state are uniform in [2, R]")
 ap.add_argument("--cols", type=int, default=12)
-ap.add_argument("--hidden", type=int, default=128)
+ap.add_argument("--hidden", type=lambda t: [int(h) for h in t.split(",")], default=[128], help="hidden units: H, or H1,H2 for two hidden layers")
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--reps", type=int, default=30, help="timed repetitions per path (at least 20)")
 ap.add_argument("--block", type=int, default=5)
@@ -31,13 +32,15 @@ ap.add_argument("--seed", type=int, default=0)
 a = ap.parse_args()
 if a.reps < 20:
     ap.error("--reps must be at least 20")
+if len(a.hidden) not in (1, 2):
+    ap.error("--hidden takes one or two layer sizes")
 if not torch.cuda.is_available():
     sys.exit("bench_policy_grad: no GPU (there is no CPU fall-back for a measurement)")
 
 N, R, cols = a.states, a.rows, a.cols
 rng = np.random.default_rng(a.seed)
 torch.manual_seed(a.seed)
-policy = PMLPPolicy(cols, [a.hidden]).cuda()
+policy = PMLPPolicy(cols, a.hidden, deep_kernels=len(a.hidden) == 2).cuda()
 rows_h = rng.integers(2, R + 1, size=N).astype(np.int32)
 obs_h = rng.integers(0, 10, size=(N, R, cols)).astype(np.int32)
 obs_h[np.arange(R)[None, :] >= rows_h[:, None]] = -1
@@ -87,7 +90,7 @@ while done < a.reps:
     done += k
 
 med = {name: statistics.median(t) for name, t in times.items()}
-out = {"bench": "policy_grad", "device": torch.cuda.get_device_name(0), "states": N, "rows": R, "cols": cols, "hidden": a.hidden, "reps": a.reps,
+out = {"bench": "policy_grad", "device": torch.cuda.get_device_name(0), "states": N, "rows": R, "cols": cols, "hidden": a.hidden[0] if len(a.hidden) == 1 else a.hidden, "reps": a.reps,
        "live_rows_mean": float(rows_h.mean())}
 for name in PATHS:
     t = sorted(times[name])

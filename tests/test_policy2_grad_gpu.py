@@ -1,0 +1,290 @@
+"""bbx_pmlp2_logprob / bbx_pmlp2_grad and PMLPPolicy.evaluate(deep_kernels) on the device against the float64 reference of
+tests/policy2_grad_cases.py (tests/test_policy2_grad_cpu.py checks that reference against autograd in double precision): the
+log-probability of every live row at every padded layer size and tile boundary, the entropy, the conventions, bit-equality with
+the sampler, the gradients at the batch sizes where the partition of the states changes, every operand permutation of the
+backward pass with exact integer data, determinism, and the autograd wrapper.  Each case prints the ratio of its bound it needed
+before it asserts (pytest -s)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import policy_cases as pc
+from tests import policy_grad_cases as gc
+from tests import policy2_grad_cases as g2
+
+pytestmark = pytest.mark.gpu
+_ids = lambda v: str(v).replace(" ", "")
+GUARD = 64
+
+
+def _p(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _prepared(weights):
+    """(prepared weights on the device, the policy that keeps them alive)"""
+    pol = pc.to_policy(weights, "cuda")
+    return pol._deep_weights()["prepared"], pol
+
+
+def _hidden(weights):
+    return weights[0][0].shape[1], weights[1][0].shape[1]
+
+
+def _logprob(weights, obs, rows, actions, entropy=True):
+    """bbx_pmlp2_logprob through the C ABI on device copies; (logprobs, entropy or None) as numpy."""
+    import torch
+    from deepgroebner_amd import _ffi
+    prep, keep = _prepared(weights)
+    N, R, cols = obs.shape
+    lp = torch.full((N,), 7.0, device="cuda"); ent = torch.full((N,), 7.0, device="cuda")
+    _ffi.check(_ffi.lib().bbx_pmlp2_logprob(_p(obs), _p(rows), _p(actions), N, R, cols, prep, *_hidden(weights), _p(lp),
+                                            _p(ent) if entropy else None, _stream()))
+    torch.cuda.synchronize()
+    return lp.cpu().numpy(), (ent.cpu().numpy() if entropy else None)
+
+
+def _grad(weights, obs, rows, actions, glogp, gent):
+    """bbx_pmlp2_grad through the C ABI, the six outputs inside one buffer with NaN guard bands between them: returns them as numpy
+    (dW1 [cols][h1], db1, dW2 [h1][h2], db2, dw3, db3) after checking that the bands and the end of the workspace are untouched."""
+    import torch
+    from deepgroebner_amd import _ffi
+    lib = _ffi.lib()
+    prep, keep = _prepared(weights)
+    N, R, cols = obs.shape
+    h1, h2 = _hidden(weights)
+    sizes = (cols * h1, h1, h1 * h2, h2, h2, 1)
+    buf = torch.full((sum(sizes) + 7 * GUARD,), float("nan"), device="cuda")
+    offs = np.cumsum([GUARD] + [s + GUARD for s in sizes[:-1]])
+    outs = [buf[int(o):int(o) + s] for o, s in zip(offs, sizes)]
+    nfl = lib.bbx_pmlp2_grad_workspace_floats(N, R, cols, h1, h2)
+    assert nfl > 0
+    ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
+    _ffi.check(lib.bbx_pmlp2_grad(_p(obs), _p(rows), _p(actions), N, R, cols, prep, h1, h2, _p(glogp), _p(gent) if gent is not None else None,
+                                  _p(ws), *[_p(o) for o in outs], _stream()))
+    torch.cuda.synchronize()
+    host = buf.cpu().numpy()
+    inside = np.zeros(len(host), dtype=bool)
+    for o, s in zip(offs, sizes):
+        inside[int(o):int(o) + s] = True
+    assert np.isnan(host[~inside]).all(), "the guard bands around the gradient outputs were written"
+    assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
+    got = [host[int(o):int(o) + s].copy() for o, s in zip(offs, sizes)]
+    got[0] = got[0].reshape(cols, h1); got[2] = got[2].reshape(h1, h2)
+    return tuple(got)
+
+
+def _cuda(*arrays):
+    import torch
+    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+# ---- log-probability and entropy ---------------------------------------------------------------------------------------------
+EVAL_SHAPES = [(1, (1, 1)), (12, (128, 128)), (13, (65, 64)), (33, (17, 128)), (64, (64, 65))]
+
+
+def _every_row(case):
+    """Actions covering every live row of a sweep case: copy j of a block records row j."""
+    return np.concatenate([np.arange(int(n)) for n in case.base_ref.n]).astype(np.int32)
+
+
+@pytest.mark.parametrize("cols,hidden", EVAL_SHAPES, ids=_ids)
+def test_logprob_and_entropy_at_every_row_edge(cols, hidden):
+    """Every live row of every count around the tiles of 16 rows and the wave of 64 recorded once, in blocks of 136 rows with
+    garbage beyond the live ones.  logprob within Ref.tol(), entropy within C_H2 2^-24 K (1 + log n); one row: 0 and 0."""
+    case = pc.row_sweep(cols, hidden, pc.LIVE_ROWS, 300, R=136, garbage=True)
+    actions = _every_row(case)
+    obs, rows, act = _cuda(case.obs, case.rows.astype(np.int32), actions)
+    lp, ent = _logprob(case.weights, obs, rows, act)
+    rl, rh, ref = gc.reference_eval(case.weights, None, None, actions, ref=case.ref)
+    assert np.isfinite(lp).all() and np.isfinite(ent).all()
+    el, eh = np.abs(lp - rl), np.abs(ent - rh)
+    r_l = float((el / ref.tol(1.0)).max()); r_h = float((eh / g2.entropy_tol(ref, 1.0)).max())
+    print("ratios %-60s N=%-5d r_l=%.3f r_h=%.3f" % (case.name, len(actions), r_l, r_h))
+    assert (el <= ref.tol()).all(), (case.name, "logprob", r_l)
+    assert (eh <= g2.entropy_tol(ref)).all(), (case.name, "entropy", r_h)
+    one = ref.n == 1
+    assert one.any() and (lp[one] == 0.0).all() and (ent[one] == 0.0).all()
+
+
+def test_conventions_are_exact():
+    """n_s <= 0: 0.0 / 0.0; n_s == 1: 0 / 0; an action outside [0, n_s): NaN with the entropy still computed; a NULL entropy
+    pointer leaves the log-probabilities as they are."""
+    case = pc.edge_case(12, (128, 128), 8, 24, (0, -3, 1, 1, 24, 40, 7, 16), 5, True)
+    actions = np.array([0, 5, 0, 1, 24, -1, 7, 15], dtype=np.int32)
+    obs, rows, act = _cuda(case.obs, case.rows.astype(np.int32), actions)
+    lp, ent = _logprob(case.weights, obs, rows, act)
+    rl, rh, ref = gc.reference_eval(case.weights, None, None, actions, ref=case.ref)
+    assert lp[0] == 0.0 and ent[0] == 0.0 and lp[1] == 0.0 and ent[1] == 0.0
+    assert lp[2] == 0.0 and ent[2] == 0.0
+    assert np.isnan(lp[3]) and ent[3] == 0.0                       # one row, action 1: outside
+    assert np.isnan(lp[4]) and np.isnan(lp[5]) and np.isnan(lp[6])
+    assert (np.abs(ent - rh) <= g2.entropy_tol(ref)).all() and ent[4] > 0 and ent[5] > 0
+    assert np.isfinite(lp[7]) and abs(lp[7] - rl[7]) <= ref.tol()[7]
+    lp2, none = _logprob(case.weights, obs, rows, act, entropy=False)
+    assert none is None and np.array_equal(lp, lp2, equal_nan=True)
+
+
+@pytest.mark.parametrize("cols,hidden", [(12, (128, 128)), (64, (65, 64))], ids=_ids)
+def test_logprob_equals_the_samplers_bit_for_bit(cols, hidden):
+    """bbx_pmlp2_act, then bbx_pmlp2_logprob with the sampled actions on the same block and weights: the same bits."""
+    import torch
+    live = pc.LIVE_ROWS + (2048,)
+    case = pc.edge_case(cols, hidden, len(live), 2048, live, 41, True)
+    pol = pc.to_policy(case.weights, "cuda")
+    obs, rows, u = _cuda(case.obs, case.rows.astype(np.int32), case.u)
+    a, l = pol.act(obs, rows, u)
+    torch.cuda.synchronize()
+    lp, _ = _logprob(case.weights, obs, rows, a)
+    assert np.array_equal(l.cpu().numpy().view(np.uint32), lp.view(np.uint32))
+    pc.check_case(case, a.cpu().numpy(), l.cpu().numpy())
+
+
+# ---- gradients ---------------------------------------------------------------------------------------------------------------
+GRAD_SHAPES = [(1, (1, 1)), (12, (64, 64)), (13, (65, 64)), (33, (17, 128)), (64, (128, 128))]
+SPG, MAXG = g2.header_constants()
+# one state; five; one more than a workgroup takes before a second is added; three workgroups with uneven shares
+GRAD_BATCHES = sorted({1, 5, SPG + 1, 2 * SPG + 1})
+GRAD_ROWS = (33, 0, 129, 1, 2, 64, 17, 31, 65, 1, 128, 16, 32, 63, 15, 127)
+
+
+def _grad_case(cols, hidden, N, seed, R=136, rows=GRAD_ROWS, with_gent=True):
+    w = pc.make_weights(cols, hidden, seed)
+    rows = np.resize(np.array(rows, dtype=np.int32), N)
+    obs = pc.fill_padding(pc.random_blocks(N, R, cols, seed + 1), rows, True, seed + 2)
+    rng = np.random.default_rng(seed + 3)
+    n = np.clip(rows, 0, R)
+    actions = (rng.integers(0, 1 << 30, size=N) % np.maximum(n, 1)).astype(np.int32)
+    glogp = rng.normal(size=N).astype(np.float32)
+    gent = rng.normal(size=N).astype(np.float32) if with_gent else None
+    return w, obs, rows, actions, glogp, gent
+
+
+def _run_grad(w, obs, rows, actions, glogp, gent, what, summed=False):
+    ref = pc.reference(w, obs, rows)
+    want, A = g2.reference_grad2(w, obs, rows, actions, glogp, gent, scale=gc.state_scale(ref) if summed else None, ref=ref)
+    got = _grad(w, *_cuda(obs, rows, actions, glogp, gent))
+    r = g2.grad_ratio(got, want, A, None if summed else ref)
+    print("ratios %-60s r_g=%.3f" % (what, r))
+    g2.check_grads(got, want, A, None if summed else ref, what=what)
+    return r
+
+
+@pytest.mark.parametrize("N", GRAD_BATCHES)
+@pytest.mark.parametrize("cols,hidden", GRAD_SHAPES, ids=_ids)
+def test_gradients_against_float64(cols, hidden, N):
+    """Row counts mixed over the tile edges, 0 and 1, garbage beyond them, glogp and gent of both signs; once more without gent
+    (NULL).  Every entry of the six gradients within C_G2 2^-24 sum_s K_s A_theta,s; the outputs have the unpadded shapes and
+    nothing around them is written."""
+    w, obs, rows, actions, glogp, gent = _grad_case(cols, hidden, N, 500 + N)
+    _run_grad(w, obs, rows, actions, glogp, gent, "grad %s N=%d" % (pc.label(cols, hidden), N))
+    if N == 5:
+        _run_grad(w, obs, rows, actions, glogp, None, "grad %s N=%d gent=NULL" % (pc.label(cols, hidden), N))
+
+
+def test_gradients_large_batch_and_determinism():
+    """More states than PMLP2_GRAD_STATES_PER_GROUP x PMLP2_GRAD_MAX_GROUPS: every workgroup loops over several states and the
+    second kernel adds PMLP2_GRAD_MAX_GROUPS partials per output.  Two calls on the same inputs return the same bits."""
+    N = SPG * MAXG + 5
+    w, obs, rows, actions, glogp, gent = _grad_case(12, (64, 64), N, 77, R=33, rows=(33, 0, 2, 1, 17, 32, 31, 16, 15))
+    actions[7] = 40; actions[11] = -1                              # bad actions contribute nothing
+    _run_grad(w, obs, rows, actions, glogp, gent, "grad 12x64x64 N=%d" % N, summed=True)
+    dev = _cuda(obs, rows, actions, glogp, gent)
+    a = _grad(w, *dev); b = _grad(w, *dev)
+    for x, y in zip(a, b):
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+
+
+def test_gradients_are_deterministic_at_the_largest_shape():
+    w, obs, rows, actions, glogp, gent = _grad_case(64, (128, 128), 2 * SPG + 1, 78)
+    dev = _cuda(obs, rows, actions, glogp, gent)
+    a = _grad(w, *dev); b = _grad(w, *dev)
+    for x, y in zip(a, b):
+        assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
+
+
+def test_states_without_a_gradient_contribute_exactly_nothing():
+    """No row, one row, a bad action: whatever their glogp / gent (NaN included for the skipped ones), the outputs are those of
+    the other states alone; n == 0 zeroes the outputs."""
+    w, obs, rows, actions, glogp, gent = _grad_case(12, (128, 128), 6, 90, R=40, rows=(0, 17, 1, 33, -2, 20))
+    actions[3] = 33
+    dev = _cuda(obs, rows, actions, glogp, gent)
+    a = _grad(w, *dev)
+    glogp2, gent2 = glogp.copy(), gent.copy()
+    glogp2[[0, 3, 4]] = np.nan; gent2[[0, 3, 4]] = np.inf; glogp2[2] = 1e30; gent2[2] = -1e30
+    b = _grad(w, *_cuda(obs, rows, actions, glogp2, gent2))
+    keep = [1, 5]
+    c = _grad(w, *_cuda(obs[keep], rows[keep], actions[keep], glogp[keep], gent[keep]))
+    for x, y, z in zip(a, b, c):
+        assert np.array_equal(x, y) and np.array_equal(x, z)
+    assert any((x != 0).any() for x in a)
+    import torch
+    z = _grad(w, torch.zeros((0, 40, 12), dtype=torch.int32, device="cuda"), *_cuda(rows[:0], actions[:0], glogp[:0], gent[:0]))
+    assert len(z) == 6 and all((x == 0).all() for x in z)
+
+
+@pytest.mark.parametrize("n", g2.INT_ROWS)
+@pytest.mark.parametrize("cols,hidden", g2.INT_SHAPES, ids=_ids)
+@pytest.mark.parametrize("kind", ["a", "b"])
+def test_operand_permutations_with_exact_integers(kind, cols, hidden, n):
+    """The two constructions of tests/policy2_grad_cases.py (paired second-layer units: dW2, db2, dw3 with dW1 = db1 = 0; paired
+    first-layer units: dW1, db1, dW2 through per-row relu masks with db2 = dw3 = 0): all six outputs equal the float64 reference
+    exactly."""
+    w, obs, rows, actions, glogp = (g2.int_case_a if kind == "a" else g2.int_case_b)(cols, hidden, n)
+    want = g2.int_case_reference(kind, w, obs, rows, actions, glogp)
+    got = _grad(w, *_cuda(obs, rows, actions, glogp, None))
+    for name, x, y in zip(g2.NAMES, got, want):
+        x = x.astype(np.float64).reshape(y.shape)
+        assert np.array_equal(x, y), (name, int((x != y).sum()), "of", y.size)
+
+
+# ---- autograd ----------------------------------------------------------------------------------------------------------------
+def _grads_of(pol):
+    l1, l2 = pol.embedding
+    return tuple(t.cpu().numpy() for t in (l1.weight.grad.t(), l1.bias.grad, l2.weight.grad.t(), l2.bias.grad, pol.deciding.weight.grad.reshape(-1),
+                                           pol.deciding.bias.grad.reshape(-1)))
+
+
+def test_evaluate_backward_and_an_optimizer_step():
+    """PMLPPolicy.evaluate with deep_kernels on the GPU (rows derived from the -1 padding), loss = (w logp).sum() - 0.01 ent.mean(),
+    backward: the .grad of all six parameters within the gradient bound; after optimizer.step() a second evaluate sees the new
+    weights; with deep_kernels off the same call takes the torch path."""
+    import torch
+    N, R, cols, hidden = 37, 40, 12, (64, 64)
+    w = pc.make_weights(cols, hidden, 21)
+    rows = np.resize(np.array((33, 2, 40, 17, 5, 32, 31), dtype=np.int32), N)
+    obs = pc.fill_padding(pc.random_blocks(N, R, cols, 22), rows, False)
+    rng = np.random.default_rng(23)
+    actions = (rng.integers(0, 1 << 30, size=N) % rows).astype(np.int32)
+    wt = rng.normal(size=N).astype(np.float32)
+    pol = pc.to_policy(w, "cuda")
+    st, act, wtd = _cuda(obs, actions, wt)
+    logp0, _ = pol.evaluate(st, act)
+    assert logp0.grad_fn is not None and not type(logp0.grad_fn).__name__.startswith("_PMLP2Evaluate")
+    pol.deep_kernels = True
+    opt = torch.optim.SGD(pol.parameters(), lr=0.05)
+    logp, ent = pol.evaluate(st, act)
+    assert logp.requires_grad and logp.grad_fn is not None and type(logp.grad_fn).__name__.startswith("_PMLP2Evaluate")
+    loss = (wtd * logp).sum() - 0.01 * ent.mean()
+    opt.zero_grad(); loss.backward()
+    ref = pc.reference(w, obs, rows)
+    want, A = g2.reference_grad2(w, obs, rows, actions, wt, np.full(N, -0.01 / N), ref=ref)
+    got = _grads_of(pol)
+    print("ratios autograd r_g=%.3f" % g2.grad_ratio(got, want, A, ref))
+    g2.check_grads(got, want, A, ref, what="autograd")
+    rl, rh, _ = gc.reference_eval(w, obs, rows, actions, ref=ref)
+    assert (np.abs(logp.detach().cpu().numpy() - rl) <= ref.tol()).all()
+    opt.step()
+    w2 = pc.weights_of(pol)
+    assert not np.array_equal(w2[0][0], w[0][0])
+    logp2, ent2 = pol.evaluate(st, act, torch.from_numpy(rows).cuda())
+    rl2, rh2, ref2 = gc.reference_eval(w2, obs, rows, actions)
+    assert (np.abs(logp2.detach().cpu().numpy() - rl2) <= ref2.tol()).all()
+    assert (np.abs(ent2.detach().cpu().numpy() - rh2) <= g2.entropy_tol(ref2)).all()
+    assert np.abs(rl2 - rl).max() > 10 * ref2.tol().max(), "the step did not move the policy: the check above proves nothing"
