@@ -175,10 +175,14 @@ static int ss_unguarded_partition(int* v, int first, int last, int pivot, cmp_fn
     first++;
   }
 }
+/* test statistic: how often std_sort of this thread fell back to heapsort and how many partition levels deep its
+ * introsort loop went (of the 2 * floor(log2 n) allowed) since the last clear; bo_stat_sort(1, ...) reads and clears */
+static __thread int bo_sort_heapsorts = 0, bo_sort_depth = 0, bo_sort_limit = 0;
 static void ss_introsort_loop(int* v, int first, int last, int depth, cmp_fn cmp, void* ctx) {
   while (last - first > 16) {
-    if (depth == 0) { ss_heapsort(v, first, last, cmp, ctx); return; }
+    if (depth == 0) { bo_sort_heapsorts++; ss_heapsort(v, first, last, cmp, ctx); return; }
     --depth;
+    if (bo_sort_limit - depth > bo_sort_depth) bo_sort_depth = bo_sort_limit - depth;
     int mid = first + (last - first) / 2;
     ss_move_median_to_first(v, first, first + 1, mid, last - 1, cmp, ctx);
     int cut = ss_unguarded_partition(v, first + 1, last, first, cmp, ctx);
@@ -190,6 +194,7 @@ static void std_sort(int* v, int n, cmp_fn cmp, void* ctx) {
   if (n <= 0) return;
   int lg = 0;
   for (int t = n; t > 1; t >>= 1) lg++;
+  bo_sort_limit = 2 * lg;
   ss_introsort_loop(v, 0, n, 2 * lg, cmp, ctx);
   if (n > 16) {
     ss_insertion_sort(v, 0, 16, cmp, ctx);
@@ -746,8 +751,11 @@ static polyvec buchberger_pairs(const polyvec* F, const pairvec* S, int selectio
   double discount = 1.0;
   /* reducers G_ as an index order into G */
   int* ord = NULL; int nord = 0, cord = 0;
-  for (int i = 0; i < G.n; i++) gord_push(&ord, &nord, &cord, i);
-  if (sort_reducers) std_sort(ord, nord, lm_asc_cmp, &G); /* 157-158: std::sort, NOT stable */
+  /* sort_reducers == 2 (tests only, a mutant): the STABLE order the environment keeps by upper_bound insertion, i.e.
+   * what a rollout starts from when the std::sort below is forgotten */
+  if (sort_reducers == 2) for (int i = 0; i < G.n; i++) gord_insert_sorted(&ord, &nord, &cord, &G, i);
+  else for (int i = 0; i < G.n; i++) gord_push(&ord, &nord, &cord, i);
+  if (sort_reducers == 1) std_sort(ord, nord, lm_asc_cmp, &G); /* 157-158: std::sort, NOT stable */
   minstd0 rng; rng.x = 1;
   if (selection == SEL_RANDOM) rng_seed(&rng, has_seed ? seed : (int)time(NULL)); /* 200-204 */
   const poly** Fp = NULL; int cF = 0;
@@ -1167,6 +1175,17 @@ int bo_update(void* plG, int* pairs, int npairs, void* plf, int fi, int elim) {
   int n = P.n;
   pr_free(&P);
   return n;
+}
+int bo_stat_sort(int reset, int* max_depth) {
+  const int h = bo_sort_heapsorts;
+  if (max_depth) *max_depth = bo_sort_depth;
+  if (reset) { bo_sort_heapsorts = 0; bo_sort_depth = 0; }
+  return h;
+}
+void bo_sort_order(void* pl, int* out) { /* std::sort of the list by lead monomial, ascending, as indices */
+  polyvec* G = PL(pl);
+  for (int i = 0; i < G->n; i++) out[i] = i;
+  std_sort(out, G->n, lm_asc_cmp, G);
 }
 void bo_minimalize(void* pl, void* out) { polyvec r = minimalize(PL(pl)); pv_free(PL(out)); *PL(out) = r; }
 void bo_interreduce(void* pl, void* out) { polyvec r = interreduce(PL(pl)); pv_free(PL(out)); *PL(out) = r; }

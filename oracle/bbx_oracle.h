@@ -50,9 +50,15 @@ int  bo_reduce(void* plg, int gi, void* plF, void* out);
 int  bo_update(void* plG, int* pairs, int npairs, void* plf, int fi, int elim);
 void bo_minimalize(void* pl, void* out);
 void bo_interreduce(void* pl, void* out);
+/* sort_reducers: 0 basis order, 1 std::sort (the reference), 2 the stable order of upper_bound insertion (a mutant for
+ * tests: "the re-sort was forgotten") */
 void bo_buchberger(void* plF, const int* pairs, int npairs, int selection, int elim, int rewards,
                    int sort_input, int sort_reducers, double gamma, int has_seed, int seed,
                    void* out, double* stats);
+void bo_sort_order(void* pl, int* out);          /* std::sort's order of pl by lead monomial, ascending, as indices */
+/* heapsort fallbacks of this thread's std::sort restatement since the last clear (returned) and the deepest partition
+ * level its introsort loop reached (test statistic) */
+int  bo_stat_sort(int reset, int* max_depth);
 
 /* ---- ideal generators ---------------------------------------------------- */
 void  bo_cyclic(int n, void* out);

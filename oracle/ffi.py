@@ -79,6 +79,7 @@ def _sig(lib, pre):
         f("pl_copy", None, _vp, C.c_int, _vp)
         f("env_last_step_bytes", C.c_longlong, _vp)
         f("stat_max_terms", C.c_int, C.c_int)
+        f("stat_sort", C.c_int, C.c_int, _ip); f("sort_order", None, _vp, _ip)
         f("run_random", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong))
     else:
         f("lme_new", _vp, C.c_char_p, C.c_int, C.c_int, C.c_int); f("lme_free", None, _vp)
@@ -295,6 +296,20 @@ class Lib:
                               out.h if want_basis else None, stats)
         keys = ("zero_reductions", "nonzero_reductions", "polynomial_additions", "total_reward", "discounted_return")
         return (out.all() if want_basis else None), dict(zip(keys, list(stats)))
+
+    def sort_order(self, G):
+        """std::sort's order of the polynomials G by lead monomial (ascending), as indices: what buchberger() starts its
+        reducers from (C restatement only)."""
+        pl = G if isinstance(G, PolyList) else PolyList(self, G)
+        out = np.zeros(max(len(pl), 1), dtype=np.int32)
+        self.fn("sort_order")(pl.h, out.ctypes.data_as(_ip))
+        return out[:len(pl)].copy()
+
+    def stat_sort(self, reset=True):
+        """(heapsort fallbacks, deepest partition level) of this thread's std::sort restatement since the last clear."""
+        d = C.c_int(0)
+        h = self.fn("stat_sort")(int(reset), C.byref(d))
+        return h, d.value
 
     def cyclic(self, n):
         out = PolyList(self)
