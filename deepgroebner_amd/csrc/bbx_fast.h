@@ -82,6 +82,14 @@ __device__ __forceinline__ int f_prefix(uint64_t mask) {
 __device__ __forceinline__ uint64_t f_u64(const M2& m) { return ((uint64_t)m.w[1] << 32) | m.w[0]; }
 __device__ __forceinline__ uint64_t f_lowmask(int n) { return n >= 64 ? ~0ull : ((1ull << n) - 1ull); }   // n in [0,64]
 
+// A wait for every vector-memory load in flight, for RARE paths only (kernel entry, behind a reset, behind the large-basis
+// update): the compiler tracks pending loads per register without regard to the path, so a load that one rare path leaves
+// unconsumed makes it wait where the common step path first overwrites that register — and on gfx9 that wait also holds
+// the wave until the previous step's observation stores are acknowledged (one counter for loads and stores).  Said here,
+// where everything has long landed, the wait costs nothing and the step has none.  (gfx9 encoding: vmcnt = 0 in bits 3:0
+// and 15:14, expcnt = 7 and lgkmcnt = 15 left alone.)  It only ever ADDS a wait: the compiler's own stay where they are.
+__device__ __forceinline__ void f_loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // shift-insert `nv` at position p (0..63) of a 64-lane register array; returns the element shifted out of lane 63
 __device__ __forceinline__ uint32_t f_insert(uint32_t& arr, uint32_t nv, int p, int lane) {
   uint32_t out = f_readlane(arr, 63);
@@ -273,6 +281,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   }
   // the first 64 pairs also live in a register (lane k <-> pairs[k]; LDS stays the complete copy): the selected pair is
   // a v_readlane, removing it a DPP shift, and the Gebauer-Moeller filter starts its gathers without a pair load
+  f_loads_landed();                                    // (the staged reducer registers: first read inside the first step's reduction)
   uint32_t PA = pairs[lane];
 
   // the random agent's hashes for 64 consecutive steps at a time, one per lane (recomputed every 64 steps)
@@ -412,9 +421,10 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   auto add_poly = [&](const BTerm<2>& t0, const BTerm<2>& t1, int sugar, int skip, auto banks) {
     constexpr int BK = decltype(banks)::value;
     const int g = nG;                                     // == m of update()
-    // 1/LC comes from a table in HBM/L2: issue the load now, consume it at the very end (the pair update below
-    // does not need it), so its latency overlaps the Gebauer-Moeller work
-    const uint32_t inv_raw = t0.c == 1 ? 1u : (uint32_t)p.inv_table[t0.c];
+    // 1/LC comes from a table in HBM/L2: the load is issued here, with no control flow around it (the table holds 1 at
+    // index 1; a conditional would make the value a scalar phi that is waited for on the spot), and stays a raw vector
+    // register until its first use behind the reducer search below, so its latency overlaps the Gebauer-Moeller work
+    const uint32_t inv_raw = (uint32_t)p.inv_table[t0.c];
     const M2 f = t0.m;
     const M2 tail = t1.c ? t1.m : m_zero<2>();
     if (lane == 0) { lm[g] = f; tm[g] = tail; }
@@ -516,7 +526,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         const bool le = k < novf && !m_gt(lm[sx[k < novf ? k : 0]], f);
         pos += __popcll(ballot64(le));
       }
-      const uint32_t inv = inv_raw;
+      const uint32_t inv = (uint32_t)uni((int)inv_raw);        // (the one wait for the table read: every lane read the same entry)
       if (lane == 0) gi[g] = make_uint2(t0.c | (t1.c << 16), inv | ((uint32_t)sugar << 16));
       const uint2 ns = make_uint2(t1.c | (negmod(mulmod(t1.c, inv)) << 16), (uint32_t)sugar | ((uint32_t)g << 16));   // .x = tc | (-tc / lc) << 16
       // the overflow order takes the new element (pos beyond the registers) or the reducer that falls out of the last bank
@@ -726,6 +736,9 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
           if (nP != 0 || q_fixed) break;                   // buchberger.cpp:313-314: redraw while the pair set is empty
         }
         }
+        // (the generator table's per-lane rows and the queue slot's words are read by v_readlane on the paths that use them: on
+        // the others, the failure exits among them, they would still count as in flight when the step is reached)
+        f_loads_landed();
         if (!ok) { if (status != BBX_ST_STARVED) { nG = 0; nP = 0; } break; }
         need_reset = 0;
         if constexpr (POL > 0 && PERSIST) {
@@ -1196,8 +1209,13 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       // (the common case first: basis means are ~35; the four-bank form only beyond 128 elements, about once per 10^5
       // episodes of 3-20-10-weighted, and said to be unlikely: the register allocator then keeps its copies out of the way)
       if (__builtin_expect(nG < 64, 1)) add_poly(r0, r1, rsug, action, std::integral_constant<int, 1>{});
-      else if (NBK == 2 || __builtin_expect(nG < 128, 1)) add_poly(r0, r1, rsug, action, std::integral_constant<int, 2>{});
-      else add_poly(r0, r1, rsug, action, std::integral_constant<int, NBK>{});
+      else {
+        if (NBK == 2 || __builtin_expect(nG < 128, 1)) add_poly(r0, r1, rsug, action, std::integral_constant<int, 2>{});
+        else add_poly(r0, r1, rsug, action, std::integral_constant<int, NBK>{});
+        // (the two copies' 1/LC read is issued once above their |G| test, and a never-taken exec == 0 skip leads from there to
+        // this join: without the wait the table read counts as in flight behind every add_poly, the common one included)
+        f_loads_landed();
+      }
       if (ACCT) bytes += 12 * (r1.c ? 2 : 1) + 8 * nG_before + 8 * (nP_before + nP);
     }
     FSTAMP(4);                                             // 4: add_poly (pair update, insert)

@@ -105,14 +105,20 @@ hipError_t pool_malloc(void** p, size_t n) { return pool_get(p, n, 0, 0u); }
 hipError_t pool_free(void* p) { return pool_put(p, 0); }
 hipError_t pool_host_malloc(void** p, size_t n, unsigned flags) { return pool_get(p, n, 1, flags); }
 hipError_t pool_host_free(void* p) { return pool_put(p, 1); }
-// 1/x mod 32003 for every x, on the device: computed and uploaded once per device and process
+// 1/x mod 32003 for every x (entry 0 is 0).  The fast class reads entry LC of every new basis element without asking
+// whether LC is 1 (bbx_fast.h, add_poly): entry 1 must be 1.
+std::vector<uint16_t> inv_table_host() {
+  std::vector<uint16_t> inv(BBX_P, 0);
+  for (uint32_t x = 1; x < BBX_P; x++) inv[x] = (uint16_t)bbx::coef_inv((int)x);
+  return inv;
+}
+// ... on the device: computed and uploaded once per device and process
 uint16_t* inv_table(int device) {
   static std::mutex mu; static uint16_t* tab[64] = {nullptr};
   if (device < 0 || device >= 64) return nullptr;
   std::lock_guard<std::mutex> g(mu);
   if (!tab[device]) {
-    std::vector<uint16_t> inv(BBX_P, 0);
-    for (uint32_t x = 1; x < BBX_P; x++) inv[x] = (uint16_t)bbx::coef_inv((int)x);
+    const std::vector<uint16_t> inv = inv_table_host();
     uint16_t* d = nullptr;
     if (hipMalloc((void**)&d, BBX_P * sizeof(uint16_t)) != hipSuccess) return nullptr;
     if (hipMemcpy(d, inv.data(), BBX_P * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
@@ -139,3 +145,9 @@ hipError_t device_info(int device, DeviceInfo* out) {
   *out = info[device]; return hipSuccess;
 }
 }  // namespace bbx_host
+
+// the host copy of the table the kernels read (tests: no device involved); `out` holds 32003 entries
+extern "C" void bbx_internal_inv_table(uint16_t* out) {
+  const std::vector<uint16_t> inv = bbx_host::inv_table_host();
+  memcpy(out, inv.data(), inv.size() * sizeof(uint16_t));
+}
