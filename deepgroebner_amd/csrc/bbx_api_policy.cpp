@@ -54,6 +54,51 @@ int launched_lds(int lrc, int dev, int max_lds) {
   return launched(lrc);
 }
 
+// ---- the training calls, plain and indexed in one body each.  d_index == null: position k of the call is recorded state k
+// (n_src == n); otherwise it is state d_index[k] of n_src recorded ones (the _at entries: refuse_index first)
+int refuse_index(int n_src, const int32_t* d_index, int n) {
+  if (n_src < 0) return fail(BBX_E_ARG, "bad policy shape (n_src = %d)", n_src);
+  if (n > 0 && !d_index) return fail(BBX_E_ARG, "null argument");
+  return BBX_OK;
+}
+int pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                 const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream) {
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, d_index, n_src,
+                                          (hipStream_t)stream));
+}
+int pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+              const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+              float* d_gb2, void* stream) {
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
+                                       d_gw2, d_gb2, d_index, n_src, (hipStream_t)stream));
+}
+int pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                  const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (n == 0) return BBX_OK;
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, d_index,
+                                               n_src, di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+int pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+               const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1,
+               float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 ||
+                           (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1,
+                                            d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, d_index, n_src, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
 int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
                    int nsteps, const float* d_u, int32_t* d_actions, float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
@@ -118,9 +163,12 @@ int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs
 // ---- the policy as a differentiable function of its weights (bbx_pmlp_grad.h)
 int bbx_pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                      int hidden, float* d_logprobs, float* d_entropy, void* stream) {
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, (hipStream_t)stream));
+  return pmlp_logprob(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, stream);
+}
+int bbx_pmlp_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                        int cols, const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, stream);
 }
 
 int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) {
@@ -133,11 +181,14 @@ int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) {
 int bbx_pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                   int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
                   void* stream) {
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
-                                       d_gw2, d_gb2, (hipStream_t)stream));
+  return pmlp_grad(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+}
+int bbx_pmlp_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                     int cols, const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1,
+                     float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
+                   stream);
 }
 
 // ---- two and three hidden layers (bbx_pmlp2.hip)
@@ -160,13 +211,13 @@ int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int ob
 // refused before a device is asked for anything
 int bbx_pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                       int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
+  return pmlp2_logprob(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, stream);
+}
+int bbx_pmlp2_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                         int cols, const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
   if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (n == 0) return BBX_OK;
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, di.cus,
-                                               di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, stream);
 }
 
 int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
@@ -178,13 +229,16 @@ int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, 
 int bbx_pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                    int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
                    float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  return pmlp2_grad(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2,
+                    d_gb2, d_gw3, d_gb3, stream);
+}
+int bbx_pmlp2_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                      int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace,
+                      float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
   if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 ||
-                           (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1,
-                                            d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
+                    d_gw2, d_gb2, d_gw3, d_gb3, stream);
 }
 
 int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,

@@ -354,31 +354,42 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
 #undef BBX_PMLP_MFMA
   return (int)hipGetLastError();
 }
-// log-probability / entropy of recorded actions and the weight gradients (bbx_pmlp_grad.h); BBX_PMLP_SHAPES(M): M(NB, KS) of the shape
+// log-probability / entropy of recorded actions and the weight gradients (bbx_pmlp_grad.h); BBX_PMLP_SHAPES(M): M(NB, KS) of the shape.
+// index != null: the indexed instantiations (position k is about recorded state index[k] of n_src)
 #define BBX_PMLP_SHAPES_K(M, N) do { if (ks == 3) M(N, 3); else if (ks == 6) M(N, 6); else if (ks == 10) M(N, 10); else if (ks == 16) M(N, 16); else M(N, 32); } while (0)
 #define BBX_PMLP_SHAPES(M) do { if (nb == 1) BBX_PMLP_SHAPES_K(M, 1); else if (nb == 2) BBX_PMLP_SHAPES_K(M, 2); else if (nb == 4) BBX_PMLP_SHAPES_K(M, 4); \
                                 else BBX_PMLP_SHAPES_K(M, 8); } while (0)
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, hipStream_t stream) {
+                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, hipStream_t stream) {
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_LOGPROB(N, K) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                   actions, n, obs_rows, cols, wp, logprobs, entropy)
-  BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB);
+#define BBX_PMLP_LOGPROB_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                        actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src)
+#define BBX_PMLP_LOGPROB(N, K) BBX_PMLP_LOGPROB_I(N, K, false)
+#define BBX_PMLP_LOGPROB_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true)
+  if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB);
+#undef BBX_PMLP_LOGPROB_AT
 #undef BBX_PMLP_LOGPROB
+#undef BBX_PMLP_LOGPROB_I
   return (int)hipGetLastError();
 }
 extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                     int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                    hipStream_t stream) {
+                                    const int32_t* index, int n_src, hipStream_t stream) {
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const int nw = n > 0 ? pmlp_grad_waves(n) : 0, ng = nb / pmlp_grad_ubw(cols, hidden);
+  // (indexed with no recorded state at all: every index is out of range, nothing contributes, and the kernel, which reads state 0
+  // in place of an index out of range, is not launched)
+  const int nw = n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0, ng = nb / pmlp_grad_ubw(cols, hidden);
   const size_t ml = pmlp_grad_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_GRAD(N, K) hipLaunchKernelGGL((bbx_pmlp_grad_kernel<N, K>), dim3((nw + waves - 1) / waves, ng), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                actions, n, obs_rows, cols, wp, glogp, gent, nw, ws)
-  if (nw > 0) BBX_PMLP_SHAPES(BBX_PMLP_GRAD);
+#define BBX_PMLP_GRAD_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_grad_kernel<N, K, I>), dim3((nw + waves - 1) / waves, ng), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                     actions, n, obs_rows, cols, wp, glogp, gent, nw, ws, index, n_src)
+#define BBX_PMLP_GRAD(N, K) BBX_PMLP_GRAD_I(N, K, false)
+#define BBX_PMLP_GRAD_AT(N, K) BBX_PMLP_GRAD_I(N, K, true)
+  if (nw > 0) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_GRAD_AT); else BBX_PMLP_SHAPES(BBX_PMLP_GRAD); }
+#undef BBX_PMLP_GRAD_AT
 #undef BBX_PMLP_GRAD
+#undef BBX_PMLP_GRAD_I
   if (int rc = (int)hipGetLastError()) return rc;
   hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
   return (int)hipGetLastError();

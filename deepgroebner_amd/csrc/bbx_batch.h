@@ -36,19 +36,20 @@ extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const f
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, hipStream_t stream);
+                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, hipStream_t stream);   // (index: null, or position k is about state index[k] of n_src)
 extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                     int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                    hipStream_t stream);
+                                    const int32_t* index, int n_src, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
                                     const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, int cus, int max_lds, hipStream_t stream);
+                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, int cus, int max_lds,
+                                        hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                      int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                     float* gw3, float* gb3, int max_lds, hipStream_t stream);
+                                     float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream);
 
 
 // The call in flight: what finish() waits for, continues and reports on.  Formed in two places only — start_flight() (a

@@ -218,13 +218,15 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
 }
 
 // log-probability / entropy of recorded actions and the weight gradients for two hidden layers (bbx_pmlp2_grad.h);
-// BBX_P2G_SHAPES(M): M(HP1, HP2, KS) of the shape
+// BBX_P2G_SHAPES(M): M(HP1, HP2, KS) of the shape.  index != null: the indexed instantiations (position k is about recorded
+// state index[k] of n_src)
 #define BBX_P2G_K(M, N1, N2) do { if (ks == 3) M(N1, N2, 3); else if (ks == 8) M(N1, N2, 8); else M(N1, N2, 16); } while (0)
 #define BBX_P2G_SHAPES(M) do { if (hp1 == 64 && hp2 == 64) BBX_P2G_K(M, 64, 64); else if (hp1 == 64) BBX_P2G_K(M, 64, 128); \
                                else if (hp2 == 64) BBX_P2G_K(M, 128, 64); else BBX_P2G_K(M, 128, 128); } while (0)
 // (hipErrorInvalidValue: the device has less LDS per workgroup than the shape needs)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, int cus, int max_lds, hipStream_t stream) {
+                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, int cus, int max_lds,
+                                        hipStream_t stream) {
   if (n <= 0) return 0;
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
   // 8 waves beside the staged weights, fewer where tall observation blocks (4 bytes of logits per row and wave) leave less room
@@ -237,24 +239,32 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
   int blocks = (n + waves - 1) / waves;
   blocks = blocks < max_blocks ? blocks : max_blocks;
   int rc = 0;
-#define BBX_P2_LOGPROB(N1, N2, K) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, cols, wp, \
-                                                                                      logprobs, entropy, lgcap)
-  BBX_P2G_SHAPES(BBX_P2_LOGPROB);
+#define BBX_P2_LOGPROB_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K, I>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, cols, \
+                                                                                              wp, logprobs, entropy, lgcap, index, n_src)
+#define BBX_P2_LOGPROB(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false)
+#define BBX_P2_LOGPROB_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true)
+  if (index) BBX_P2G_SHAPES(BBX_P2_LOGPROB_AT); else BBX_P2G_SHAPES(BBX_P2_LOGPROB);
+#undef BBX_P2_LOGPROB_AT
 #undef BBX_P2_LOGPROB
+#undef BBX_P2_LOGPROB_I
   return rc ? rc : (int)hipGetLastError();
 }
 extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                      int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                     float* gw3, float* gb3, int max_lds, hipStream_t stream) {
+                                     float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream) {
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
   const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
   const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows);
   if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
   int rc = 0;
-#define BBX_P2_GRAD(N1, N2, K) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K>>(groups, threads, ml, stream, obs, rows, actions, n, obs_rows, cols, wp, glogp, gent, \
-                                                                                groups, ws)
-  if (groups > 0) BBX_P2G_SHAPES(BBX_P2_GRAD);
+#define BBX_P2_GRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I>>(groups, threads, ml, stream, obs, rows, actions, n, obs_rows, cols, wp, glogp, \
+                                                                                        gent, groups, ws, index, n_src)
+#define BBX_P2_GRAD(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, false)
+#define BBX_P2_GRAD_AT(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, true)
+  if (groups > 0) { if (index) BBX_P2G_SHAPES(BBX_P2_GRAD_AT); else BBX_P2G_SHAPES(BBX_P2_GRAD); }
+#undef BBX_P2_GRAD_AT
 #undef BBX_P2_GRAD
+#undef BBX_P2_GRAD_I
   if (rc) return rc;
   if ((rc = (int)hipGetLastError())) return rc;
   const int total = cols * h1 + h1 + h1 * h2 + 2 * h2 + 1;

@@ -34,6 +34,11 @@
 // partition depends on (n, cols, hidden1, hidden2) alone.
 // Every barrier is reached by the whole workgroup: the state loop, the row count, the action and the tile loop are the same
 // for all its threads, and a state that contributes nothing (no row, one row, a bad action) is skipped before its first barrier.
+//
+// Indexed form (IDX; bbx_pmlp2_logprob_at, bbx_pmlp2_grad_at): position k of the call is about recorded state index[k] — obs, rows
+// and actions are read there, the per-call arrays (logprobs, entropy, glogp, gent) at k.  An index outside [0, n_src): NaN / NaN,
+// nothing for the gradients (skipped before its first barrier: the index is the same for the whole workgroup), and no read of the
+// recorded arrays at that index.
 #pragma once
 #include "bbx_pmlp.h"
 
@@ -71,11 +76,11 @@ __device__ __forceinline__ void pmlp2_logits_tile(float* lg, const int32_t* __re
   if (lg4 == 0 && r0 + lr < n) lg[r0 + lr] = part + b3;
 }
 
-template <int HP1, int HP2, int KS>
+template <int HP1, int HP2, int KS, bool IDX = false>
 __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                 const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                 const float* __restrict__ wp, float* __restrict__ logprobs,
-                                                                float* __restrict__ entropy, int lgcap) {
+                                                                float* __restrict__ entropy, int lgcap, const int32_t* __restrict__ index, int n_src) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int A2F = HP1 * HP2;
   float* a2 = (float*)smem;
@@ -89,30 +94,36 @@ __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* _
   const float b3 = a2g[A2F + 2 * HP2];
   const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE)), nw = (int)blockDim.x / WAVE;
   float* lg = a2 + A2F + 2 * HP2 + (size_t)wave * lgcap;                      // logits of this wave's state
-  for (int s = (int)blockIdx.x * nw + wave; s < B; s += (int)gridDim.x * nw) {
+  for (int k = (int)blockIdx.x * nw + wave; k < B; k += (int)gridDim.x * nw) {   // position k of the call: recorded state s
+    int s = k;
+    if constexpr (IDX) {
+      s = uni(index[k]);
+      if (s < 0 || s >= n_src) { if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); } continue; }
+    }
     int n = uni(rows[s]);
     const int a = uni(actions[s]);
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS;
-    if (n <= 0) { if (lane == 0) { logprobs[s] = 0.f; if (entropy) entropy[s] = 0.f; } continue; }
+    if (n <= 0) { if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; } continue; }
     const int32_t* ob = obs + (size_t)s * obs_rows * cols;
     wave_sync();                                                              // (the previous state's logits have been read)
     for (int r0 = 0; r0 < n; r0 += 16) pmlp2_logits_tile<HP1, HP2, KS>(lg, ob, r0, n, obs_rows, cols, W1p, b1p, a2, b2l, w3l, b3, lane);
     wave_sync();
     const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
     const bool ok = a >= 0 && a < n;
-    if (lane == 0) logprobs[s] = ok ? lg[a] - sm.logz : __builtin_nanf("");
+    if (lane == 0) logprobs[k] = ok ? lg[a] - sm.logz : __builtin_nanf("");
     if (entropy) {
       const float H = pmlp_entropy_wave(lg, n, lane, sm);
-      if (lane == 0) entropy[s] = H;
+      if (lane == 0) entropy[k] = H;
     }
   }
 }
 
-template <int HP1, int HP2, int KS>
+template <int HP1, int HP2, int KS, bool IDX = false>
 __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                                      const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                                      const float* __restrict__ wp, const float* __restrict__ glogp,
-                                                                                     const float* __restrict__ gent, int groups, float* __restrict__ ws) {
+                                                                                     const float* __restrict__ gent, int groups, float* __restrict__ ws,
+                                                                                     const int32_t* __restrict__ index, int n_src) {
   constexpr int NB1 = HP1 / 32, NB2 = HP2 / 32, NW = NB1 > NB2 ? NB1 : NB2;  // pmlp2_grad_waves
   constexpr int CB = KS == 16 ? 2 : 1;                                        // pmlp2_grad_cb
   constexpr int S1 = HP1 + PMLP2_GRAD_PAD, S2 = HP2 + PMLP2_GRAD_PAD, S4 = HP1 / 16, A2F = HP1 * HP2;
@@ -145,7 +156,12 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
     for (int cb = 0; cb < CB; cb++) dW1[cb][v] = 0.f;
   }
 
-  for (int s = (int)blockIdx.x; s < B; s += groups) {
+  for (int k = (int)blockIdx.x; k < B; k += groups) {                        // position k of the call: recorded state s
+    int s = k;
+    if constexpr (IDX) {
+      s = uni(index[k]);
+      if (s < 0 || s >= n_src) continue;                                      // nothing, and nothing read there
+    }
     int n = uni(rows[s]);
     const int a = uni(actions[s]);
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS;
@@ -156,7 +172,7 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
     __syncthreads();
     const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);                    // (every wave for itself: the same numbers)
     const float H = pmlp_entropy_wave(lg, n, lane, sm);
-    const float gl = glogp[s], ge = gent ? gent[s] : 0.f;
+    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
     const float rse = 1.f / sm.se;
     const int n32 = (n + 31) & ~31;
     __syncthreads();                                                          // (every wave has read the logits)

@@ -62,34 +62,41 @@ __device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __rest
 }
 
 // (pmlp_softmax_wave / pmlp_entropy_wave: bbx_pmlp.h, beside pmlp_sample, whose order they keep)
-template <int NB, int KS>
+template <int NB, int KS, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                   const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
-                                                                  const float* __restrict__ wp, float* __restrict__ logprobs, float* __restrict__ entropy) {
+                                                                  const float* __restrict__ wp, float* __restrict__ logprobs, float* __restrict__ entropy,
+                                                                  const int32_t* __restrict__ index, int n_src) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
-  const int s = blockIdx.x * ((int)blockDim.x / WAVE) + wave;
-  if (s >= B) return;
+  const int k = blockIdx.x * ((int)blockDim.x / WAVE) + wave;         // my position in the call
+  if (k >= B) return;
+  int s = k;                                                          // the recorded state it is about
+  if constexpr (IDX) {
+    s = uni(index[k]);
+    if (s < 0 || s >= n_src) { if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); } return; }
+  }
   float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);
   const int nraw = rows[s];
   const int a = uni(actions[s]);
   const int n = pmlp_logits_wave<NB, KS>(lg, obs + (size_t)s * obs_rows * cols, nraw, obs_rows, cols, wp, lane & 31, lane >> 5);
-  if (n <= 0) { if (lane == 0) { logprobs[s] = 0.f; if (entropy) entropy[s] = 0.f; } return; }
+  if (n <= 0) { if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; } return; }
   wave_sync();
   const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
   const bool ok = a >= 0 && a < n;
-  if (lane == 0) logprobs[s] = ok ? lg[a] - sm.logz : __builtin_nanf("");
+  if (lane == 0) logprobs[k] = ok ? lg[a] - sm.logz : __builtin_nanf("");
   if (entropy) {
     const float H = pmlp_entropy_wave(lg, n, lane, sm);
-    if (lane == 0) entropy[s] = H;
+    if (lane == 0) entropy[k] = H;
   }
 }
 
-template <int NB, int KS>
+template <int NB, int KS, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                const float* __restrict__ wp, const float* __restrict__ glogp,
-                                                               const float* __restrict__ gent, int nwaves, float* __restrict__ ws) {
+                                                               const float* __restrict__ gent, int nwaves, float* __restrict__ ws,
+                                                               const int32_t* __restrict__ index, int n_src) {
   constexpr int HP = 32 * NB;
   constexpr int CB = KS == 32 ? 2 : 1;                               // pmlp_grad_cb
   constexpr int UBW = NB < (CB == 2 ? 2 : 4) ? NB : (CB == 2 ? 2 : 4);   // pmlp_grad_ubw
@@ -115,8 +122,17 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __
       for (int v = 0; v < 16; v++) dW[u][cb][v] = 0.f;
   }
 
-  for (int s = p; s < B; s += nwaves) {
-    const int nraw = rows[s];
+  for (int k = p; k < B; k += nwaves) {                               // position k of the call: recorded state s
+    int s = k;
+    bool in_src = true;
+    if constexpr (IDX) {
+      // an index out of range: no row, which the test below skips — and state 0 in its place for the addresses (the launcher
+      // sees to n_src > 0).  A branch around the state here instead costs 20-30 vector registers and, from 33 columns on, spills
+      s = uni(index[k]);
+      in_src = s >= 0 && s < n_src;
+      s = in_src ? s : 0;
+    }
+    const int nraw = in_src ? rows[s] : 0;
     const int a = uni(actions[s]);
     const int32_t* ob = obs + (size_t)s * obs_rows * cols;
     wave_sync();                                                      // (the previous state's g_r have been read)
@@ -129,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __
     wave_sync();
     const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
     const float H = pmlp_entropy_wave(lg, n, lane, sm);
-    const float gl = glogp[s], ge = gent ? gent[s] : 0.f;
+    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
     const float rse = 1.f / sm.se;
     const int n32 = (n + 31) & ~31;
     for (int r = lane; r < n32; r += WAVE) {                          // (every lane reads and writes its own entries only)

@@ -4,6 +4,8 @@ device, replacing the per-step host round trip of the reference's agents.
     PMLPPolicy                 ParallelMultilayerPerceptron           networks.py:522-571 (:49-95, :414-460)
     discount_rewards, compute_advantages                              pg.py:20-76
     DeviceTrajectoryBuffer     TrajectoryBuffer (store/finish/get)    pg.py:79-240
+    get_index + PMLPPolicy.evaluate_at   the update's minibatches as slices of an index list over the buffer: the training
+                               kernels read the recorded states where the rollout left them (bbx_pmlp_logprob_at / bbx_pmlp_grad_at)
     run_rollout                PGAgent.run_episode(s)                 pg.py:451-503   (one library call per vector step)
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
@@ -71,26 +73,36 @@ def compute_advantages(rewards, values, gam, lam):
 class _PMLPEvaluate(torch.autograd.Function):
     """log pi(a | s) and the entropy of pi(. | s) of a one-hidden-layer PMLPPolicy through bbx_pmlp_logprob, differentiable
     with respect to the four parameter tensors through bbx_pmlp_grad (the hidden activations are recomputed there: nothing of
-    size [N, R, hidden] is kept between forward and backward).  No gradient for states, actions or rows."""
+    size [N, R, hidden] is kept between forward and backward).  No gradient for states, actions or rows.
+    index (int32 [n], optional): the call is about the recorded states index[k] of states [..., R, cols], rows and actions, which
+    are then whole buffers read in place (bbx_pmlp_logprob_at / bbx_pmlp_grad_at); the outputs have length n."""
 
     @staticmethod
-    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2):
-        N, R, cols = states.shape
+    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, index=None):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
         w = policy._fused_weights()
         logp = torch.empty(N, dtype=torch.float32, device=states.device)
         ent = torch.empty(N, dtype=torch.float32, device=states.device)
         p = lambda x: C.c_void_p(x.data_ptr())
         with torch.cuda.device(states.device):
-            _ffi.check(_ffi.lib().bbx_pmlp_logprob(p(states), p(rows), p(actions), N, R, cols, w["prepared"], w["hidden"], p(logp), p(ent),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if index is None:
+                _ffi.check(_ffi.lib().bbx_pmlp_logprob(p(states), p(rows), p(actions), N, R, cols, w["prepared"], w["hidden"], p(logp), p(ent), s))
+            else:
+                _ffi.check(_ffi.lib().bbx_pmlp_logprob_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, w["prepared"], w["hidden"],
+                                                          p(logp), p(ent), s))
         ctx.policy, ctx.prep, ctx.hidden = policy, w["keep"], w["hidden"]     # (the prepared weights of THIS forward pass)
-        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2)
+        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, index)
         return logp, ent
 
     @staticmethod
     def backward(ctx, glogp, gent):
-        states, rows, actions, w1, b1, w2, b2 = ctx.saved_tensors
-        N, R, cols = states.shape
+        states, rows, actions, w1, b1, w2, b2, index = ctx.saved_tensors
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
         hidden = ctx.hidden
         dev = states.device
         glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
@@ -101,18 +113,26 @@ class _PMLPEvaluate(torch.autograd.Function):
         p = lambda x: C.c_void_p(x.data_ptr())
         with torch.cuda.device(dev):
             ws = ctx.policy._grad_workspace(N, R, cols, hidden, dev)
-            _ffi.check(_ffi.lib().bbx_pmlp_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), hidden, p(glogp), p(gent), p(ws),
-                                                p(gw1), p(gb1), p(gw2), p(gb2), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype)
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if index is None:
+                _ffi.check(_ffi.lib().bbx_pmlp_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), hidden, p(glogp), p(gent), p(ws),
+                                                    p(gw1), p(gb1), p(gw2), p(gb2), s))
+            else:
+                _ffi.check(_ffi.lib().bbx_pmlp_grad_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(ctx.prep), hidden, p(glogp),
+                                                       p(gent), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), s))
+        return None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype), None
 
 
 class _PMLP2Evaluate(torch.autograd.Function):
     """_PMLPEvaluate for two hidden layers: bbx_pmlp2_logprob forward, bbx_pmlp2_grad backward (both hidden tiles are recomputed
-    there), gradients for the six parameter tensors in torch.nn.Linear's own layouts.  No gradient for states, actions or rows."""
+    there), gradients for the six parameter tensors in torch.nn.Linear's own layouts.  No gradient for states, actions or rows.
+    index: as in _PMLPEvaluate (bbx_pmlp2_logprob_at / bbx_pmlp2_grad_at)."""
 
     @staticmethod
-    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, w3, b3):
-        N, R, cols = states.shape
+    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, w3, b3, index=None):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
         logp = torch.empty(N, dtype=torch.float32, device=states.device)
         ent = torch.empty(N, dtype=torch.float32, device=states.device)
         p = lambda x: C.c_void_p(x.data_ptr())
@@ -122,16 +142,22 @@ class _PMLP2Evaluate(torch.autograd.Function):
             # (the prepared buffer is refilled in place when the weights change: backward reads THIS forward pass's weights
             # from a copy of its own, made on the stream behind the fill)
             prep = w["keep"][0].clone()
-            _ffi.check(_ffi.lib().bbx_pmlp2_logprob(p(states), p(rows), p(actions), N, R, cols, p(prep), h1, h2, p(logp), p(ent),
-                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if index is None:
+                _ffi.check(_ffi.lib().bbx_pmlp2_logprob(p(states), p(rows), p(actions), N, R, cols, p(prep), h1, h2, p(logp), p(ent), s))
+            else:
+                _ffi.check(_ffi.lib().bbx_pmlp2_logprob_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(prep), h1, h2, p(logp),
+                                                           p(ent), s))
         ctx.policy, ctx.prep, ctx.hidden = policy, prep, (h1, h2)
-        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, w3, b3)
+        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, w3, b3, index)
         return logp, ent
 
     @staticmethod
     def backward(ctx, glogp, gent):
-        states, rows, actions, w1, b1, w2, b2, w3, b3 = ctx.saved_tensors
-        N, R, cols = states.shape
+        states, rows, actions, w1, b1, w2, b2, w3, b3, index = ctx.saved_tensors
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
         h1, h2 = ctx.hidden
         dev = states.device
         glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
@@ -140,10 +166,15 @@ class _PMLP2Evaluate(torch.autograd.Function):
         p = lambda x: C.c_void_p(x.data_ptr())
         with torch.cuda.device(dev):
             ws = ctx.policy._grad2_workspace(N, R, cols, h1, h2, dev)
-            _ffi.check(_ffi.lib().bbx_pmlp2_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), h1, h2, p(glogp), p(gent), p(ws),
-                                                 p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if index is None:
+                _ffi.check(_ffi.lib().bbx_pmlp2_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), h1, h2, p(glogp), p(gent), p(ws),
+                                                     p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), s))
+            else:
+                _ffi.check(_ffi.lib().bbx_pmlp2_grad_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(ctx.prep), h1, h2, p(glogp),
+                                                        p(gent), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), s))
         return (None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.t().to(w2.dtype), gb2.to(b2.dtype),
-                gw3.view(1, -1).to(w3.dtype), gb3.to(b3.dtype))
+                gw3.view(1, -1).to(w3.dtype), gb3.to(b3.dtype), None)
 
 
 class PMLPPolicy(torch.nn.Module):
@@ -303,6 +334,36 @@ class PMLPPolicy(torch.nn.Module):
                                         self.deciding.weight, self.deciding.bias)
         return self.evaluate_torch(states, actions, rows)
 
+    def evaluate_at(self, states, actions, rows, index):
+        """evaluate() of the recorded states index[k] WITHOUT gathering them: states int [S, R, cols] or [T, B, R, cols] with
+        actions and rows [S] or [T, B] are whole buffers (DeviceTrajectoryBuffer.states / .actions / .rows as the rollout kernels
+        left them), index int [n] holds flat step numbers into them (DeviceTrajectoryBuffer.get_index) -> (logprobs float32 [n],
+        entropy float32 [n]), differentiable with respect to the module's parameters; for an index in range, the numbers of
+        evaluate(states[index], actions[index], rows[index]) bit for bit.  An index outside the buffer on the kernel path: NaN
+        and NaN, nothing for the gradients.
+        The kernels (bbx_pmlp_logprob_at / bbx_pmlp_grad_at, bbx_pmlp2_..._at) read the buffers in place: under evaluate()'s
+        conditions, and only where states, rows and actions ARE contiguous int32 CUDA tensors already — a buffer is never
+        converted or copied as a whole.  Anything else gathers the n states and takes evaluate()."""
+        R, cols = states.shape[-2:]
+        lin = self.embedding[0]
+        S = rows.numel()
+        in_place = (states.is_cuda and 1 <= R <= 2048 and states.numel() == S * R * cols and actions.numel() == S
+                    and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows, actions)))
+        one = len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features)
+        two = (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
+               and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters()))
+        if in_place and (one or two):
+            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
+            if one:
+                return _PMLPEvaluate.apply(self, states, rows, actions, lin.weight, lin.bias, self.deciding.weight, self.deciding.bias, idx)
+            l2 = self.embedding[1]
+            return _PMLP2Evaluate.apply(self, states, rows, actions, lin.weight, lin.bias, l2.weight, l2.bias, self.deciding.weight, self.deciding.bias, idx)
+        j = index.to(device=states.device, dtype=torch.int64)
+        if states.dim() == 4:                                         # (no reshape: a non-contiguous buffer would be copied whole)
+            t, b = j // states.shape[1], j % states.shape[1]
+            return self.evaluate(states[t, b], actions[t, b], rows[t, b])
+        return self.evaluate(states[j], actions[j], rows[j])
+
     def evaluate_torch(self, states, actions, rows=None):
         """evaluate with torch ops and autograd (any depth, any device; the baseline of the kernels): forward, gather, and
         -(exp(lp) lp) summed over the live rows."""
@@ -413,15 +474,13 @@ class DeviceTrajectoryBuffer:
         self.returns, self.advantages, self.complete = ret, adv, comp
         return ret, adv, comp
 
-    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
-        """Training data of all complete-episode steps whose state had more than one row (pg.py:162-240): (states or None,
-        actions, logprobs, advantages, values-to-fit), advantages normalised by their mean and population std over the
-        complete steps (pg.py:176-178: before the single-row filter, like the reference), steps ordered trajectory after
-        trajectory (environment-major).  batch_size=None: one tuple of whole tensors.  Otherwise the reference's
-        padded_batch: a list of such tuples of at most batch_size steps each, the state block of a batch cut to the most
-        rows any of its states has (-1 padding beyond a state's own rows, as stored); sort=True orders the steps by their
-        number of rows first (less padding); drop_remainder=True leaves a short last batch out.  with_rows=True: every tuple
-        carries the states' row counts (int32) as a sixth element (what PMLPPolicy.evaluate takes as `rows`)."""
+    def get_index(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
+        """get() without the state blocks: the same selection, order, advantage normalisation and batching, but the first element
+        of every tuple is an int32 tensor of flat step numbers t * B + b — positions in self.states.view(-1, R, cols),
+        self.rows.view(-1) and self.actions.view(-1) — for PMLPPolicy.evaluate_at, which reads the states where the rollout
+        left them.  With batch_size the tuples hold slices of ONE index tensor (a shuffle of the epoch is a permutation of it);
+        nothing of the size of a state block is allocated, nothing waits for the device per batch, and a buffer without states
+        gives the same indices."""
         if self.returns is None:
             self.finish()
         T = self.t
@@ -432,19 +491,44 @@ class DeviceTrajectoryBuffer:
             adv = (adv - adv.mean()) / adv.std(unbiased=False)
         rows = em(self.rows)[comp]
         keep = rows != 1
-        st = em(self.states)[comp][keep] if self.states is not None else None
-        out = [st, em(self.actions)[comp][keep], em(self.logprobs)[comp][keep], adv[keep], em(self.returns)[comp].to(torch.float32)[keep]]
-        rows = rows[keep]
-        if batch_size is None and not sort:
-            return tuple(out + [rows]) if with_rows else tuple(out)
+        dev = self.rows.device
+        step = torch.arange(T, dtype=torch.int32, device=dev)[None, :] * self.B + torch.arange(self.B, dtype=torch.int32, device=dev)[:, None]
+        idx, adv, rows = step[comp][keep], adv[keep], rows[keep]
         if sort:
             order = torch.argsort(rows, stable=True)
-            out = [None if x is None else x[order] for x in out]
-            rows = rows[order]
-        if batch_size is None:
-            return tuple(out + [rows]) if with_rows else tuple(out)
+            idx, adv, rows = idx[order], adv[order], rows[order]
+        j = idx.to(torch.int64)
+        at = lambda x: x[:T].reshape(-1)[j]
+        out = [idx, at(self.actions), at(self.logprobs), adv, at(self.returns).to(torch.float32)]
         if with_rows:
-            out = out + [rows]
+            out.append(rows)
+        if batch_size is None:
+            return tuple(out)
+        n = int(idx.numel())
+        batches = []
+        for i in range(0, n, batch_size):
+            k = min(i + batch_size, n)
+            if drop_remainder and k - i < batch_size:
+                break
+            batches.append(tuple(x[i:k] for x in out))
+        return batches
+
+    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
+        """Training data of all complete-episode steps whose state had more than one row (pg.py:162-240): (states or None,
+        actions, logprobs, advantages, values-to-fit), advantages normalised by their mean and population std over the
+        complete steps (pg.py:176-178: before the single-row filter, like the reference), steps ordered trajectory after
+        trajectory (environment-major).  batch_size=None: one tuple of whole tensors.  Otherwise the reference's
+        padded_batch: a list of such tuples of at most batch_size steps each, the state block of a batch cut to the most
+        rows any of its states has (-1 padding beyond a state's own rows, as stored); sort=True orders the steps by their
+        number of rows first (less padding); drop_remainder=True leaves a short last batch out.  with_rows=True: every tuple
+        carries the states' row counts (int32) as a sixth element (what PMLPPolicy.evaluate takes as `rows`).
+        The selection is get_index's; the states are gathered here, once."""
+        whole = self.get_index(None, normalize_advantages, sort, False, True)
+        rows = whole[5]
+        st = self.states[:self.t].reshape((-1,) + tuple(self.states.shape[2:]))[whole[0].to(torch.int64)] if self.states is not None else None
+        out = [st] + list(whole[1:6 if with_rows else 5])
+        if batch_size is None:
+            return tuple(out)
         n = int(rows.numel())
         batches = []
         for i in range(0, n, batch_size):

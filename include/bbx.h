@@ -273,6 +273,33 @@ int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, 
 int bbx_pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
                    const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace,
                    float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+/* The four calls above, INDEXED: position k in [0, n) of the call is about recorded state s = d_index[k] of n_src recorded ones —
+ * d_obs [n_src][obs_rows][cols], d_rows [n_src] and d_actions [n_src] are read at s, nothing is gathered or copied; d_index,
+ * d_logprobs, d_entropy, d_glogp and d_gent have length n and are addressed by k.  What a training epoch over a trajectory buffer
+ * needs: its minibatches are slices of one int32 list of step numbers over the arrays as the rollout kernels left them, a
+ * shuffle is a permutation of that list.  All offsets are 64-bit (n_src obs_rows cols may exceed 2^31).
+ *   Every convention is that of the call without _at, word for word: shapes and refusals (before anything is queued; the
+ *     two-layer pair without a device), n == 0 (the grad entries then only zero their outputs), NULL d_entropy / d_gent, no
+ *     allocation, no read-back, recordable into a HIP graph, deterministic.  The workspace of the grad entries holds
+ *     bbx_pmlp_grad_workspace_floats(n, ...) / bbx_pmlp2_grad_workspace_floats(n, ...) floats for THIS n (not n_src).
+ *   In addition: n_src < 0, or a NULL d_index with n > 0: BBX_E_ARG.
+ *   An index outside [0, n_src): logprob = NaN and entropy = NaN at its position; it contributes NOTHING to any gradient (its
+ *     d_glogp / d_gent are not read into any sum), and nothing is read from d_obs, d_rows or d_actions at that index.
+ *   Repeated indices are legal; every occurrence counts.
+ *   For every index in range the outputs equal, bit for bit, those of the call without _at on the gathered contiguous arrays
+ *     d_obs[d_index], d_rows[d_index], d_actions[d_index]: the same tile code, the same order of maximum and sum, the same partition
+ *     of the n positions over waves and workgroups, the same second kernel. */
+int bbx_pmlp_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                        int obs_rows, int cols, const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream);
+int bbx_pmlp_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                     int obs_rows, int cols, const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent,
+                     float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp2_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                         int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy,
+                         void* stream);
+int bbx_pmlp2_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                      int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent,
+                      float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
 /* ... and for three hidden layers (hidden_layers=[hidden1, hidden2, hidden3], each <= 128): the same kernel with a middle layer
  * whose output stays in registers as the next layer's B operands; d_w3 [hidden2][hidden3], d_b3 [hidden3], d_w4 [hidden3],
  * d_b4 [1].  All three layers are padded to the widest one's tile size (64 or 128 units). */

@@ -8,12 +8,24 @@ and autograd over the whole [N, R, cols] block), on identical tensors in the sam
 Each repetition is timed with device events; the rate is states over the MEDIAN repetition; the two paths alternate in blocks
 of --block repetitions so that drift hits both.  Peak memory: torch.cuda.max_memory_allocated over one evaluate + backward of
 each path, above what is allocated before it.
+
+    python scripts/bench_policy_grad.py --from-buffer [--T 64] [--B 1024] [--rows 64] [--batch-size 4096] [--pairs 5] [--hidden ...]
+
+One PPO pass over all minibatches of a DeviceTrajectoryBuffer of T x B recorded steps (about a quarter of them left out: episodes
+still running at the end of the buffer, states with one row), two ways, alternating in one process:
+    gather   buffer.get(batch_size, sort=True)        then evaluate    + loss + backward per minibatch
+    index    buffer.get_index(batch_size, sort=True)  then evaluate_at + loss + backward per minibatch (nothing of the size of a
+             state block is allocated: the kernels read the buffer in place)
+Each pass is timed from its get / get_index to the end of its last backward (wall clock between device synchronisations: get()
+waits for the device per minibatch); states/s over the median pass with min-max, and torch.cuda.max_memory_allocated of a pass
+beyond what the buffer and the policy hold.  Prints one JSON line.
 """
 import argparse
 import json
 import os
 import statistics
 import sys
+import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,7 +41,14 @@ ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--reps", type=int, default=30, help="timed repetitions per path (at least 20)")
 ap.add_argument("--block", type=int, default=5)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--from-buffer", action="store_true", help="one PPO pass over a trajectory buffer: get + evaluate against get_index + evaluate_at")
+ap.add_argument("--T", type=int, default=64, help="--from-buffer: recorded steps per environment")
+ap.add_argument("--B", type=int, default=1024, help="--from-buffer: environments")
+ap.add_argument("--batch-size", type=int, default=4096, help="--from-buffer: steps per minibatch")
+ap.add_argument("--pairs", type=int, default=5, help="--from-buffer: timed (gather, index) pairs of passes (at least 5)")
 a = ap.parse_args()
+if a.from_buffer and a.pairs < 5:
+    ap.error("--pairs must be at least 5")
 if a.reps < 20:
     ap.error("--reps must be at least 20")
 if len(a.hidden) not in (1, 2):
@@ -41,6 +60,81 @@ N, R, cols = a.states, a.rows, a.cols
 rng = np.random.default_rng(a.seed)
 torch.manual_seed(a.seed)
 policy = PMLPPolicy(cols, a.hidden, deep_kernels=len(a.hidden) == 2).cuda()
+
+
+def from_buffer():
+    from deepgroebner_amd.rollout import DeviceTrajectoryBuffer
+    T, B = a.T, a.B
+    gen = torch.Generator(device="cuda"); gen.manual_seed(a.seed)
+    rnd = lambda *shape: torch.rand(shape, device="cuda", generator=gen)
+    buf = DeviceTrajectoryBuffer(T, B, obs_shape=(R, cols))
+    # row counts uniform in [2, R] as in the other modes, one state in eight with a single row; an episode ends at a step with
+    # probability 8 / T (the steps behind an environment's last end, about T / 8 of them, are incomplete): about a quarter left out
+    n = torch.randint(2, R + 1, (T, B), device="cuda", generator=gen, dtype=torch.int32)
+    buf.rows.copy_(torch.where(rnd(T, B) < 0.125, torch.ones_like(n), n))
+    buf.dones.copy_(rnd(T, B) < 8.0 / T)
+    buf.states.copy_(torch.randint(0, 10, buf.states.shape, device="cuda", generator=gen, dtype=torch.int32))
+    buf.states.masked_fill_(torch.arange(R, device="cuda")[None, None, :, None] >= buf.rows[:, :, None, None], -1)
+    buf.actions.copy_((rnd(T, B) * buf.rows).to(torch.int32).clamp_(max=R - 1))
+    buf.logprobs.copy_(-torch.log(buf.rows.float()))
+    buf.rewards.copy_(-torch.randint(1, 30, (T, B), device="cuda", generator=gen).double())
+    buf.values.copy_(rnd(T, B).double())
+    buf.t = T
+    buf.finish()
+
+    def loss_of(logp, ent, old, adv):
+        ratio = torch.exp(logp - old)
+        return -torch.min(ratio * adv, torch.clamp(ratio, 0.8, 1.2) * adv).mean() - 0.01 * ent.mean()
+
+    def gather():
+        policy.zero_grad(set_to_none=True)
+        count = 0
+        for st, act, old, adv, _, rows in buf.get(a.batch_size, sort=True, with_rows=True):
+            logp, ent = policy.evaluate(st, act, rows)
+            loss_of(logp, ent, old, adv).backward()
+            count += act.numel()
+        return count
+
+    def index():
+        policy.zero_grad(set_to_none=True)
+        count = 0
+        for idx, act, old, adv, _ in buf.get_index(a.batch_size, sort=True):
+            logp, ent = policy.evaluate_at(buf.states, buf.actions, buf.rows, idx)
+            loss_of(logp, ent, old, adv).backward()
+            count += idx.numel()
+        return count
+
+    paths = {"gather": gather, "index": index}
+    grads, times, peak, count = {}, {k: [] for k in paths}, {}, {}
+    for name, fn in paths.items():                     # warm up; the gradients of the two paths must be the same numbers
+        fn()
+        torch.cuda.synchronize()
+        grads[name] = [p.grad.detach().clone() for p in policy.parameters()]
+    same = all(torch.equal(x, y) for x, y in zip(grads["gather"], grads["index"]))
+    del grads
+    for _ in range(a.pairs):
+        for name, fn in paths.items():
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            t0 = time.perf_counter()
+            count[name] = fn()
+            torch.cuda.synchronize()
+            times[name].append(time.perf_counter() - t0)
+            peak[name] = max(peak.get(name, 0), torch.cuda.max_memory_allocated() - base)
+    out = {"bench": "policy_grad_from_buffer", "device": torch.cuda.get_device_name(0), "T": T, "B": B, "rows": R, "cols": cols,
+           "hidden": a.hidden[0] if len(a.hidden) == 1 else a.hidden, "batch_size": a.batch_size, "pairs": a.pairs,
+           "steps_selected": count["index"], "steps_recorded": T * B, "state_block_bytes": buf.states.numel() * 4, "gradients_identical": same}
+    for name in paths:
+        t = sorted(times[name]); med = statistics.median(t)
+        out[name] = {"states_per_s": count[name] / med, "median_ms": med * 1e3, "min_ms": t[0] * 1e3, "max_ms": t[-1] * 1e3, "peak_bytes": int(peak[name])}
+    out["index_over_gather"] = statistics.median(times["gather"]) / statistics.median(times["index"])
+    print(json.dumps(out))
+
+
+if a.from_buffer:
+    from_buffer()
+    sys.exit(0)
 rows_h = rng.integers(2, R + 1, size=N).astype(np.int32)
 obs_h = rng.integers(0, 10, size=(N, R, cols)).astype(np.int32)
 obs_h[np.arange(R)[None, :] >= rows_h[:, None]] = -1
