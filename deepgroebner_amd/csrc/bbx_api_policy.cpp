@@ -62,10 +62,11 @@ int refuse_index(int n_src, const int32_t* d_index, int n) {
   return BBX_OK;
 }
 int pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-                 const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream) {
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+                 const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream, const PmlpLoss* loss = nullptr) {
+  // (loss: the forward kernel of a PPO call, which may leave d_logprobs out)
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || (!d_logprobs && !loss))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
   if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, d_index, n_src,
+  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, d_index, n_src, loss,
                                           (hipStream_t)stream));
 }
 int pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
@@ -78,14 +79,14 @@ int pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_acti
                                        d_gw2, d_gb2, d_index, n_src, (hipStream_t)stream));
 }
 int pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-                  const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
+                  const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream, const PmlpLoss* loss = nullptr) {
   if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_logprobs)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || (!d_logprobs && !loss))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
   if (n == 0) return BBX_OK;
   int dev = 0; DeviceInfo di{};
   HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
   return launched_lds(bbx_launch_pmlp2_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, d_index,
-                                               n_src, di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+                                               n_src, loss, di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
 }
 int pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1,
@@ -97,6 +98,56 @@ int pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_act
   HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
   return launched_lds(bbx_launch_pmlp2_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1,
                                             d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, d_index, n_src, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+
+// ---- the PPO calls: the forward body with the loss epilogue, the statistics kernel, the gradient body on the coefficients the
+// epilogue wrote.  Everything either body would refuse is refused here first, before anything is queued
+struct PpoArgs {
+  const float* old_logprobs; const float* advantages; int mode; float scale, eps, ent_coef, c_kl;
+  float* logprobs; float* entropy; float* coef; double* stats;
+};
+int refuse_ppo(const PpoArgs& a, int n) {
+  if (a.mode < 0 || a.mode > 2) return fail(BBX_E_ARG, "bad loss mode %d (0: policy gradient, 1: PPO-clip, 2: PPO-penalty)", a.mode);
+  if (!(a.eps >= 0.f)) return fail(BBX_E_ARG, "bad clip range (eps = %g)", (double)a.eps);
+  if (n > 0 && (!a.coef || !a.stats || !a.old_logprobs || !a.advantages)) return fail(BBX_E_ARG, "null argument");
+  return BBX_OK;
+}
+int ppo_workspace(int n, int grad_floats) {
+  const int fl = pmlp_ppo_workspace_floats(n, grad_floats);
+  return fl < 0 ? fail(BBX_E_ARG, "bad policy shape (n = %d: the workspace would not fit an int)", n) : fl;
+}
+int ppo_stats(const float* tail, int n, double* d_stats, void* stream) {
+  if (!d_stats) return BBX_OK;                                        // (n == 0 and no statistics wanted)
+  return launched(bbx_launch_pmlp_ppo_stats(tail, n, d_stats, (hipStream_t)stream));
+}
+int pmlp_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+             const float* d_prepared, int hidden, const PpoArgs& a, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  if (int rc = refuse_ppo(a, n)) return rc;
+  const int gfl = pmlp_grad_workspace_floats(n, cols, hidden);
+  if (ppo_workspace(n, gfl) < 0) return BBX_E_ARG;
+  const PmlpLoss loss{a.old_logprobs, a.advantages, a.coef, d_workspace + gfl, n, a.mode, a.scale, a.eps, a.ent_coef, a.c_kl};
+  if (int rc = pmlp_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, a.logprobs, a.entropy, stream, &loss)) return rc;
+  if (int rc = ppo_stats(loss.tail, n, a.stats, stream)) return rc;
+  return pmlp_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, a.coef, a.coef ? a.coef + n : nullptr, d_workspace, d_gw1,
+                   d_gb1, d_gw2, d_gb2, stream);
+}
+int pmlp2_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+              const float* d_prepared, int hidden1, int hidden2, const PpoArgs& a, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+              float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows || !d_actions)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (int rc = refuse_ppo(a, n)) return rc;
+  const int gfl = pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
+  if (ppo_workspace(n, gfl) < 0) return BBX_E_ARG;
+  const PmlpLoss loss{a.old_logprobs, a.advantages, a.coef, d_workspace + gfl, n, a.mode, a.scale, a.eps, a.ent_coef, a.c_kl};
+  if (int rc = pmlp2_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, a.logprobs, a.entropy, stream, &loss)) return rc;
+  if (int rc = ppo_stats(loss.tail, n, a.stats, stream)) return rc;
+  return pmlp2_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, a.coef, a.coef ? a.coef + n : nullptr, d_workspace,
+                    d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
 }
 
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
@@ -191,6 +242,29 @@ int bbx_pmlp_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t*
                    stream);
 }
 
+// ---- forward, PPO loss and gradients in one call
+int bbx_pmlp_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden) {
+  const int gfl = bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden);
+  return gfl < 0 ? gfl : ppo_workspace(n, gfl);
+}
+int bbx_pmlp_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                      int hidden, const float* d_old_logprobs, const float* d_advantages, int mode, float scale, float eps, float ent_coef, float c_kl,
+                      float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+                      float* d_gb2, void* stream) {
+  return pmlp_ppo(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
+                  d_gw2, d_gb2, stream);
+}
+int bbx_pmlp_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                         int cols, const float* d_prepared, int hidden, const float* d_old_logprobs, const float* d_advantages, int mode, float scale,
+                         float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace,
+                         float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
+                  d_gw2, d_gb2, stream);
+}
+
 // ---- two and three hidden layers (bbx_pmlp2.hip)
 int bbx_pmlp2_prepared_floats(int cols, int hidden1, int hidden2) { return pmlp_deep_floats(cols, hidden1, 0, hidden2, false); }
 int bbx_pmlp3_prepared_floats(int cols, int hidden1, int hidden2, int hidden3) { return pmlp_deep_floats(cols, hidden1, hidden2, hidden3, true); }
@@ -239,6 +313,29 @@ int bbx_pmlp2_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t
   if (int rc = refuse_index(n_src, d_index, n)) return rc;
   return pmlp2_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
                     d_gw2, d_gb2, d_gw3, d_gb3, stream);
+}
+
+int bbx_pmlp2_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
+  const int gfl = bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
+  return gfl < 0 ? gfl : ppo_workspace(n, gfl);
+}
+int bbx_pmlp2_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
+                       int hidden1, int hidden2, const float* d_old_logprobs, const float* d_advantages, int mode, float scale, float eps, float ent_coef,
+                       float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1,
+                       float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  return pmlp2_ppo(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2,
+                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
+                   d_gw2, d_gb2, d_gw3, d_gb3, stream);
+}
+int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
+                          int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_old_logprobs, const float* d_advantages, int mode,
+                          float scale, float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats,
+                          float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2,
+                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
+                   d_gw2, d_gb2, d_gw3, d_gb3, stream);
 }
 
 int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,

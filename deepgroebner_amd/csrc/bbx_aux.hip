@@ -360,18 +360,30 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
 #define BBX_PMLP_SHAPES(M) do { if (nb == 1) BBX_PMLP_SHAPES_K(M, 1); else if (nb == 2) BBX_PMLP_SHAPES_K(M, 2); else if (nb == 4) BBX_PMLP_SHAPES_K(M, 4); \
                                 else BBX_PMLP_SHAPES_K(M, 8); } while (0)
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, hipStream_t stream) {
+                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss,
+                                       hipStream_t stream) {
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_LOGPROB_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                        actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src)
-#define BBX_PMLP_LOGPROB(N, K) BBX_PMLP_LOGPROB_I(N, K, false)
-#define BBX_PMLP_LOGPROB_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true)
-  if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB);
+  const PmlpLoss ls = loss ? *loss : PmlpLoss{};
+#define BBX_PMLP_LOGPROB_I(N, K, I, L) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I, L>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                           actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src, ls)
+#define BBX_PMLP_LOGPROB(N, K) BBX_PMLP_LOGPROB_I(N, K, false, false)
+#define BBX_PMLP_LOGPROB_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true, false)
+#define BBX_PMLP_LOSS(N, K) BBX_PMLP_LOGPROB_I(N, K, false, true)
+#define BBX_PMLP_LOSS_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true, true)
+  if (loss) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOSS_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOSS); }
+  else if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB);
+#undef BBX_PMLP_LOSS_AT
+#undef BBX_PMLP_LOSS
 #undef BBX_PMLP_LOGPROB_AT
 #undef BBX_PMLP_LOGPROB
 #undef BBX_PMLP_LOGPROB_I
+  return (int)hipGetLastError();
+}
+// the statistics of a PPO call, one or two hidden layers, from the tail its forward kernel wrote (n == 0: zeros)
+extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_pmlp_ppo_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
   return (int)hipGetLastError();
 }
 extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,

@@ -36,7 +36,9 @@ extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const f
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, hipStream_t stream);   // (index: null, or position k is about state index[k] of n_src)
+                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss,
+                                       hipStream_t stream);   // (index: null, or position k is about state index[k] of n_src; loss: null, or the loss epilogue's arguments)
+extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                     int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
                                     const int32_t* index, int n_src, hipStream_t stream);
@@ -45,8 +47,8 @@ extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const 
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
                                     const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, int cus, int max_lds,
-                                        hipStream_t stream);
+                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss, int cus,
+                                        int max_lds, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                      int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
                                      float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream);

@@ -78,6 +78,42 @@ __device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int l
   return __logf(sm.se) - sd / sm.se;
 }
 
+// The loss epilogue of the forward kernels (their LOSS instantiations: bbx_pmlp_ppo_grad, bbx_pmlp2_ppo_grad), called by lane 0
+// once a wave has logprob_k and H_k of position k: the coefficients dL/dlogprob_k, dL/dH_k of
+//   L = -scale sum_k u_k - scale ent_coef sum_k H_k
+// for the gradient kernels, and u_k, H_k, old_k - new_k and the flags for the statistics kernel.  float32, in this order, no
+// contraction into fused multiply-adds: the same inputs give the same bits whatever the compiler makes of the callers.
+// A NaN log-probability (index out of range, action outside the live rows) is not counted: zeros everywhere.
+__device__ __forceinline__ void pmlp_loss_lane0(const PmlpLoss& L, int k, float logprob, float H) {
+#pragma clang fp contract(off)
+  const size_t n = (size_t)L.n;
+  float gl = 0.f, ge = 0.f, u = 0.f, h = 0.f, dk = 0.f;
+  int flags = 0;
+  if (logprob == logprob) {
+    const float nw = logprob, old = L.old_logprobs[k], A = L.advantages[k];
+    const float d = nw - old, r = __expf(d), sA = L.scale * A;
+    flags = PMLP_LOSS_COUNTED;
+    dk = old - nw;
+    h = H;
+    if (L.mode == 0) { u = nw * A; gl = -sA; }
+    else if (L.mode == 1) {
+      const float lo = 1.f - L.eps, hi = 1.f + L.eps;
+      const float a = r * A, b = fminf(fmaxf(r, lo), hi) * A;
+      u = fminf(a, b);
+      if (a <= b) gl = -(sA * r); else flags |= PMLP_LOSS_CLIPPED;
+    } else { u = r * A - L.c_kl * dk; gl = -(sA * r) - L.scale * L.c_kl; }
+    ge = -(L.scale * L.ent_coef);
+  }
+  L.coef[k] = gl; L.coef[n + k] = ge;
+  L.tail[k] = u; L.tail[n + k] = h; L.tail[2 * n + k] = dk; ((int*)L.tail)[3 * n + k] = flags;
+}
+// ... with the kernels' own two outputs, either of which a PPO call may leave out
+__device__ __forceinline__ void pmlp_loss_out(const PmlpLoss& L, float* logprobs, float* entropy, int k, float logprob, float H) {
+  if (logprobs) logprobs[k] = logprob;
+  if (entropy) entropy[k] = H;
+  pmlp_loss_lane0(L, k, logprob, H);
+}
+
 // The hidden layer on the matrix cores, exact f32 (v_mfma_f32_32x32x2_f32 = an fmaf chain), everything in registers: a
 // tile is 32 hidden units x 32 rows of the block, D[unit][row] = sum_k W1[k][unit] x[row][k] + b1[unit]:
 //   A operand  lane l: W1[2s + (l >> 5)][unit = 32 nb + (l & 31)]        (coalesced loads, the same for every wave: L1)

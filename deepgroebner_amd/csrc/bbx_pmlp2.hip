@@ -225,9 +225,10 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
                                else if (hp2 == 64) BBX_P2G_K(M, 128, 64); else BBX_P2G_K(M, 128, 128); } while (0)
 // (hipErrorInvalidValue: the device has less LDS per workgroup than the shape needs)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, int cus, int max_lds,
-                                        hipStream_t stream) {
+                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss, int cus,
+                                        int max_lds, hipStream_t stream) {
   if (n <= 0) return 0;
+  const PmlpLoss ls = loss ? *loss : PmlpLoss{};
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
   // 8 waves beside the staged weights, fewer where tall observation blocks (4 bytes of logits per row and wave) leave less room
   int waves = PMLP2_WAVES;
@@ -239,11 +240,16 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
   int blocks = (n + waves - 1) / waves;
   blocks = blocks < max_blocks ? blocks : max_blocks;
   int rc = 0;
-#define BBX_P2_LOGPROB_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K, I>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, cols, \
-                                                                                              wp, logprobs, entropy, lgcap, index, n_src)
-#define BBX_P2_LOGPROB(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false)
-#define BBX_P2_LOGPROB_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true)
-  if (index) BBX_P2G_SHAPES(BBX_P2_LOGPROB_AT); else BBX_P2G_SHAPES(BBX_P2_LOGPROB);
+#define BBX_P2_LOGPROB_I(N1, N2, K, I, L) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K, I, L>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, \
+                                                                                                    cols, wp, logprobs, entropy, lgcap, index, n_src, ls)
+#define BBX_P2_LOGPROB(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false, false)
+#define BBX_P2_LOGPROB_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true, false)
+#define BBX_P2_LOSS(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false, true)
+#define BBX_P2_LOSS_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true, true)
+  if (loss) { if (index) BBX_P2G_SHAPES(BBX_P2_LOSS_AT); else BBX_P2G_SHAPES(BBX_P2_LOSS); }
+  else if (index) BBX_P2G_SHAPES(BBX_P2_LOGPROB_AT); else BBX_P2G_SHAPES(BBX_P2_LOGPROB);
+#undef BBX_P2_LOSS_AT
+#undef BBX_P2_LOSS
 #undef BBX_P2_LOGPROB_AT
 #undef BBX_P2_LOGPROB
 #undef BBX_P2_LOGPROB_I

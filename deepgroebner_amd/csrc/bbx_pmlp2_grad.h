@@ -76,11 +76,15 @@ __device__ __forceinline__ void pmlp2_logits_tile(float* lg, const int32_t* __re
   if (lg4 == 0 && r0 + lr < n) lg[r0 + lr] = part + b3;
 }
 
-template <int HP1, int HP2, int KS, bool IDX = false>
+// LOSS: the instantiations of bbx_pmlp2_ppo_grad — lane 0 goes on from logprob_k and H_k to the loss's coefficients and terms
+// (pmlp_loss_lane0); logprobs and entropy may then both be null, and H is computed whether entropy is wanted or not.  Without
+// LOSS the argument `loss` is not read.
+template <int HP1, int HP2, int KS, bool IDX = false, bool LOSS = false>
 __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                 const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                 const float* __restrict__ wp, float* __restrict__ logprobs,
-                                                                float* __restrict__ entropy, int lgcap, const int32_t* __restrict__ index, int n_src) {
+                                                                float* __restrict__ entropy, int lgcap, const int32_t* __restrict__ index, int n_src,
+                                                                PmlpLoss loss) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int A2F = HP1 * HP2;
   float* a2 = (float*)smem;
@@ -98,18 +102,31 @@ __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* _
     int s = k;
     if constexpr (IDX) {
       s = uni(index[k]);
-      if (s < 0 || s >= n_src) { if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); } continue; }
+      if (s < 0 || s >= n_src) {
+        if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
+        else if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); }
+        continue;
+      }
     }
     int n = uni(rows[s]);
     const int a = uni(actions[s]);
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS;
-    if (n <= 0) { if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; } continue; }
+    if (n <= 0) {
+      if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
+      else if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; }
+      continue;
+    }
     const int32_t* ob = obs + (size_t)s * obs_rows * cols;
     wave_sync();                                                              // (the previous state's logits have been read)
     for (int r0 = 0; r0 < n; r0 += 16) pmlp2_logits_tile<HP1, HP2, KS>(lg, ob, r0, n, obs_rows, cols, W1p, b1p, a2, b2l, w3l, b3, lane);
     wave_sync();
     const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
     const bool ok = a >= 0 && a < n;
+    if constexpr (LOSS) {
+      const float H = pmlp_entropy_wave(lg, n, lane, sm);
+      if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, ok ? lg[a] - sm.logz : __builtin_nanf(""), H);
+      continue;
+    }
     if (lane == 0) logprobs[k] = ok ? lg[a] - sm.logz : __builtin_nanf("");
     if (entropy) {
       const float H = pmlp_entropy_wave(lg, n, lane, sm);

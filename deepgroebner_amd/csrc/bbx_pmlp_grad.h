@@ -62,11 +62,14 @@ __device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __rest
 }
 
 // (pmlp_softmax_wave / pmlp_entropy_wave: bbx_pmlp.h, beside pmlp_sample, whose order they keep)
-template <int NB, int KS, bool IDX = false>
+// LOSS: the instantiations of bbx_pmlp_ppo_grad — lane 0 goes on from logprob_k and H_k to the loss's coefficients and terms
+// (pmlp_loss_lane0); logprobs and entropy may then both be null, and H is computed whether entropy is wanted or not.  Without
+// LOSS the argument `loss` is not read.
+template <int NB, int KS, bool IDX = false, bool LOSS = false>
 __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                   const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                   const float* __restrict__ wp, float* __restrict__ logprobs, float* __restrict__ entropy,
-                                                                  const int32_t* __restrict__ index, int n_src) {
+                                                                  const int32_t* __restrict__ index, int n_src, PmlpLoss loss) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
   const int k = blockIdx.x * ((int)blockDim.x / WAVE) + wave;         // my position in the call
@@ -74,16 +77,29 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t*
   int s = k;                                                          // the recorded state it is about
   if constexpr (IDX) {
     s = uni(index[k]);
-    if (s < 0 || s >= n_src) { if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); } return; }
+    if (s < 0 || s >= n_src) {
+      if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
+      else if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); }
+      return;
+    }
   }
   float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);
   const int nraw = rows[s];
   const int a = uni(actions[s]);
   const int n = pmlp_logits_wave<NB, KS>(lg, obs + (size_t)s * obs_rows * cols, nraw, obs_rows, cols, wp, lane & 31, lane >> 5);
-  if (n <= 0) { if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; } return; }
+  if (n <= 0) {
+    if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
+    else if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; }
+    return;
+  }
   wave_sync();
   const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
   const bool ok = a >= 0 && a < n;
+  if constexpr (LOSS) {
+    const float H = pmlp_entropy_wave(lg, n, lane, sm);
+    if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, ok ? lg[a] - sm.logz : __builtin_nanf(""), H);
+    return;
+  }
   if (lane == 0) logprobs[k] = ok ? lg[a] - sm.logz : __builtin_nanf("");
   if (entropy) {
     const float H = pmlp_entropy_wave(lg, n, lane, sm);
@@ -261,4 +277,39 @@ __global__ __launch_bounds__(256) void bbx_pmlp_grad_reduce_kernel(const float* 
   part[q][j] = sum;
   __syncthreads();
   if (q == 0 && out) *out = (part[0][j] + part[1][j]) + (part[2][j] + part[3][j]);
+}
+
+// The statistics of a PPO call (bbx_pmlp_ppo_grad, bbx_pmlp2_ppo_grad) from the tail the loss epilogue wrote: stats[0..5] = counted
+// positions, sum u_k, sum H_k, sum (old_k - new_k), positions clipped, positions not counted; the sums in double over the float32
+// terms.  ONE workgroup of PMLP_PPO_STAT_THREADS threads: thread t adds positions t, t + threads, ...; the 64 lanes of a wave are
+// added by a butterfly (every lane ends with the same sum), the 16 waves in order by one thread per statistic.  No atomics, and a
+// partition that depends on n alone.  n == 0: zeros.
+__global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+  __shared__ double part[PMLP_PPO_STAT_THREADS / WAVE][6];
+  const size_t n = (size_t)n_;
+  const int32_t* flags = (const int32_t*)tail + 3 * n;
+  double acc[6] = {0., 0., 0., 0., 0., 0.};
+  for (size_t k = threadIdx.x; k < n; k += PMLP_PPO_STAT_THREADS) {
+    const int f = flags[k];
+    if (f & PMLP_LOSS_COUNTED) {
+      acc[0] += 1.; acc[1] += (double)tail[k]; acc[2] += (double)tail[n + k]; acc[3] += (double)tail[2 * n + k];
+      if (f & PMLP_LOSS_CLIPPED) acc[4] += 1.;
+    } else acc[5] += 1.;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) acc[i] += __shfl_xor(acc[i], m, WAVE);
+  }
+  const int wave = (int)(threadIdx.x / WAVE);
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) part[wave][i] = acc[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double t = 0.;
+    for (int w = 0; w < PMLP_PPO_STAT_THREADS / WAVE; w++) t += part[w][threadIdx.x];
+    stats[threadIdx.x] = t;
+  }
 }

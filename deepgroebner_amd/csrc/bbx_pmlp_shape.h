@@ -71,6 +71,26 @@ BBX_HD constexpr int pmlp2_grad_workspace_floats(int n, int cols, int h1, int h2
   return pmlp2_grad_groups(n) * pmlp2_grad_layout(32 * pmlp2_grad_cb(cols), pmlp2_hp_for(h1), pmlp2_hp_for(h2)).total;
 }
 
+// ---- the PPO loss between the forward and the gradient kernels (bbx_pmlp.h: pmlp_loss_lane0; bbx_pmlp_ppo_grad of include/bbx.h).
+// What the forward kernels' loss epilogue reads and writes, all of length n and addressed by the position k of the call:
+// coef [2n] = glogp | gent (what the gradient kernels take), tail [4n] = u | H | old - new | flags (int32: PMLP_LOSS_*), which
+// lies in the call's workspace behind the gradient kernels' partial sums and is what the statistics kernel adds up.
+struct PmlpLoss {
+  const float* old_logprobs; const float* advantages; float* coef; float* tail;
+  int n, mode;                                     // mode: 0 policy gradient, 1 PPO-clip, 2 PPO-penalty
+  float scale, eps, ent_coef, c_kl;
+};
+constexpr int PMLP_LOSS_COUNTED = 1, PMLP_LOSS_CLIPPED = 2;
+constexpr int PMLP_PPO_TAIL = 4;                  // floats per position behind the gradient workspace
+// the statistics kernel: ONE workgroup of this many threads, thread t adding positions t, t + threads, ... in double, then the
+// lanes of a wave, then the waves in order: a function of n alone
+constexpr int PMLP_PPO_STAT_THREADS = 1024;
+// floats of a PPO call's workspace (grad_floats: the gradient kernels' own, a multiple of 4); -1: more than an int holds
+BBX_HD constexpr int pmlp_ppo_workspace_floats(int n, int grad_floats) {
+  const long long t = (long long)grad_floats + (long long)PMLP_PPO_TAIL * n;
+  return t > 0x7fffffffLL ? -1 : (int)t;
+}
+
 // ---- the policies built into the step kernels
 // a rollout with one hidden layer, step kernels of W-word monomials (bbx_binom_policy_kernel; 8-byte monomials with 3 variables
 // and k = 2 also bbx_fast_policy_rollout_kernel): 33..128 hidden units, 6 k-steps, or 10 with 16-byte monomials

@@ -6,6 +6,8 @@ device, replacing the per-step host round trip of the reference's agents.
     DeviceTrajectoryBuffer     TrajectoryBuffer (store/finish/get)    pg.py:79-240
     get_index + PMLPPolicy.evaluate_at   the update's minibatches as slices of an index list over the buffer: the training
                                kernels read the recorded states where the rollout left them (bbx_pmlp_logprob_at / bbx_pmlp_grad_at)
+    PMLPPolicy.ppo_step_at, ppo_update   one minibatch of the update — forward, PPO loss, statistics, weight gradients — in one library
+                               call (bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at), and the epochs around it     pg.py _fit_policy_model
     run_rollout                PGAgent.run_episode(s)                 pg.py:451-503   (one library call per vector step)
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
@@ -279,9 +281,12 @@ class PMLPPolicy(torch.nn.Module):
             nfl = _ffi.lib().bbx_pmlp_prepared_floats(cols, hidden)
             _ffi.check(min(nfl, 0))
             prep = torch.empty(nfl, dtype=torch.float32, device=w1.device)
+            # (b2 travels by value in the C call; reading it back would make every optimiser step wait for the device: the call gets
+            # 0 and the bias is copied on the device into its place, the first of the layout's last four floats)
             _ffi.check(_ffi.lib().bbx_pmlp_prepare(C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
-                                                   C.c_float(float(self.deciding.bias.item())), cols, hidden, C.c_void_p(prep.data_ptr()),
+                                                   C.c_float(0.0), cols, hidden, C.c_void_p(prep.data_ptr()),
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            prep[nfl - 4:nfl - 3].copy_(self.deciding.bias.detach().reshape(1))
             c = {"key": key, "keep": prep, "prepared": C.c_void_p(prep.data_ptr()), "hidden": hidden}
             self.__dict__["_fused_cache"] = c
         return c
@@ -344,17 +349,11 @@ class PMLPPolicy(torch.nn.Module):
         The kernels (bbx_pmlp_logprob_at / bbx_pmlp_grad_at, bbx_pmlp2_..._at) read the buffers in place: under evaluate()'s
         conditions, and only where states, rows and actions ARE contiguous int32 CUDA tensors already — a buffer is never
         converted or copied as a whole.  Anything else gathers the n states and takes evaluate()."""
-        R, cols = states.shape[-2:]
         lin = self.embedding[0]
-        S = rows.numel()
-        in_place = (states.is_cuda and 1 <= R <= 2048 and states.numel() == S * R * cols and actions.numel() == S
-                    and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows, actions)))
-        one = len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features)
-        two = (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
-               and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters()))
-        if in_place and (one or two):
+        depth = self._in_place_depth(states, actions, rows)
+        if depth:
             idx = index.to(device=states.device, dtype=torch.int32).contiguous()
-            if one:
+            if depth == 1:
                 return _PMLPEvaluate.apply(self, states, rows, actions, lin.weight, lin.bias, self.deciding.weight, self.deciding.bias, idx)
             l2 = self.embedding[1]
             return _PMLP2Evaluate.apply(self, states, rows, actions, lin.weight, lin.bias, l2.weight, l2.bias, self.deciding.weight, self.deciding.bias, idx)
@@ -363,6 +362,151 @@ class PMLPPolicy(torch.nn.Module):
             t, b = j // states.shape[1], j % states.shape[1]
             return self.evaluate(states[t, b], actions[t, b], rows[t, b])
         return self.evaluate(states[j], actions[j], rows[j])
+
+    def _in_place_depth(self, states, actions, rows):
+        """1 or 2 where the training kernels of that many hidden layers can read states [..., R, cols], actions and rows where they
+        lie (evaluate()'s conditions, and contiguous int32 CUDA tensors of matching sizes); 0: they cannot."""
+        R, cols = states.shape[-2:]
+        lin = self.embedding[0]
+        S = rows.numel()
+        in_place = (states.is_cuda and 1 <= R <= 2048 and states.numel() == S * R * cols and actions.numel() == S
+                    and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows, actions)))
+        if not in_place:
+            return 0
+        if len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features):
+            return 1
+        if (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
+                and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
+            return 2
+        return 0
+
+    LOSS_MODES = {"pg": 0, "clip": 1, "penalty": 2}
+
+    def ppo_step_at(self, states, actions, rows, index, old_logprobs, advantages, clip=0.2, ent_coef=0.0, mode="clip", c_kl=0.0):
+        """One minibatch of the policy update (pg.py _fit_policy_model) in one library call: from the recorded states index[k] of
+        the buffers states / actions / rows (as evaluate_at takes them), the rollout's log-probabilities old_logprobs [n] and the
+        advantages [n] to the gradients of
+            L = -mean_k u_k - ent_coef mean_k H_k
+            u_k = logprob_k A_k                                         mode "pg"
+                  min(r_k A_k, clamp(r_k, 1 - clip, 1 + clip) A_k)      mode "clip"       (r_k = exp(logprob_k - old_k))
+                  r_k A_k - c_kl (old_k - logprob_k)                    mode "penalty"
+        ADDED to the parameters' .grad as loss.backward() would (None becomes the tensor), in torch.nn.Linear's layouts.  The means
+        are over the n positions (scale 1 / n); a position whose log-probability is NaN (index out of range, action outside the live
+        rows) contributes nothing.  Returns (stats float64 [6] on the device: counted positions, sum u, sum H, sum (old - new),
+        positions clipped, positions not counted; logprobs float32 [n]; entropy float32 [n]) — nothing is read back, nothing waits.
+        Under evaluate_at's conditions for the kernels: bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at (no autograd, no torch op over
+        the n positions); anywhere else the same formulae with torch ops through evaluate_at and backward()."""
+        depth = self._in_place_depth(states, actions, rows)
+        if depth:
+            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
+            return self._ppo_kernels(depth, states, rows, actions, idx, old_logprobs, advantages, clip, ent_coef, mode, c_kl)
+        return self._ppo_torch(self.evaluate_at(states, actions, rows, index), old_logprobs, advantages, clip, ent_coef, mode, c_kl)
+
+    def ppo_step(self, states, actions, rows=None, old_logprobs=None, advantages=None, clip=0.2, ent_coef=0.0, mode="clip", c_kl=0.0):
+        """ppo_step_at for gathered tensors, as evaluate takes them: states int [N, R, cols], actions [N], rows [N] (None: the rows
+        whose last column is not -1) — bbx_pmlp_ppo_grad / bbx_pmlp2_ppo_grad under evaluate()'s conditions for the kernels."""
+        N, R, cols = states.shape
+        lin = self.embedding[0]
+        depth = 0
+        if states.is_cuda and 1 <= R <= 2048:
+            if len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features):
+                depth = 1
+            elif (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
+                  and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
+                depth = 2
+        if depth:
+            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
+            st = states if states.dtype == torch.int32 else states.to(torch.int32)
+            return self._ppo_kernels(depth, st.contiguous(), rows, actions.to(torch.int32).contiguous(), None, old_logprobs, advantages, clip,
+                                     ent_coef, mode, c_kl)
+        return self._ppo_torch(self.evaluate(states, actions, rows), old_logprobs, advantages, clip, ent_coef, mode, c_kl)
+
+    def _ppo_workspace(self, depth, N, R, cols, hidden, device):
+        """The workspace of bbx_pmlp_ppo_grad / bbx_pmlp2_ppo_grad, kept between calls (it grows only; calls on one stream run in
+        order)."""
+        lib = _ffi.lib()
+        nfl = lib.bbx_pmlp_ppo_workspace_floats(N, R, cols, *hidden) if depth == 1 else lib.bbx_pmlp2_ppo_workspace_floats(N, R, cols, *hidden)
+        _ffi.check(min(nfl, 0))
+        ws = self.__dict__.get("_ppo_ws")
+        if ws is None or ws.numel() < nfl or ws.device != device:
+            ws = torch.empty(nfl, dtype=torch.float32, device=device)
+            self.__dict__["_ppo_ws"] = ws
+        return ws
+
+    def _ppo_kernels(self, depth, states, rows, actions, index, old_logprobs, advantages, clip, ent_coef, mode, c_kl):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
+        dev = states.device
+        old = old_logprobs.to(device=dev, dtype=torch.float32).contiguous()
+        adv = advantages.to(device=dev, dtype=torch.float32).contiguous()
+        if old.numel() != N or adv.numel() != N:
+            raise ValueError("ppo_step: %d positions, %d old log-probabilities, %d advantages" % (N, old.numel(), adv.numel()))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        logp, ent, coef = new(N), new(N), new(2 * N)
+        stats = torch.empty(6, dtype=torch.float64, device=dev)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        loss = (self.LOSS_MODES[mode], C.c_float(1.0 / N if N else 0.0), C.c_float(clip), C.c_float(ent_coef), C.c_float(c_kl))
+        lib = _ffi.lib()
+        with torch.cuda.device(dev):
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            src = (p(states), p(rows), p(actions)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
+            if depth == 1:
+                w = self._fused_weights()
+                hidden = (w["hidden"],)
+                grads = [new(cols, hidden[0]), new(hidden[0]), new(hidden[0]), new(1)]
+                fn = lib.bbx_pmlp_ppo_grad if index is None else lib.bbx_pmlp_ppo_grad_at
+            else:
+                w = self._deep_weights()
+                hidden = tuple(w["hidden"])
+                grads = [new(cols, hidden[0]), new(hidden[0]), new(hidden[0], hidden[1]), new(hidden[1]), new(hidden[1]), new(1)]
+                fn = lib.bbx_pmlp2_ppo_grad if index is None else lib.bbx_pmlp2_ppo_grad_at
+            ws = self._ppo_workspace(depth, N, R, cols, hidden, dev)
+            _ffi.check(fn(*src, w["prepared"], *hidden, p(old), p(adv), *loss, p(logp), p(ent), p(coef), p(stats), p(ws), *[p(g) for g in grads], s))
+        # torch.nn.Linear's layouts, added as backward() would
+        lin = self.embedding[0]
+        if depth == 1:
+            params = (lin.weight, lin.bias, self.deciding.weight, self.deciding.bias)
+            shaped = (grads[0].t(), grads[1], grads[2].view(1, -1), grads[3])
+        else:
+            l2 = self.embedding[1]
+            params = (lin.weight, lin.bias, l2.weight, l2.bias, self.deciding.weight, self.deciding.bias)
+            shaped = (grads[0].t(), grads[1], grads[2].t(), grads[3], grads[4].view(1, -1), grads[5])
+        for q, g in zip(params, shaped):
+            if q.grad is None:
+                q.grad = g.contiguous()
+            else:
+                q.grad.add_(g)
+        return stats, logp, ent
+
+    def _ppo_torch(self, evaluated, old_logprobs, advantages, clip, ent_coef, mode, c_kl):
+        """The loss epilogue of the kernels with torch ops, float32 in the same order, and backward() through `evaluated`."""
+        logp, ent = evaluated
+        kind = self.LOSS_MODES[mode]
+        n = logp.numel()
+        old = old_logprobs.to(device=logp.device, dtype=torch.float32)
+        A = advantages.to(device=logp.device, dtype=torch.float32)
+        counted = ~torch.isnan(logp)
+        new = torch.where(counted, logp, old.detach())               # (a NaN must not reach exp: 0 * NaN in its backward)
+        r = torch.exp(new - old)
+        clipped = torch.zeros_like(counted)
+        if kind == 0:
+            u = new * A
+        elif kind == 1:
+            a, b = r * A, torch.clamp(r, 1.0 - clip, 1.0 + clip) * A
+            u = torch.min(a, b)
+            clipped = (a > b) & counted
+        else:
+            u = r * A - c_kl * (old - new)
+        zero = torch.zeros_like(u)
+        u = torch.where(counted, u, zero); H = torch.where(counted, ent, zero)
+        if n:
+            loss = -u.mean() - ent_coef * H.mean()
+            if loss.requires_grad:
+                loss.backward()
+        d = lambda x: x.detach().to(torch.float64).sum()
+        stats = torch.stack([d(counted), d(u), d(H), d(torch.where(counted, old - new, zero)), d(clipped), d(~counted)])
+        return stats, logp.detach(), ent.detach()
 
     def evaluate_torch(self, states, actions, rows=None):
         """evaluate with torch ops and autograd (any depth, any device; the baseline of the kernels): forward, gather, and
@@ -538,6 +682,44 @@ class DeviceTrajectoryBuffer:
             mr = int(rows[i:j].max()) if self.states is not None else 0
             batches.append(tuple(None if x is None else (x[i:j, :mr] if k == 0 else x[i:j]) for k, x in enumerate(out)))
         return batches
+
+
+def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef=0.0, kld_limit=None, mode="clip", shuffle=True, generator=None,
+               c_kl=0.0):
+    """The policy update of the reference (pg.py _fit_policy_model) over a finished DeviceTrajectoryBuffer with states: `epochs`
+    passes over buffer.get_index()'s steps in minibatches of batch_size — per epoch ONE permutation of the index list (shuffle; from
+    `generator`, which lives on the buffer's device), per minibatch one policy.ppo_step_at on the buffers as the rollout left them,
+    then optimizer.step() and optimizer.zero_grad(); the optimiser is the caller's.  One host read per epoch: the minibatches'
+    stacked statistics.  With kld_limit the update stops after an epoch whose mean old - new log-probability exceeds it.
+    Returns one dict per epoch run: "stats" (float64 [minibatches, 6], ppo_step_at's), and over the epoch's counted positions
+    "loss", "entropy", "kl" (mean old - new) and "clip_frac"."""
+    if buffer.states is None:
+        raise ValueError("ppo_update: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
+    idx, _, old, adv, _ = buffer.get_index(None)
+    n = int(idx.numel())
+    out = []
+    optimizer.zero_grad()
+    for _ in range(epochs):
+        if shuffle:
+            perm = torch.randperm(n, device=idx.device, generator=generator)
+            e_idx, e_old, e_adv = idx[perm], old[perm], adv[perm]
+        else:
+            e_idx, e_old, e_adv = idx, old, adv
+        stats = []
+        for i in range(0, n, batch_size):
+            k = min(i + batch_size, n)
+            st, _, _ = policy.ppo_step_at(buffer.states, buffer.actions, buffer.rows, e_idx[i:k], e_old[i:k], e_adv[i:k], clip=clip, ent_coef=ent_coef,
+                                          mode=mode, c_kl=c_kl)
+            optimizer.step()
+            optimizer.zero_grad()
+            stats.append(st)
+        st = torch.stack(stats).cpu().numpy() if stats else np.zeros((0, 6))     # the epoch's one host read
+        tot = st.sum(axis=0) if len(st) else np.zeros(6)
+        cnt = max(tot[0], 1.0)
+        out.append({"stats": st, "loss": -(tot[1] + ent_coef * tot[2]) / cnt, "entropy": tot[2] / cnt, "kl": tot[3] / cnt, "clip_frac": tot[4] / cnt})
+        if kld_limit is not None and out[-1]["kl"] > kld_limit:
+            break
+    return out
 
 
 @_with_gc_paused

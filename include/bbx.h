@@ -300,6 +300,58 @@ int bbx_pmlp2_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int3
 int bbx_pmlp2_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
                       int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent,
                       float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+/* One call per PPO minibatch: from the recorded states, the rollout's log-probabilities and the advantages to the weight gradients
+ * of the PPO objective and the numbers a training loop watches — the forward kernel of bbx_pmlp[2]_logprob[_at] with a loss
+ * epilogue, a statistics kernel, and the gradient and reduce kernels of bbx_pmlp[2]_grad[_at], queued from here: no autograd, no
+ * elementwise pass over the n positions in between, no host wait.
+ *   Per position k, with new = logprob_k, old = d_old_logprobs[k], A = d_advantages[k], in float32 and in this order
+ *   (exp is the fast form of the kernels; no fused multiply-adds):
+ *       d = new - old            r = exp(d)                   sA = scale * A
+ *       mode 0 (policy gradient):   u = new * A                      gl = -sA
+ *       mode 1 (PPO-clip):          a = r * A;  b = fminf(fmaxf(r, lo), hi) * A      (lo = 1.f - eps, hi = 1.f + eps)
+ *                                   u = fminf(a, b)                  gl = (a <= b) ? -(sA * r) : 0.f         "clipped" iff a > b
+ *       mode 2 (PPO-penalty):       u = r * A - c_kl * (old - new)   gl = -(sA * r) - scale * c_kl
+ *       every mode:                 ge = -(scale * ent_coef)
+ *   gl = dL/dlogprob_k and ge = dL/dH_k of the objective L = -scale sum_k u_k - scale ent_coef sum_k H_k over the counted positions
+ *   (mode 1: what autograd gives for -(min(r A, clamp(r, lo, hi) A)).sum() * scale, ties inside the clip range included).  The
+ *   caller passes scale (1 / n for means): nothing is counted in a pass of its own.
+ *   d_coef [2 n] receives gl at k and ge at n + k.  THE GRADIENTS ARE, BIT FOR BIT, THOSE OF bbx_pmlp_grad[_at] (bbx_pmlp2_grad[_at])
+ *   CALLED WITH d_glogp = d_coef, d_gent = d_coef + n ON THE SAME INPUTS; d_logprobs and d_entropy (either may be NULL) are those of
+ *   bbx_pmlp[2]_logprob[_at], bit for bit.
+ *   Positions that do not count: a NaN log-probability (an index out of range, an action outside the live rows): gl = ge = 0.f,
+ *   u left out of every sum.  A state without live rows counts, with logprob = 0 and H = 0 (the gradient kernel skips it, as
+ *   always).  What the caller puts into d_old_logprobs / d_advantages is not checked.
+ *   d_stats, double [6]: counted positions, sum u_k, sum H_k, sum (old_k - new_k), positions clipped (mode 1; else 0), positions
+ *   not counted — sums in double over the float32 terms by one workgroup, thread t adding positions t, t + 1024, ..., then lanes,
+ *   then waves in a fixed order: no floating-point atomics, a partition that depends on n alone, the same bits on any device.
+ *   (loss = -scale (stats[1] + ent_coef stats[2]); approximate KL = stats[3] / stats[0]; clip fraction = stats[4] / stats[0].)
+ *   d_workspace holds bbx_pmlp_ppo_workspace_floats(n, ...) floats (16-byte aligned): the gradient kernels' workspace, then
+ *   u | H | old - new | flags, n each.
+ *   Every convention of the logprob / grad entries holds word for word: shapes and refusals before anything is queued (the
+ *   two-layer entries without a device), n == 0 (gradients zeroed, d_stats zeros; the arrays of length n may be NULL), outputs
+ *   overwritten, no allocation, no read-back, asynchronous on `stream`, recordable into a HIP graph, deterministic, 64-bit offsets;
+ *   _at: position k is about recorded state d_index[k] of n_src, the per-call arrays (d_old_logprobs, d_advantages, d_logprobs,
+ *   d_entropy, d_coef) are addressed by k.  In addition BBX_E_ARG for: mode outside 0..2, eps < 0, a NULL d_coef / d_stats /
+ *   d_old_logprobs / d_advantages with n > 0, an n whose workspace size does not fit an int. */
+int bbx_pmlp_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden);   /* < 0: shape not supported */
+int bbx_pmlp_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                      const float* d_prepared, int hidden, const float* d_old_logprobs, const float* d_advantages, int mode, float scale,
+                      float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats,
+                      float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                         int obs_rows, int cols, const float* d_prepared, int hidden, const float* d_old_logprobs, const float* d_advantages,
+                         int mode, float scale, float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef,
+                         double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp2_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2);   /* < 0: not supported */
+int bbx_pmlp2_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols,
+                       const float* d_prepared, int hidden1, int hidden2, const float* d_old_logprobs, const float* d_advantages, int mode,
+                       float scale, float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats,
+                       float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n,
+                          int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_old_logprobs,
+                          const float* d_advantages, int mode, float scale, float eps, float ent_coef, float c_kl, float* d_logprobs,
+                          float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+                          float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
 /* ... and for three hidden layers (hidden_layers=[hidden1, hidden2, hidden3], each <= 128): the same kernel with a middle layer
  * whose output stays in registers as the next layer's B operands; d_w3 [hidden2][hidden3], d_b3 [hidden3], d_w4 [hidden3],
  * d_b4 [1].  All three layers are padded to the widest one's tile size (64 or 128 units). */

@@ -5,8 +5,11 @@ and autograd over the whole [N, R, cols] block), on identical tensors in the sam
 
     python scripts/bench_policy_grad.py [--states 4096] [--rows 64] [--cols 12] [--hidden 128 | 128,128] [--reps 30]
 
-Each repetition is timed with device events; the rate is states over the MEDIAN repetition; the two paths alternate in blocks
-of --block repetitions so that drift hits both.  Peak memory: torch.cuda.max_memory_allocated over one evaluate + backward of
+A third path, "ppo": PMLPPolicy.ppo_step — forward, the same loss and the gradients in one library call (bbx_pmlp_ppo_grad /
+bbx_pmlp2_ppo_grad), no autograd.
+
+Each repetition is timed with device events; the rate is states over the MEDIAN repetition; the paths alternate in blocks
+of --block repetitions so that drift hits all of them.  Peak memory: torch.cuda.max_memory_allocated over one evaluate + backward of
 each path, above what is allocated before it.
 
     python scripts/bench_policy_grad.py --from-buffer [--T 64] [--B 1024] [--rows 64] [--batch-size 4096] [--pairs 5] [--hidden ...]
@@ -16,6 +19,9 @@ still running at the end of the buffer, states with one row), two ways, alternat
     gather   buffer.get(batch_size, sort=True)        then evaluate    + loss + backward per minibatch
     index    buffer.get_index(batch_size, sort=True)  then evaluate_at + loss + backward per minibatch (nothing of the size of a
              state block is allocated: the kernels read the buffer in place)
+    ppo      buffer.get_index(batch_size, sort=True)  then ppo_step_at per minibatch: forward, loss and gradients in one library call
+             (bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at), no autograd; "ppo_vs_index" pairs every ppo pass with the index pass
+             before it
 Each pass is timed from its get / get_index to the end of its last backward (wall clock between device synchronisations: get()
 waits for the device per minibatch); states/s over the median pass with min-max, and torch.cuda.max_memory_allocated of a pass
 beyond what the buffer and the policy hold.  Prints one JSON line.
@@ -104,13 +110,25 @@ def from_buffer():
             count += idx.numel()
         return count
 
-    paths = {"gather": gather, "index": index}
+    def ppo():
+        policy.zero_grad(set_to_none=True)
+        count = 0
+        for idx, act, old, adv, _ in buf.get_index(a.batch_size, sort=True):
+            policy.ppo_step_at(buf.states, buf.actions, buf.rows, idx, old, adv, clip=0.2, ent_coef=0.01)
+            count += idx.numel()
+        return count
+
+    paths = {"gather": gather, "index": index, "ppo": ppo}
     grads, times, peak, count = {}, {k: [] for k in paths}, {}, {}
     for name, fn in paths.items():                     # warm up; the gradients of the two paths must be the same numbers
         fn()
         torch.cuda.synchronize()
         grads[name] = [p.grad.detach().clone() for p in policy.parameters()]
     same = all(torch.equal(x, y) for x, y in zip(grads["gather"], grads["index"]))
+    # (the fused loss rounds 1 / n and the ratio in its own order: the same gradients up to float32 rounding, not bit for bit; per
+    # parameter, relative to its largest entry, the deciding bias left out as in the plain mode: its gradient is rounding on every path)
+    ppo_rel = max(float((x - y).abs().max() / y.abs().max().clamp(min=1e-30))
+                  for (n, _), x, y in zip(policy.named_parameters(), grads["ppo"], grads["index"]) if n != "deciding.bias")
     del grads
     for _ in range(a.pairs):
         for name, fn in paths.items():
@@ -129,6 +147,8 @@ def from_buffer():
         t = sorted(times[name]); med = statistics.median(t)
         out[name] = {"states_per_s": count[name] / med, "median_ms": med * 1e3, "min_ms": t[0] * 1e3, "max_ms": t[-1] * 1e3, "peak_bytes": int(peak[name])}
     out["index_over_gather"] = statistics.median(times["gather"]) / statistics.median(times["index"])
+    pairs = sorted(i / p for i, p in zip(times["index"], times["ppo"]))
+    out["ppo_vs_index"] = {"median": statistics.median(pairs), "min": pairs[0], "max": pairs[-1], "rel_grad_difference": ppo_rel}
     print(json.dumps(out))
 
 
@@ -153,16 +173,23 @@ def step(evaluate):
     loss.backward()
 
 
-PATHS = {"kernel": policy.evaluate, "torch": policy.evaluate_torch}
+def ppo_step(_):
+    """The same evaluation through PMLPPolicy.ppo_step: one library call, no autograd."""
+    policy.zero_grad(set_to_none=True)
+    policy.ppo_step(states, actions, None, old, adv, clip=0.2, ent_coef=0.01)      # (rows from the padding, as the other paths)
+
+
+PATHS = {"kernel": policy.evaluate, "torch": policy.evaluate_torch, "ppo": None}
+run = lambda fn: ppo_step(fn) if fn is None else step(fn)
 grads, peak = {}, {}
 for name, fn in PATHS.items():
     for _ in range(a.warmup):
-        step(fn)
+        run(fn)
     torch.cuda.synchronize()
     grads[name] = [p.grad.detach().clone() for p in policy.parameters()]
     base = torch.cuda.memory_allocated()
     torch.cuda.reset_peak_memory_stats()
-    step(fn)
+    run(fn)
     torch.cuda.synchronize()
     peak[name] = torch.cuda.max_memory_allocated() - base
 # faster and different is not faster: the two paths' gradients on these tensors
@@ -178,7 +205,7 @@ while done < a.reps:
     for name, fn in PATHS.items():
         for _ in range(k):
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(); step(fn); e1.record()
+            e0.record(); run(fn); e1.record()
             e1.synchronize()
             times[name].append(e0.elapsed_time(e1) * 1e-3)
     done += k
@@ -192,4 +219,10 @@ for name in PATHS:
                  "peak_bytes": int(peak[name])}
 out["kernel_over_torch"] = med["torch"] / med["kernel"]
 out["rel_grad_difference"] = rel
+# the new path against the autograd path through the same kernels: repetition i of one against repetition i of the other (they
+# alternate in blocks), and the gradients (relative to each parameter's largest entry)
+pairs = sorted(k / p for k, p in zip(times["kernel"], times["ppo"]))
+out["ppo_vs_kernel"] = {"median": statistics.median(pairs), "min": pairs[0], "max": pairs[-1],
+                        "rel_grad_difference": max(float((x - y).abs().max() / y.abs().max().clamp(min=1e-30))
+                                                   for n, x, y in zip(names, grads["ppo"], grads["kernel"]) if n != "deciding.bias")}
 print(json.dumps(out))
