@@ -1066,9 +1066,11 @@ def test_make_strat_pipeline(tmp_path):
 
 
 def test_step_obs_ragged_block_and_growth():
-    """bbx_step_obs (what env.step()/reset() call): the ragged observation block against the oracle's matrices on a
-    distribution whose pair sets outgrow the initial 128-row device block (5-10-5-uniform: |P| in the hundreds), so the
-    block is enlarged and rewritten mid-run; step_ragged's flat/offsets view agrees with the list view."""
+    """bbx_step_obs (what env.step()/reset() call) on the pinned side of the 64-environment split (B = 3: the padded block is
+    pinned host memory, squeezed on the host; tests/test_host_step_large_gpu.py holds the device-buffer side): the ragged
+    observation block against the oracle's matrices on a distribution whose pair sets outgrow the initial 128-row block
+    (5-10-5-uniform: |P| in the hundreds), so the block is enlarged and rewritten mid-run; step_ragged's flat/offsets view
+    agrees with the list view."""
     from deepgroebner_amd import VecLeadMonomialsEnv
     bo = ffi.load("bo")
     B, k = 3, 2
