@@ -348,6 +348,26 @@ static inline BBX_HD BbxGenDraw bbx_gen_decode(const Acc& acc, uint32_t flags, i
 }
 #endif
 
+// ------------------------------------------------------------------ the fast class's working copy of a basis element's info
+// The record keeps, per basis element, ginfo = { lc | tc << 16 , 1/lc | sugar << 16 } (tc: the tail coefficient, 0 = no tail).
+// The only thing a step of the fast class ever wants of the first word is the tail coefficient of the MONIC element, with
+// either sign — the two coefficients of an S-polynomial —, so its LDS copy (bbx_fast.h) holds those instead, formed once when
+// the element enters, and the record's word aside in an array nothing hot reads:
+//   hot word  mt | nmt << 16,  mt = tc / lc mod p,  nmt = -mt mod p  (both 0 iff tc == 0; nmt is the reducer word's upper half)
+// Stated once, here, for the kernel and for the host check (tests/spoly_coef_check.cpp).
+static inline BBX_HD uint32_t bbx_coef_mulmod(uint32_t a, uint32_t b) {      // a b mod p for a, b < p: mulmod of bbx_device.h
+  const uint32_t x = a * b;
+  const uint32_t q = (uint32_t)(((uint64_t)x * 1099408559ull) >> 45);
+  return x - q * BBX_P;
+}
+static inline BBX_HD uint32_t bbx_ginfo_hot(uint32_t rec_x, uint32_t inv) {  // record word, 1/lc -> hot word
+  const uint32_t mt = bbx_coef_mulmod(rec_x >> 16, inv);
+  return mt | ((mt ? BBX_P - mt : 0u) << 16);
+}
+// hot word + the word kept aside -> record word.  (The hot word alone does not determine it — lc is gone —, which is why the
+// record's word is kept; the function is where a layout that packs the two differently would say so.)
+static inline BBX_HD uint32_t bbx_ginfo_record(uint32_t hot_x, uint32_t kept) { (void)hot_x; return kept; }
+
 // position-keyed commutative hash used for parity traces (same definition in oracle/trace.py)
 static inline BBX_HD uint64_t bbx_mix64(uint64_t idx, uint32_t word) {
   uint64_t z = ((idx << 32) | (uint64_t)word) + 0x9E3779B97F4A7C15ull;

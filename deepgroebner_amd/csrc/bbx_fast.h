@@ -3,11 +3,15 @@
 //   i.e. what the reference's C++ LeadMonomialsEnv always runs (buchberger.cpp:377) on 3-20-10-weighted.
 //
 // One wavefront owns one environment for the whole launch.  Where the state lives:
-//   registers  reducer-order arrays (lead monomial, tail monomial, {tc, 1/lc, sugar, basis index}), lane l holds
+//   registers  reducer-order arrays (lead monomial, tail monomial, {tc, -tc/lc, sugar, basis index}), lane l holds
 //              reducers l and l+64: the first-divisor scan is pure VALU + ballot, the chosen reducer is fetched with
 //              v_readlane, and the sorted insert is a DPP wave shift (no memory traffic at all in a reduction round)
 //   LDS        basis-order arrays (lm, tm, ginfo) and the pair list, which are gathered by per-lane index
-//              (pair criteria, observation): 4 KB per environment at compile-time offsets
+//              (pair criteria, observation), at compile-time offsets: 9.25 KB per environment (4.5 KB in the policy
+//              kernels).  ginfo is a WORKING form, { tc/lc | (-tc/lc) << 16 , 1/lc | sugar << 16 }: the two coefficients of an
+//              S-polynomial, formed once when the element enters (bbx_ginfo_hot, bbx_common.h), so that a step selects
+//              them with a mask and a shift; the record's first word { lc | tc << 16 } waits in gc[], which only the
+//              write-back and the reducers beyond the registers read
 //   HBM        the record (binomial layout, bbx_common.h) is read at launch start and written back at launch end;
 //              observations are written every step
 // An environment that outgrows |G| <= 128 / |P| <= 256 leaves a consistent record behind (BBX_ST_SPILL) and is
@@ -30,14 +34,22 @@ typedef Mono<2> M2;
 // registers (two banks of 64, FastState); with NBK = 4 reducers 128..255 exist as an ORDER only — their basis indices in
 // reducer order, u16 sx[] in LDS — and everything about them is read through the basis-order arrays when it is needed
 // (the overflow paths of the reduction and of the sorted insert: cold code, no register state of its own).  NBK = 2
-// (4 KB per environment) is what the policy kernels run — their registers and LDS also hold the policy —, NBK = 4 (8.25 KB,
-// 16 environments per CU = 132 KB of the CU's 160) everything else: on 3-20-10-weighted a basis passes 128 elements about
+// (4.5 KB per environment) is what the policy kernels run — their registers and LDS also hold the policy —, NBK = 4 (9.25 KB,
+// 16 environments per CU = 148 KB of the CU's 160) everything else: on 3-20-10-weighted a basis passes 128 elements about
 // once per 10^5 episodes, and an environment that leaves the class is waited for by every join.
 template <int NBK> struct FLay {
   static constexpr int G = 64 * NBK, P = 2 * G, OVF = G > 128 ? G - 128 : 0;
-  static constexpr int OFF_LM = 0, OFF_TM = 8 * G, OFF_GI = 16 * G, OFF_PR = 24 * G, OFF_SX = 24 * G + 4 * P, BYTES = OFF_SX + 2 * OVF;
+  static constexpr int OFF_LM = 0, OFF_TM = 8 * G, OFF_GI = 16 * G, OFF_PR = 24 * G, OFF_SX = 24 * G + 4 * P, OFF_GC = OFF_SX + 2 * OVF;
+  static constexpr int BYTES = OFF_GC + 4 * G;             // gc[]: the record's ginfo word per basis element, kept aside (cold)
 };
 constexpr int FNBK_WIDE = 4, FNBK_POL = 2;
+// Four workgroups of four waves per CU (one wave per SIMD each) is what the class is tuned for: 16 working copies must fit the
+// CU's 160 KB, with the policy kernels' logits (4 bytes per pair) and, for the largest two-layer policy, 128 x 128 + 2 x 128 + 4
+// floats of weights next to them.  A layout that grows past that loses the fourth workgroup without a word: said here instead.
+static_assert(FLay<FNBK_WIDE>::BYTES == 9472 && FLay<FNBK_POL>::BYTES == 4608, "FLay: bytes per environment (DESIGN.md 4.1, LDS budget)");
+static_assert(FLay<FNBK_WIDE>::OFF_GC % 4 == 0 && FLay<FNBK_WIDE>::BYTES % 16 == 0 && FLay<FNBK_POL>::BYTES % 16 == 0, "FLay: alignment of gc[] and of the next wave's region");
+static_assert(16 * FLay<FNBK_WIDE>::BYTES == 151552 && 16 * FLay<FNBK_WIDE>::BYTES <= 160 * 1024, "16 environments per CU no longer fit its LDS");
+static_assert(16 * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + 66576 == 156688 && 156688 <= 160 * 1024, "policy2<128,128>: 16 environments per CU no longer fit its LDS");
 constexpr uint32_t FSENT = 0xFFFFFFFFu;               // sentinel monomial word: divides nothing, greater than everything
 
 struct BbxFastParams {
@@ -249,6 +261,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   char* lbase = smem + wave_in_block * (FLDS_BYTES + (POL > 0 ? 4 * FP : 0));   // (POL: + the logits of up to FP rows)
   M2* lm = (M2*)(lbase + FOFF_LM); M2* tm = (M2*)(lbase + FOFF_TM);
   uint2* gi = (uint2*)(lbase + FOFF_GI); uint32_t* pairs = (uint32_t*)(lbase + FOFF_PR);
+  // gi[g] = { tc/lc | (-tc/lc) << 16 , 1/lc | sugar << 16 } (bbx_ginfo_hot); gc[g] = lc | tc << 16, the record's word, cold
+  uint32_t* gc = (uint32_t*)(lbase + LY::OFF_GC);
   const int limG = p.lim_G < FG ? p.lim_G : FG, limP = p.lim_P < FP ? p.lim_P : FP;
 
   uint16_t* sx = (uint16_t*)(lbase + LY::OFF_SX);         // OVF: basis indices of reducers 128.. in reducer order
@@ -271,7 +285,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         if (i < nG) {
           if constexpr (b < FRB) { S.slm[b] = g_slm[i]; S.stm[b] = g_stm[i]; S.sin[b] = g_si[i]; }
           else sx[i - 64 * FRB] = (uint16_t)(g_si[i].y >> 16);
-          lm[i] = g_lm[i]; tm[i] = g_tm[i]; gi[i] = g_gi[i];
+          const uint2 rg = g_gi[i];
+          lm[i] = g_lm[i]; tm[i] = g_tm[i]; gc[i] = rg.x; gi[i] = make_uint2(bbx_ginfo_hot(rg.x, rg.y & 0xffffu), rg.y);
         }
       });
       for (int i = lane; i < nP; i += WAVE) pairs[i] = g_pr[i];
@@ -527,8 +542,9 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         pos += __popcll(ballot64(le));
       }
       const uint32_t inv = (uint32_t)uni((int)inv_raw);        // (the one wait for the table read: every lane read the same entry)
-      if (lane == 0) gi[g] = make_uint2(t0.c | (t1.c << 16), inv | ((uint32_t)sugar << 16));
-      const uint2 ns = make_uint2(t1.c | (negmod(mulmod(t1.c, inv)) << 16), (uint32_t)sugar | ((uint32_t)g << 16));   // .x = tc | (-tc / lc) << 16
+      const uint32_t rec_x = t0.c | (t1.c << 16), hot_x = bbx_ginfo_hot(rec_x, inv);   // tc / lc | (-tc / lc) << 16
+      if (lane == 0) { gi[g] = make_uint2(hot_x, inv | ((uint32_t)sugar << 16)); gc[g] = rec_x; }
+      const uint2 ns = make_uint2(t1.c | (hot_x & 0xffff0000u), (uint32_t)sugar | ((uint32_t)g << 16));   // .x = tc | (-tc / lc) << 16
       // the overflow order takes the new element (pos beyond the registers) or the reducer that falls out of the last bank
       int ovq = -1; uint32_t ovg = 0;
       if (OVF && BK > FRB && g >= 64 * FRB) {
@@ -570,8 +586,9 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   };
 
   // A reset's whole ideal in one pass: the state n add_poly calls leave behind from an empty basis, in closed form.  The
-  // caller has written generator f of the insertion order to the basis-order arrays at f (lead coefficient 1, so 1/LC = 1
-  // and the sugar is the lead's degree); `in_order`: that order is already the reducer order (sort_input).  It guarantees
+  // caller has written generator f of the insertion order to the basis-order arrays at f (lead coefficient 1, so 1/LC = 1,
+  // gi[f].x = tc | (-tc) << 16 and the sugar is the lead's degree; gc[f] is written here, for all of the reset's writers: by
+  // each of them it cost the fused policy kernels scratch); `in_order`: that order is already the reducer order (sort_input).  It guarantees
   // n <= 11 (every pair fits a lane), limG >= n and limP >= n + n(n-1)/2 (none of the sequential loop's capacity checks
   // could fire) and has cleared the reducers.
   //   pair (i, j), i < j, is created when j enters iff no k < j has lcm(k, j) properly dividing lcm(i, j), i is the smallest
@@ -588,13 +605,15 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     const M2 L = lm[ln];                                 // (lanes >= n: stale entries, never used as a generator)
     {
       const M2 T = tm[ln];
-      const uint32_t c = gi[ln].x >> 16, sugar = m_deg(L);
+      // (lead coefficient 1: the working word tc | (-tc) << 16 the caller wrote IS the reducer word)
+      const uint32_t cx = gi[ln].x, sugar = m_deg(L);
+      if (mine) gc[ln] = 1u | (cx << 16);                 // the record's word lc | tc << 16 (read at the write-back)
       const int rk = in_order ? ln : gen_sorted_rank<2>(L, n);
       const int to = 4 * (mine ? rk : ln);              // (lanes >= n stay: a permutation)
       auto put = [&](uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(to, (int)v); };
       S.slm[0].w[0] = put(mine ? L.w[0] : FSENT); S.slm[0].w[1] = put(mine ? L.w[1] : FSENT);
       S.stm[0].w[0] = put(T.w[0]); S.stm[0].w[1] = put(T.w[1]);
-      S.sin[0].x = put(c | (negmod(mulmod(c, 1u)) << 16)); S.sin[0].y = put(sugar | ((uint32_t)ln << 16));
+      S.sin[0].x = put(cx); S.sin[0].y = put(sugar | ((uint32_t)ln << 16));
     }
     int j = 0;                                             // lane -> (i, j): j = #{t >= 1 : t(t-1)/2 <= lane}
 #pragma unroll
@@ -664,10 +683,10 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
               }
               rank = gen_sorted_rank<2>(tabL, npoly);
               FSTAMP(6);                                     // 6: reset: drawing the ideal
-              if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+              if (one_pass && lane < npoly) { lm[rank] = tabL; tm[rank] = tabT; gi[rank] = make_uint2(tabC | (negmod(tabC) << 16), 1u | (m_deg(tabL) << 16)); }
             }
             if (batch && !sorted) {                          // (already in basis order: lane f writes generator f)
-              if (lane < npoly) { lm[lane] = tabL; tm[lane] = tabT; gi[lane] = make_uint2(1u | (tabC << 16), 1u | (m_deg(tabL) << 16)); }
+              if (lane < npoly) { lm[lane] = tabL; tm[lane] = tabT; gi[lane] = make_uint2(tabC | (negmod(tabC) << 16), 1u | (m_deg(tabL) << 16)); }
               FSTAMP(6);
             }
             for (int fidx = 0; fidx < npoly && ok && !(one_pass && sorted) && !batch; fidx++) {
@@ -680,7 +699,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
               } else if (!gen_binomial<2>(x, gtab, GL, gflags, ncp, t0.m, t1.m, t1.c)) { status = BBX_ST_GEN_FAIL; ok = false; break; }
               if (!sorted) FSTAMP(6);
               if (one_pass) {                                // basis-order arrays only: install_ideal does the rest
-                if (lane == 0) { lm[fidx] = t0.m; tm[fidx] = t1.m; gi[fidx] = make_uint2(1u | (t1.c << 16), 1u | (m_deg(t0.m) << 16)); }
+                if (lane == 0) { lm[fidx] = t0.m; tm[fidx] = t1.m; gi[fidx] = make_uint2(t1.c | (negmod(t1.c) << 16), 1u | (m_deg(t0.m) << 16)); }
                 continue;
               }
               if (__builtin_expect(npoly <= 64, 1)) add_poly(t0, t1, (int)m_deg(t0.m), -1, std::integral_constant<int, 1>{});
@@ -934,18 +953,21 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     int hsug, bytes;
     {
       const M2 lmi = lm[gi_], lmj = lm[gj_];
-      const uint2 ii = gi[gi_], ij = gi[gj_];
+      uint2 ii = gi[gi_], ij = gi[gj_];
+      // (both words of each entry are said to be needed whole: the reads then stay 8-byte reads that pair with the lead
+      // monomials' — one ds_read2st64_b64 per member — instead of four narrowed ones)
+      asm volatile("" : "+v"(ii.x), "+v"(ii.y), "+v"(ij.x), "+v"(ij.y));
       const M2 gamma = m_lcm(lmi, lmj);
       const M2 si = m_div(gamma, lmi), sj = m_div(gamma, lmj);
       BTerm<2> a, b;
-      const uint32_t tci = ii.x >> 16, tcj = ij.x >> 16;
-      a.c = tci ? mulmod(tci, ii.y & 0xffffu) : 0u;           a.m = m_mul(tm[gi_], si);
-      b.c = tcj ? negmod(mulmod(tcj, ij.y & 0xffffu)) : 0u;   b.m = m_mul(tm[gj_], sj);
+      // tc_i / lc_i and -tc_j / lc_j: halves of the working word, formed when the element entered (0: no tail)
+      a.c = ii.x & 0xffffu;   a.m = m_mul(tm[gi_], si);
+      b.c = ij.x >> 16;       b.m = m_mul(tm[gj_], sj);
       const int sgi = (int)(ii.y >> 16) + (int)m_deg(si), sgj = (int)(ij.y >> 16) + (int)m_deg(sj);
       hsug = uni(sgi > sgj ? sgi : sgj);
       if (hsug > 65535) { status = BBX_ST_DEG_OVERFLOW; break; }
       merge2<2>(a, b, h0, h1);
-      bytes = ACCT ? 12 * ((tci ? 2 : 1) + (tcj ? 2 : 1) + (h0.c ? 1 : 0) + (h1.c ? 1 : 0)) : 0;
+      bytes = ACCT ? 12 * ((a.c ? 2 : 1) + (b.c ? 2 : 1) + (h0.c ? 1 : 0) + (h1.c ? 1 : 0)) : 0;
     }
 
     FSTAMP(2);                                             // 2: S-polynomial
@@ -1002,9 +1024,9 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
             const int gs = (int)f_readlane((uint32_t)gk, l);
             const M2 fm = f_readlane(fl, l), ft = tm[gs];
             const uint2 info = gi[gs];
-            const uint32_t tc = info.x >> 16, q1 = h0b - fm.w[1];
+            const uint32_t tc = gc[gs] >> 16, q1 = h0b - fm.w[1];
             nb0 = (uint32_t)uni((int)(ft.w[0] + (h0a - fm.w[0]))); nb1 = (uint32_t)uni((int)(ft.w[1] + q1));
-            sxw = (uint32_t)uni((int)(tc | (negmod(mulmod(tc, info.y & 0xffffu)) << 16)));
+            sxw = (uint32_t)uni((int)(tc | (info.x & 0xffff0000u)));             // -tc / lc: the working word's upper half
             fs = uni((int)((info.y >> 16) + (q1 >> 16)));
           }
         }
@@ -1287,11 +1309,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         else {                                                       // the record's reducer-order entry, rebuilt from the basis-order arrays
           const int gk = sx[i - 64 * FRB];
           const uint2 info = gi[gk];
-          const uint32_t tc = info.x >> 16;
           g_slm[i] = lm[gk]; g_stm[i] = tm[gk];
-          g_si[i] = make_uint2(tc | (negmod(mulmod(tc, info.y & 0xffffu)) << 16), (info.y >> 16) | ((uint32_t)gk << 16));
+          g_si[i] = make_uint2((gc[gk] >> 16) | (info.x & 0xffff0000u), (info.y >> 16) | ((uint32_t)gk << 16));
         }
-        g_lm[i] = lm[i]; g_tm[i] = tm[i]; g_gi[i] = gi[i];
+        const uint2 wi = gi[i];
+        g_lm[i] = lm[i]; g_tm[i] = tm[i]; g_gi[i] = make_uint2(bbx_ginfo_record(wi.x, gc[i]), wi.y);
       }
     });
     for (int i = lane; i < nP; i += WAVE) g_pr[i] = pairs[i];

@@ -28,6 +28,9 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
   f.sort_input = p->sort_input;
   f.ctl = p->ctl; f.sess_target = p->sess_target; f.ctl_stats = p->ctl_stats; f.slice_ticks = p->slice_ticks; f.mbox = p->mbox;
   f.gamma = p->gamma; f.values = p->values;
+  // (four workgroups of four waves per CU, one wave per SIMD each: 4 x 4 x 9472 = 151,552 of the CU's 163,840 bytes; a layout that
+  // no longer fits would lose the fourth workgroup without a word)
+  static_assert(4 * 4 * FLay<FNBK_WIDE>::BYTES == 151552 && 4 * 4 * FLay<FNBK_WIDE>::BYTES <= 163840, "fast class: 16 environments per CU");
   const size_t lds = (size_t)envs_per_block * FLay<FNBK_WIDE>::BYTES, lds_pol = (size_t)envs_per_block * FLay<FNBK_POL>::BYTES;
 #ifdef BBX_PROF_BUILD
   static unsigned long long* d_prof = nullptr;
@@ -56,8 +59,10 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
       q.f.actions = nullptr; q.f.rewards = nullptr; q.f.dones = nullptr; q.f.rows = q.pol.post_obs ? q.pol.rows_t : nullptr; q.f.obs_every_step = 0; q.f.auto_reset = 1;
       if (q.pol.hidden2 > 0) {                             // two hidden layers: envs_per_block = BBX_POL2_WAVES (plan_launch)
         const int h1 = pmlp2_hp_for(q.pol.hidden), h2 = pmlp2_hp_for(q.pol.hidden2);
-        // per wave its state and the logits of up to 256 rows (5 KB), per workgroup the layers behind the first (65 KB at 128 x 128):
-        // 16 waves = 145 KB of the CU's 160
+        // per wave its state and the logits of up to 256 rows (5.5 KB), per workgroup the layers behind the first (65 KB at 128 x 128):
+        // 16 waves = 153 KB of the CU's 160
+        static_assert((size_t)BBX_POL2_WAVES * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)128 * 128 + 2 * 128 + 4) * sizeof(float) == 156688,
+                      "policy2<128,128>: the workgroup's LDS (the CU holds 163,840 bytes)");
         const size_t rl2 = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)h1 * h2 + 2 * h2 + 4) * sizeof(float);
 #define BBX_FP2(A, C) launch_lds<bbx_fast_policy2_rollout_kernel<A, C>>(blocks, threads, rl2, stream, q)
         return h1 == 64 && h2 == 64 ? BBX_FP2(64, 64) : h1 == 64 ? BBX_FP2(64, 128) : h2 == 64 ? BBX_FP2(128, 64) : BBX_FP2(128, 128);
