@@ -121,6 +121,11 @@ SIGNATURES = {
     "bbx_values_seeded": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp]),
     "bbx_values_device": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp, _vp]),
     "bbx_gae_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "bbx_pmlp_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
+    "bbx_pmlp2_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "bbx_pmlp3_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "bbx_policy_greedy": (C.c_int, [_vp, C.c_int]),
+    "bbx_episodes_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_persistent": (C.c_int, [_vp, C.c_int]),
     "bbx_join": (C.c_int, [_vp, _vp]),
     "bbx_graph_replayed": (C.c_int, [_vp, _vp]),

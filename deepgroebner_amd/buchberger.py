@@ -85,6 +85,7 @@ class VecLeadMonomialsEnv:
         self._h = h
         self.batch, self.k, self.cols, self.nvars = src.batch, src.k, src.cols, src.nvars
         self.rows = src.rows.copy()
+        self._policy_greedy = getattr(src, "_policy_greedy", False)   # (bbx_copy carries the configuration, this switch included)
         self._rewards = np.zeros(self.batch, dtype=np.float64)
         self._dones = np.zeros(self.batch, dtype=np.uint8)
         return self
@@ -347,6 +348,15 @@ class VecLeadMonomialsEnv:
     def accounting(self, enable):
         """Toggle per-step algorithmic-byte accounting (stats()[:, 6]); off selects the leanest kernel."""
         _ffi.check(_ffi.lib().bbx_accounting(self._h, int(enable)))
+
+    def policy_greedy(self, enable):
+        """Evaluation mode of the policy calls on this handle (bbx_policy_greedy): while on, policy_step_device,
+        policy_rollout_device and policy2_rollout_device take the highest-probability pair instead of drawing one and do not
+        read `u`, which may be None.  Returns what the switch was before (for callers that restore it)."""
+        before = getattr(self, "_policy_greedy", False)
+        _ffi.check(_ffi.lib().bbx_policy_greedy(self._h, int(bool(enable))))
+        self._policy_greedy = bool(enable)
+        return before
 
     def prefetch(self):
         """Generate and upload ideals until every environment's ring is full."""

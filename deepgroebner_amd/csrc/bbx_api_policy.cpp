@@ -28,15 +28,23 @@ int pmlp_deep_floats(int cols, int h1, int hm, int h2, bool three) {
 }
 
 int pmlp_deep_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int h1, int hm, int h2,
-                  bool three, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+                  bool three, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream, bool greedy = false) {
+  // (greedy: the argmax in place of the draw — d_u is not read)
+  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || (!d_u && !greedy) || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
   if (pmlp_deep_floats(cols, h1, hm, h2, three) < 0) return BBX_E_UNSUPPORTED;
   int dev = 0; DeviceInfo di{};
   HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));   // (cached: this sits on the per-step path of a policy rollout)
-  int lrc = bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, di.cus, di.max_lds, (hipStream_t)stream);
+  int lrc = bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, greedy ? 1 : 0, di.cus, di.max_lds, (hipStream_t)stream);
   if (lrc == (int)hipErrorInvalidValue)
     return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, di.max_lds);
   return launched(lrc);
+}
+
+int pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden, const float* d_u,
+             int32_t* d_actions, float* d_logprobs, void* stream, bool greedy) {
+  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || (!d_u && !greedy) || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  return launched(bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, greedy ? 1 : 0, (hipStream_t)stream));
 }
 
 // the training calls for two hidden layers: the shape first (it needs no device and outranks a null pointer: a caller sizing
@@ -154,7 +162,7 @@ int pmlp2_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_acti
 int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
                    int nsteps, const float* d_u, int32_t* d_actions, float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
                    int32_t* d_obs, int obs_rows, long long obs_step_stride, void* stream) {
-  if (int rc = refuse_args(!b || !d_prepared || !d_u || !d_actions || !d_logprobs, nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0,
+  if (int rc = refuse_args(!b || !d_prepared || (!d_u && !b->policy_greedy) || !d_actions || !d_logprobs, nsteps < 1 || (d_obs && obs_rows < 1) || obs_step_stride < 0,
                            "bad rollout arguments", d_obs ? obs_rows : 0)) return rc;
   const int cols = 2 * b->nvars * b->k;
   if (int rc = admit(b, cols, hidden, hidden2)) return rc;
@@ -162,7 +170,8 @@ int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden
   if (traced(b)) return fail(BBX_E_UNSUPPORTED, "policy rollouts are not traced");
   if (d_obs && obs_step_stride != 0 && obs_step_stride < (long long)b->B * obs_rows * cols) return fail(BBX_E_ARG, "obs_step_stride smaller than one block");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  BbxPolicy pol{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0, hidden2};
+  const int greedy = b->policy_greedy ? 1 : 0;
+  BbxPolicy pol{d_prepared, hidden, greedy, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, obs_step_stride, b->B, 0, hidden2};
   BbxParams p; fill_params(b, &p);
   p.nsteps = nsteps; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
   p.obs = d_obs; p.obs_rows = d_obs ? obs_rows : 0; p.obs_fill = 0;   // (no block: the kernels size their logits for every row they score)
@@ -206,9 +215,11 @@ int bbx_pmlp_prepare(const float* d_w1, const float* d_b1, const float* d_w2, fl
 
 int bbx_pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
                  const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
-  if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || !d_u || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, (hipStream_t)stream));
+  return pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream, false);
+}
+int bbx_pmlp_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
+                        int32_t* d_actions, float* d_logprobs, void* stream) {
+  return pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, nullptr, d_actions, d_logprobs, stream, true);
 }
 
 // ---- the policy as a differentiable function of its weights (bbx_pmlp_grad.h)
@@ -280,6 +291,10 @@ int bbx_pmlp2_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int ob
                   const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
   return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, d_u, d_actions, d_logprobs, stream);
 }
+int bbx_pmlp2_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                         int32_t* d_actions, float* d_logprobs, void* stream) {
+  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, nullptr, d_actions, d_logprobs, stream, true);
+}
 
 // ---- two hidden layers as a differentiable function of the weights (bbx_pmlp2_grad.h).  Shapes: those of bbx_pmlp2_act,
 // refused before a device is asked for anything
@@ -349,17 +364,32 @@ int bbx_pmlp3_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int ob
                   int hidden3, const float* d_u, int32_t* d_actions, float* d_logprobs, void* stream) {
   return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, hidden2, hidden3, true, d_u, d_actions, d_logprobs, stream);
 }
+int bbx_pmlp3_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                         int hidden3, int32_t* d_actions, float* d_logprobs, void* stream) {
+  return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, hidden2, hidden3, true, nullptr, d_actions, d_logprobs, stream, true);
+}
+
+// the handle's policy calls (bbx_policy_step_device, bbx_policy_rollout_device, bbx_policy2_rollout_device) take the argmax
+// instead of drawing while this is on: BbxPolicy.greedy of every launch they make.  A running session was begun in the other
+// mode: it ends here
+int bbx_policy_greedy(bbx_batch* b, int enable) {
+  if (!b) return fail(BBX_E_ARG, "null argument");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  if (b->ps_active) { if (int rc = session_close(b, true, nullptr, false)) return rc; }
+  b->policy_greedy = enable != 0;
+  return BBX_OK;
+}
 
 int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, const float* d_u, int32_t* d_actions, float* d_logprobs,
                            double* d_rewards, uint8_t* d_dones, int32_t* d_rows, int32_t* d_obs, int obs_rows, int obs_fill, void* stream) {
-  if (int rc = refuse_args(!b || !d_prepared || !d_u || !d_actions || !d_logprobs || !d_rows || !d_obs, obs_rows < 1, "obs_rows must be positive", obs_rows)) return rc;
+  if (int rc = refuse_args(!b || !d_prepared || (!d_u && !b->policy_greedy) || !d_actions || !d_logprobs || !d_rows || !d_obs, obs_rows < 1, "obs_rows must be positive", obs_rows)) return rc;
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
   const int cols = 2 * b->nvars * b->k;
   if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
   // one launch for policy + step where the step kernel has the policy built in (the register/LDS-resident class, lean
   // variant, 33..128 hidden units, at most 12 columns); everywhere else the two launches it replaces
   if (!(lean_fast(b) && pmlp_fused_step_has(cols, hidden))) {
-    int rc = bbx_pmlp_act(d_obs, d_rows, b->B, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream);
+    int rc = pmlp_act(d_obs, d_rows, b->B, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, stream, b->policy_greedy);
     if (rc) return rc;
     return step_device(b, d_actions, d_rewards, d_dones, d_rows, d_obs, obs_rows, obs_fill, stream, 1);
   }
@@ -368,8 +398,9 @@ int bbx_policy_step_device(bbx_batch* b, const float* d_prepared, int hidden, co
   // uniforms of consecutive calls must then be consecutive [B] slices of one array (what a rollout loop that draws its
   // random numbers a chunk of steps at a time passes), every other argument the same from call to call
   const bool session = b->ps_enabled && b->nvars == 3 && b->k == 2 && b->device_gen;
-  BbxPolicy pol = session ? BbxPolicy{d_prepared, hidden, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, 0, 0, 1}
-                          : BbxPolicy{d_prepared, hidden, d_u, d_actions, d_logprobs, 0, nullptr, nullptr, nullptr, 0, 0, 0};
+  const int greedy = b->policy_greedy ? 1 : 0;
+  BbxPolicy pol = session ? BbxPolicy{d_prepared, hidden, greedy, d_u, d_actions, d_logprobs, 1, d_rewards, d_dones, d_rows, 0, 0, 1}
+                          : BbxPolicy{d_prepared, hidden, greedy, d_u, d_actions, d_logprobs, 0, nullptr, nullptr, nullptr, 0, 0, 0};
   BbxParams p; fill_params(b, &p);
   p.nsteps = 1; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 1;
   p.obs = d_obs; p.obs_rows = obs_rows; p.obs_fill = obs_fill; p.trace = nullptr;

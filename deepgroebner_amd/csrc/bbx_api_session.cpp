@@ -150,7 +150,7 @@ static bool session_same_policy(const bbx_batch* b, const BbxParams& p) {
   const BbxPolicy* a = b->ps_p.policy; const BbxPolicy* c = p.policy;
   return (!a && !c) || (a && c && is_policy_step_call(p) && a->wp == c->wp && a->hidden == c->hidden && a->actions == c->actions &&
                         a->logprobs == c->logprobs && a->rewards_t == c->rewards_t && a->dones_t == c->dones_t && a->rows_t == c->rows_t &&
-                        c->u == a->u + (size_t)b->ps_target * (size_t)b->B);
+                        a->greedy == c->greedy && (a->greedy || c->u == a->u + (size_t)b->ps_target * (size_t)b->B));   // (greedy: u is not read)
 }
 
 // The call p becomes the call in flight.  A session's calls are continued by its own kernels, which keep their policy (ps_pol):

@@ -307,6 +307,18 @@ extern "C" int bbx_gae_device(const double* d_rewards, const double* d_values, c
   return BBX_OK;
 }
 
+// per-episode returns and lengths of a [nsteps][batch] block of rewards and dones (bbx_episodes_kernel): no handle, asynchronous.
+// T == 0 with carries: nothing to add to them
+extern "C" int bbx_episodes_device(const double* d_rewards, const uint8_t* d_dones, int nsteps, int batch, double* d_carry_return,
+                                   int32_t* d_carry_len, int32_t* d_ep_count, double* d_ep_return, int32_t* d_ep_len, void* stream) {
+  if (nsteps < 0 || batch < 1) return fail(BBX_E_ARG, "bad arguments (nsteps = %d, batch = %d)", nsteps, batch);
+  if (nsteps == 0) return BBX_OK;
+  if (!d_rewards || !d_dones || !d_ep_return || !d_ep_len) return fail(BBX_E_ARG, "null argument");
+  const int lrc = bbx_launch_episodes(d_rewards, d_dones, nsteps, batch, d_carry_return, d_carry_len, d_ep_count, d_ep_return, d_ep_len, (hipStream_t)stream);
+  if (lrc) return fail(BBX_E_DEVICE, "episodes launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  return BBX_OK;
+}
+
 extern "C" int bbx_value(bbx_batch* b, int idx, const char* strategy, double gamma, double* out) {
   if (!b || !strategy || !out || idx < 0 || idx >= b->B) return fail(BBX_E_ARG, "bad arguments");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;

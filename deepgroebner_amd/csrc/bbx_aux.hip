@@ -267,6 +267,37 @@ extern "C" int bbx_launch_gae(const double* rewards, const double* values, const
   return (int)hipGetLastError();
 }
 
+// ---- per-episode returns and lengths from the [T][B] rewards and dones of a rollout (run_episodes, pg.py: one return and one
+// length per episode) -----------------------------------------------------------------------------------------------------
+// One thread per environment, forward scan over t: a plain double add per step, in step order (what the CPU loop of
+// rollout.episode_returns does).  The step that ends an episode carries its return and its length, every other step zeros;
+// what an unfinished episode has gathered goes back to the carries, so that a long evaluation is a chain of chunks.
+__global__ void bbx_episodes_kernel(const double* __restrict__ rewards, const uint8_t* __restrict__ dones, int T, int B,
+                                    double* __restrict__ carry_return, int32_t* __restrict__ carry_len, int32_t* __restrict__ ep_count,
+                                    double* __restrict__ ep_return, int32_t* __restrict__ ep_len) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= B) return;
+  double acc = carry_return ? carry_return[e] : 0.0;
+  int len = carry_len ? carry_len[e] : 0;
+  int count = 0;
+#pragma unroll 8                                            // (the loads of a row do not depend on the row above: issued ahead of the chain)
+  for (int t = 0; t < T; t++) {
+    const size_t i = (size_t)t * B + e;
+    acc += rewards[i]; len += 1;
+    const bool d = dones[i] != 0;
+    ep_return[i] = d ? acc : 0.0; ep_len[i] = d ? len : 0;
+    if (d) { count++; acc = 0.0; len = 0; }
+  }
+  if (carry_return) carry_return[e] = acc;
+  if (carry_len) carry_len[e] = len;
+  if (ep_count) ep_count[e] += count;
+}
+extern "C" int bbx_launch_episodes(const double* rewards, const uint8_t* dones, int T, int B, double* carry_return, int32_t* carry_len, int32_t* ep_count,
+                                   double* ep_return, int32_t* ep_len, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_episodes_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, dones, T, B, carry_return, carry_len, ep_count, ep_return, ep_len);
+  return (int)hipGetLastError();
+}
+
 // enlarged records (bbx_api.cpp grow_records): every environment's live state moves from its record in the old layout to
 // its record in the new one; an environment that was waiting for room (bbx_st_capacity) is released
 template <int W>
@@ -342,11 +373,11 @@ extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const f
   return (int)hipGetLastError();
 }
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
-                                   int32_t* actions, float* logprobs, hipStream_t stream) {
+                                   int32_t* actions, float* logprobs, int greedy, hipStream_t stream) {
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
 #define BBX_PMLP_MFMA(N, K) hipLaunchKernelGGL((bbx_pmlp_act_mfma_kernel<N, K>), dim3((B + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, B, \
-                                                obs_rows, cols, wp, u, actions, logprobs)
+                                                obs_rows, cols, wp, u, actions, logprobs, greedy)
 #define BBX_PMLP_MFMA_K(N) do { if (ks == 3) BBX_PMLP_MFMA(N, 3); else if (ks == 6) BBX_PMLP_MFMA(N, 6); else if (ks == 10) BBX_PMLP_MFMA(N, 10); \
                                 else if (ks == 16) BBX_PMLP_MFMA(N, 16); else BBX_PMLP_MFMA(N, 32); } while (0)
   if (nb == 1) BBX_PMLP_MFMA_K(1); else if (nb == 2) BBX_PMLP_MFMA_K(2); else if (nb == 4) BBX_PMLP_MFMA_K(4); else BBX_PMLP_MFMA_K(8);

@@ -24,6 +24,8 @@ extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, in
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream);
 extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
                               double* returns, double* advantages, uint8_t* complete, hipStream_t stream);
+extern "C" int bbx_launch_episodes(const double* rewards, const uint8_t* dones, int T, int B, double* carry_return, int32_t* carry_len, int32_t* ep_count,
+                                   double* ep_return, int32_t* ep_len, hipStream_t stream);
 extern "C" int bbx_launch_relayout(const char* src_recs, char* dst_recs, const BbxLayout* Ls, const BbxLayout* Ld, int B, hipStream_t stream);
 extern "C" int bbx_launch_ctl(unsigned long long* ctl, unsigned long long value, hipStream_t stream);
 extern "C" int bbx_launch_gather_lite(const char* recs, uint32_t rec_bytes, int B, void* out, hipStream_t stream);
@@ -34,7 +36,7 @@ extern "C" int bbx_launch_init(char* recs, uint32_t rec_bytes, int B, const uint
 extern "C" int bbx_launch_mark_reset(char* recs, uint32_t rec_bytes, int B, const uint8_t* mask, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const float* w2, float b2, int cols, int hidden, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
-                                   int32_t* actions, float* logprobs, hipStream_t stream);
+                                   int32_t* actions, float* logprobs, int greedy, hipStream_t stream);   // (greedy: the argmax, u unread)
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                        int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss,
                                        hipStream_t stream);   // (index: null, or position k is about state index[k] of n_src; loss: null, or the loss epilogue's arguments)
@@ -45,7 +47,7 @@ extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, con
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
-                                    const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
+                                    const float* u, int32_t* actions, float* logprobs, int greedy, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                         int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss, int cus,
                                         int max_lds, hipStream_t stream);
@@ -98,7 +100,7 @@ enum class BbxClass { FAST, BINOM_STAGED, GENERAL_STAGED, BINOM_HBM, GENERAL_HBM
 inline bool lds_staged(BbxClass c) { return c == BbxClass::FAST || c == BbxClass::BINOM_STAGED || c == BbxClass::GENERAL_STAGED; }
 
 // What create_common decides about a handle, and all of it that bbx_copy carries over.  L changes when the records grow
-// (grow_records), accounting with bbx_accounting; nothing else changes after creation.
+// (grow_records), accounting with bbx_accounting, policy_greedy with bbx_policy_greedy; nothing else changes after creation.
 struct bbx_config {
   int B = 0, device = 0, k = 1, nvars = 0, W = 2;
   int elim = 0, rewards = 0, sort_input = 0, sort_reducers = 1;
@@ -113,6 +115,7 @@ struct bbx_config {
   int ncu = 0;                        // compute units of the device
   bool no_growth = false;             // bbx_caps.no_growth: the configured capacities are hard limits (BBX_E_CAPACITY)
   bool accounting = true;             // count algorithmic bytes (bbx_accounting)
+  bool policy_greedy = false;         // the policy calls on this handle take the argmax instead of drawing (bbx_policy_greedy)
 };
 
 struct bbx_batch : bbx_config {

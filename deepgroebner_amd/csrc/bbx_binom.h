@@ -519,6 +519,9 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     if (need_reset) {
       bool reset_ok;
       if constexpr (CACHE) reset_ok = bin_reset_inl<W>(e, p, L, env, nG, nP, q_head, &status, gen_state, peel_lds);
+      // (the policy kernels have always had the reset inlined — the inliner's own choice, which the size of the policy's epilogue
+      // tips: out of line their counters live in scratch memory and ~90 registers are saved around the call)
+      else if constexpr (POL > 0) { [[clang::always_inline]] reset_ok = bin_reset<W>(e, p, L, env, nG, nP, q_head, &status, gen_state, peel_lds); }
       else reset_ok = bin_reset<W>(e, p, L, env, nG, nP, q_head, &status, gen_state, peel_lds);
       if (!reset_ok) {
         if (STAGED && (status == BBX_ST_G_FULL || status == BBX_ST_P_FULL)) { status = BBX_ST_SPILL; nG = 0; nP = 0; }
@@ -548,7 +551,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
       pol_tt = uni((p.sess_target ? p.sess_target : p.nsteps) - budget);   // (a continuation: the budget carries on from the first pass;
                                                                             // behind a session's kernel: what is owed of the session's total)
       const size_t tb = (size_t)pol_tt * (size_t)p.B + (size_t)env;
-      const float uu = pol->u[tb];
+      const float uu = pol->greedy ? 0.f : pol->u[tb];          // (greedy: never read, may be null)
       const bool pre_obs = pol->post_obs == 0;
       if (p.obs && pre_obs) { bin_obs<W, false>(e, p, env, nP, true, false, nullptr, (size_t)pol_tt * (size_t)pol->obs_tstride); obs_trunc |= nP > p.obs_rows ? 1 : 0; }
       if (lane == 0 && pol->rows_t && pre_obs) pol->rows_t[tb] = nP;
@@ -587,7 +590,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
           if (lg4 == 0 && r < n) lg[r] = part + w3l[16 * POL2];   // (+ the deciding bias, read per tile: one register fewer across it)
         }
         wave_sync();
-        action = pmlp_sample(lg, n, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+        action = pmlp_pick(lg, n, env, uu, pol->greedy, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
       } else {
       const float* wp = pol->wp;
       const int plr = lane & 31, plk = lane >> 5;
@@ -620,7 +623,7 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
         if (plk == 0 && r < n) lg[r] = logit + b2;
       }
       wave_sync();
-      action = pmlp_sample(lg, n, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      action = pmlp_pick(lg, n, env, uu, pol->greedy, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
       }
     } else
     if (p.agent == BBX_AGENT_EXTERNAL) action = p.actions[env];

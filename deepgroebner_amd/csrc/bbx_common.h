@@ -171,6 +171,10 @@ enum { BBX_REW_ADDITIONS = 0, BBX_REW_REDUCTIONS = 1 };
 // one-hidden-layer PMLP policy (networks.py:49-95, 414-460) for the policy + step launch: device pointers
 struct BbxPolicy {
   const float* wp; int32_t hidden;     // prepared weights (bbx_pmlp_prepare) of a [cols] -> [hidden] -> 1 network
+  // != 0: the kernels take the row of the largest logit (the first on ties) instead of drawing; u is not read and may be null
+  // (bbx_policy_greedy).  By value, like everything here: a recorded graph keeps the mode it was captured with.  (In the four
+  // bytes between `hidden` and the next pointer: the struct, and with it the kernels' argument block, is as large as it was)
+  int32_t greedy;
   const float* u;                      // [B] uniforms in [0, 1) for the inverse-CDF draw
   int32_t* actions; float* logprobs;   // [B] outputs: the sampled row and its log-probability
   // policy ROLLOUT (nsteps > 1 inside one launch): the arrays above are [nsteps][B] and so are these; the observation

@@ -862,7 +862,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       // the session (PERSIST: the agent's step counter against what it was when the session began)
       pol_tt = PERSIST ? uni(t_agent - pol_t0) : uni((p.sess_target ? p.sess_target : p.nsteps) - (t_stop - t_agent));
       const size_t tb = (size_t)pol_tt * (size_t)p.B + (size_t)env;
-      const float uu = pol->u[tb];                           // (requested before the observation goes out)
+      const int pol_greedy = pol->greedy;                    // (bbx_policy_greedy: the argmax instead of the draw)
+      const float uu = pol_greedy ? 0.f : pol->u[tb];        // (requested before the observation goes out; greedy: never read, may be null)
       const bool pre_obs = pol->post_obs == 0;
       if (p.obs && pre_obs) { o3_toff = (size_t)pol_tt * (size_t)pol->obs_tstride; write_obs32(); note_rows(); }
       if (lane == 0 && pol->rows_t && pre_obs) pol->rows_t[tb] = nP;
@@ -892,7 +893,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
           if (lg4 == 0 && r < pn) lg[r] = part + b3;
         }
         wave_sync();
-        action = pmlp_sample(lg, pn, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+        action = pmlp_pick(lg, pn, env, uu, pol_greedy, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
       } else {
       const PolW wp = pol_w;
       const int plr = lane & 31, plk = lane >> 5;
@@ -914,7 +915,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         if (plk == 0 && r < pn) lg[r] = logit + b2;
       }
       wave_sync();
-      action = pmlp_sample(lg, pn, env, uu, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
+      action = pmlp_pick(lg, pn, env, uu, pol_greedy, pol->actions + (size_t)pol_tt * (size_t)pol->stride_out, pol->logprobs + (size_t)pol_tt * (size_t)pol->stride_out);
       }
     } else
     if (agent == BBX_AGENT_HASH) action = (int)(((uint64_t)f_readlane(hv, t_agent & 63) * (uint32_t)nP) >> 32);   // bbx_agent_action32
@@ -1403,7 +1404,7 @@ __global__ __launch_bounds__(256, 4) void bbx_fast_policy_kernel(BbxFastPolicyPa
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int env = blockIdx.x * (blockDim.x / WAVE) + (int)(threadIdx.x / WAVE);
   const int action = pmlp_act_wave<NB, KS>(smem, env, env < q.f.B, q.f.obs, q.f.rows, q.f.obs_rows, 2 * q.f.k * q.f.nvars, q.pol.wp, q.pol.u,
-                                           q.pol.actions, q.pol.logprobs);
+                                           q.pol.actions, q.pol.logprobs, q.pol.greedy);
   __syncthreads();                                     // the policy's LDS scratch becomes the step's state
   fast_body<false, false, false, false, 0, false, false, FNBK_POL>(q.f, smem, action);   // (the policy's registers and LDS leave room for two banks)
 }

@@ -70,6 +70,31 @@ __device__ __forceinline__ PmlpSoftmax pmlp_softmax_wave(const float* lg, int n,
   const float logz = mx + __logf(se);
   return {mx, se, logz};
 }
+// The greedy pick in place of the draw (evaluation: run_episodes(greedy=True), pg.py): the row of the largest logit, the first
+// one on ties.  The same reductions in the same order as pmlp_sample, so lg[pick] - logz is, for that action, what the sampler
+// and the log-probability kernels give, bit for bit.  The row is found by comparing BITS with the maximum (which is one of the
+// logits, carried through compares and selects only): lane-strided, one ballot per 64 rows, the first group that hits ends the
+// search; nothing is recomputed in floating point.  Lane 0 writes action and log-probability; returns the row (wave-uniform).
+__device__ __forceinline__ int pmlp_greedy(const float* lg, int n, int env, int32_t* __restrict__ actions, float* __restrict__ logprobs) {
+  const int lane = lane_id();
+  wave_sync();
+  if (n <= 0) { if (lane == 0) { actions[env] = 0; logprobs[env] = 0.f; } return 0; }
+  const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+  const uint32_t mxb = __builtin_bit_cast(uint32_t, sm.mx);
+  int pick = 0;                                              // (no row matches: every logit is a NaN)
+  for (int base = 0; base < n; base += WAVE) {
+    const int r = base + lane;
+    const uint64_t hit = ballot64(r < n && __builtin_bit_cast(uint32_t, lg[r]) == mxb);
+    if (hit) { pick = base + (int)__builtin_ctzll(hit); break; }
+  }
+  if (lane == 0) { actions[env] = pick; logprobs[env] = lg[pick] - sm.logz; }
+  return uni(pick);
+}
+// what every policy kernel ends with: the draw from uu, or (greedy != 0, wave-uniform: a kernel argument or BbxPolicy.greedy,
+// so it travels by value and a recorded graph keeps the mode it was captured with) the argmax, which does not look at uu
+__device__ __forceinline__ int pmlp_pick(const float* lg, int n, int env, float uu, int greedy, int32_t* __restrict__ actions, float* __restrict__ logprobs) {
+  return greedy ? pmlp_greedy(lg, n, env, actions, logprobs) : pmlp_sample(lg, n, env, uu, actions, logprobs);
+}
 // H = log(se) - (sum_r e_r (z_r - mx)) / se
 __device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int lane, const PmlpSoftmax& sm) {
   float sd = 0.f;
@@ -178,7 +203,7 @@ __device__ __forceinline__ float pmlp_tile(const float (&xa)[KS], WP wp, int lr,
 template <int NB, int KS>
 __device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                              int obs_rows, int cols, const float* __restrict__ wp, const float* __restrict__ u,
-                                             int32_t* __restrict__ actions, float* __restrict__ logprobs) {
+                                             int32_t* __restrict__ actions, float* __restrict__ logprobs, int greedy = 0) {
   constexpr int HP = 32 * NB;
   constexpr int G = (KS <= 10 ? 2 : 1) < NB ? (KS <= 10 ? 2 : 1) : NB;   // unit blocks in flight together
   const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
@@ -186,7 +211,7 @@ __device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, con
   if (!live) return 0;
   const int lr = lane & 31, lk = lane >> 5;
   const int nraw = rows[env];
-  const float uu = u[env];
+  const float uu = greedy ? 0.f : u[env];                   // (greedy: u is not read and may be null)
   const float b2 = wp[(size_t)(2 * KS + 2) * HP];
   const int32_t* ob = obs + (size_t)env * obs_rows * cols;
   int n = 0;
@@ -207,15 +232,15 @@ __device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, con
   }
   if (n <= 0) { if (lane == 0) { actions[env] = 0; logprobs[env] = 0.f; } return 0; }
   wave_sync();
-  return pmlp_sample(lg, n, env, uu, actions, logprobs);
+  return pmlp_pick(lg, n, env, uu, greedy, actions, logprobs);
 }
 template <int NB, int KS>
 __global__ __launch_bounds__(256, 4) void bbx_pmlp_act_mfma_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows, int B, int obs_rows,
                                                                    int cols, const float* __restrict__ wp, const float* __restrict__ u,
-                                                                   int32_t* __restrict__ actions, float* __restrict__ logprobs) {
+                                                                   int32_t* __restrict__ actions, float* __restrict__ logprobs, int greedy) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int env = blockIdx.x * ((int)blockDim.x / WAVE) + (int)(threadIdx.x / WAVE);
-  pmlp_act_wave<NB, KS>(smem, env, env < B, obs, rows, obs_rows, cols, wp, u, actions, logprobs);
+  pmlp_act_wave<NB, KS>(smem, env, env < B, obs, rows, obs_rows, cols, wp, u, actions, logprobs, greedy);
 }
 // LDS bytes of pmlp_act_wave for a workgroup of `waves` waves (the logits)
 __host__ __device__ constexpr size_t pmlp_lds_bytes(int waves, int obs_rows) { return (size_t)waves * pmlp_lgcap(obs_rows) * sizeof(float); }

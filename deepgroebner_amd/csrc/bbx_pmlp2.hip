@@ -66,7 +66,7 @@ template <int HP1, int HPM, int HP2, int KS, int NWAVES>
 __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows, int B,
                                                                              int obs_rows, int cols, const float* __restrict__ wp,
                                                                              const float* __restrict__ u, int32_t* __restrict__ actions,
-                                                                             float* __restrict__ logprobs, int lgcap) {
+                                                                             float* __restrict__ logprobs, int lgcap, int greedy) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NK1 = HP1 / 16, NKM = HPM / 16, NK2 = HP2 / 16;    // blocks of 16 units per layer
   constexpr int HPI = HPM ? HPM : HP1, AMF = HP1 * HPM, A2F = AMF + HPI * HP2 + HPM;   // (A2F: everything in LDS in front of b2)
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
   if (PRE) {
     int e0 = (int)blockIdx.x * ((int)blockDim.x / WAVE) + (int)(threadIdx.x / WAVE);
     e0 = e0 < B ? e0 : B - 1;
-    n0 = rows[e0]; uu0 = u[e0];
+    n0 = rows[e0]; uu0 = greedy ? 0.f : u[e0];           // (greedy: u is not read and may be null)
     int r = (int)(threadIdx.x & 15); r = r < obs_rows ? r : obs_rows - 1;
     const int32_t* xr = obs + ((size_t)e0 * obs_rows + r) * cols;
 #pragma unroll
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
     const bool valid = env < B;
     const bool round0 = PRE && base == (int)blockIdx.x * nw;
     int n = valid ? uni(round0 ? n0 : rows[env]) : 0;
-    const float uu = valid ? (round0 ? uu0 : u[env]) : 0.f;
+    const float uu = valid && !greedy ? (round0 ? uu0 : u[env]) : 0.f;
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS; n = n > 0 ? n : 0;
     const int T = (n + 15) >> 4;
     __syncthreads();                                                          // (the previous round is over: logits, queue)
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
     __syncthreads();                                                          // (every tile of the workgroup's environments is in)
     if (valid) {
       if (n <= 0) { if (lane == 0) { actions[env] = 0; logprobs[env] = 0.f; } }
-      else pmlp_sample(lg, n, env, uu, actions, logprobs);
+      else pmlp_pick(lg, n, env, uu, greedy, actions, logprobs);
     }
   }
 }
@@ -185,7 +185,7 @@ extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const 
 }
 
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
-                                    const float* u, int32_t* actions, float* logprobs, int cus, int max_lds, hipStream_t stream) {
+                                    const float* u, int32_t* actions, float* logprobs, int greedy, int cus, int max_lds, hipStream_t stream) {
   const auto [hp1, hpm, hp2] = pmlp2_pads(h1, hm, h2);
   const int ks = pmlp2_ks_for(cols);
   // 64 KB of second-layer weights: two workgroups of 8 waves per CU; with a middle layer of that size (128 KB): one workgroup
@@ -204,7 +204,7 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
   int blocks = (B + waves - 1) / waves;
   blocks = blocks < max_blocks ? blocks : max_blocks;
   int rc = 0;
-#define BBX_P2(N1, NM, N2, K, NW) rc = launch_lds<bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>>(blocks, NW * WAVE, ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions, logprobs, lgcap)
+#define BBX_P2(N1, NM, N2, K, NW) rc = launch_lds<bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>>(blocks, NW * WAVE, ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions, logprobs, lgcap, greedy)
 #define BBX_P2_K(N1, NM, N2, NW) do { if (ks == 3) BBX_P2(N1, NM, N2, 3, NW); else if (ks == 8) BBX_P2(N1, NM, N2, 8, NW); else BBX_P2(N1, NM, N2, 16, NW); } while (0)
   if (hpm == 128 && waves == 16) BBX_P2_K(128, 128, 128, 16);
   else if (hpm == 128 && waves == 8) BBX_P2_K(128, 128, 128, 8);

@@ -12,6 +12,9 @@ device, replacing the per-step host round trip of the reference's agents.
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
                                (bbx_values_device: written on the device beside the steps); finish(): one GAE kernel
+    act / run_rollout / run_rollout_fused (greedy=True)   the highest-probability pair at every step   pg.py run_episodes(greedy=True)
+    episode_returns            one return and one length per episode from a rollout's rewards and dones (bbx_episodes_device)
+    evaluate_policy            the first K episodes of every environment under a policy   scripts/eval.py
 
 PyTorch is the plumbing here (device memory, autograd for training); the policy evaluation + sampling of the default
 one-hidden-layer network runs in hand-written HIP: on the matrix cores, either as a kernel of its own fed by the padded
@@ -20,6 +23,7 @@ loop (bbx_policy_rollout_device).  Two hidden layers of at most 128 units run in
 (bbx_policy2_rollout_device) or as a kernel of their own (bbx_pmlp2_act), three as a kernel of their own (bbx_pmlp3_act); deeper
 or wider networks take the torch path.  Actions never visit the host.
 """
+import collections
 import contextlib
 import ctypes as C
 import functools
@@ -202,11 +206,17 @@ class PMLPPolicy(torch.nn.Module):
         return torch.log_softmax(x, dim=-1)
 
     @torch.no_grad()
-    def act(self, obs, rows, u, actions=None, logprobs=None, stream=None):
+    def act(self, obs, rows, u, actions=None, logprobs=None, stream=None, greedy=False):
         """Sample one action per environment by inverse CDF from the uniforms u [B] -> (actions int32 [B], logprobs
         float32 [B]) on the device.  One hidden layer: the fused HIP kernel (bbx_pmlp_act); two or three hidden layers of at
-        most 128 units: bbx_pmlp2_act / bbx_pmlp3_act; otherwise torch ops."""
+        most 128 units: bbx_pmlp2_act / bbx_pmlp3_act; otherwise torch ops.
+        greedy=True (evaluation, run_episodes(greedy=True) of pg.py): the highest-probability row, the first one on ties,
+        through the *_act_greedy kernels; u is not read and may be None.  Shapes the kernels refuse and CPU tensors: act_torch."""
         B, R, cols = obs.shape
+        if not obs.is_cuda:
+            return self.act_torch(obs, rows, u, actions, logprobs, greedy=greedy)
+        lib = _ffi.lib()
+        uarg = () if greedy else (C.c_void_p(u.data_ptr()),)
         if actions is None:
             actions = torch.empty(B, dtype=torch.int32, device=obs.device)
         if logprobs is None:
@@ -214,17 +224,21 @@ class PMLPPolicy(torch.nn.Module):
         if len(self.embedding) == 1 and self.fused_ok(cols, self.embedding[0].out_features) and R <= 2048:   # (the kernels score <= 2048 rows)
             w = self._fused_weights()
             s = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
-            _ffi.check(_ffi.lib().bbx_pmlp_act(C.c_void_p(obs.data_ptr()), C.c_void_p(rows.data_ptr()), B, R, cols, w["prepared"], w["hidden"],
-                                               C.c_void_p(u.data_ptr()), C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
+            fn = lib.bbx_pmlp_act_greedy if greedy else lib.bbx_pmlp_act
+            _ffi.check(fn(C.c_void_p(obs.data_ptr()), C.c_void_p(rows.data_ptr()), B, R, cols, w["prepared"], w["hidden"],
+                          *uarg, C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
             return actions, logprobs
         if self.deep_ok(cols) and R <= self.deep_max_rows():
             w = self._deep_weights()
             s = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
-            fn = _ffi.lib().bbx_pmlp2_act if len(w["hidden"]) == 2 else _ffi.lib().bbx_pmlp3_act
+            if greedy:
+                fn = lib.bbx_pmlp2_act_greedy if len(w["hidden"]) == 2 else lib.bbx_pmlp3_act_greedy
+            else:
+                fn = lib.bbx_pmlp2_act if len(w["hidden"]) == 2 else lib.bbx_pmlp3_act
             _ffi.check(fn(C.c_void_p(obs.data_ptr()), C.c_void_p(rows.data_ptr()), B, R, cols, w["prepared"], *w["hidden"],
-                          C.c_void_p(u.data_ptr()), C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
+                          *uarg, C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
             return actions, logprobs
-        return self.act_torch(obs, rows, u, actions, logprobs)
+        return self.act_torch(obs, rows, u, actions, logprobs, greedy=greedy)
 
     def deep_ok(self, cols):
         """Two or three hidden layers of at most 128 units: the shapes bbx_pmlp2_act / bbx_pmlp3_act are built for."""
@@ -535,15 +549,21 @@ class PMLPPolicy(torch.nn.Module):
             x = torch.relu(layer(x))
         return self.deciding(x).squeeze(-1)
 
-    def act_torch(self, obs, rows, u, actions=None, logprobs=None):
-        """The same draw with torch ops (the reference of the fused kernel; any depth)."""
+    def act_torch(self, obs, rows, u, actions=None, logprobs=None, greedy=False):
+        """The same draw with torch ops (the reference of the fused kernel; any depth).  greedy=True: the argmax over the live
+        rows, the first index on ties (u unused, may be None)."""
         lp = self.forward(obs)
         n = torch.clamp(rows, max=obs.shape[1]).to(torch.int64)
         valid = torch.arange(obs.shape[1], device=obs.device)[None, :] < n[:, None]
-        p = torch.where(valid, torch.exp(lp - lp.max(dim=1, keepdim=True).values), torch.zeros_like(lp))
-        cdf = torch.cumsum(p, dim=1)
-        target = u * cdf[:, -1]
-        a = torch.minimum((cdf <= target[:, None]).sum(dim=1), n - 1).clamp(min=0)
+        if greedy:
+            best = torch.where(valid, lp, torch.full_like(lp, float("-inf")))
+            top = best.max(dim=1, keepdim=True).values
+            a = ((best == top) & valid).to(torch.int64).argmax(dim=1)   # (0 / 1 flags: argmax returns the first 1; no live row: 0)
+        else:
+            p = torch.where(valid, torch.exp(lp - lp.max(dim=1, keepdim=True).values), torch.zeros_like(lp))
+            cdf = torch.cumsum(p, dim=1)
+            target = u * cdf[:, -1]
+            a = torch.minimum((cdf <= target[:, None]).sum(dim=1), n - 1).clamp(min=0)
         out_a = a.to(torch.int32)
         out_l = lp.gather(1, a[:, None]).squeeze(1)
         if actions is not None:
@@ -724,7 +744,7 @@ def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef
 
 @_with_gc_paused
 @torch.no_grad()
-def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256):
+def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False):
     """run_rollout with the policy INSIDE the step kernel: `chunk` vector steps per launch, environments never wait for each
     other between steps.  One hidden layer: bbx_policy_rollout_device; two hidden layers of at most 128 units:
     bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
@@ -734,7 +754,9 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
     values inside the T-step policy kernels would need a rollout to completion nested in the kernels' step loop — a different
     piece of work.  Returns (total reward per environment, finished episodes) like
     run_rollout.  The rollout kernels are the lean ones (no algorithmic-byte accounting): the handle's accounting is switched
-    off here."""
+    off here.
+    greedy=True: the highest-probability pair at every step (env.policy_greedy for the duration of the call, restored
+    afterwards); no uniforms are drawn."""
     B, cols = env.batch, env.cols
     depth = len(policy.embedding)
     if not (depth == 1 or (depth == 2 and policy.deep_ok(cols))):
@@ -762,20 +784,24 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
             raise IndexError("trajectory buffer holds %d steps, %d are stored already: no room for %d more" % (buffer.T, buffer.t, nsteps))
         if keep_states and tuple(buffer.states.shape[2:]) != (obs_rows, cols):
             raise ValueError("buffer.states has blocks of %s, the environment writes (%d, %d)" % (tuple(buffer.states.shape[2:]), obs_rows, cols))
-    for t0 in range(0, nsteps, chunk):
-        n = min(chunk, nsteps - t0)
-        u = torch.rand((n, B), device=dev, generator=generator)
-        if buffer is not None:
-            t = buffer.t
-            obs = buffer.states[t:t + n] if keep_states else obs1
-            if keep_states:
-                obs.fill_(-1)                           # the kernel writes the live rows only; the rest is the reference's padding
-            rollout(n, u, buffer.actions[t:t + n], buffer.logprobs[t:t + n], buffer.rewards[t:t + n], buffer.dones[t:t + n], buffer.rows[t:t + n],
-                    obs, obs_rows, B * obs_rows * cols if keep_states else 0, stream.cuda_stream)
-            buffer.t += n
-        else:
-            rollout(n, u, act, logp, None, None, None, obs1, obs_rows, 0, stream.cuda_stream)
-        env.sync()
+    was_greedy = env.policy_greedy(greedy)
+    try:
+        for t0 in range(0, nsteps, chunk):
+            n = min(chunk, nsteps - t0)
+            u = None if greedy else torch.rand((n, B), device=dev, generator=generator)
+            if buffer is not None:
+                t = buffer.t
+                obs = buffer.states[t:t + n] if keep_states else obs1
+                if keep_states:
+                    obs.fill_(-1)                       # the kernel writes the live rows only; the rest is the reference's padding
+                rollout(n, u, buffer.actions[t:t + n], buffer.logprobs[t:t + n], buffer.rewards[t:t + n], buffer.dones[t:t + n], buffer.rows[t:t + n],
+                        obs, obs_rows, B * obs_rows * cols if keep_states else 0, stream.cuda_stream)
+                buffer.t += n
+            else:
+                rollout(n, u, act, logp, None, None, None, obs1, obs_rows, 0, stream.cuda_stream)
+            env.sync()
+    finally:
+        env.policy_greedy(was_greedy)
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)
     episodes = torch.tensor(d[:, 2], device=dev)
@@ -785,7 +811,7 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
 @_with_gc_paused
 @torch.no_grad()
 def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, sync_every=64, graph=False,
-                value_strategy=None, value_gamma=None):
+                value_strategy=None, value_gamma=None, greedy=False):
     """nsteps vector steps of `env` (a VecLeadMonomialsEnv already reset) under `policy`, everything on the device
     (obs_rows: rows of the observation block per environment — a pair set with more rows makes env.sync() raise
     BBX_E_CAPACITY, it is never cut silently; 256 is what the register/LDS-resident class holds):
@@ -800,7 +826,9 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     about to see at step t (pg.py:451-475 with --value_model: value, then action, then step; after an auto-reset it is the
     new episode's first state), written on the device by env.values_device straight into the buffer's row, its rollouts
     overlapping the steps that follow; value_gamma defaults to buffer.gam.  No extra host wait.  None: no values, call for call
-    what it was.  With graph=True: ValueError."""
+    what it was.  With graph=True: ValueError.
+    greedy=True: the highest-probability pair at every step (policy.act(greedy=True); env.policy_greedy for the duration of the
+    call, restored afterwards); no uniforms are drawn."""
     if value_strategy is not None and graph:
         raise ValueError("run_rollout: value_strategy cannot be recorded into a graph (bbx_values_device keeps host bookkeeping)")
     if value_strategy is not None and buffer is None:
@@ -811,7 +839,7 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     dev = torch.device("cuda", torch.cuda.current_device())
     one_call = len(policy.embedding) == 1 and policy.fused_ok(cols, policy.embedding[0].out_features) and hasattr(env, "policy_step_device")
     if graph and not one_call and buffer is None:
-        return _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every)
+        return _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every, greedy)
     stream = torch.cuda.current_stream()
     obs = torch.empty((B, obs_rows, cols), dtype=torch.int32, device=dev)
     rew = torch.zeros(B, dtype=torch.float64, device=dev); done = torch.zeros(B, dtype=torch.uint8, device=dev)
@@ -824,28 +852,34 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     keep_states = buffer is not None and buffer.states is not None
     w = policy._fused_weights() if one_call else None
     nsync = 0
-    for t0 in range(0, nsteps, sync_every):
-        n = min(sync_every, nsteps - t0)
-        u_all = torch.rand((n, B), device=dev, generator=generator)   # one generator launch per chunk of steps
-        for i in range(n):
-            if buffer is not None:                      # what the policy is about to see
-                t = buffer.t
-                if keep_states:
-                    buffer.states[t].copy_(obs)
-                buffer.rows[t].copy_(rows)
-                if value_strategy is not None:          # value, then action, then step (pg.py:461-465)
-                    env.values_device(buffer.values[t], value_strategy, value_gamma, None, stream.cuda_stream)
-            if one_call:                                # policy + step: one library call (one kernel where the class has it)
-                env.policy_step_device(w["prepared"], w["hidden"], u_all[i], act, logp, rew, done, rows, obs, obs_rows, 2, stream.cuda_stream)   # (2: incremental padding)
-            else:
-                policy.act(obs, rows, u_all[i], act, logp, stream)
-                env.step_device(act, rew, done, rows, obs, obs_rows, 2, stream.cuda_stream, auto_reset=True)
-            if buffer is not None:
-                buffer.actions[t].copy_(act); buffer.logprobs[t].copy_(logp)
-                buffer.rewards[t].copy_(rew); buffer.dones[t].copy_(done)
-                buffer.t += 1
-        env.sync()
-        nsync += 1
+    was_greedy = env.policy_greedy(greedy) if one_call else None
+    try:
+        for t0 in range(0, nsteps, sync_every):
+            n = min(sync_every, nsteps - t0)
+            u_all = None if greedy else torch.rand((n, B), device=dev, generator=generator)   # one generator launch per chunk of steps
+            for i in range(n):
+                u = None if greedy else u_all[i]
+                if buffer is not None:                  # what the policy is about to see
+                    t = buffer.t
+                    if keep_states:
+                        buffer.states[t].copy_(obs)
+                    buffer.rows[t].copy_(rows)
+                    if value_strategy is not None:      # value, then action, then step (pg.py:461-465)
+                        env.values_device(buffer.values[t], value_strategy, value_gamma, None, stream.cuda_stream)
+                if one_call:                            # policy + step: one library call (one kernel where the class has it)
+                    env.policy_step_device(w["prepared"], w["hidden"], u, act, logp, rew, done, rows, obs, obs_rows, 2, stream.cuda_stream)   # (2: incremental padding)
+                else:
+                    policy.act(obs, rows, u, act, logp, stream, greedy=greedy)
+                    env.step_device(act, rew, done, rows, obs, obs_rows, 2, stream.cuda_stream, auto_reset=True)
+                if buffer is not None:
+                    buffer.actions[t].copy_(act); buffer.logprobs[t].copy_(logp)
+                    buffer.rewards[t].copy_(rew); buffer.dones[t].copy_(done)
+                    buffer.t += 1
+            env.sync()
+            nsync += 1
+    finally:
+        if one_call:
+            env.policy_greedy(was_greedy)
     # totals from the environments' own counters (additions rewards: reward = -additions, buchberger.cpp:328)
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)
@@ -853,14 +887,14 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     return total, episodes
 
 
-def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every):
+def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every, greedy=False):
     """run_rollout with the vector step replayed from a HIP graph (see there).  The graph and its buffers live on `env`
     (one per policy object and block height) and are reused by later calls; the policy's parameters are read in place, so
     optimiser steps between calls are seen."""
     B, cols = env.batch, env.cols
     dev = torch.device("cuda", torch.cuda.current_device())
     cache = env.__dict__.setdefault("_step_graphs", {})
-    key = (id(policy), obs_rows, sync_every)
+    key = (id(policy), obs_rows, sync_every, bool(greedy))     # (a recording keeps the mode it was captured with)
     c = cache.get(key)
     if c is None:
         c = {"obs": torch.empty((B, obs_rows, cols), dtype=torch.int32, device=dev),
@@ -874,7 +908,7 @@ def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every):
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                  # the library GEMMs pick their workspaces outside the capture
             for _ in range(3):
-                policy.act(c["obs"], c["rows"], c["u"][0], c["act"], c["logp"], side)
+                policy.act(c["obs"], c["rows"], c["u"][0], c["act"], c["logp"], side, greedy=greedy)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         env.sync()
@@ -882,7 +916,7 @@ def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every):
         with torch.cuda.graph(g):
             cs = torch.cuda.current_stream()
             u = c["u"].index_select(0, c["i"]).squeeze(0)
-            policy.act(c["obs"], c["rows"], u, c["act"], c["logp"], cs)
+            policy.act(c["obs"], c["rows"], u, c["act"], c["logp"], cs, greedy=greedy)
             env.step_device(c["act"], c["rew"], c["done"], c["rows"], c["obs"], obs_rows, 2, cs.cuda_stream, auto_reset=True)
             c["i"].add_(1)
         c["graph"] = g
@@ -895,7 +929,8 @@ def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every):
     env.sync()
     for t0 in range(0, nsteps, sync_every):
         n = min(sync_every, nsteps - t0)
-        c["u"][:n].copy_(torch.rand((n, B), device=dev, generator=generator))
+        if not greedy:
+            c["u"][:n].copy_(torch.rand((n, B), device=dev, generator=generator))
         c["i"].zero_()
         for _ in range(n):
             c["graph"].replay()
@@ -909,3 +944,111 @@ def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every):
             raise
     d = env.stats() - st0
     return torch.tensor(-d[:, 1].astype(np.float64), device=dev), torch.tensor(d[:, 2], device=dev)
+
+
+def episode_returns(rewards, dones, carry=None):
+    """Per-episode returns and lengths from the [T, B] rewards (float64) and done flags (bool / uint8) of a rollout: one
+    return and one length per episode, what run_episodes logs (pg.py).  Per environment b, in step order: acc += r[t, b]
+    (a plain double add), len += 1; where dones[t, b] is set, ep_return[t, b] = acc, ep_len[t, b] = len and both start again
+    from zero; every other entry is 0.  Returns (ep_return float64 [T, B], ep_len int32 [T, B]).
+    carry: None (every environment starts a new episode at t = 0, what is left over at the end is dropped) or a tuple
+    (carry_return float64 [B], carry_len int32 [B], ep_count int32 [B] or None) of tensors on the device of `rewards`, updated
+    in place: an episode that spans calls is finished by a later one, ep_count gains the episodes finished here — a long
+    evaluation is a chain of chunks.
+    Tensors on the GPU: one kernel (bbx_episodes_device, one thread per environment).  CPU tensors (or numpy arrays): the
+    torch loop below, whose results the kernel reproduces exactly."""
+    rewards = torch.as_tensor(rewards)
+    dones = torch.as_tensor(dones)
+    if rewards.dim() != 2 or tuple(dones.shape) != tuple(rewards.shape):
+        raise ValueError("episode_returns: rewards and dones are [T, B] arrays of one shape (got %s and %s)" % (tuple(rewards.shape), tuple(dones.shape)))
+    T, B = rewards.shape
+    r = rewards.to(torch.float64).contiguous()
+    d = (dones if dones.dtype in (torch.bool, torch.uint8) else dones != 0).contiguous()
+    cret, clen, count = carry if carry is not None else (None, None, None)
+    ep_ret = torch.zeros((T, B), dtype=torch.float64, device=r.device)
+    ep_len = torch.zeros((T, B), dtype=torch.int32, device=r.device)
+    if r.is_cuda:
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        with torch.cuda.device(r.device):
+            _ffi.check(_ffi.lib().bbx_episodes_device(p(r), p(d), T, B, p(cret), p(clen), p(count), p(ep_ret), p(ep_len),
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return ep_ret, ep_len
+    acc = cret.clone() if cret is not None else torch.zeros(B, dtype=torch.float64)
+    ln = clen.clone() if clen is not None else torch.zeros(B, dtype=torch.int32)
+    for t in range(T):
+        acc = acc + r[t]
+        ln = ln + 1
+        dd = d[t].to(torch.bool)
+        ep_ret[t] = torch.where(dd, acc, torch.zeros_like(acc))
+        ep_len[t] = torch.where(dd, ln, torch.zeros_like(ln))
+        acc = torch.where(dd, torch.zeros_like(acc), acc)
+        ln = torch.where(dd, torch.zeros_like(ln), ln)
+        if count is not None:
+            count += dd.to(count.dtype)
+    if cret is not None:
+        cret.copy_(acc)
+    if clen is not None:
+        clen.copy_(ln)
+    return ep_ret, ep_len
+
+
+Evaluation = collections.namedtuple("Evaluation", ["returns", "lengths", "complete", "steps"])
+
+
+def evaluate_policy(env, policy, episodes, greedy=True, obs_rows=256, chunk=64, max_steps=None, generator=None):
+    """The first `episodes` episodes of every environment of `env` under `policy` (run_episodes(..., greedy=True) and
+    scripts/eval.py of the reference, for a whole batch): env.reset(), then chunks of `chunk` vector steps — the fused rollout
+    (run_rollout_fused) where the handle's kernel class has the policy built in, run_rollout's per-step path where it raises
+    BbxError -5; decided once, at the first chunk, before anything is stepped.  The environments simply keep stepping (auto-reset);
+    after each chunk bbx_episodes_device (episode_returns, with carries) turns the chunk's rewards and dones into per-episode
+    returns and lengths, and every finished episode whose ordinal within its environment is below `episodes` is scattered, on the
+    device, into
+        returns  float64 [B, episodes]      lengths  int32 [B, episodes].
+    Later episodes of faster environments are ignored: that is what keeps a batch stepping in lockstep from over-weighting short
+    episodes.  One host read per chunk (the smallest episode count); the loop ends when it reaches `episodes`, or at `max_steps`
+    vector steps — the result then has complete=False, with NaN / -1 in the entries no episode reached.
+    greedy=True takes the highest-probability pair at every step (no uniforms drawn); False samples (generator: torch's).
+    On a handle built from a LIST of ideals (environment e takes ideals e, e + B, e + 2B, ... in turn), returns[e, j] belongs to
+    ideal (e + j * B) % nideals.
+    Returns Evaluation(returns, lengths, complete, steps)."""
+    if episodes < 1 or chunk < 1:
+        raise ValueError("evaluate_policy: episodes and chunk must be positive")
+    B = env.batch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    env.reset()
+    buf = DeviceTrajectoryBuffer(chunk, B, device=dev)
+    # one spare column: where every entry that is not one of the first `episodes` finished episodes lands
+    returns = torch.full((B, episodes + 1), float("nan"), dtype=torch.float64, device=dev)
+    lengths = torch.full((B, episodes + 1), -1, dtype=torch.int32, device=dev)
+    cret = torch.zeros(B, dtype=torch.float64, device=dev)
+    clen = torch.zeros(B, dtype=torch.int32, device=dev)
+    count = torch.zeros(B, dtype=torch.int32, device=dev)
+    fused = None
+    steps, finished = 0, 0
+    while finished < episodes and (max_steps is None or steps < max_steps):
+        n = chunk if max_steps is None else min(chunk, max_steps - steps)
+        buf.t = 0
+        if fused is None:
+            try:
+                run_rollout_fused(env, policy, n, buffer=buf, obs_rows=obs_rows, generator=generator, chunk=n, greedy=greedy)
+                fused = True
+            except _ffi.BbxError as ex:                 # (refused before anything was queued: the class has no policy path)
+                if ex.code != -5:
+                    raise
+                fused = False
+                buf.t = 0
+                run_rollout(env, policy, n, buffer=buf, obs_rows=obs_rows, generator=generator, sync_every=n, greedy=greedy)
+        elif fused:
+            run_rollout_fused(env, policy, n, buffer=buf, obs_rows=obs_rows, generator=generator, chunk=n, greedy=greedy)
+        else:
+            run_rollout(env, policy, n, buffer=buf, obs_rows=obs_rows, generator=generator, sync_every=n, greedy=greedy)
+        d = buf.dones[:n]
+        before = count.clone()
+        ep_ret, ep_len = episode_returns(buf.rewards[:n], d, (cret, clen, count))
+        ordinal = before.to(torch.int64)[None, :] + torch.cumsum(d.to(torch.int64), dim=0) - 1
+        col = torch.where(d & (ordinal < episodes), ordinal, torch.full_like(ordinal, episodes)).t().contiguous()   # [B, n]
+        returns.scatter_(1, col, ep_ret.t().contiguous())
+        lengths.scatter_(1, col, ep_len.t().contiguous())
+        steps += n
+        finished = int(count.min())                     # the one host read of the chunk
+    return Evaluation(returns[:, :episodes].contiguous(), lengths[:, :episodes].contiguous(), finished >= episodes, steps)

@@ -423,6 +423,34 @@ int bbx_values_device(bbx_batch* b, const char* strategy, double gamma, const in
  * asynchronous on `stream`. */
 int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
                    double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream);
+/* Evaluation (run_episodes(..., greedy=True), pg.py; scripts/eval.py): the policy takes the row of the largest logit at every
+ * step instead of drawing one.
+ * The greedy forms of bbx_pmlp_act, bbx_pmlp2_act and bbx_pmlp3_act: the same arguments without d_u, the same shape refusals, the
+ * same row-count convention (n = clamp(d_rows[e], 0, min(obs_rows, BBX_POLICY_MAX_ROWS)); n == 0: action 0, log-probability 0),
+ * asynchronous on `stream`.  d_actions[e] = the smallest row whose logit equals the maximum bit for bit; d_logprobs[e] = its
+ * log-probability, from the sampler's reductions in the sampler's order: the same bits *_act and *_logprob give for that action. */
+int bbx_pmlp_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden,
+                        int32_t* d_actions, float* d_logprobs, void* stream);
+int bbx_pmlp2_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1,
+                         int hidden2, int32_t* d_actions, float* d_logprobs, void* stream);
+int bbx_pmlp3_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden1,
+                         int hidden2, int hidden3, int32_t* d_actions, float* d_logprobs, void* stream);
+/* A switch of the handle, like bbx_accounting: while it is on, bbx_policy_step_device, bbx_policy_rollout_device and
+ * bbx_policy2_rollout_device take the argmax (as the *_act_greedy calls do) and ignore d_u, which may then be NULL; where
+ * bbx_policy_step_device stands for two calls, the first is the greedy act.  Nothing else about those calls changes: same
+ * outputs, same auto-reset, same step loop.  The mode travels with each launch by value, so a recorded graph keeps the mode it
+ * was captured with.  A running persistent session or mailbox session is ended first.  Off when a handle is created. */
+int bbx_policy_greedy(bbx_batch* b, int enable);
+/* Per-episode returns and lengths from the [nsteps][batch] d_rewards and d_dones a rollout leaves on the device (one return and
+ * one length per episode: what run_episodes logs).  Per environment e: acc = d_carry_return[e], len = d_carry_len[e]; for
+ * t = 0 .. nsteps - 1: acc += r[t][e] (a plain double add, in step order), len += 1; where d_dones[t][e] is set:
+ * d_ep_return[t][e] = acc, d_ep_len[t][e] = len, d_ep_count[e] += 1, acc = len = 0; elsewhere d_ep_return[t][e] = 0.0 and
+ * d_ep_len[t][e] = 0.  The carries are written back, so a long evaluation is a chain of chunks.  NULL carries: start from zero,
+ * nothing written back; d_ep_count may be NULL.  nsteps == 0 is legal (nothing happens).  nsteps < 0, batch < 1, or NULL
+ * d_rewards / d_dones / d_ep_return / d_ep_len with nsteps > 0: BBX_E_ARG.  One kernel, one thread per environment; needs no
+ * handle; asynchronous on `stream`. */
+int bbx_episodes_device(const double* d_rewards, const uint8_t* d_dones, int nsteps, int batch, double* d_carry_return,
+                        int32_t* d_carry_len, int32_t* d_ep_count, double* d_ep_return, int32_t* d_ep_len, void* stream);
 /* obs_every_step != 0 materialises the observation in d_obs after every step (what a device-side policy
  * would consume), otherwise only the state at the end of the rollout is written */
 int bbx_rollout_device(bbx_batch* b, int agent, int nsteps, int auto_reset, double* d_rewards, uint8_t* d_dones,

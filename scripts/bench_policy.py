@@ -2,7 +2,7 @@
 log-softmax over the rows of the padded observation block + inverse-CDF draw] -> [bbx_step_device_autoreset: one step of
 every environment, next padded block] on the device; the host only enqueues kernels.
 
-    python scripts/bench_policy.py [--batch 4096] [--steps 2000] [--hidden 128] [--store]
+    python scripts/bench_policy.py [--batch 4096] [--steps 2000] [--hidden 128] [--store] [--greedy]
 """
 import argparse
 import json
@@ -31,6 +31,7 @@ ap.add_argument("--per-step", action="store_true", help="one library call per ve
                                                        "kernel (bbx_policy_rollout_device: --chunk steps per launch, policy inside the step loop)")
 ap.add_argument("--chunk", type=int, default=256)
 ap.add_argument("--store-states", action="store_true", help="--store plus the observation block of every step")
+ap.add_argument("--greedy", action="store_true", help="the highest-probability pair at every step instead of a draw (evaluation: no uniforms)")
 ap.add_argument("--no-persistent", action="store_true", help="--per-step: one kernel per call instead of calls that join a persistent session")
 a = ap.parse_args()
 hidden = [int(h) for h in str(a.hidden).split(",")]
@@ -48,8 +49,8 @@ if a.per_step and not a.no_persistent and not a.store and not a.store_states:
     env.persistent(True)      # (per-step outputs are then only final at sync(): nothing in this mode reads them in between)
 def go(nsteps, buf):
     if a.per_step:
-        return run_rollout(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, graph=a.graph)
-    return run_rollout_fused(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, chunk=a.chunk)
+        return run_rollout(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, graph=a.graph, greedy=a.greedy)
+    return run_rollout_fused(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, chunk=a.chunk, greedy=a.greedy)
 go(300, None)                                                      # steady state + warm-up
 st0 = env.stats()
 store = a.store or a.store_states
@@ -63,7 +64,7 @@ st = env.stats()
 d = st - st0
 assert (d[:, 0] == a.steps).all() and (st[:, 4] == 0).all()
 assert int(episodes.sum()) == int(d[:, 2].sum()) and float(total.sum()) == -float(d[:, 1].sum())
-print(json.dumps({"dist": a.dist, "batch": B, "steps": a.steps, "policy": "PMLP(%s)" % hidden,
+print(json.dumps({"dist": a.dist, "batch": B, "steps": a.steps, "policy": "PMLP(%s)" % hidden, "actions": "greedy" if a.greedy else "sampled",
                   "mode": ("policy kernel (bbx_pmlp%d_act) + bbx_step_device_autoreset per step" % len(hidden) if policy.deep_ok(env.cols) else
                            "torch ops + bbx_step_device_autoreset per step" + (", replayed from a HIP graph" if a.graph else "")) if len(hidden) > 1 and a.per_step else ("one call per step (bbx_policy_step_device)" + (", calls joining persistent sessions" if a.per_step and not a.no_persistent and not a.store and not a.store_states else "")) if a.per_step else "policy rollout kernel, %d steps per launch" % a.chunk,
                   "store": "trajectory + states" if a.store_states else ("trajectory" if a.store else "nothing"),
