@@ -953,20 +953,28 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     BTerm<2> h0, h1;
     int hsug, bytes;
     {
+      // every operand of the pair — lead monomial, tail monomial and working word of both members — is requested before
+      // anything waits for one of them: one LDS round trip on the step's critical path
       const M2 lmi = lm[gi_], lmj = lm[gj_];
       uint2 ii = gi[gi_], ij = gi[gj_];
-      // (both words of each entry are said to be needed whole: the reads then stay 8-byte reads that pair with the lead
-      // monomials' — one ds_read2st64_b64 per member — instead of four narrowed ones)
+      const M2 tmi = tm[gi_], tmj = tm[gj_];
+      // (both words of each entry are said to be needed whole: the reads then stay 8-byte reads, two ds_read_b64 next to the
+      // members' two ds_read2st64_b64 of lead and tail monomial, instead of four narrowed ones)
       asm volatile("" : "+v"(ii.x), "+v"(ii.y), "+v"(ij.x), "+v"(ij.y));
       const M2 gamma = m_lcm(lmi, lmj);
       const M2 si = m_div(gamma, lmi), sj = m_div(gamma, lmj);
       BTerm<2> a, b;
       // tc_i / lc_i and -tc_j / lc_j: halves of the working word, formed when the element entered (0: no tail)
-      a.c = ii.x & 0xffffu;   a.m = m_mul(tm[gi_], si);
-      b.c = ij.x >> 16;       b.m = m_mul(tm[gj_], sj);
+      a.c = ii.x & 0xffffu;   a.m = m_mul(tmi, si);
+      b.c = ij.x >> 16;       b.m = m_mul(tmj, sj);
       const int sgi = (int)(ii.y >> 16) + (int)m_deg(si), sgj = (int)(ij.y >> 16) + (int)m_deg(sj);
       hsug = uni(sgi > sgj ? sgi : sgj);
-      if (hsug > 65535) { status = BBX_ST_DEG_OVERFLOW; break; }
+      // A pair whose sugar is past the 16-bit bound is NOT refused here: a test with an exit in this place let the compiler
+      // sink the tail monomials' reads below it — a second, dependent LDS round trip in every step — and kept a flag word and
+      // a second branch for the same condition.  The test behind the reduction refuses the pair, and nothing persistent is
+      // written before it: with hsug past the bound the reduction leaves at its first divisor (FA_PICK; round_cpp's loop
+      // condition holds the bound), without a divisor it only moves the at most two terms of h into r, and the wrapped
+      // degree fields of an h that is thrown away harm nobody.
       merge2<2>(a, b, h0, h1);
       bytes = ACCT ? 12 * ((a.c ? 2 : 1) + (b.c ? 2 : 1) + (h0.c ? 1 : 0) + (h1.c ? 1 : 0)) : 0;
     }
