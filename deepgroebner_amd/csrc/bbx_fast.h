@@ -500,20 +500,27 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         }
       }
     }
-    int w = 0;
-    for (int base = 0; base < nP_old; base += WAVE) {
-      const int k = base + lane;
-      const bool valid = k < nP_old;
-      uint32_t pr; M2 li, lj;
-      if (base == 0) { pr = pr_first; li = li_first; lj = lj_first; }
-      else { pr = valid ? pairs[k] : 0u; li = lm[pr & 0xffffu]; lj = lm[pr >> 16]; }
+    auto stays = [&](uint32_t pr, const M2& li, const M2& lj, int k) {
       const uint32_t a0 = pk_max(li.w[0], lj.w[0]), a1 = pk_max(li.w[1], lj.w[1]);
       const uint32_t b0 = pk_max(li.w[0], f.w[0]), b1 = pk_max(li.w[1], f.w[1]);
       const uint32_t c0 = pk_max(lj.w[0], f.w[0]), c1 = pk_max(lj.w[1], f.w[1]);
       const bool fdiv = (pk_subsat(f.w[0], a0) | (pk_subsat(f.w[1], a1) & 0xffffu)) == 0;
       const bool eqi = ((a0 ^ b0) | ((a1 ^ b1) & 0xffffu)) == 0;
       const bool eqj = ((a0 ^ c0) | ((a1 ^ c1) & 0xffffu)) == 0;
-      const bool keep = valid && k != skip && !(fdiv && !eqi && !eqj);
+      return (k < nP_old) & (k != skip) & !(fdiv & !eqi & !eqj);   // (no short cut: nothing here is worth a branch around it)
+    };
+    // The first 64 old pairs come straight from the registers, and they are nearly always all there are: they are filtered
+    // and compacted without a loop around them, and only what lies beyond them (rare) goes through the loop, from LDS.  (As one
+    // loop whose first round took its operands from the registers, every insertion paid that loop's control, the selects
+    // between the two sources and the copies of five registers into the loop's: 23 instructions by the counters)
+    const bool keep_first = stays(pr_first, li_first, lj_first, lane);
+    const uint64_t mask_first = ballot64(keep_first);
+    if (keep_first) pairs[f_prefix(mask_first)] = pr_first;
+    int w = __popcll(mask_first);
+    for (int base = WAVE; base < nP_old; base += WAVE) {
+      const int k = base + lane;
+      const uint32_t pr = k < nP_old ? pairs[k] : 0u;
+      const bool keep = stays(pr, lm[pr & 0xffffu], lm[pr >> 16], k);
       const uint64_t mask = ballot64(keep);
       if (keep) pairs[w + f_prefix(mask)] = pr;
       w += __popcll(mask);

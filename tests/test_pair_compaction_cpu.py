@@ -1,0 +1,130 @@
+"""An insertion of the fast class filters and compacts the pair list in two parts: the first 64 old pairs straight from the
+register copy, without a loop around them, and whatever lies beyond them from LDS in a loop of its own; the new pairs (i, g)
+are appended behind the survivors.  tests/test_pair_compaction_gpu.py runs the headline shape on the seeds below; this file
+asserts, on the oracle alone, that each seed really shows the situation it stands for — old pairs dropped in front of the pair
+the next step selects, a selection among several new pairs, an insertion that appends nothing, lists beyond 64 pairs, a list
+that crosses 64 pairs upwards and one that comes back (seeds 3000 .. 4999 were searched, 320 steps each; fixed here: a seed
+that stops showing its case fails the test, it is never skipped).  A step t below is the insertion, the step that selects
+from the list it left is t + 1.
+Not found among those 2000 seeds: an insertion that takes the list across 64 pairs with the next action at or beyond 64 in the
+same step.  Its two halves are covered: cases `insertion_into_more_than_64_pairs` and `insertion_crosses_64_pairs` here, and
+`beyond_64_pairs_and_back` of tests/test_step_prefetch_cpu.py (a selection beyond the register copy)."""
+import functools
+
+import numpy as np
+
+from oracle import ffi
+from tests.test_step_events_cpu import agent_seeds
+from tests.test_step_prefetch_cpu import DIST, LAUNCHES, T
+
+# case -> seeds that show it (the GPU test runs the union as one batch)
+CASE_SEEDS = {
+    "drops_old_pairs_and_selects_behind_the_gap": (3000, 3001, 3002),
+    "selects_a_new_pair_that_is_not_the_first": (3000, 3001, 3002),
+    "insertion_emits_no_pair": (3008, 3014, 3032),
+    "insertion_into_more_than_64_pairs": (3097, 3167, 3295),
+    "insertion_crosses_64_pairs": (3097, 3167, 3295),
+    "insertion_back_to_64_pairs_or_fewer": (3344, 3598, 4151),
+}
+# steps the search reported, re-asserted below (a subset of what shows() finds)
+KNOWN_STEPS = {
+    ("drops_old_pairs_and_selects_behind_the_gap", 3000): (0, 11, 12),
+    ("selects_a_new_pair_that_is_not_the_first", 3000): (2, 3, 4),
+    ("insertion_emits_no_pair", 3008): (65,), ("insertion_emits_no_pair", 3014): (193,), ("insertion_emits_no_pair", 3032): (186,),
+    ("insertion_crosses_64_pairs", 3097): (66,), ("insertion_crosses_64_pairs", 3167): (231,), ("insertion_crosses_64_pairs", 3295): (65,),
+    ("insertion_back_to_64_pairs_or_fewer", 3344): (152,), ("insertion_back_to_64_pairs_or_fewer", 3598): (282,),
+    ("insertion_back_to_64_pairs_or_fewer", 4151): (184,),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def walk(seed, steps=T):
+    """The oracle under the hash agent with auto-reset.  Per step t: the row count it found (nP0) and left (nP1), whether it
+    inserted an element (ins), and for an insertion how many old pairs stay (kept), how many new pairs are appended (emitted),
+    how many of the kept ones stand in front of the first old pair that is dropped without being the selected one (gap; -1: no
+    such pair), and the action of step t + 1 on the list it left (nxt; -1: the episode ended)."""
+    bo = ffi.load("bo")
+    a = agent_seeds([seed])[0]
+    o = bo.env(DIST)
+    o.seed(seed)
+    o.reset()
+    rec = {k: np.full(steps, -1, dtype=np.int64) for k in ("nP0", "nP1", "ins", "kept", "emitted", "gap", "nxt")}
+    for t in range(steps):
+        old = [tuple(int(x) for x in p) for p in o.pairs()]
+        g = o.nG
+        act = ffi.agent_action(a, t, len(old))
+        o.step(act)
+        new = [tuple(int(x) for x in p) for p in o.pairs()]
+        rec["nP0"][t], rec["nP1"][t], rec["ins"][t] = len(old), len(new), int(o.nG == g + 1)
+        if new:
+            rec["nxt"][t] = ffi.agent_action(a, t + 1, len(new))
+        if o.nG == g + 1:
+            kept = [p for p in new if g not in p]
+            # (the update keeps the old pairs' order and appends the new ones: buchberger.cpp:70-98)
+            assert new[:len(kept)] == kept and all(p[1] == g for p in new[len(kept):])
+            stays, it = [], 0
+            for l, p in enumerate(old):
+                hit = l != act and it < len(kept) and kept[it] == p
+                stays.append(hit)
+                it += int(hit)
+            assert it == len(kept)
+            others = [l for l, s in enumerate(stays) if not s and l != act]
+            rec["kept"][t], rec["emitted"][t] = len(kept), len(new) - len(kept)
+            rec["gap"][t] = sum(stays[:others[0]]) if others else -1
+        if o.nP == 0:
+            o.reset()
+    return rec
+
+
+def shows(case, w):
+    """Steps t at which the walk `w` shows `case`."""
+    ins, live = w["ins"] == 1, w["nP1"] > 0
+    if case == "drops_old_pairs_and_selects_behind_the_gap":   # an OLD pair that moved by more than the selected one's slot
+        return np.flatnonzero(ins & live & (w["nP0"] <= 64) & (w["gap"] >= 0) & (w["nxt"] >= w["gap"]) & (w["nxt"] < w["kept"]))
+    if case == "selects_a_new_pair_that_is_not_the_first":     # a NEW pair, not the first of at least two
+        return np.flatnonzero(ins & (w["nP0"] <= 64) & (w["emitted"] >= 2) & (w["nxt"] > w["kept"]))
+    if case == "insertion_emits_no_pair":
+        return np.flatnonzero(ins & live & (w["emitted"] == 0))
+    if case == "insertion_into_more_than_64_pairs":            # the loop over what lies beyond the register copy runs
+        return np.flatnonzero(ins & (w["nP0"] > 64))
+    if case == "insertion_crosses_64_pairs":
+        return np.flatnonzero(ins & (w["nP0"] <= 64) & (w["nP1"] > 64))
+    if case == "insertion_back_to_64_pairs_or_fewer":
+        return np.flatnonzero(ins & live & (w["nP0"] > 64) & (w["nP1"] <= 64))
+    raise KeyError(case)
+
+
+def all_seeds():
+    return tuple(sorted({s for v in CASE_SEEDS.values() for s in v}))
+
+
+def test_every_case_has_seeds_that_show_it():
+    for case, seeds in CASE_SEEDS.items():
+        assert len(seeds) == 3
+        for s in seeds:
+            assert len(shows(case, walk(s))), (case, s)
+    for (case, s), steps in KNOWN_STEPS.items():
+        assert s in CASE_SEEDS[case] and set(steps) <= set(int(t) for t in shows(case, walk(s))), (case, s, shows(case, walk(s)))
+    assert 1 <= len(all_seeds()) <= 256
+
+
+def test_case_steps_fall_inside_the_launches():
+    """The GPU test chains launches of LAUNCHES steps: every case shows at a step that is not the last of a launch — the step
+    behind it is taken by the same kernel, from the register copy that kernel read back — on at least two of its seeds (seed
+    3008 emits no pair at step 65 only, the last step of the third launch: the next kernel stages the list from the record)."""
+    ends = set(int(x) for x in np.cumsum(LAUNCHES))
+    assert sum(LAUNCHES) == T
+    for case, seeds in CASE_SEEDS.items():
+        inside = [s for s in seeds if any(int(t) + 1 not in ends for t in shows(case, walk(s)))]
+        assert len(inside) >= 2, (case, inside)
+
+
+def test_dropping_old_pairs_is_common():
+    """The filter is no corner case: on these seeds a third of the insertions or more drop an old pair besides the selected
+    one."""
+    drops = total = 0
+    for s in all_seeds():
+        w = walk(s)
+        total += int((w["ins"] == 1).sum())
+        drops += int(((w["ins"] == 1) & (w["gap"] >= 0)).sum())
+    assert total > 1000 and 3 * drops >= total, (drops, total)
