@@ -158,6 +158,50 @@ int pmlp2_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_acti
                     d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
 }
 
+// ---- the critic (bbx_pmlp_value.h): values, their weight gradients, and the fit call — the forward body with the squared-error
+// epilogue, the statistics kernel, the gradient body on the coefficients the epilogue wrote.  The refusals of the policy's
+// training calls, in their order; everything either body would refuse is refused by the fit call first
+static_assert(BBX_POOL_SUM == PMLP_POOL_SUM && BBX_POOL_MEAN == PMLP_POOL_MEAN && BBX_POOL_LSE == PMLP_POOL_LSE, "include/bbx.h and bbx_pmlp_shape.h disagree");
+int refuse_pool(int pool) {
+  return pool < BBX_POOL_SUM || pool > BBX_POOL_LSE ? fail(BBX_E_ARG, "bad pool %d (0: sum, 1: mean, 2: log-sum-exp)", pool) : BBX_OK;
+}
+int pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+               int hidden, int pool, float* d_values, double* d_values64, void* stream, const PmlpFit* fit = nullptr) {
+  // (fit: the forward kernel of a fit call, which may leave both value outputs out)
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || (!d_values && !d_values64 && !fit))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  if (int rc = refuse_pool(pool)) return rc;
+  return launched(bbx_launch_pmlp_value(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, d_index, n_src, fit, (hipStream_t)stream));
+}
+int pmlp_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+                    int hidden, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_gvalue)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  if (int rc = refuse_pool(pool)) return rc;
+  return launched(bbx_launch_pmlp_value_grad(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
+                                             d_index, n_src, (hipStream_t)stream));
+}
+int fit_workspace(int n, int grad_floats) {
+  const int fl = pmlp_fit_workspace_floats(n, grad_floats);
+  return fl < 0 ? fail(BBX_E_ARG, "bad policy shape (n = %d: the workspace would not fit an int)", n) : fl;
+}
+int pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+                   int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace,
+                   float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
+  if (int rc = refuse_pool(pool)) return rc;
+  if (n > 0 && (!d_targets || !d_coef || !d_stats)) return fail(BBX_E_ARG, "null argument");
+  const int gfl = pmlp_grad_workspace_floats(n, cols, hidden);
+  if (fit_workspace(n, gfl) < 0) return BBX_E_ARG;
+  const PmlpFit fit{d_targets, d_coef, d_workspace + gfl, n, scale};
+  if (int rc = pmlp_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_values, nullptr, stream, &fit)) return rc;
+  if (d_stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, n, d_stats, (hipStream_t)stream))) return rc; }
+  return pmlp_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_coef, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+}
+
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
 int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
                    int nsteps, const float* d_u, int32_t* d_actions, float* d_logprobs, double* d_rewards, uint8_t* d_dones, int32_t* d_rows,
@@ -274,6 +318,45 @@ int bbx_pmlp_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int3
   return pmlp_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden,
                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
                   d_gw2, d_gb2, stream);
+}
+
+// ---- the critic: a pooled value of the row scores, its weight gradients, the squared-error fit (bbx_pmlp_value.h)
+int bbx_pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                   float* d_values, double* d_values64, void* stream) {
+  return pmlp_value(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, stream);
+}
+int bbx_pmlp_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                      const float* d_prepared, int hidden, int pool, float* d_values, double* d_values64, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, stream);
+}
+int bbx_pmlp_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) { return bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden); }
+int bbx_pmlp_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                        const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  return pmlp_value_grad(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+}
+int bbx_pmlp_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                           const float* d_prepared, int hidden, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1,
+                           float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+}
+int bbx_pmlp_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden) {
+  const int gfl = bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden);
+  return gfl < 0 ? gfl : fit_workspace(n, gfl);
+}
+int bbx_pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                       const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
+                       float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  return pmlp_value_fit(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_targets, scale, d_values, d_coef, d_stats, d_workspace,
+                        d_gw1, d_gb1, d_gw2, d_gb2, stream);
+}
+int bbx_pmlp_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                          const float* d_prepared, int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef,
+                          double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp_value_fit(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_targets, scale, d_values, d_coef, d_stats, d_workspace,
+                        d_gw1, d_gb1, d_gw2, d_gb2, stream);
 }
 
 // ---- two and three hidden layers (bbx_pmlp2.hip)

@@ -3,6 +3,7 @@
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 #include "bbx_pmlp_grad.h"
+#include "bbx_pmlp_value.h"
 #include "bbx_binom.h"
 
 extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream);
@@ -433,6 +434,53 @@ extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, con
 #undef BBX_PMLP_GRAD_AT
 #undef BBX_PMLP_GRAD
 #undef BBX_PMLP_GRAD_I
+  if (int rc = (int)hipGetLastError()) return rc;
+  hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
+  return (int)hipGetLastError();
+}
+// the critic (bbx_pmlp_value.h) over the same (NB, KS) table.  values of n positions (fit != null: with the squared-error epilogue)
+extern "C" int bbx_launch_pmlp_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
+                                     float* values, double* values64, const int32_t* index, int n_src, const PmlpFit* fit, hipStream_t stream) {
+  if (n <= 0) return 0;
+  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
+  const size_t ml = pmlp_lds_bytes(waves, obs_rows);
+  const PmlpFit ft = fit ? *fit : PmlpFit{};
+#define BBX_PMLP_VALUE_I(N, K, I, F) hipLaunchKernelGGL((bbx_pmlp_value_kernel<N, K, I, F>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                         n, obs_rows, cols, wp, pool, values, values64, index, n_src, ft)
+#define BBX_PMLP_VALUE(N, K) BBX_PMLP_VALUE_I(N, K, false, false)
+#define BBX_PMLP_VALUE_AT(N, K) BBX_PMLP_VALUE_I(N, K, true, false)
+#define BBX_PMLP_FIT(N, K) BBX_PMLP_VALUE_I(N, K, false, true)
+#define BBX_PMLP_FIT_AT(N, K) BBX_PMLP_VALUE_I(N, K, true, true)
+  if (fit) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_FIT_AT); else BBX_PMLP_SHAPES(BBX_PMLP_FIT); }
+  else if (index) BBX_PMLP_SHAPES(BBX_PMLP_VALUE_AT); else BBX_PMLP_SHAPES(BBX_PMLP_VALUE);
+#undef BBX_PMLP_FIT_AT
+#undef BBX_PMLP_FIT
+#undef BBX_PMLP_VALUE_AT
+#undef BBX_PMLP_VALUE
+#undef BBX_PMLP_VALUE_I
+  return (int)hipGetLastError();
+}
+// the statistics of a fit call from the tail its forward kernel wrote (n == 0: zeros)
+extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* stats, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_pmlp_value_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
+  return (int)hipGetLastError();
+}
+// the critic's weight gradients: bbx_launch_pmlp_grad's partition and second kernel
+extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
+                                          const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, const int32_t* index, int n_src,
+                                          hipStream_t stream) {
+  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
+  // (indexed with no recorded state at all: the kernel, which reads state 0 in place of an index out of range, is not launched)
+  const int nw = n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0, ng = nb / pmlp_grad_ubw(cols, hidden);
+  const size_t ml = pmlp_grad_lds_bytes(waves, obs_rows);
+#define BBX_PMLP_VGRAD_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_value_grad_kernel<N, K, I>), dim3((nw + waves - 1) / waves, ng), dim3(waves * WAVE), ml, stream, obs, \
+                                                      rows, n, obs_rows, cols, wp, pool, gvalue, nw, ws, index, n_src)
+#define BBX_PMLP_VGRAD(N, K) BBX_PMLP_VGRAD_I(N, K, false)
+#define BBX_PMLP_VGRAD_AT(N, K) BBX_PMLP_VGRAD_I(N, K, true)
+  if (nw > 0) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_VGRAD_AT); else BBX_PMLP_SHAPES(BBX_PMLP_VGRAD); }
+#undef BBX_PMLP_VGRAD_AT
+#undef BBX_PMLP_VGRAD
+#undef BBX_PMLP_VGRAD_I
   if (int rc = (int)hipGetLastError()) return rc;
   hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
   return (int)hipGetLastError();

@@ -44,6 +44,12 @@ extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats
 extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                     int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
                                     const int32_t* index, int n_src, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
+                                     float* values, double* values64, const int32_t* index, int n_src, const struct PmlpFit* fit, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* stats, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
+                                          const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, const int32_t* index, int n_src,
+                                          hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,

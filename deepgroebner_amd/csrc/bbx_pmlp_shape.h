@@ -91,6 +91,23 @@ BBX_HD constexpr int pmlp_ppo_workspace_floats(int n, int grad_floats) {
   return t > 0x7fffffffLL ? -1 : (int)t;
 }
 
+// ---- the critic (bbx_pmlp_value.h; bbx_pmlp_value / bbx_pmlp_value_grad / bbx_pmlp_value_fit of include/bbx.h): the one-layer
+// policy's weights and gradient partition, a pool over a state's row scores in place of the softmax (BBX_POOL_* of include/bbx.h)
+constexpr int PMLP_POOL_SUM = 0, PMLP_POOL_MEAN = 1, PMLP_POOL_LSE = 2;
+// what the forward kernel's fit epilogue reads and writes, all of length n and addressed by the position k of the call:
+// coef [n] = scale (V - target) (what the gradient kernel takes), tail [4n] = d^2 | V | target | flags (int32: PMLP_LOSS_COUNTED),
+// which lies in the call's workspace behind the gradient kernel's partial sums and is what the statistics kernel adds up
+struct PmlpFit {
+  const float* targets; float* coef; float* tail;
+  int n;
+  float scale;
+};
+constexpr int PMLP_FIT_TAIL = 4;                  // floats per position behind the gradient workspace
+BBX_HD constexpr int pmlp_fit_workspace_floats(int n, int grad_floats) {   // -1: more than an int holds
+  const long long t = (long long)grad_floats + (long long)PMLP_FIT_TAIL * n;
+  return t > 0x7fffffffLL ? -1 : (int)t;
+}
+
 // ---- the policies built into the step kernels
 // a rollout with one hidden layer, step kernels of W-word monomials (bbx_binom_policy_kernel; 8-byte monomials with 3 variables
 // and k = 2 also bbx_fast_policy_rollout_kernel): 33..128 hidden units, 6 k-steps, or 10 with 16-byte monomials

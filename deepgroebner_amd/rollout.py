@@ -8,6 +8,9 @@ device, replacing the per-step host round trip of the reference's agents.
                                kernels read the recorded states where the rollout left them (bbx_pmlp_logprob_at / bbx_pmlp_grad_at)
     PMLPPolicy.ppo_step_at, ppo_update   one minibatch of the update — forward, PPO loss, statistics, weight gradients — in one library
                                call (bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at), and the epochs around it     pg.py _fit_policy_model
+    PMLPValue, fill_values, value_update   a learned baseline (--value_model mlp, pg.py _fit_value_model): a critic over the recorded
+                               state blocks — one launch for a whole buffer's values after the rollout (bbx_pmlp_value), one library
+                               call per minibatch of the squared-error fit (bbx_pmlp_value_fit_at); run_rollout_fused(critic=...)
     run_rollout                PGAgent.run_episode(s)                 pg.py:451-503   (one library call per vector step)
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
@@ -573,6 +576,315 @@ class PMLPPolicy(torch.nn.Module):
         return out_a, out_l
 
 
+class _PMLPValueEvaluate(torch.autograd.Function):
+    """The values of a one-hidden-layer PMLPValue through bbx_pmlp_value, differentiable with respect to the four parameter tensors
+    through bbx_pmlp_value_grad (the hidden activations are recomputed there).  No gradient for states or rows.
+    index (int32 [n], optional): as in _PMLPEvaluate — states and rows are whole buffers read in place (bbx_pmlp_value_at /
+    bbx_pmlp_value_grad_at), the output has length n."""
+
+    @staticmethod
+    def forward(ctx, critic, states, rows, w1, b1, w2, b2, index=None):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
+        values = torch.empty(N, dtype=torch.float32, device=states.device)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(states.device):
+            w = critic._fused_weights()
+            # (the prepared buffer is refilled in place when the weights change: backward reads THIS forward pass's weights from a
+            # copy of its own, made on the stream behind the fill)
+            prep = w["keep"].clone()
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
+            fn = _ffi.lib().bbx_pmlp_value if index is None else _ffi.lib().bbx_pmlp_value_at
+            _ffi.check(fn(*src, p(prep), w["hidden"], critic.pool_id, p(values), None, s))
+        ctx.critic, ctx.prep, ctx.hidden, ctx.pool = critic, prep, w["hidden"], critic.pool_id
+        ctx.save_for_backward(states, rows, w1, b1, w2, b2, index)
+        return values
+
+    @staticmethod
+    def backward(ctx, gvalue):
+        states, rows, w1, b1, w2, b2, index = ctx.saved_tensors
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
+        hidden = ctx.hidden
+        dev = states.device
+        gvalue = gvalue.contiguous().float()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        gw1, gb1, gw2, gb2 = new(cols, hidden), new(hidden), new(hidden), new(1)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            ws = ctx.critic._workspace("grad", N, R, cols, hidden, dev)
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
+            fn = _ffi.lib().bbx_pmlp_value_grad if index is None else _ffi.lib().bbx_pmlp_value_grad_at
+            _ffi.check(fn(*src, p(ctx.prep), hidden, ctx.pool, p(gvalue), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), s))
+        return None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype), None
+
+
+class PMLPValue(torch.nn.Module):
+    """A learned value baseline (critic) over the observation block: the row embedding of PMLPPolicy (`embedding`, relu), one
+    linear unit per row (`head`), and a pool over a state's live rows in place of the softmax:
+        pool="sum"   V = sum_r z_r        pool="mean"   V = that sum / n        pool="lse"   V = log sum_r exp z_r
+    A state without live rows is worth 0.  One hidden layer of at most 256 units over at most 64 columns, float32 on the GPU: the
+    HIP kernels (bbx_pmlp_value / bbx_pmlp_value_grad / bbx_pmlp_value_fit and their _at forms, which read a trajectory buffer in
+    place); CPU tensors, more hidden layers or wider ones: the torch path (forward, values_torch, evaluate_torch).  `last_path`
+    names the path the last call took ("kernels" or "torch")."""
+
+    POOLS = {"sum": 0, "mean": 1, "lse": 2}                           # BBX_POOL_* of include/bbx.h
+
+    def __init__(self, cols, hidden_layers=(128,), pool="sum"):
+        super().__init__()
+        if pool not in self.POOLS:
+            raise ValueError("PMLPValue: pool is one of %s (got %r)" % (sorted(self.POOLS), pool))
+        dims = [cols] + list(hidden_layers)
+        self.embedding = torch.nn.ModuleList([torch.nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:])])
+        self.head = torch.nn.Linear(dims[-1], 1)
+        self.cols, self.pool, self.pool_id = cols, pool, self.POOLS[pool]
+        self.last_path = None
+
+    # ---- the torch path
+    def _scores(self, batch):
+        x = batch.to(self.head.weight.dtype)
+        for layer in self.embedding:
+            x = torch.relu(layer(x))
+        return self.head(x).squeeze(-1)
+
+    def evaluate_torch(self, states, rows=None):
+        """Values float [N] of states int [N, R, cols] with torch ops and autograd (any depth, any device; the baseline of the
+        kernels).  rows [N]: the live rows per state (None: those whose last column is not -1)."""
+        self.last_path = "torch"
+        N, R, _ = states.shape
+        if rows is None:
+            live = states[:, :, -1] != -1
+        else:                                                         # (the count masks, whatever the rows beyond it hold)
+            live = torch.arange(R, device=states.device)[None, :] < torch.clamp(rows.to(torch.int64), 0, R)[:, None]
+        z = self._scores(states)
+        n = live.sum(1)
+        zero = torch.zeros_like(z)
+        if self.pool == "lse":
+            v = torch.logsumexp(torch.where(live, z, torch.full_like(z, -1e9)), dim=1)
+        else:
+            v = torch.where(live, z, zero).sum(dim=1)
+            if self.pool == "mean":
+                v = v / torch.clamp(n, min=1).to(v.dtype)
+        return torch.where(n > 0, v, torch.zeros_like(v))
+
+    def forward(self, batch):
+        """int [B, R, cols] with -1 padding -> values [B]."""
+        return self.evaluate_torch(batch)
+
+    @torch.no_grad()
+    def values_torch(self, states, rows=None, out=None, out64=None):
+        R, cols = states.shape[-2:]
+        v = self.evaluate_torch(states.reshape(-1, R, cols), None if rows is None else rows.reshape(-1))
+        return self._deliver(v, out, out64)
+
+    @staticmethod
+    def _deliver(v, out, out64):
+        if out64 is not None:
+            out64.view(-1).copy_(v.to(torch.float64))
+        if out is not None:
+            out.view(-1).copy_(v)
+        return out if out is not None else (out64 if out64 is not None else v)
+
+    # ---- the kernels
+    def kernels_ok(self, states):
+        """Whether the HIP kernels take states [..., R, cols] with this module's weights (otherwise: the torch path)."""
+        R, cols = states.shape[-2:]
+        lin = self.embedding[0]
+        return (states.is_cuda and len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
+                and PMLPPolicy.fused_ok(cols, lin.out_features) and 1 <= R <= 2048)
+
+    def _in_place(self, states, rows):
+        """Whether the _at kernels can read states [..., R, cols] and rows where they lie (contiguous int32 CUDA tensors of
+        matching sizes): a buffer is never converted or copied as a whole."""
+        R, cols = states.shape[-2:]
+        return (self.kernels_ok(states) and states.numel() == rows.numel() * R * cols
+                and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows)))
+
+    def _fused_weights(self):
+        """The kernels' view of the weights (bbx_pmlp_prepare, the one-layer policy's layout), rebuilt only when a parameter
+        changed (an optimiser step bumps the tensors' version counters), in the same buffer."""
+        if len(self.embedding) != 1:
+            raise ValueError("_fused_weights: the kernels take one hidden layer (this critic has %d)" % len(self.embedding))
+        lin = self.embedding[0]
+        key = tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
+        c = self.__dict__.get("_fused_cache")
+        if c is None or c["key"] != key:
+            cols, hidden = lin.in_features, lin.out_features
+            w1 = lin.weight.detach().t().contiguous().float()
+            b1 = lin.bias.detach().contiguous().float()
+            w2 = self.head.weight.detach().reshape(-1).contiguous().float()
+            nfl = _ffi.lib().bbx_pmlp_prepared_floats(cols, hidden)
+            _ffi.check(min(nfl, 0))
+            prep = c["keep"] if c is not None and c["keep"].numel() == nfl and c["keep"].device == w1.device else \
+                torch.empty(nfl, dtype=torch.float32, device=w1.device)
+            # (b2 travels by value in the C call; reading it back would make every optimiser step wait for the device: the call gets
+            # 0 and the bias is copied on the device into its place, the first of the layout's last four floats)
+            _ffi.check(_ffi.lib().bbx_pmlp_prepare(C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
+                                                   C.c_float(0.0), cols, hidden, C.c_void_p(prep.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            prep[nfl - 4:nfl - 3].copy_(self.head.bias.detach().reshape(1))
+            c = {"key": key, "keep": prep, "prepared": C.c_void_p(prep.data_ptr()), "hidden": hidden}
+            self.__dict__["_fused_cache"] = c
+        return c
+
+    def _workspace(self, kind, N, R, cols, hidden, device):
+        """The workspace of bbx_pmlp_value_grad ("grad") / bbx_pmlp_value_fit ("fit"), kept between calls (it grows only; calls on
+        one stream run in order)."""
+        lib = _ffi.lib()
+        nfl = (lib.bbx_pmlp_value_fit_workspace_floats if kind == "fit" else lib.bbx_pmlp_value_grad_workspace_floats)(N, R, cols, hidden)
+        _ffi.check(min(nfl, 0))
+        ws = self.__dict__.get("_ws")
+        if ws is None or ws.numel() < nfl or ws.device != device:
+            ws = torch.empty(nfl, dtype=torch.float32, device=device)
+            self.__dict__["_ws"] = ws
+        return ws
+
+    @staticmethod
+    def _row_counts(states, rows):
+        return (states[:, :, -1] != -1).sum(1).to(torch.int32) if rows is None else rows
+
+    def _value_call(self, states, rows, index, out, out64):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
+        dev = states.device
+        if out is None and out64 is None:
+            out = torch.empty(N, dtype=torch.float32, device=dev)
+        for o, dt in ((out, torch.float32), (out64, torch.float64)):
+            if o is not None and not (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() == N):
+                raise ValueError("PMLPValue.values: out / out64 are contiguous float32 / float64 CUDA tensors of %d elements" % N)
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+        with torch.cuda.device(dev):
+            w = self._fused_weights()
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
+            fn = _ffi.lib().bbx_pmlp_value if index is None else _ffi.lib().bbx_pmlp_value_at
+            _ffi.check(fn(*src, w["prepared"], w["hidden"], self.pool_id, p(out), p(out64), s))
+        self.last_path = "kernels"
+        return out if out is not None else out64
+
+    @torch.no_grad()
+    def values(self, states, rows, out=None, out64=None):
+        """Values of states int [..., R, cols] with rows [...] live rows each, no autograd: float32 into `out` and / or the same
+        numbers widened into `out64` (float64: what DeviceTrajectoryBuffer.values holds), each of rows.numel() elements; neither:
+        a new float32 tensor.  Returns out (out64 where only that was given).  On the GPU under kernels_ok: one bbx_pmlp_value
+        call, over the tensors in place where they are contiguous int32; otherwise values_torch."""
+        if not self.kernels_ok(states):
+            return self.values_torch(states, rows, out, out64)
+        R, cols = states.shape[-2:]
+        st = (states if states.dtype == torch.int32 else states.to(torch.int32)).contiguous()
+        rw = self._row_counts(st.view(-1, R, cols), None if rows is None else rows.reshape(-1)).to(torch.int32).contiguous()
+        return self._value_call(st, rw, None, out, out64)
+
+    @torch.no_grad()
+    def values_at(self, states, rows, index, out=None, out64=None):
+        """values() of the recorded states index[k] of the buffers states [S, R, cols] or [T, B, R, cols] and rows, read in place
+        (bbx_pmlp_value_at; an index outside the buffer: NaN); where the kernels cannot read them in place the n states are
+        gathered."""
+        if self._in_place(states, rows):
+            return self._value_call(states, rows, index.to(device=states.device, dtype=torch.int32).contiguous(), out, out64)
+        st, rw = self._gather(states, rows, index)
+        return self.values(st, rw, out, out64)
+
+    @staticmethod
+    def _gather(states, rows, index):
+        R, cols = states.shape[-2:]
+        j = index.to(device=states.device, dtype=torch.int64)
+        if states.dim() == 4:                                         # (no reshape: a non-contiguous buffer would be copied whole)
+            t, b = j // states.shape[1], j % states.shape[1]
+            return states[t, b], rows[t, b]
+        return states[j], rows[j]
+
+    def evaluate(self, states, rows=None):
+        """Values float32 [N] of states int [N, R, cols], differentiable with respect to the module's parameters: under kernels_ok
+        bbx_pmlp_value forward and bbx_pmlp_value_grad backward; otherwise evaluate_torch."""
+        if not self.kernels_ok(states):
+            return self.evaluate_torch(states, rows)
+        rows = self._row_counts(states, rows).to(torch.int32).contiguous()
+        st = states if states.dtype == torch.int32 else states.to(torch.int32)
+        self.last_path = "kernels"
+        lin = self.embedding[0]
+        return _PMLPValueEvaluate.apply(self, st.contiguous(), rows, lin.weight, lin.bias, self.head.weight, self.head.bias)
+
+    def evaluate_at(self, states, rows, index):
+        """evaluate() of the recorded states index[k] without gathering them (bbx_pmlp_value_at / bbx_pmlp_value_grad_at), as
+        PMLPPolicy.evaluate_at; where the kernels cannot read the buffers in place the n states are gathered."""
+        if self._in_place(states, rows):
+            self.last_path = "kernels"
+            lin = self.embedding[0]
+            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
+            return _PMLPValueEvaluate.apply(self, states, rows, lin.weight, lin.bias, self.head.weight, self.head.bias, idx)
+        return self.evaluate(*self._gather(states, rows, index))
+
+    def fit_step_at(self, states, rows, index, targets):
+        """One minibatch of the squared-error fit in one library call (bbx_pmlp_value_fit_at): from the recorded states index[k] of
+        the buffers states / rows and the targets [n] to the gradients of
+            L = 1/2 mean_k (V_k - target_k)^2
+        ADDED to the parameters' .grad as loss.backward() would.  Returns (stats float64 [6] on the device: counted positions,
+        sum d^2, sum V, sum target, sum target^2, positions not counted; values float32 [n]) — nothing is read back, nothing waits.
+        Where the kernels cannot read the buffers in place: fit_step on the gathered states."""
+        if self._in_place(states, rows):
+            return self._fit_kernels(states, rows, index.to(device=states.device, dtype=torch.int32).contiguous(), targets)
+        st, rw = self._gather(states, rows, index)
+        return self.fit_step(st, rw, targets)
+
+    def fit_step(self, states, rows, targets):
+        """fit_step_at for gathered tensors: states int [N, R, cols], rows [N] (None: the rows whose last column is not -1) —
+        bbx_pmlp_value_fit under kernels_ok; otherwise the same formulae with torch ops and backward()."""
+        if self.kernels_ok(states):
+            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
+            st = states if states.dtype == torch.int32 else states.to(torch.int32)
+            return self._fit_kernels(st.contiguous(), rows, None, targets)
+        v = self.evaluate_torch(states, rows)
+        n = v.numel()
+        t = targets.to(device=v.device, dtype=v.dtype)
+        d = v - t
+        if n:
+            loss = 0.5 * (d * d).sum() / n
+            if loss.requires_grad:
+                loss.backward()
+        s = lambda x: x.detach().to(torch.float64).sum()
+        zero = torch.zeros((), dtype=torch.float64, device=v.device)
+        stats = torch.stack([zero + n, s(d * d), s(v), s(t), s(t * t), zero])
+        return stats, v.detach()
+
+    def _fit_kernels(self, states, rows, index, targets):
+        R, cols = states.shape[-2:]
+        S = rows.numel()
+        N = S if index is None else index.numel()
+        dev = states.device
+        tg = targets.to(device=dev, dtype=torch.float32).contiguous()
+        if tg.numel() != N:
+            raise ValueError("fit_step: %d positions, %d targets" % (N, tg.numel()))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        values, coef = new(N), new(N)
+        stats = torch.empty(6, dtype=torch.float64, device=dev)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        lib = _ffi.lib()
+        with torch.cuda.device(dev):
+            w = self._fused_weights()
+            hidden = w["hidden"]
+            grads = [new(cols, hidden), new(hidden), new(hidden), new(1)]
+            ws = self._workspace("fit", N, R, cols, hidden, dev)
+            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
+            fn = lib.bbx_pmlp_value_fit if index is None else lib.bbx_pmlp_value_fit_at
+            _ffi.check(fn(*src, w["prepared"], hidden, self.pool_id, p(tg), C.c_float(1.0 / N if N else 0.0), p(values), p(coef), p(stats), p(ws),
+                          *[p(g) for g in grads], s))
+        self.last_path = "kernels"
+        lin = self.embedding[0]
+        for q, g in zip((lin.weight, lin.bias, self.head.weight, self.head.bias), (grads[0].t(), grads[1], grads[2].view(1, -1), grads[3])):
+            if q.grad is None:
+                q.grad = g.contiguous()
+            else:
+                q.grad.add_(g)
+        return stats, values
+
+
 class DeviceTrajectoryBuffer:
     """TrajectoryBuffer (pg.py:79-240) for a batch of environments stepping in lockstep, kept on the device: per step the
     -1-padded state block [B, R, cols] (optional), action, reward, log-probability, value and done flag of every
@@ -602,6 +914,20 @@ class DeviceTrajectoryBuffer:
         if value is not None:
             self.values[t].copy_(value)
         self.t += 1
+
+    def fill_values(self, critic, t0=0, t1=None):
+        """self.values[t0:t1] (t1 None: the steps stored so far) <- the critic's values of the stored states, float64: a learned
+        baseline for GAE after a rollout that recorded none (run_rollout_fused).  On the device one bbx_pmlp_value call over the
+        block in place (PMLPValue.values with out64); CPU buffers take the critic's torch path.  returns / advantages / complete
+        are cleared, so that the next get_index() finishes again.  A buffer that keeps no states: ValueError."""
+        if self.states is None:
+            raise ValueError("fill_values: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
+        t1 = self.t if t1 is None else t1
+        if not 0 <= t0 <= t1 <= self.T:
+            raise IndexError("fill_values: steps [%d, %d) of a buffer of %d" % (t0, t1, self.T))
+        if t1 > t0:
+            critic.values(self.states[t0:t1], self.rows[t0:t1], out64=self.values[t0:t1])
+        self.returns = self.advantages = self.complete = None
 
     def finish(self):
         """Reverse scan over time with episode boundaries: ret_t = r_t + gam ret_{t+1}; delta_t = r_t - v_t + gam v_{t+1};
@@ -742,9 +1068,44 @@ def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef
     return out
 
 
+def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, generator=None):
+    """The counterpart of ppo_update for a PMLPValue critic (pg.py _fit_value_model): `epochs` passes over buffer.get_index()'s steps
+    in minibatches of batch_size, the targets its fifth element (the discounted returns) — per epoch ONE permutation of the index
+    list (shuffle; from `generator`, which lives on the buffer's device), per minibatch one critic.fit_step_at on the buffers as the
+    rollout left them, then optimizer.step() and optimizer.zero_grad(); the optimiser is the caller's.  One host read per epoch: the
+    minibatches' stacked statistics.  Returns one dict per epoch: "stats" (float64 [minibatches, 6], fit_step_at's), and over the
+    epoch's counted positions "loss" (1/2 mean (V - target)^2, each minibatch under the weights it saw) and "explained_variance"
+    (1 - mean (V - target)^2 / var(target); NaN where the targets do not vary)."""
+    if buffer.states is None:
+        raise ValueError("value_update: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
+    idx, _, _, _, ret = buffer.get_index(None)
+    n = int(idx.numel())
+    out = []
+    optimizer.zero_grad()
+    for _ in range(epochs):
+        if shuffle:
+            perm = torch.randperm(n, device=idx.device, generator=generator)
+            e_idx, e_ret = idx[perm], ret[perm]
+        else:
+            e_idx, e_ret = idx, ret
+        stats = []
+        for i in range(0, n, batch_size):
+            k = min(i + batch_size, n)
+            st, _ = critic.fit_step_at(buffer.states, buffer.rows, e_idx[i:k], e_ret[i:k])
+            optimizer.step()
+            optimizer.zero_grad()
+            stats.append(st)
+        st = torch.stack(stats).cpu().numpy() if stats else np.zeros((0, 6))     # the epoch's one host read
+        tot = st.sum(axis=0) if len(st) else np.zeros(6)
+        cnt = max(tot[0], 1.0)
+        var = tot[4] / cnt - (tot[3] / cnt) ** 2
+        out.append({"stats": st, "loss": 0.5 * tot[1] / cnt, "explained_variance": 1.0 - (tot[1] / cnt) / var if var > 0 else float("nan")})
+    return out
+
+
 @_with_gc_paused
 @torch.no_grad()
-def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False):
+def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False, critic=None):
     """run_rollout with the policy INSIDE the step kernel: `chunk` vector steps per launch, environments never wait for each
     other between steps.  One hidden layer: bbx_policy_rollout_device; two hidden layers of at most 128 units:
     bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
@@ -752,11 +1113,17 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
     trajectory buffer's own arrays (no copies).  Raises BbxError (BBX_E_UNSUPPORTED) where the batch's kernel class has no
     built-in policy — callers fall back to run_rollout.  There is no value_strategy here (run_rollout has it): baseline
     values inside the T-step policy kernels would need a rollout to completion nested in the kernels' step loop — a different
-    piece of work.  Returns (total reward per environment, finished episodes) like
+    piece of work; a LEARNED baseline is what `critic` is for.  Returns (total reward per environment, finished episodes) like
     run_rollout.  The rollout kernels are the lean ones (no algorithmic-byte accounting): the handle's accounting is switched
     off here.
     greedy=True: the highest-probability pair at every step (env.policy_greedy for the duration of the call, restored
-    afterwards); no uniforms are drawn."""
+    afterwards); no uniforms are drawn.
+    critic (a PMLPValue; needs a buffer that keeps states): after the last chunk buffer.fill_values(critic, ...) writes the
+    critic's values of the steps recorded here into buffer.values — one launch over the recorded block, nothing per step; the
+    rollout itself is the one without a critic, draw for draw.  None: buffer.values is left as it is.  A critic without a
+    state-keeping buffer: ValueError before anything is queued."""
+    if critic is not None and (buffer is None or buffer.states is None):
+        raise ValueError("run_rollout_fused: a critic reads the recorded states (buffer=DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
     B, cols = env.batch, env.cols
     depth = len(policy.embedding)
     if not (depth == 1 or (depth == 2 and policy.deep_ok(cols))):
@@ -784,6 +1151,7 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
             raise IndexError("trajectory buffer holds %d steps, %d are stored already: no room for %d more" % (buffer.T, buffer.t, nsteps))
         if keep_states and tuple(buffer.states.shape[2:]) != (obs_rows, cols):
             raise ValueError("buffer.states has blocks of %s, the environment writes (%d, %d)" % (tuple(buffer.states.shape[2:]), obs_rows, cols))
+    t_start = buffer.t if buffer is not None else 0
     was_greedy = env.policy_greedy(greedy)
     try:
         for t0 in range(0, nsteps, chunk):
@@ -802,6 +1170,8 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
             env.sync()
     finally:
         env.policy_greedy(was_greedy)
+    if critic is not None:
+        buffer.fill_values(critic, t_start, buffer.t)
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)
     episodes = torch.tensor(d[:, 2], device=dev)

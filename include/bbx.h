@@ -352,6 +352,57 @@ int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int
                           const float* d_advantages, int mode, float scale, float eps, float ent_coef, float c_kl, float* d_logprobs,
                           float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
                           float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+/* A learned value baseline (critic) over recorded states: ONE hidden layer with exactly the parameters, layouts and prepared
+ * weights of the one-layer policy (bbx_pmlp_prepare, unchanged) and the shapes of bbx_pmlp_logprob (cols <= 64, hidden <= 256,
+ * obs_rows <= BBX_POLICY_MAX_ROWS).  The row score z_r = w2 . relu(W1^T x_r + b1) + b2 comes from the policy kernels' tile code
+ * (for the same block and weights: the same bits as their logits); the live rows are n_s = clamp(d_rows[s], 0, min(obs_rows, 2048));
+ * the value is V(s) = pool over the live rows of z_r, float32:
+ *   BBX_POOL_SUM   lane t of the state's wave adds z_t, z_{t+64}, ... in increasing row order from 0.f, the 64 lanes are then added
+ *                  in the fixed order of the policy kernels' wave sum.             dV/dz_r = 1
+ *   BBX_POOL_MEAN  that sum divided by (float)n_s (an IEEE division).             dV/dz_r = 1 / (float)n_s   (g_r = g / (float)n_s)
+ *   BBX_POOL_LSE   the log-partition of the policy kernels (max + log sum exp, their order and fast exp / log).
+ *                  g_r = g * (exp(z_r - max) * (1.f / se)): the probability expression of bbx_pmlp_grad.
+ *   n_s <= 0: V = 0.0f and no gradient (a finished state is worth nothing: what GAE assumes behind a done flag).  A state with ONE
+ *   live row contributes to the gradients like any other (bbx_pmlp_grad skips such states; these calls do not).  Rows beyond the
+ *   live rows play no part, whether they hold -1 padding or anything else.
+ * Every convention of bbx_pmlp_logprob[_at] / bbx_pmlp_grad[_at] / bbx_pmlp_ppo_grad[_at] holds word for word: no handle,
+ * asynchronous on `stream`, no allocation, no read-back, 64-bit offsets, refusals before anything is queued and without a device
+ * (BBX_E_UNSUPPORTED for shapes; BBX_E_ARG for a pool outside 0..2 and the NULLs named here), n == 0 legal (gradients zeroed, stats
+ * zeros), outputs overwritten, deterministic (no floating-point atomics; the partition depends on the shape and n alone); _at:
+ * position k is about recorded state d_index[k] of n_src, repeated indices count every time, an index outside [0, n_src) gives NaN at
+ * its position, reads nothing at that index and contributes nothing to any gradient.
+ * bbx_pmlp_value[_at]: d_values [n] float and d_values64 [n] (the same number widened: the [nsteps][batch] double array
+ *   bbx_gae_device reads can be filled directly) — either may be NULL, both NULL with n > 0: BBX_E_ARG.
+ * bbx_pmlp_value_grad[_at]: the gradients of L = sum_k d_gvalue[k] V_k in the layouts bbx_pmlp_prepare reads; d_workspace holds
+ *   bbx_pmlp_value_grad_workspace_floats(n, ...) = bbx_pmlp_grad_workspace_floats(n, ...) floats (the policy gradient's partition
+ *   and second kernel).  A state without live rows or an index out of range: its d_gvalue is not read.
+ * bbx_pmlp_value_fit[_at]: one call per minibatch of the squared-error fit, L = scale 1/2 sum_k d_k^2.  Per position, in float32
+ *   and in this order, no fused multiply-adds:   d = V - target   u = d * d   coef = scale * d.   d_coef [n] receives coef; THE
+ *   GRADIENTS ARE, BIT FOR BIT, THOSE OF bbx_pmlp_value_grad[_at] CALLED WITH d_gvalue = d_coef; d_values (may be NULL) is, bit for
+ *   bit, that of bbx_pmlp_value[_at].  A NaN value (an index out of range): coef = 0, left out of every sum.  A state without live
+ *   rows counts, with V = 0.  d_stats, double [6]: counted positions, sum d^2, sum V, sum target, sum target^2 (the float32 product),
+ *   positions not counted — in double over the float32 terms, by one workgroup in the thread, lane and wave order of the PPO
+ *   statistics.  (loss = scale stats[1] / 2; explained variance = 1 - (stats[1] / c) / (stats[4] / c - (stats[3] / c)^2), c = stats[0].)
+ *   d_workspace holds bbx_pmlp_value_fit_workspace_floats(n, ...) floats (16-byte aligned): the gradient workspace, then
+ *   d^2 | V | target | flags, n each.  d_targets, d_coef or d_stats NULL with n > 0: BBX_E_ARG. */
+enum { BBX_POOL_SUM = 0, BBX_POOL_MEAN = 1, BBX_POOL_LSE = 2 };
+int bbx_pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                   float* d_values, double* d_values64, void* stream);
+int bbx_pmlp_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                      const float* d_prepared, int hidden, int pool, float* d_values, double* d_values64, void* stream);
+int bbx_pmlp_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden);   /* < 0: shape not supported */
+int bbx_pmlp_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                        const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                           const float* d_prepared, int hidden, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1,
+                           float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden);   /* < 0: shape not supported */
+int bbx_pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
+                       const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
+                       float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                          const float* d_prepared, int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef,
+                          double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
 /* ... and for three hidden layers (hidden_layers=[hidden1, hidden2, hidden3], each <= 128): the same kernel with a middle layer
  * whose output stays in registers as the next layer's B operands; d_w3 [hidden2][hidden3], d_b3 [hidden3], d_w4 [hidden3],
  * d_b4 [1].  All three layers are padded to the widest one's tile size (64 or 128 units). */
