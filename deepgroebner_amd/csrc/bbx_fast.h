@@ -102,12 +102,40 @@ __device__ __forceinline__ uint64_t f_lowmask(int n) { return n >= 64 ? ~0ull : 
 // and 15:14, expcnt = 7 and lgkmcnt = 15 left alone.)  It only ever ADDS a wait: the compiler's own stay where they are.
 __device__ __forceinline__ void f_loads_landed() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
-// shift-insert `nv` at position p (0..63) of a 64-lane register array; returns the element shifted out of lane 63
-__device__ __forceinline__ uint32_t f_insert(uint32_t& arr, uint32_t nv, int p, int lane) {
-  uint32_t out = f_readlane(arr, 63);
-  uint32_t sh = f_wave_shr(arr);
-  arr = lane > p ? sh : (lane == p ? nv : arr);
-  return out;
+// shift-insert the wave-uniform words nv[0..5] at lane p (0..63, wave-uniform) of six 64-lane register arrays, in place: the
+// lanes from p on take their lower neighbour's word (a DPP move executed by those lanes alone: lane p is among them because
+// a DPP source lane that exec leaves out counts as invalid, and a lane with an invalid source is not written), then lane p
+// takes the new word.
+// Two vector instructions per array on the array's own register — old and new state are one register, so nothing is
+// selected or built in a temporary — and four scalar ones for all six.  (A new word the compiler holds in a vector register
+// — it is the same in every lane — is moved from there: v_mov_b32 takes either.)
+// The block REPLACES exec by its own masks and puts the incoming one back: only for code every lane of the wave runs
+// (wave-uniform control flow, as add_poly's), and volatile, so that it is never sunk or duplicated into a masked region.  (In-place DPP: every lane's source is read
+// before any lane is written.  Wait states: the arrays may have been written by the instruction in front of the block — two
+// states before a DPP reads them, which the two scalar moves in front provide; exec written by the scalar unit needs none.)
+__device__ __forceinline__ void f_insert6(uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3, uint32_t& a4, uint32_t& a5,
+                                          const uint32_t (&nv)[6], int p) {
+  const uint64_t at = 1ull << p, from = ~f_lowmask(p);
+  uint64_t all;
+  asm volatile("s_mov_b64 %[all], exec\n\t"
+      "s_mov_b64 exec, %[from]\n\t"
+      "v_mov_b32_dpp %[a0], %[a0] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %[a1], %[a1] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %[a2], %[a2] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %[a3], %[a3] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %[a4], %[a4] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32_dpp %[a5], %[a5] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+      "s_mov_b64 exec, %[at]\n\t"
+      "v_mov_b32 %[a0], %[n0]\n\t"
+      "v_mov_b32 %[a1], %[n1]\n\t"
+      "v_mov_b32 %[a2], %[n2]\n\t"
+      "v_mov_b32 %[a3], %[n3]\n\t"
+      "v_mov_b32 %[a4], %[n4]\n\t"
+      "v_mov_b32 %[a5], %[n5]\n\t"
+      "s_mov_b64 exec, %[all]"
+      : [a0] "+v"(a0), [a1] "+v"(a1), [a2] "+v"(a2), [a3] "+v"(a3), [a4] "+v"(a4), [a5] "+v"(a5), [all] "=&s"(all)
+      : [n0] "s"(nv[0]), [n1] "s"(nv[1]), [n2] "s"(nv[2]), [n3] "s"(nv[3]), [n4] "s"(nv[4]), [n5] "s"(nv[5]),
+        [at] "s"(at), [from] "s"(from));
 }
 // shift the whole array up by one, `carry` enters lane 0; returns the element shifted out of lane 63
 __device__ __forceinline__ uint32_t f_shift_in(uint32_t& arr, uint32_t carry, int lane) {
@@ -562,12 +590,15 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       if (!(OVF && BK > FRB) || pos < 64 * FRB) {
         const int pb = RB == 1 ? 0 : pos >> 6, q = RB == 1 ? pos : pos & 63;
         uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0;
+        const uint32_t nv[6] = {f.w[0], f.w[1], tail.w[0], tail.w[1], ns.x, ns.y};
         f_banks<RB>([&](auto b_) {
           constexpr int b = decltype(b_)::value;
           if (RB == 1 || pb == b) {
-            c0 = f_insert(S.slm[b].w[0], f.w[0], q, lane); c1 = f_insert(S.slm[b].w[1], f.w[1], q, lane);
-            c2 = f_insert(S.stm[b].w[0], tail.w[0], q, lane); c3 = f_insert(S.stm[b].w[1], tail.w[1], q, lane);
-            c4 = f_insert(S.sin[b].x, ns.x, q, lane); c5 = f_insert(S.sin[b].y, ns.y, q, lane);
+            if constexpr (b + 1 < RB) {                        // (what falls out of lane 63 enters the next bank)
+              c0 = f_readlane(S.slm[b].w[0], 63); c1 = f_readlane(S.slm[b].w[1], 63); c2 = f_readlane(S.stm[b].w[0], 63);
+              c3 = f_readlane(S.stm[b].w[1], 63); c4 = f_readlane(S.sin[b].x, 63); c5 = f_readlane(S.sin[b].y, 63);
+            }
+            f_insert6(S.slm[b].w[0], S.slm[b].w[1], S.stm[b].w[0], S.stm[b].w[1], S.sin[b].x, S.sin[b].y, nv, q);
           } else if (b > 0 && pb < b && g >= 64 * b) {
             c0 = f_shift_in(S.slm[b].w[0], c0, lane); c1 = f_shift_in(S.slm[b].w[1], c1, lane);
             c2 = f_shift_in(S.stm[b].w[0], c2, lane); c3 = f_shift_in(S.stm[b].w[1], c3, lane);
@@ -982,7 +1013,11 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       // written before it: with hsug past the bound the reduction leaves at its first divisor (FA_PICK; round_cpp's loop
       // condition holds the bound), without a divisor it only moves the at most two terms of h into r, and the wrapped
       // degree fields of an h that is thrown away harm nobody.
-      merge2<2>(a, b, h0, h1);
+      // The two terms are put in order (polynomials.cpp:148-177 on single optional terms: the grevlex-larger leads, equal
+      // monomials add up, a zero sum drops the term) by merge2 in the accounting variants, whose byte count needs the merged
+      // coefficients.  The lean variants hand them over as they are: every lane holds the same six words, and the reduction
+      // loop's assembly owns this very operation in scalar form (FA_ORDER below) — 21 vector instructions less per step.
+      if constexpr (ACCT) merge2<2>(a, b, h0, h1); else { h0 = a; h1 = b; }
       bytes = ACCT ? 12 * ((a.c ? 2 : 1) + (b.c ? 2 : 1) + (h0.c ? 1 : 0) + (h1.c ? 1 : 0)) : 0;
     }
 
@@ -1121,7 +1156,39 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         "s_cbranch_vccz " NEXT "_%=\n\t" \
         FA_PICK(P) \
         "s_branch L_red_%=\n\t"
+      // (h0, h1) put in order: the new lead term against the old tail term (polynomials.cpp:148-177 on single optional terms).
+      // Twice in the block: in front of the loop it orders the S-polynomial's two scaled tails as they come (N = "0", falling
+      // through into the loop top: nothing is counted as a reduction), behind L_red the new term of a reduction round.
+#define FA_ORDER(N, LAST) \
+        "s_cmp_eq_u32 %[h0c], 0\n\t" \
+        "s_cbranch_scc1 L_shift" N "_%=\n\t" \
+        "s_cmp_eq_u32 %[h1c], 0\n\t" \
+        "s_cbranch_scc1 L_top_%=\n\t" \
+        "s_xor_b32 %[sxx], %[h1b], 0xffff\n\t"           /* grevlex keys: high word ^ 0xffff, low word complemented */ \
+        "s_xor_b32 %[sq], %[h0b], 0xffff\n\t" \
+        "s_cmp_lt_u32 %[sxx], %[sq]\n\t" \
+        "s_cbranch_scc1 L_top_%=\n\t"                     /* the new term leads: nothing moves */ \
+        "s_cmp_eq_u32 %[sxx], %[sq]\n\t" \
+        "s_cbranch_scc0 L_swap" N "_%=\n\t" \
+        "s_cmp_lt_u32 %[h1a], %[h0a]\n\t" \
+        "s_cbranch_scc1 L_swap" N "_%=\n\t" \
+        "s_cmp_eq_u32 %[h1a], %[h0a]\n\t" \
+        "s_cbranch_scc0 L_top_%=\n\t" \
+        "s_add_u32 %[sxx], %[h0c], %[h1c]\n\t"            /* equal monomials: one term, coefficients added mod p */ \
+        "s_add_u32 %[sq], %[sxx], 0xffff82fd\n\t" \
+        "s_min_u32 %[h0c], %[sxx], %[sq]\n\t" \
+        "s_mov_b32 %[h1c], 0\n\t" \
+        "s_branch L_top_%=\n\t" \
+        "L_swap" N "_%=:\n\t"                                  /* the old tail leads */ \
+        "s_mov_b32 %[sxx], %[h0c]\n\t" "s_mov_b32 %[h0c], %[h1c]\n\t" "s_mov_b32 %[h1c], %[sxx]\n\t" \
+        "s_mov_b32 %[sxx], %[h0a]\n\t" "s_mov_b32 %[h0a], %[h1a]\n\t" "s_mov_b32 %[h1a], %[sxx]\n\t" \
+        "s_mov_b32 %[sxx], %[h0b]\n\t" "s_mov_b32 %[h0b], %[h1b]\n\t" "s_mov_b32 %[h1b], %[sxx]\n\t" \
+        "s_branch L_top_%=\n\t" \
+        "L_shift" N "_%=:\n\t"                                 /* the new term vanished (a reducer without tail): h <- its tail term */ \
+        "s_mov_b32 %[h0c], %[h1c]\n\t" "s_mov_b32 %[h0a], %[h1a]\n\t" "s_mov_b32 %[h0b], %[h1b]\n\t" "s_mov_b32 %[h1c], 0\n\t" \
+        LAST
 #define FA_HEAD(NEXT) \
+        FA_ORDER("0", "") \
         "L_top_%=:\n\t" \
         "s_cmp_eq_u32 %[h0c], 0\n\t" \
         "s_cbranch_scc1 L_done_%=\n\t" \
@@ -1136,33 +1203,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         "s_mul_i32 %[sq], %[sq], 0x7d03\n\t" \
         "s_sub_u32 %[h0c], %[sxx], %[sq]\n\t" \
         "s_add_u32 %[nred], %[nred], 1\n\t" \
-        "s_cmp_eq_u32 %[h0c], 0\n\t" \
-        "s_cbranch_scc1 L_shift_%=\n\t" \
-        "s_cmp_eq_u32 %[h1c], 0\n\t" \
-        "s_cbranch_scc1 L_top_%=\n\t" \
-        "s_xor_b32 %[sxx], %[h1b], 0xffff\n\t"           /* grevlex keys: high word ^ 0xffff, low word complemented */ \
-        "s_xor_b32 %[sq], %[h0b], 0xffff\n\t" \
-        "s_cmp_lt_u32 %[sxx], %[sq]\n\t" \
-        "s_cbranch_scc1 L_top_%=\n\t"                     /* the new term leads: nothing moves */ \
-        "s_cmp_eq_u32 %[sxx], %[sq]\n\t" \
-        "s_cbranch_scc0 L_swap_%=\n\t" \
-        "s_cmp_lt_u32 %[h1a], %[h0a]\n\t" \
-        "s_cbranch_scc1 L_swap_%=\n\t" \
-        "s_cmp_eq_u32 %[h1a], %[h0a]\n\t" \
-        "s_cbranch_scc0 L_top_%=\n\t" \
-        "s_add_u32 %[sxx], %[h0c], %[h1c]\n\t"            /* equal monomials: one term, coefficients added mod p */ \
-        "s_add_u32 %[sq], %[sxx], 0xffff82fd\n\t" \
-        "s_min_u32 %[h0c], %[sxx], %[sq]\n\t" \
-        "s_mov_b32 %[h1c], 0\n\t" \
-        "s_branch L_top_%=\n\t" \
-        "L_swap_%=:\n\t"                                  /* the old tail leads */ \
-        "s_mov_b32 %[sxx], %[h0c]\n\t" "s_mov_b32 %[h0c], %[h1c]\n\t" "s_mov_b32 %[h1c], %[sxx]\n\t" \
-        "s_mov_b32 %[sxx], %[h0a]\n\t" "s_mov_b32 %[h0a], %[h1a]\n\t" "s_mov_b32 %[h1a], %[sxx]\n\t" \
-        "s_mov_b32 %[sxx], %[h0b]\n\t" "s_mov_b32 %[h0b], %[h1b]\n\t" "s_mov_b32 %[h1b], %[sxx]\n\t" \
-        "s_branch L_top_%=\n\t" \
-        "L_shift_%=:\n\t"                                 /* the new term vanished (a reducer without tail): h <- its tail term */ \
-        "s_mov_b32 %[h0c], %[h1c]\n\t" "s_mov_b32 %[h0a], %[h1a]\n\t" "s_mov_b32 %[h0b], %[h1b]\n\t" "s_mov_b32 %[h1c], 0\n\t" \
-        "s_branch L_top_%=\n\t"
+        FA_ORDER("", "s_branch L_top_%=\n\t")
 #define FA_TAIL \
         "L_tm_%=:\n\t"                                    /* r <- r + LT h ; h <- h - LT h */ \
         "s_cmp_eq_u32 %[r0c], 0\n\t" \
@@ -1206,6 +1247,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
 #undef FA_PICK
 #undef FA_TRY
 #undef FA_HEAD
+#undef FA_ORDER
 #undef FA_TAIL
 #undef FA_OUTS
 #undef FA_BANK
