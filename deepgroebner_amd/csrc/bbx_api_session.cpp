@@ -50,14 +50,21 @@ int ps_write_ctl(bbx_batch* b, bool stop) {              // all writes to the co
   return BBX_OK;
 }
 
+// What is queued on the session stream from here on runs behind the last write to the control word that travelled on the
+// control stream (a join's new total, the stop).  (A mailbox session's word is written by the host, not on a stream.)
+int ps_behind_ctl(bbx_batch* b) {
+  if (b->ps_mbox) return BBX_OK;
+  HIPCHK(hipEventRecord(b->ps_ev, b->ps_ctl_stream));
+  HIPCHK(hipStreamWaitEvent(b->ps_stream, b->ps_ev, 0));
+  return BBX_OK;
+}
+
 // Queue a kernel of the session on its stream: the first one (every environment starts with the steps issued so far) or a
-// later one (every environment takes what it still owes of the total), behind the last write to the control word and
-// behind what the caller queued on `after` (or null).  `sliced`: it leaves when its time slice is over.
+// later one (every environment takes what it still owes of the total), behind what the caller queued on `after` (or null).
+// `sliced`: it leaves when its time slice is over.  The caller has ordered the stream behind the control word's last write
+// where there was one since the stream's last kernel (ps_behind_ctl: a join, the stop; a session's initial value is written
+// on the session stream itself, launch_session_begin).
 int session_kernel(bbx_batch* b, bool first, hipStream_t after, bool sliced, bool behind_after) {
-  if (!b->ps_mbox) {                                       // (a mailbox session's control word is written by the host, not on a stream)
-    HIPCHK(hipEventRecord(b->ps_ev, b->ps_ctl_stream));
-    HIPCHK(hipStreamWaitEvent(b->ps_stream, b->ps_ev, 0));
-  }
   if (behind_after) {                                      // (`after` may be the NULL stream: the session stream does not wait for it by itself)
     HIPCHK(hipEventRecord(b->ps_ev, after));
     HIPCHK(hipStreamWaitEvent(b->ps_stream, b->ps_ev, 0));
@@ -87,6 +94,7 @@ int session_close(bbx_batch* b, bool wait, hipStream_t then, bool sliced) {
   if (!b->ps_active) return BBX_OK;
   b->ps_active = false;
   int rc = ps_write_ctl(b, true);
+  if (!rc) rc = ps_behind_ctl(b);                          // once, for every closing kernel queued below
   if (rc) return rc;
   if (!sliced) {
     // The host will not be there to start the next kernel when a slice ends, and ONE kernel without time limit would keep
@@ -171,7 +179,11 @@ static int launch_session_join(bbx_batch* b, const BbxParams& p, hipStream_t str
   if (rc) return rc;
   start_flight(b, p, b->ps_stream, obs_external, true);
   // the session's kernel may have left meanwhile (its slice was over, or no news for 20 ms): the next one
-  if (hipStreamQuery(b->ps_stream) == hipSuccess) { rc = session_kernel(b, false, stream, true, true); if (rc) return rc; }
+  if (hipStreamQuery(b->ps_stream) == hipSuccess) {
+    rc = ps_behind_ctl(b);
+    if (!rc) rc = session_kernel(b, false, stream, true, true);
+    if (rc) return rc;
+  }
   b->ps_joined++;
   return BBX_OK;
 }
@@ -183,13 +195,14 @@ static int launch_session_begin(bbx_batch* b, const BbxParams& p, hipStream_t st
   // The control word is the handle's, not the session's: the kernels that close the PREVIOUS session (queued on the session
   // stream, possibly not yet run) still poll it, and a new total written now would be theirs to take — steps of this session
   // under the last one's agent and buffers (found by scripts/fuzz_sessions.py: two calls of different shapes back to back).
-  // The write therefore waits for everything queued on the session stream so far.
-  if (!b->ps_mbox) {
-    HIPCHK(hipEventRecord(b->ps_ev, b->ps_stream));
-    HIPCHK(hipStreamWaitEvent(b->ps_ctl_stream, b->ps_ev, 0));
-  }
-  int rc = ps_write_ctl(b, false);
-  if (rc) return rc;
+  // The write therefore runs behind everything queued on the session stream so far: ON that stream, directly in front of the
+  // session's first kernel, which then starts behind one kernel boundary and the caller's event instead of a hop through the
+  // control stream and back while the device idles.  The control stream waits for the write (an event recorded behind it, off
+  // the first kernel's path): the totals of later calls and the stop stay ordered behind the initial value.
+  int lrc = bbx_launch_ctl(b->d_ctl, (unsigned long long)b->ps_target, b->ps_stream);
+  if (lrc) return fail(BBX_E_DEVICE, "control launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  HIPCHK(hipEventRecord(b->ps_ev, b->ps_stream));
+  HIPCHK(hipStreamWaitEvent(b->ps_ctl_stream, b->ps_ev, 0));
   start_flight(b, p, b->ps_stream, obs_external, true);
   return session_kernel(b, true, stream, true, true);
 }

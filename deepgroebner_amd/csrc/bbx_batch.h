@@ -269,6 +269,7 @@ void start_flight(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs
 void continue_session(bbx_batch* b);
 int ensure_session_streams(bbx_batch* b);
 int ps_write_ctl(bbx_batch* b, bool stop);
+int ps_behind_ctl(bbx_batch* b);                                         // the session stream waits for the control word's last write
 int session_kernel(bbx_batch* b, bool first, hipStream_t after, bool sliced, bool behind_after = false);   // behind_after: ordered behind what `after` (possibly the NULL stream) holds
 int session_close(bbx_batch* b, bool wait, hipStream_t then, bool sliced);
 bool session_same_call(const BbxParams& a, const BbxParams& c);

@@ -74,6 +74,20 @@ static inline BBX_HD bool bbx_pass_has_work(int st, int need_reset, int budget, 
 // environment stepped without auto-reset stays done)
 static inline BBX_HD int bbx_done_flag(int done_last, int nP, int need_reset) { return (done_last || (nP == 0 && !need_reset)) ? 1 : 0; }
 
+// The user priority (s_setprio, 0..3) of a wave of the register/LDS-resident step kernels (fast_body, bbx_fast.h): a slot of
+// 2^BBX_PRIO_TICK_SHIFT ticks of the 100 MHz clock every wave reads alike (its low 32 bits: 2^32 is a whole number of cycles of
+// four slots, the wrap is no seam), offset by the wave's rank among those it shares a SIMD with.  At any tick the four ranks
+// hold the four priorities, and over a cycle of four slots every rank holds each priority for one slot
+// (tests/prio_phase_check.cpp).  The slot length is held between two demands that pull apart: several looks long (a wave looks
+// every 64 steps, ~10.5 k ticks — until its next look it keeps the last slot's priority, which another wave may hold by then)
+// and short enough that a launch of 1024 steps (~200 k ticks) holds a whole cycle.  Measured (profiles/r17_bench_ab.txt, plain
+// bench.py against the rotation keyed on steps): shift 13 -1.9 %, 14 -0.1 %, 15 +1.5 %.
+#ifndef BBX_PRIO_TICK_SHIFT
+#define BBX_PRIO_TICK_SHIFT 15
+#endif
+static_assert(BBX_PRIO_TICK_SHIFT >= 0 && BBX_PRIO_TICK_SHIFT <= 30, "2^32 ticks must hold a whole number of cycles of four slots");
+static inline BBX_HD int bbx_prio_phase(uint32_t ticks, int rank) { return (int)(((ticks >> BBX_PRIO_TICK_SHIFT) + (uint32_t)rank) & 3u); }
+
 // The status block ("lite"): what every step kernel leaves per environment and the host reads after every launch.
 //   word0   bits 0..15 the status (BBX_ST_*), bit 16 BBX_LITE_OBS_TRUNC (BbxHdr.obs_trunc != 0), bits 17.. a sequence number
 //   budget  the steps still owed; BBX_LITE_GONE on top of it once a mailbox session's wave has left

@@ -270,6 +270,40 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   int pol_t0 = 0;                                      // POL + PERSIST: agent step counter minus session step, fixed for the kernel
   if (POL > 0 && PERSIST) { int vz_; asm volatile("v_mov_b32 %0, 0" : "=v"(vz_)); pol_t0 = vz_ + (t_agent - (p.set_budget ? 0 : uni(ghdr->sess_done))); }
   if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget_in > 0 && nP > 0)))) return;
+  // A later kernel of a session (those that close it, as a rule) whose environment owes nothing and has been told to stop: the
+  // wave would stage the record, meet the stop at its first loop top, write the observation of the state it found once more
+  // and store everything back as it was.  It leaves from here instead, storing what that path changes or may change: the
+  // header words below, dones / rows and the status block — field by field the write-back at the end of this function for a
+  // wave that took no step; record arrays, reward and observation block hold those values already.  Only
+  // where the status AS FOUND is OK (a transient one, mapped to OK above, has an exit behind it that wrote no observation),
+  // no reset is due, the record fits the class (else: the hand-over below) and the control word, read as the poll reads
+  // it, carries the stop bit and no total beyond the steps taken.  Without the stop bit the wave stays and polls: the kernel
+  // a joining call starts must not leave the session idle.
+  if constexpr (PERSIST) {
+    if (p.sess_target && !p.set_budget && !p.mbox && uni(ghdr->status) == BBX_ST_OK && !need_reset && budget_in <= 0 &&
+        nG <= (p.lim_G < FG ? p.lim_G : FG) && nP <= (p.lim_P < FP ? p.lim_P : FP)) {
+      const unsigned long long w = __hip_atomic_load(p.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (uni((int)(uint32_t)w) <= uni(ghdr->sess_done) && (uni((int)(uint32_t)(w >> 32)) & 1)) {
+        if (lane == 0) {
+          const int done_last = done_in ? 1 : 0;
+          const int trunc_all = ghdr->obs_trunc | ((POL == 0 && p.obs && nP > p.obs_rows) ? 1 : 0);
+          ghdr->arena_used = 0; ghdr->steps_done = 0; ghdr->budget = budget_in; ghdr->done_last = done_last; ghdr->obs_trunc = trunc_all;
+          if (p.dones) p.dones[env] = (uint8_t)bbx_done_flag(done_last, nP, 0);
+          if (p.rows) p.rows[env] = nP;
+          if (p.lite) {
+            int32_t* lw = p.lite + 4 * (size_t)env;
+            const int word0 = bbx_lite_word0(BBX_ST_OK, trunc_all, p.done_seq);
+            if (p.done_seq) {                              // (the store forms of bbx_common.h, BbxLite)
+              lw[1] = q_head; lw[2] = budget_in; lw[3] = nP;
+              __threadfence_system();
+              __hip_atomic_store(lw, word0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            } else *(int4*)lw = make_int4(word0, q_head, budget_in, nP);
+          }
+        }
+        return;
+      }
+    }
+  }
   // The steps still owed are not counted down: t_stop is the agent step count at which the issued steps are exhausted (what
   // is owed = t_stop - t_agent, formed in the loop's slow path and at the write-back), and t_event the count at which the
   // loop top has something other than a plain step to do: the smaller of t_stop and the next multiple of 64, or t_agent
@@ -837,17 +871,22 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       if ((t_agent & 63) == 0 && t_agent != uni(t_entry)) {
         hv = bbx_agent_hash32(agent_seed, (uint32_t)(t_agent + lane));
         bool slice_over = false;
+        const uint32_t ticks = (uint32_t)__builtin_amdgcn_s_memrealtime();   // (100 MHz, the same for every wave of the device)
         if constexpr (PERSIST) {                           // the time slice (see BBX_ST_TIMESLICE): 64 steps are ~0.2 ms of a 10 ms slice
           const uint32_t lim = f_cold_params()->slice_ticks;
-          slice_over = lim && (uint32_t)__builtin_amdgcn_s_memrealtime() - t_begin > lim;
+          slice_over = lim && ticks - t_begin > lim;
         }
 #ifndef BBX_NO_PRIO_ROTATION
         // The instruction arbiter serves the OLDEST wave first, and this kernel is bound by the one scalar unit its waves share:
         // left alone, the waves of the workgroups dispatched first run at 2.1 us per step and those dispatched last at 3.8,
         // so every launch ends with a phase in which only the starved quarter is left, too few waves to fill the unit.
-        // Rotating the user priority (which ranks above age) every 2^BBX_PRIO_SHIFT steps, offset by the workgroup's quarter of
-        // the grid, gives every wave of a SIMD the same share over time: all finish together.  (s_setprio takes an immediate.)
-        switch (((t_agent >> BBX_PRIO_SHIFT) + (env >> 10)) & 3) {
+        // The user priority (which ranks above age) therefore rotates, offset by the workgroup's quarter of the grid — the four
+        // waves of a SIMD come from the four quarters.  The slot is a stretch of TIME (bbx_prio_phase, bbx_common.h), looked up
+        // here every 2^BBX_PRIO_SHIFT steps: every wave reads the same clock, so the four hold four different priorities at any
+        // moment (but for the lag of one look) however far they have drifted apart in steps, and age never decides.  Keyed on
+        // the wave's own step count, as it was, waves that had drifted apart spent part of the time at EQUAL priority, where the
+        // older one wins again.  (s_setprio takes an immediate.)
+        switch (bbx_prio_phase(ticks, env >> 10)) {
           case 0: __builtin_amdgcn_s_setprio(0); break;
           case 1: __builtin_amdgcn_s_setprio(1); break;
           case 2: __builtin_amdgcn_s_setprio(2); break;
