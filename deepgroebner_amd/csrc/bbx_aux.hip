@@ -386,31 +386,29 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
 #undef BBX_PMLP_MFMA
   return (int)hipGetLastError();
 }
-// log-probability / entropy of recorded actions and the weight gradients (bbx_pmlp_grad.h); BBX_PMLP_SHAPES(M): M(NB, KS) of the shape.
-// index != null: the indexed instantiations (position k is about recorded state index[k] of n_src)
-#define BBX_PMLP_SHAPES_K(M, N) do { if (ks == 3) M(N, 3); else if (ks == 6) M(N, 6); else if (ks == 10) M(N, 10); else if (ks == 16) M(N, 16); else M(N, 32); } while (0)
-#define BBX_PMLP_SHAPES(M) do { if (nb == 1) BBX_PMLP_SHAPES_K(M, 1); else if (nb == 2) BBX_PMLP_SHAPES_K(M, 2); else if (nb == 4) BBX_PMLP_SHAPES_K(M, 4); \
-                                else BBX_PMLP_SHAPES_K(M, 8); } while (0)
+// log-probability / entropy of recorded actions, the weight gradients (bbx_pmlp_grad.h) and the critic (bbx_pmlp_value.h), all over
+// the same (NB, KS) table.  BBX_PMLP_DISPATCH(M): M(NB, KS, IDX, EPI) of the shape (`nb`, `ks`), of `index` (non-null: the
+// indexed instantiations, position k is about recorded state index[k] of n_src) and of `epi` (the forward kernels' epilogue:
+// LOSS or FIT; the gradient kernels have none and their M ignores it)
+#define BBX_PMLP_DISPATCH_IE(M, N, K) do { if (index) { if (epi) M(N, K, true, true); else M(N, K, true, false); } \
+                                           else if (epi) M(N, K, false, true); else M(N, K, false, false); } while (0)
+#define BBX_PMLP_DISPATCH_K(M, N) do { if (ks == 3) BBX_PMLP_DISPATCH_IE(M, N, 3); else if (ks == 6) BBX_PMLP_DISPATCH_IE(M, N, 6); \
+                                       else if (ks == 10) BBX_PMLP_DISPATCH_IE(M, N, 10); else if (ks == 16) BBX_PMLP_DISPATCH_IE(M, N, 16); \
+                                       else BBX_PMLP_DISPATCH_IE(M, N, 32); } while (0)
+#define BBX_PMLP_DISPATCH(M) do { if (nb == 1) BBX_PMLP_DISPATCH_K(M, 1); else if (nb == 2) BBX_PMLP_DISPATCH_K(M, 2); \
+                                  else if (nb == 4) BBX_PMLP_DISPATCH_K(M, 4); else BBX_PMLP_DISPATCH_K(M, 8); } while (0)
 extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                        int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss,
                                        hipStream_t stream) {
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
+  const bool epi = loss != nullptr;
   const PmlpLoss ls = loss ? *loss : PmlpLoss{};
-#define BBX_PMLP_LOGPROB_I(N, K, I, L) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I, L>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                           actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src, ls)
-#define BBX_PMLP_LOGPROB(N, K) BBX_PMLP_LOGPROB_I(N, K, false, false)
-#define BBX_PMLP_LOGPROB_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true, false)
-#define BBX_PMLP_LOSS(N, K) BBX_PMLP_LOGPROB_I(N, K, false, true)
-#define BBX_PMLP_LOSS_AT(N, K) BBX_PMLP_LOGPROB_I(N, K, true, true)
-  if (loss) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOSS_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOSS); }
-  else if (index) BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB_AT); else BBX_PMLP_SHAPES(BBX_PMLP_LOGPROB);
-#undef BBX_PMLP_LOSS_AT
-#undef BBX_PMLP_LOSS
-#undef BBX_PMLP_LOGPROB_AT
+#define BBX_PMLP_LOGPROB(N, K, I, L) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I, L>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                         actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src, ls)
+  BBX_PMLP_DISPATCH(BBX_PMLP_LOGPROB);
 #undef BBX_PMLP_LOGPROB
-#undef BBX_PMLP_LOGPROB_I
   return (int)hipGetLastError();
 }
 // the statistics of a PPO call, one or two hidden layers, from the tail its forward kernel wrote (n == 0: zeros)
@@ -418,46 +416,49 @@ extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats
   hipLaunchKernelGGL(bbx_pmlp_ppo_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
   return (int)hipGetLastError();
 }
-extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                    int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                    const int32_t* index, int n_src, hipStream_t stream) {
-  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
+// how the policy's and the critic's gradient kernels are launched: nw waves per unit group (0: no launch, the second kernel writes
+// zeros), ng unit groups
+struct PmlpGradLaunch {
+  static constexpr int waves = 4;
+  int nw, ng;
+  dim3 grid;
+  size_t lds;
   // (indexed with no recorded state at all: every index is out of range, nothing contributes, and the kernel, which reads state 0
   // in place of an index out of range, is not launched)
-  const int nw = n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0, ng = nb / pmlp_grad_ubw(cols, hidden);
-  const size_t ml = pmlp_grad_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_GRAD_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_grad_kernel<N, K, I>), dim3((nw + waves - 1) / waves, ng), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                     actions, n, obs_rows, cols, wp, glogp, gent, nw, ws, index, n_src)
-#define BBX_PMLP_GRAD(N, K) BBX_PMLP_GRAD_I(N, K, false)
-#define BBX_PMLP_GRAD_AT(N, K) BBX_PMLP_GRAD_I(N, K, true)
-  if (nw > 0) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_GRAD_AT); else BBX_PMLP_SHAPES(BBX_PMLP_GRAD); }
-#undef BBX_PMLP_GRAD_AT
-#undef BBX_PMLP_GRAD
-#undef BBX_PMLP_GRAD_I
+  PmlpGradLaunch(int n, int obs_rows, int cols, int hidden, const int32_t* index, int n_src)
+      : nw(n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0), ng(pmlp_nb_for(hidden) / pmlp_grad_ubw(cols, hidden)),
+        grid((nw + waves - 1) / waves, ng), lds(pmlp_grad_lds_bytes(waves, obs_rows)) {}
+};
+// the second kernel of either, unless launching the first has failed: the nw partial sums of every output added in order
+static int pmlp_grad_reduce(const float* ws, int nw, int cols, int hidden, float* gw1, float* gb1, float* gw2, float* gb2, hipStream_t stream) {
   if (int rc = (int)hipGetLastError()) return rc;
   hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
   return (int)hipGetLastError();
 }
-// the critic (bbx_pmlp_value.h) over the same (NB, KS) table.  values of n positions (fit != null: with the squared-error epilogue)
+extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
+                                    int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
+                                    const int32_t* index, int n_src, hipStream_t stream) {
+  const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
+  const bool epi = false;
+  const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
+#define BBX_PMLP_GRAD(N, K, I, E) hipLaunchKernelGGL((bbx_pmlp_grad_kernel<N, K, I>), L.grid, dim3(L.waves * WAVE), L.lds, stream, obs, rows, actions, n, obs_rows, \
+                                                      cols, wp, glogp, gent, L.nw, ws, index, n_src)
+  if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_GRAD);
+#undef BBX_PMLP_GRAD
+  return pmlp_grad_reduce(ws, L.nw, cols, hidden, gw1, gb1, gw2, gb2, stream);
+}
+// the critic: values of n positions (fit != null: with the squared-error epilogue)
 extern "C" int bbx_launch_pmlp_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
                                      float* values, double* values64, const int32_t* index, int n_src, const PmlpFit* fit, hipStream_t stream) {
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
+  const bool epi = fit != nullptr;
   const PmlpFit ft = fit ? *fit : PmlpFit{};
-#define BBX_PMLP_VALUE_I(N, K, I, F) hipLaunchKernelGGL((bbx_pmlp_value_kernel<N, K, I, F>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                         n, obs_rows, cols, wp, pool, values, values64, index, n_src, ft)
-#define BBX_PMLP_VALUE(N, K) BBX_PMLP_VALUE_I(N, K, false, false)
-#define BBX_PMLP_VALUE_AT(N, K) BBX_PMLP_VALUE_I(N, K, true, false)
-#define BBX_PMLP_FIT(N, K) BBX_PMLP_VALUE_I(N, K, false, true)
-#define BBX_PMLP_FIT_AT(N, K) BBX_PMLP_VALUE_I(N, K, true, true)
-  if (fit) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_FIT_AT); else BBX_PMLP_SHAPES(BBX_PMLP_FIT); }
-  else if (index) BBX_PMLP_SHAPES(BBX_PMLP_VALUE_AT); else BBX_PMLP_SHAPES(BBX_PMLP_VALUE);
-#undef BBX_PMLP_FIT_AT
-#undef BBX_PMLP_FIT
-#undef BBX_PMLP_VALUE_AT
+#define BBX_PMLP_VALUE(N, K, I, F) hipLaunchKernelGGL((bbx_pmlp_value_kernel<N, K, I, F>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
+                                                       n, obs_rows, cols, wp, pool, values, values64, index, n_src, ft)
+  BBX_PMLP_DISPATCH(BBX_PMLP_VALUE);
 #undef BBX_PMLP_VALUE
-#undef BBX_PMLP_VALUE_I
   return (int)hipGetLastError();
 }
 // the statistics of a fit call from the tail its forward kernel wrote (n == 0: zeros)
@@ -465,28 +466,22 @@ extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* sta
   hipLaunchKernelGGL(bbx_pmlp_value_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
   return (int)hipGetLastError();
 }
-// the critic's weight gradients: bbx_launch_pmlp_grad's partition and second kernel
+// the critic's weight gradients
 extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
                                           const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, const int32_t* index, int n_src,
                                           hipStream_t stream) {
-  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  // (indexed with no recorded state at all: the kernel, which reads state 0 in place of an index out of range, is not launched)
-  const int nw = n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0, ng = nb / pmlp_grad_ubw(cols, hidden);
-  const size_t ml = pmlp_grad_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_VGRAD_I(N, K, I) hipLaunchKernelGGL((bbx_pmlp_value_grad_kernel<N, K, I>), dim3((nw + waves - 1) / waves, ng), dim3(waves * WAVE), ml, stream, obs, \
-                                                      rows, n, obs_rows, cols, wp, pool, gvalue, nw, ws, index, n_src)
-#define BBX_PMLP_VGRAD(N, K) BBX_PMLP_VGRAD_I(N, K, false)
-#define BBX_PMLP_VGRAD_AT(N, K) BBX_PMLP_VGRAD_I(N, K, true)
-  if (nw > 0) { if (index) BBX_PMLP_SHAPES(BBX_PMLP_VGRAD_AT); else BBX_PMLP_SHAPES(BBX_PMLP_VGRAD); }
-#undef BBX_PMLP_VGRAD_AT
+  const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
+  const bool epi = false;
+  const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
+#define BBX_PMLP_VGRAD(N, K, I, E) hipLaunchKernelGGL((bbx_pmlp_value_grad_kernel<N, K, I>), L.grid, dim3(L.waves * WAVE), L.lds, stream, obs, rows, n, obs_rows, cols, \
+                                                       wp, pool, gvalue, L.nw, ws, index, n_src)
+  if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_VGRAD);
 #undef BBX_PMLP_VGRAD
-#undef BBX_PMLP_VGRAD_I
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
-  return (int)hipGetLastError();
+  return pmlp_grad_reduce(ws, L.nw, cols, hidden, gw1, gb1, gw2, gb2, stream);
 }
-#undef BBX_PMLP_SHAPES
-#undef BBX_PMLP_SHAPES_K
+#undef BBX_PMLP_DISPATCH
+#undef BBX_PMLP_DISPATCH_K
+#undef BBX_PMLP_DISPATCH_IE
 
 
 // ------------------------------------------------------------------ host-callable launcher

@@ -102,6 +102,13 @@ __device__ __forceinline__ float pmlp_entropy_wave(const float* lg, int n, int l
   sd = lane63_f32(wave_sum_f32(sd));
   return __logf(sm.se) - sd / sm.se;
 }
+// the policy gradient's coefficient of row r in dL/dz:   g_r = gl (delta_{r,a} - p_r) - ge p_r (log p_r + H)
+// with t = z_r, p_r = exp(t - mx) rse (rse = 1.f / se) and log p_r = t - logz; the one- and the two-layer gradient kernels write it
+// over the logits in LDS
+__device__ __forceinline__ float pmlp_policy_coef(float t, bool is_a, const PmlpSoftmax& sm, float H, float gl, float ge, float rse) {
+  const float pr = __expf(t - sm.mx) * rse;
+  return gl * ((is_a ? 1.f : 0.f) - pr) - ge * pr * ((t - sm.logz) + H);
+}
 
 // The loss epilogue of the forward kernels (their LOSS instantiations: bbx_pmlp_ppo_grad, bbx_pmlp2_ppo_grad), called by lane 0
 // once a wave has logprob_k and H_k of position k: the coefficients dL/dlogprob_k, dL/dH_k of
@@ -200,20 +207,16 @@ __device__ __forceinline__ float pmlp_tile(const float (&xa)[KS], WP wp, int lr,
   }
   return part + __shfl_xor(part, 32, WAVE);                  // the other half of the row's units
 }
+// the logits of one state or environment into lg (the wave's LDS array); returns the live row count.  The one row loop of every
+// one-layer kernel: the stand-alone and built-in policies (pmlp_act_wave) and the log-probability, value and gradient kernels
+// (bbx_pmlp_grad.h, bbx_pmlp_value.h) score a block with the same bits.  nraw = rows[...] as loaded: the caller requests it (and
+// whatever else it needs from memory) in front of the call, and the count is first looked at behind the first tile
 template <int NB, int KS>
-__device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
-                                             int obs_rows, int cols, const float* __restrict__ wp, const float* __restrict__ u,
-                                             int32_t* __restrict__ actions, float* __restrict__ logprobs, int greedy = 0) {
+__device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __restrict__ ob, int nraw, int obs_rows, int cols, const float* __restrict__ wp,
+                                                int lr, int lk) {
   constexpr int HP = 32 * NB;
   constexpr int G = (KS <= 10 ? 2 : 1) < NB ? (KS <= 10 ? 2 : 1) : NB;   // unit blocks in flight together
-  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
-  float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);   // logits of this wave's environment
-  if (!live) return 0;
-  const int lr = lane & 31, lk = lane >> 5;
-  const int nraw = rows[env];
-  const float uu = greedy ? 0.f : u[env];                   // (greedy: u is not read and may be null)
   const float b2 = wp[(size_t)(2 * KS + 2) * HP];
-  const int32_t* ob = obs + (size_t)env * obs_rows * cols;
   int n = 0;
   for (int r0 = 0;; r0 += 32) {
     int r = r0 + lr; r = r < obs_rows ? r : obs_rows - 1;    // inside the block whatever the row count is
@@ -230,6 +233,18 @@ __device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, con
     if (lk == 0 && r0 + lr < n) lg[r0 + lr] = logit + b2;
     if (r0 + 32 >= n) break;
   }
+  return n;
+}
+template <int NB, int KS>
+__device__ __forceinline__ int pmlp_act_wave(char* smem, int env, bool live, const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
+                                             int obs_rows, int cols, const float* __restrict__ wp, const float* __restrict__ u,
+                                             int32_t* __restrict__ actions, float* __restrict__ logprobs, int greedy = 0) {
+  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
+  float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);   // logits of this wave's environment
+  if (!live) return 0;
+  const int nraw = rows[env];
+  const float uu = greedy ? 0.f : u[env];                   // (greedy: u is not read and may be null)
+  const int n = pmlp_logits_wave<NB, KS>(lg, obs + (size_t)env * obs_rows * cols, nraw, obs_rows, cols, wp, lane & 31, lane >> 5);
   if (n <= 0) { if (lane == 0) { actions[env] = 0; logprobs[env] = 0.f; } return 0; }
   wave_sync();
   return pmlp_pick(lg, n, env, uu, greedy, actions, logprobs);

@@ -194,12 +194,7 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
     const int n32 = (n + 31) & ~31;
     __syncthreads();                                                          // (every wave has read the logits)
     for (int r = (int)threadIdx.x; r < n32; r += (int)blockDim.x) {           // (every thread reads and writes its own entries only)
-      float g = 0.f;
-      if (r < n) {
-        const float t = lg[r];
-        const float pr = __expf(t - sm.mx) * rse;
-        g = gl * ((r == a ? 1.f : 0.f) - pr) - ge * pr * ((t - sm.logz) + H);
-      }
+      const float g = r < n ? pmlp_policy_coef(lg[r], r == a, sm, H, gl, ge, rse) : 0.f;
       lg[r] = g; db3a += g;
     }
     __syncthreads();

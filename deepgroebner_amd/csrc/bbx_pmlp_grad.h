@@ -4,17 +4,18 @@
 // with respect to W1, b1, w2, b2 — what the reference's update (pg.py _fit_policy_model) needs per recorded state.  Nothing of
 // size [n][rows][hidden] ever exists in memory: the backward pass recomputes the hidden tile.
 //
-// Forward (bbx_pmlp_logprob_kernel): one wave per state; the logits go to the wave's LDS array through pmlp_tile exactly as in
-// pmlp_act_wave (same tile code, same G, same max / sum order, same lg[a] - logz: the log-probability of an action bbx_pmlp_act
-// has just sampled from the same block and weights is that call's, bit for bit).  Entropy: with e_r = exp(z_r - max),
+// Forward (bbx_pmlp_logprob_kernel): one wave per state; the logits go to the wave's LDS array through pmlp_logits_wave, the row
+// loop of pmlp_act_wave (bbx_pmlp.h), then the same max / sum order and the same lg[a] - logz: the log-probability of an action
+// bbx_pmlp_act has just sampled from the same block and weights is that call's, bit for bit.  Entropy: with e_r = exp(z_r - max),
 // se = sum e_r:   H = log(se) - (sum_r e_r (z_r - max)) / se   (= logZ - sum_r p_r z_r with the maximum taken out of both terms,
 // so that large logits do not cancel).
 //
 // Backward (bbx_pmlp_grad_kernel + bbx_pmlp_grad_reduce_kernel): a wave takes states p, p + waves, ... (pmlp_grad_waves(n) waves
 // per unit group: bbx_pmlp_shape.h).  Per state: the logits as above, then p_r, H and
-//   g_r = glogp (delta_{r,a} - p_r) - gent p_r (log p_r + H)
-// overwrite the logits in LDS (zero beyond the live rows, up to the next multiple of 32).  Per 32-row tile and unit block the
-// hidden tile is recomputed THE OTHER WAY ROUND, D'[row][unit]: the operands of pmlp_tile swapped —
+//   g_r = glogp (delta_{r,a} - p_r) - gent p_r (log p_r + H)          (pmlp_policy_coef, bbx_pmlp.h)
+// overwrite the logits in LDS (zero beyond the live rows, up to the next multiple of 32).  That is the kernel's own head; what
+// follows is PmlpGradWave below, which the critic's gradient kernel (bbx_pmlp_value.h) runs behind a head of its own.  Per 32-row
+// tile and unit block the hidden tile is recomputed THE OTHER WAY ROUND, D'[row][unit]: the operands of pmlp_tile swapped —
 //   A operand  lane l: x[row r0 + (l & 31)][2s + (l >> 5)]           B operand  lane l: W1[2s + (l >> 5)][unit 32 ub + (l & 31)]
 //   D'         lane l, register v: row r0 + (v & 3) + 8 (v >> 2) + 4 (l >> 5), unit 32 ub + (l & 31); starts at b1[unit]
 // so a UNIT's 32 rows lie along the registers of lanes l and l + 32: relu, dh = g_r w2[unit] [h > 0], dw2 += g_r relu(h) and
@@ -25,7 +26,7 @@
 // dW1, db1, dw2 and db2 stay in registers across all states of the wave; at the end the wave writes its partial sums to the
 // caller's workspace, and the second kernel adds the partials of every output in a fixed order: no floating-point atomics,
 // and the partition depends on n and the shape alone, so the same inputs give the same bits on any device.
-// 8 unit blocks x 2 column blocks x 16 accumulators do not fit in a wave: a wave owns PMLP_GRAD_UBW unit blocks (at most 64 dW1
+// 8 unit blocks x 2 column blocks x 16 accumulators do not fit in a wave: a wave owns pmlp_grad_ubw unit blocks (at most 64 dW1
 // accumulators) and the unit groups are spread ACROSS THE GRID (blockIdx.y); every group computes the logits of its states
 // itself (db2 is taken from group 0).
 #pragma once
@@ -35,33 +36,8 @@
 __host__ __device__ constexpr int pmlp_grad_lgcap(int obs_rows) { return ((pmlp_lgcap(obs_rows) + 31) / 32) * 32; }
 __host__ __device__ constexpr size_t pmlp_grad_lds_bytes(int waves, int obs_rows) { return (size_t)waves * pmlp_grad_lgcap(obs_rows) * sizeof(float); }
 
-// the logits of one state into lg (pmlp_act_wave's loop, written again: that one stays as it is); returns the live row count
-template <int NB, int KS>
-__device__ __forceinline__ int pmlp_logits_wave(float* lg, const int32_t* __restrict__ ob, int nraw, int obs_rows, int cols, const float* __restrict__ wp,
-                                                int lr, int lk) {
-  constexpr int HP = 32 * NB;
-  constexpr int G = (KS <= 10 ? 2 : 1) < NB ? (KS <= 10 ? 2 : 1) : NB;
-  const float b2 = wp[(size_t)(2 * KS + 2) * HP];
-  int n = 0;
-  for (int r0 = 0;; r0 += 32) {
-    int r = r0 + lr; r = r < obs_rows ? r : obs_rows - 1;    // inside the block whatever the row count is
-    const int32_t* xr = ob + (size_t)r * cols;
-    float xa[KS];
-#pragma unroll
-    for (int s2 = 0; s2 < KS; s2++) {
-      const int k = 2 * s2 + lk;
-      const int32_t xi = xr[k < cols ? k : 0];
-      xa[s2] = k < cols ? (float)xi : 0.f;
-    }
-    const float logit = pmlp_tile<NB, KS, G>(xa, wp, lr, lk);
-    if (r0 == 0) { n = uni(nraw); n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS; }
-    if (lk == 0 && r0 + lr < n) lg[r0 + lr] = logit + b2;
-    if (r0 + 32 >= n) break;
-  }
-  return n;
-}
-
-// (pmlp_softmax_wave / pmlp_entropy_wave: bbx_pmlp.h, beside pmlp_sample, whose order they keep)
+// (pmlp_logits_wave: bbx_pmlp.h, the row loop pmlp_act_wave runs; pmlp_softmax_wave / pmlp_entropy_wave / pmlp_policy_coef: beside
+// pmlp_sample, whose order they keep)
 // LOSS: the instantiations of bbx_pmlp_ppo_grad — lane 0 goes on from logprob_k and H_k to the loss's coefficients and terms
 // (pmlp_loss_lane0); logprobs and entropy may then both be null, and H is computed whether entropy is wanted or not.  Without
 // LOSS the argument `loss` is not read.
@@ -107,73 +83,63 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t*
   }
 }
 
-template <int NB, int KS, bool IDX = false>
-__global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
-                                                               const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
-                                                               const float* __restrict__ wp, const float* __restrict__ glogp,
-                                                               const float* __restrict__ gent, int nwaves, float* __restrict__ ws,
-                                                               const int32_t* __restrict__ index, int n_src) {
-  constexpr int HP = 32 * NB;
-  constexpr int CB = KS == 32 ? 2 : 1;                               // pmlp_grad_cb
-  constexpr int UBW = NB < (CB == 2 ? 2 : 4) ? NB : (CB == 2 ? 2 : 4);   // pmlp_grad_ubw
-  constexpr int UW = 32 * UBW, NG = NB / UBW;
-  constexpr int PW = UW * (32 * CB + 2) + 4;                         // pmlp_grad_partial_floats
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
-  const int p = blockIdx.x * ((int)blockDim.x / WAVE) + wave;       // my place among the group's waves
-  const int grp = blockIdx.y;                                        // my unit group: unit blocks grp UBW ...
-  if (p >= nwaves) return;
-  float* lg = (float*)smem + (size_t)wave * pmlp_grad_lgcap(obs_rows);
-  const int lr = lane & 31, lk = lane >> 5;
-  const float* wl = wp + lk * HP + grp * UW + lr;                    // my B-operand column: + 2 s HP + 32 u
+// The back half of a gradient kernel, one code for the policy's (bbx_pmlp_grad_kernel) and the critic's (bbx_pmlp_value_grad_kernel,
+// bbx_pmlp_value.h): what a wave keeps across its states, and what it does to a state before and after the kernel's own head has
+// written the row coefficients g_r over the scores in LDS.  The shape constants are bbx_pmlp_shape.h's at the built-in shape.
+template <int NB, int KS>
+struct PmlpGradWave {
+  static_assert(pmlp_ks_for(2 * KS) == KS && pmlp_nb_for(32 * NB) == NB, "not a built-in shape");
+  static constexpr int HP = 32 * NB;
+  static constexpr int CB = pmlp_grad_cb(2 * KS), UBW = pmlp_grad_ubw(2 * KS, HP);   // column blocks; unit blocks of a wave
+  static constexpr int UW = 32 * UBW, NG = NB / UBW;                                 // units of a wave; unit groups (blockIdx.y)
+  static constexpr int PW = pmlp_grad_partial_floats(2 * KS, HP);
 
+  int lr, lk;
+  const float* wl;                                                    // my B-operand column: + 2 s HP + 32 u
   bbx_f32x16 dW[UBW][CB];
-  float db1a[UBW], dw2a[UBW], db2a = 0.f;
+  float db1a[UBW], dw2a[UBW], db2a;                                   // (db2a: the kernel's head adds the g_r it writes)
+
+  __device__ __forceinline__ void start(const float* __restrict__ wp, int lane) {
+    lr = lane & 31; lk = lane >> 5;
+    wl = wp + lk * HP + (int)blockIdx.y * UW + lr;
+    db2a = 0.f;
 #pragma unroll
-  for (int u = 0; u < UBW; u++) {
-    db1a[u] = 0.f; dw2a[u] = 0.f;
+    for (int u = 0; u < UBW; u++) {
+      db1a[u] = 0.f; dw2a[u] = 0.f;
 #pragma unroll
-    for (int cb = 0; cb < CB; cb++)
+      for (int cb = 0; cb < CB; cb++)
 #pragma unroll
-      for (int v = 0; v < 16; v++) dW[u][cb][v] = 0.f;
+        for (int v = 0; v < 16; v++) dW[u][cb][v] = 0.f;
+    }
   }
 
-  for (int k = p; k < B; k += nwaves) {                               // position k of the call: recorded state s
+  // position k of the call -> the recorded state it is about.  An index out of range: in_src = false, for which the caller takes
+  // no row (the kernels skip such a state) — and state 0 in its place for the addresses (the launcher sees to n_src > 0).  A
+  // branch around the state here instead costs 20-30 vector registers and, from 33 columns on, spills
+  template <bool IDX>
+  static __device__ __forceinline__ int state_of(const int32_t* __restrict__ index, int n_src, int k, bool& in_src) {
     int s = k;
-    bool in_src = true;
+    in_src = true;
     if constexpr (IDX) {
-      // an index out of range: no row, which the test below skips — and state 0 in its place for the addresses (the launcher
-      // sees to n_src > 0).  A branch around the state here instead costs 20-30 vector registers and, from 33 columns on, spills
       s = uni(index[k]);
       in_src = s >= 0 && s < n_src;
       s = in_src ? s : 0;
     }
-    const int nraw = in_src ? rows[s] : 0;
-    const int a = uni(actions[s]);
-    const int32_t* ob = obs + (size_t)s * obs_rows * cols;
+    return s;
+  }
+
+  // the scores of a state into lg; returns the live row count
+  __device__ __forceinline__ int logits(float* lg, const int32_t* __restrict__ ob, int nraw, int obs_rows, int cols, const float* __restrict__ wp) {
     wave_sync();                                                      // (the previous state's g_r have been read)
     // (the weights are the same for every state and tile: their base pointers are opaque per use, so that the optimiser does not
     // hoist hundreds of loads out of the loops into registers the dW1 accumulators need)
     const float* wq = wp;
     asm volatile("" : "+s"(wq));
-    const int n = pmlp_logits_wave<NB, KS>(lg, ob, nraw, obs_rows, cols, wq, lr, lk);
-    if (n <= 1 || a < 0 || a >= n) continue;                         // no row, one row (delta - p = 0) or a bad action: nothing
-    wave_sync();
-    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
-    const float H = pmlp_entropy_wave(lg, n, lane, sm);
-    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
-    const float rse = 1.f / sm.se;
-    const int n32 = (n + 31) & ~31;
-    for (int r = lane; r < n32; r += WAVE) {                          // (every lane reads and writes its own entries only)
-      float g = 0.f;
-      if (r < n) {
-        const float t = lg[r];
-        const float pr = __expf(t - sm.mx) * rse;
-        g = gl * ((r == a ? 1.f : 0.f) - pr) - ge * pr * ((t - sm.logz) + H);
-      }
-      lg[r] = g; db2a += g;
-    }
-    wave_sync();
+    return pmlp_logits_wave<NB, KS>(lg, ob, nraw, obs_rows, cols, wq, lr, lk);
+  }
+
+  // the n > 0 rows of a state, their g_r in lg (zero up to the next multiple of 32), into the accumulators
+  __device__ __forceinline__ void tiles(const float* lg, const int32_t* __restrict__ ob, int n, int cols) {
     for (int r0 = 0; r0 < n; r0 += 32) {
       // the rows of this tile twice: as the k-step operands of the hidden tile (row on the lane), and in the permuted row
       // order of the accumulator registers with the column on the lane (dW1's A operands); rows beyond n count as zero
@@ -235,19 +201,58 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __
     }
   }
 
-  // the wave's partial sums: dW1 [32 CB][UW] | db1 [UW] | dw2 [UW] | db2
-  float* part = ws + ((size_t)p * NG + grp) * PW;
+  // the partial sums of wave p of my unit group, as bbx_pmlp_grad_reduce_kernel reads them: dW1 [32 CB][UW] | db1 [UW] | dw2 [UW] | db2
+  __device__ __forceinline__ void store(float* __restrict__ ws, int p, int lane) {
+    float* part = ws + ((size_t)p * NG + (int)blockIdx.y) * PW;
 #pragma unroll
-  for (int u = 0; u < UBW; u++) {
+    for (int u = 0; u < UBW; u++) {
 #pragma unroll
-    for (int cb = 0; cb < CB; cb++)
+      for (int cb = 0; cb < CB; cb++)
 #pragma unroll
-      for (int v = 0; v < 16; v++) part[(32 * cb + (v & 3) + 8 * (v >> 2) + 4 * lk) * UW + 32 * u + lr] = dW[u][cb][v];
-    const float tb = db1a[u] + __shfl_xor(db1a[u], 32, WAVE), tw = dw2a[u] + __shfl_xor(dw2a[u], 32, WAVE);   // the unit's other 16 rows
-    if (lk == 0) { part[32 * CB * UW + 32 * u + lr] = tb; part[32 * CB * UW + UW + 32 * u + lr] = tw; }
+        for (int v = 0; v < 16; v++) part[(32 * cb + (v & 3) + 8 * (v >> 2) + 4 * lk) * UW + 32 * u + lr] = dW[u][cb][v];
+      const float tb = db1a[u] + __shfl_xor(db1a[u], 32, WAVE), tw = dw2a[u] + __shfl_xor(dw2a[u], 32, WAVE);   // the unit's other 16 rows
+      if (lk == 0) { part[32 * CB * UW + 32 * u + lr] = tb; part[32 * CB * UW + UW + 32 * u + lr] = tw; }
+    }
+    const float t2 = wave_sum_f32(db2a);
+    if (lane == WAVE - 1) part[32 * CB * UW + 2 * UW] = t2;
   }
-  const float t2 = wave_sum_f32(db2a);
-  if (lane == WAVE - 1) part[32 * CB * UW + 2 * UW] = t2;
+};
+
+template <int NB, int KS, bool IDX = false>
+__global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
+                                                               const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
+                                                               const float* __restrict__ wp, const float* __restrict__ glogp,
+                                                               const float* __restrict__ gent, int nwaves, float* __restrict__ ws,
+                                                               const int32_t* __restrict__ index, int n_src) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
+  const int p = blockIdx.x * ((int)blockDim.x / WAVE) + wave;       // my place among the group's waves
+  if (p >= nwaves) return;
+  float* lg = (float*)smem + (size_t)wave * pmlp_grad_lgcap(obs_rows);
+  PmlpGradWave<NB, KS> G;
+  G.start(wp, lane);
+  for (int k = p; k < B; k += nwaves) {                               // position k of the call: recorded state s
+    bool in_src;
+    const int s = G.template state_of<IDX>(index, n_src, k, in_src);
+    const int nraw = in_src ? rows[s] : 0;
+    const int a = uni(actions[s]);
+    const int32_t* ob = obs + (size_t)s * obs_rows * cols;
+    const int n = G.logits(lg, ob, nraw, obs_rows, cols, wp);
+    if (n <= 1 || a < 0 || a >= n) continue;                         // no row, one row (delta - p = 0) or a bad action: nothing
+    wave_sync();
+    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+    const float H = pmlp_entropy_wave(lg, n, lane, sm);
+    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
+    const float rse = 1.f / sm.se;
+    const int n32 = (n + 31) & ~31;
+    for (int r = lane; r < n32; r += WAVE) {                          // (every lane reads and writes its own entries only)
+      const float g = r < n ? pmlp_policy_coef(lg[r], r == a, sm, H, gl, ge, rse) : 0.f;
+      lg[r] = g; G.db2a += g;
+    }
+    wave_sync();
+    G.tiles(lg, ob, n, cols);
+  }
+  G.store(ws, p, lane);
 }
 
 // The second stage: output i of dW1 [cols][hidden] | db1 [hidden] | dw2 [hidden] | db2 is the sum of its nwaves partials —
@@ -279,23 +284,11 @@ __global__ __launch_bounds__(256) void bbx_pmlp_grad_reduce_kernel(const float* 
   if (q == 0 && out) *out = (part[0][j] + part[1][j]) + (part[2][j] + part[3][j]);
 }
 
-// The statistics of a PPO call (bbx_pmlp_ppo_grad, bbx_pmlp2_ppo_grad) from the tail the loss epilogue wrote: stats[0..5] = counted
-// positions, sum u_k, sum H_k, sum (old_k - new_k), positions clipped, positions not counted; the sums in double over the float32
-// terms.  ONE workgroup of PMLP_PPO_STAT_THREADS threads: thread t adds positions t, t + threads, ...; the 64 lanes of a wave are
-// added by a butterfly (every lane ends with the same sum), the 16 waves in order by one thread per statistic.  No atomics, and a
-// partition that depends on n alone.  n == 0: zeros.
-__global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+// What both statistics kernels (bbx_pmlp_ppo_stats_kernel; bbx_pmlp_value_stats_kernel, bbx_pmlp_value.h) end with: the six sums
+// of the workgroup's PMLP_PPO_STAT_THREADS threads into stats[0..5] — the 64 lanes of a wave by a butterfly (every lane ends with
+// the same sum), the 16 waves in order by one thread per statistic.
+__device__ __forceinline__ void pmlp_stats_sum(double (&acc)[6], double* __restrict__ stats) {
   __shared__ double part[PMLP_PPO_STAT_THREADS / WAVE][6];
-  const size_t n = (size_t)n_;
-  const int32_t* flags = (const int32_t*)tail + 3 * n;
-  double acc[6] = {0., 0., 0., 0., 0., 0.};
-  for (size_t k = threadIdx.x; k < n; k += PMLP_PPO_STAT_THREADS) {
-    const int f = flags[k];
-    if (f & PMLP_LOSS_COUNTED) {
-      acc[0] += 1.; acc[1] += (double)tail[k]; acc[2] += (double)tail[n + k]; acc[3] += (double)tail[2 * n + k];
-      if (f & PMLP_LOSS_CLIPPED) acc[4] += 1.;
-    } else acc[5] += 1.;
-  }
 #pragma unroll
   for (int i = 0; i < 6; i++) {
 #pragma unroll
@@ -312,4 +305,22 @@ __global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kern
     for (int w = 0; w < PMLP_PPO_STAT_THREADS / WAVE; w++) t += part[w][threadIdx.x];
     stats[threadIdx.x] = t;
   }
+}
+
+// The statistics of a PPO call (bbx_pmlp_ppo_grad, bbx_pmlp2_ppo_grad) from the tail the loss epilogue wrote: stats[0..5] = counted
+// positions, sum u_k, sum H_k, sum (old_k - new_k), positions clipped, positions not counted; the sums in double over the float32
+// terms.  ONE workgroup of PMLP_PPO_STAT_THREADS threads: thread t adds positions t, t + threads, ..., then pmlp_stats_sum.  No
+// atomics, and a partition that depends on n alone.  n == 0: zeros.
+__global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+  const size_t n = (size_t)n_;
+  const int32_t* flags = (const int32_t*)tail + 3 * n;
+  double acc[6] = {0., 0., 0., 0., 0., 0.};
+  for (size_t k = threadIdx.x; k < n; k += PMLP_PPO_STAT_THREADS) {
+    const int f = flags[k];
+    if (f & PMLP_LOSS_COUNTED) {
+      acc[0] += 1.; acc[1] += (double)tail[k]; acc[2] += (double)tail[n + k]; acc[3] += (double)tail[2 * n + k];
+      if (f & PMLP_LOSS_CLIPPED) acc[4] += 1.;
+    } else acc[5] += 1.;
+  }
+  pmlp_stats_sum(acc, stats);
 }
