@@ -1,16 +1,15 @@
-"""The consumer side of the batched environment: policy, trajectory buffer and rollout loop, all on the
-device, replacing the per-step host round trip of the reference's agents.
+"""The consumer side of the batched environment: trajectory buffer, rollout loops and update loops, all on the
+device, replacing the per-step host round trip of the reference's agents.  The policy and the critic they drive (PMLPPolicy,
+PMLPValue) and the kernel calls behind them are deepgroebner_amd.pmlp's; both names are importable from here as well.
 
-    PMLPPolicy                 ParallelMultilayerPerceptron           networks.py:522-571 (:49-95, :414-460)
     discount_rewards, compute_advantages                              pg.py:20-76
     DeviceTrajectoryBuffer     TrajectoryBuffer (store/finish/get)    pg.py:79-240
     get_index + PMLPPolicy.evaluate_at   the update's minibatches as slices of an index list over the buffer: the training
                                kernels read the recorded states where the rollout left them (bbx_pmlp_logprob_at / bbx_pmlp_grad_at)
-    PMLPPolicy.ppo_step_at, ppo_update   one minibatch of the update — forward, PPO loss, statistics, weight gradients — in one library
-                               call (bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at), and the epochs around it     pg.py _fit_policy_model
-    PMLPValue, fill_values, value_update   a learned baseline (--value_model mlp, pg.py _fit_value_model): a critic over the recorded
-                               state blocks — one launch for a whole buffer's values after the rollout (bbx_pmlp_value), one library
-                               call per minibatch of the squared-error fit (bbx_pmlp_value_fit_at); run_rollout_fused(critic=...)
+    ppo_update                 the epochs of the policy update around PMLPPolicy.ppo_step_at          pg.py _fit_policy_model
+    fill_values, value_update  a learned baseline (--value_model mlp, pg.py _fit_value_model): one launch for a whole buffer's values
+                               after the rollout (PMLPValue.values), the epochs of the squared-error fit around PMLPValue.fit_step_at;
+                               run_rollout_fused(critic=...)
     run_rollout                PGAgent.run_episode(s)                 pg.py:451-503   (one library call per vector step)
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
@@ -19,12 +18,10 @@ device, replacing the per-step host round trip of the reference's agents.
     episode_returns            one return and one length per episode from a rollout's rewards and dones (bbx_episodes_device)
     evaluate_policy            the first K episodes of every environment under a policy   scripts/eval.py
 
-PyTorch is the plumbing here (device memory, autograd for training); the policy evaluation + sampling of the default
-one-hidden-layer network runs in hand-written HIP: on the matrix cores, either as a kernel of its own fed by the padded
-observation block (bbx_pmlp_act), in front of the step in the same launch (bbx_policy_step_device), or inside the step
-loop (bbx_policy_rollout_device).  Two hidden layers of at most 128 units run inside the step loop too
-(bbx_policy2_rollout_device) or as a kernel of their own (bbx_pmlp2_act), three as a kernel of their own (bbx_pmlp3_act); deeper
-or wider networks take the torch path.  Actions never visit the host.
+PyTorch is the plumbing here (device memory, autograd for training); the policy evaluation + sampling runs in hand-written
+HIP (deepgroebner_amd.pmlp has which network takes which kernel), in front of the step in the same launch
+(bbx_policy_step_device) or inside the step loop (bbx_policy_rollout_device, bbx_policy2_rollout_device) where the network
+allows.  Actions never visit the host.
 """
 import collections
 import contextlib
@@ -36,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from .pmlp import PMLPPolicy, PMLPValue  # noqa: F401
 
 
 @contextlib.contextmanager
@@ -77,812 +75,6 @@ def compute_advantages(rewards, values, gam, lam):
     delta = rewards - values
     delta[:-1] += gam * values[1:]
     return discount_rewards(delta, gam * lam)
-
-
-class _PMLPEvaluate(torch.autograd.Function):
-    """log pi(a | s) and the entropy of pi(. | s) of a one-hidden-layer PMLPPolicy through bbx_pmlp_logprob, differentiable
-    with respect to the four parameter tensors through bbx_pmlp_grad (the hidden activations are recomputed there: nothing of
-    size [N, R, hidden] is kept between forward and backward).  No gradient for states, actions or rows.
-    index (int32 [n], optional): the call is about the recorded states index[k] of states [..., R, cols], rows and actions, which
-    are then whole buffers read in place (bbx_pmlp_logprob_at / bbx_pmlp_grad_at); the outputs have length n."""
-
-    @staticmethod
-    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, index=None):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        w = policy._fused_weights()
-        logp = torch.empty(N, dtype=torch.float32, device=states.device)
-        ent = torch.empty(N, dtype=torch.float32, device=states.device)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(states.device):
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if index is None:
-                _ffi.check(_ffi.lib().bbx_pmlp_logprob(p(states), p(rows), p(actions), N, R, cols, w["prepared"], w["hidden"], p(logp), p(ent), s))
-            else:
-                _ffi.check(_ffi.lib().bbx_pmlp_logprob_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, w["prepared"], w["hidden"],
-                                                          p(logp), p(ent), s))
-        ctx.policy, ctx.prep, ctx.hidden = policy, w["keep"], w["hidden"]     # (the prepared weights of THIS forward pass)
-        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, index)
-        return logp, ent
-
-    @staticmethod
-    def backward(ctx, glogp, gent):
-        states, rows, actions, w1, b1, w2, b2, index = ctx.saved_tensors
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        hidden = ctx.hidden
-        dev = states.device
-        glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
-        gw1 = torch.empty((cols, hidden), dtype=torch.float32, device=dev)
-        gb1 = torch.empty(hidden, dtype=torch.float32, device=dev)
-        gw2 = torch.empty(hidden, dtype=torch.float32, device=dev)
-        gb2 = torch.empty(1, dtype=torch.float32, device=dev)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(dev):
-            ws = ctx.policy._grad_workspace(N, R, cols, hidden, dev)
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if index is None:
-                _ffi.check(_ffi.lib().bbx_pmlp_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), hidden, p(glogp), p(gent), p(ws),
-                                                    p(gw1), p(gb1), p(gw2), p(gb2), s))
-            else:
-                _ffi.check(_ffi.lib().bbx_pmlp_grad_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(ctx.prep), hidden, p(glogp),
-                                                       p(gent), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), s))
-        return None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype), None
-
-
-class _PMLP2Evaluate(torch.autograd.Function):
-    """_PMLPEvaluate for two hidden layers: bbx_pmlp2_logprob forward, bbx_pmlp2_grad backward (both hidden tiles are recomputed
-    there), gradients for the six parameter tensors in torch.nn.Linear's own layouts.  No gradient for states, actions or rows.
-    index: as in _PMLPEvaluate (bbx_pmlp2_logprob_at / bbx_pmlp2_grad_at)."""
-
-    @staticmethod
-    def forward(ctx, policy, states, rows, actions, w1, b1, w2, b2, w3, b3, index=None):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        logp = torch.empty(N, dtype=torch.float32, device=states.device)
-        ent = torch.empty(N, dtype=torch.float32, device=states.device)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(states.device):
-            w = policy._deep_weights()
-            h1, h2 = w["hidden"]
-            # (the prepared buffer is refilled in place when the weights change: backward reads THIS forward pass's weights
-            # from a copy of its own, made on the stream behind the fill)
-            prep = w["keep"][0].clone()
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if index is None:
-                _ffi.check(_ffi.lib().bbx_pmlp2_logprob(p(states), p(rows), p(actions), N, R, cols, p(prep), h1, h2, p(logp), p(ent), s))
-            else:
-                _ffi.check(_ffi.lib().bbx_pmlp2_logprob_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(prep), h1, h2, p(logp),
-                                                           p(ent), s))
-        ctx.policy, ctx.prep, ctx.hidden = policy, prep, (h1, h2)
-        ctx.save_for_backward(states, rows, actions, w1, b1, w2, b2, w3, b3, index)
-        return logp, ent
-
-    @staticmethod
-    def backward(ctx, glogp, gent):
-        states, rows, actions, w1, b1, w2, b2, w3, b3, index = ctx.saved_tensors
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        h1, h2 = ctx.hidden
-        dev = states.device
-        glogp = glogp.contiguous().float(); gent = gent.contiguous().float()
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        gw1, gb1, gw2, gb2, gw3, gb3 = new(cols, h1), new(h1), new(h1, h2), new(h2), new(h2), new(1)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(dev):
-            ws = ctx.policy._grad2_workspace(N, R, cols, h1, h2, dev)
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            if index is None:
-                _ffi.check(_ffi.lib().bbx_pmlp2_grad(p(states), p(rows), p(actions), N, R, cols, p(ctx.prep), h1, h2, p(glogp), p(gent), p(ws),
-                                                     p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), s))
-            else:
-                _ffi.check(_ffi.lib().bbx_pmlp2_grad_at(p(states), p(rows), p(actions), S, p(index), N, R, cols, p(ctx.prep), h1, h2, p(glogp),
-                                                        p(gent), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), p(gw3), p(gb3), s))
-        return (None, None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.t().to(w2.dtype), gb2.to(b2.dtype),
-                gw3.view(1, -1).to(w3.dtype), gb3.to(b3.dtype), None)
-
-
-class PMLPPolicy(torch.nn.Module):
-    """ParallelMultilayerPerceptron(hidden_layers) of the reference: every row of the -1-padded [batch, rows, cols] int
-    block is embedded by the same MLP (relu), scored by one linear unit, padded rows get -1e9, log-softmax over rows."""
-
-    def __init__(self, cols, hidden_layers=(128,), deep_kernels=False):
-        super().__init__()
-        self.deep_kernels = deep_kernels                              # two hidden layers: evaluate through bbx_pmlp2_logprob / bbx_pmlp2_grad
-        dims = [cols] + list(hidden_layers)
-        self.embedding = torch.nn.ModuleList([torch.nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:])])
-        self.deciding = torch.nn.Linear(dims[-1], 1)
-        self.cols = cols
-
-    def forward(self, batch):
-        """int [B, R, cols] with -1 padding -> log-probabilities float32 [B, R] (about -1e9 on padded rows)."""
-        mask = batch[:, :, -1] != -1                                  # ParallelEmbeddingLayer.compute_mask
-        x = batch.to(torch.float32)
-        for layer in self.embedding:
-            x = torch.relu(layer(x))
-        x = self.deciding(x).squeeze(-1)
-        x = x + (~mask).to(torch.float32) * -1e9
-        return torch.log_softmax(x, dim=-1)
-
-    @torch.no_grad()
-    def act(self, obs, rows, u, actions=None, logprobs=None, stream=None, greedy=False):
-        """Sample one action per environment by inverse CDF from the uniforms u [B] -> (actions int32 [B], logprobs
-        float32 [B]) on the device.  One hidden layer: the fused HIP kernel (bbx_pmlp_act); two or three hidden layers of at
-        most 128 units: bbx_pmlp2_act / bbx_pmlp3_act; otherwise torch ops.
-        greedy=True (evaluation, run_episodes(greedy=True) of pg.py): the highest-probability row, the first one on ties,
-        through the *_act_greedy kernels; u is not read and may be None.  Shapes the kernels refuse and CPU tensors: act_torch."""
-        B, R, cols = obs.shape
-        if not obs.is_cuda:
-            return self.act_torch(obs, rows, u, actions, logprobs, greedy=greedy)
-        lib = _ffi.lib()
-        uarg = () if greedy else (C.c_void_p(u.data_ptr()),)
-        if actions is None:
-            actions = torch.empty(B, dtype=torch.int32, device=obs.device)
-        if logprobs is None:
-            logprobs = torch.empty(B, dtype=torch.float32, device=obs.device)
-        if len(self.embedding) == 1 and self.fused_ok(cols, self.embedding[0].out_features) and R <= 2048:   # (the kernels score <= 2048 rows)
-            w = self._fused_weights()
-            s = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
-            fn = lib.bbx_pmlp_act_greedy if greedy else lib.bbx_pmlp_act
-            _ffi.check(fn(C.c_void_p(obs.data_ptr()), C.c_void_p(rows.data_ptr()), B, R, cols, w["prepared"], w["hidden"],
-                          *uarg, C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
-            return actions, logprobs
-        if self.deep_ok(cols) and R <= self.deep_max_rows():
-            w = self._deep_weights()
-            s = (stream if stream is not None else torch.cuda.current_stream()).cuda_stream
-            if greedy:
-                fn = lib.bbx_pmlp2_act_greedy if len(w["hidden"]) == 2 else lib.bbx_pmlp3_act_greedy
-            else:
-                fn = lib.bbx_pmlp2_act if len(w["hidden"]) == 2 else lib.bbx_pmlp3_act
-            _ffi.check(fn(C.c_void_p(obs.data_ptr()), C.c_void_p(rows.data_ptr()), B, R, cols, w["prepared"], *w["hidden"],
-                          *uarg, C.c_void_p(actions.data_ptr()), C.c_void_p(logprobs.data_ptr()), C.c_void_p(s)))
-            return actions, logprobs
-        return self.act_torch(obs, rows, u, actions, logprobs, greedy=greedy)
-
-    def deep_ok(self, cols):
-        """Two or three hidden layers of at most 128 units: the shapes bbx_pmlp2_act / bbx_pmlp3_act are built for."""
-        return len(self.embedding) in (2, 3) and all(1 <= l.out_features <= 128 for l in self.embedding) and 1 <= cols <= 64
-
-    def deep_max_rows(self):
-        """Rows per environment the two- / three-layer kernels score: the logits of a wave's environment live in LDS beside the
-        staged weights — 2048 rows, 1024 where three layers wider than 64 units (128 KB of weights) leave less room."""
-        return 1024 if len(self.embedding) == 3 and max(l.out_features for l in self.embedding) > 64 else 2048
-
-    def _deep_weights(self):
-        """The two- / three-layer kernel's view of the weights (bbx_pmlp2_prepare / bbx_pmlp3_prepare), rebuilt only when a
-        parameter changed, in the same buffer (a recorded graph keeps reading it)."""
-        key = tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        c = self.__dict__.get("_deep_cache")
-        if c is None or c["key"] != key:
-            cols = self.embedding[0].in_features
-            hidden = [l.out_features for l in self.embedding]
-            t = []
-            for l in self.embedding:
-                t += [l.weight.detach().t().contiguous().float(), l.bias.detach().contiguous().float()]
-            t += [self.deciding.weight.detach().reshape(-1).contiguous().float(), self.deciding.bias.detach().reshape(-1).contiguous().float()]
-            lib = _ffi.lib()
-            nfl = lib.bbx_pmlp2_prepared_floats(cols, *hidden) if len(hidden) == 2 else lib.bbx_pmlp3_prepared_floats(cols, *hidden)
-            _ffi.check(min(nfl, 0))
-            prep = c["keep"][0] if c is not None and c["keep"][0].numel() == nfl and c["keep"][0].device == t[0].device else \
-                torch.empty(nfl, dtype=torch.float32, device=t[0].device)
-            prepare = lib.bbx_pmlp2_prepare if len(hidden) == 2 else lib.bbx_pmlp3_prepare
-            _ffi.check(prepare(*[C.c_void_p(x.data_ptr()) for x in t], cols, *hidden, C.c_void_p(prep.data_ptr()),
-                               C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            c = {"key": key, "keep": (prep, t), "prepared": C.c_void_p(prep.data_ptr()), "hidden": hidden}
-            self.__dict__["_deep_cache"] = c
-        return c
-
-    @staticmethod
-    def fused_ok(cols, hidden):
-        """Shapes the policy kernel is built for (bbx_pmlp_prepared_floats >= 0)."""
-        return 1 <= hidden <= 256 and 1 <= cols <= 64
-
-    def _fused_weights(self):
-        """The kernels' view of the weights (bbx_pmlp_prepare: transposed, zero-padded to the tile sizes), rebuilt only when
-        a parameter changed (an optimiser step bumps the tensors' version counters): no per-step transposes, no per-step
-        host read of b2.  One hidden layer only: the layout has no room for a second."""
-        if len(self.embedding) != 1:
-            raise ValueError("_fused_weights: the one-layer kernels' weights of a policy with %d hidden layers (two: _deep_weights)" % len(self.embedding))
-        lin = self.embedding[0]
-        key = tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        c = self.__dict__.get("_fused_cache")
-        if c is None or c["key"] != key:
-            cols, hidden = lin.in_features, lin.out_features
-            w1 = lin.weight.detach().t().contiguous().float()
-            b1 = lin.bias.detach().contiguous().float()
-            w2 = self.deciding.weight.detach().reshape(-1).contiguous().float()
-            nfl = _ffi.lib().bbx_pmlp_prepared_floats(cols, hidden)
-            _ffi.check(min(nfl, 0))
-            prep = torch.empty(nfl, dtype=torch.float32, device=w1.device)
-            # (b2 travels by value in the C call; reading it back would make every optimiser step wait for the device: the call gets
-            # 0 and the bias is copied on the device into its place, the first of the layout's last four floats)
-            _ffi.check(_ffi.lib().bbx_pmlp_prepare(C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
-                                                   C.c_float(0.0), cols, hidden, C.c_void_p(prep.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            prep[nfl - 4:nfl - 3].copy_(self.deciding.bias.detach().reshape(1))
-            c = {"key": key, "keep": prep, "prepared": C.c_void_p(prep.data_ptr()), "hidden": hidden}
-            self.__dict__["_fused_cache"] = c
-        return c
-
-    def _grad_workspace(self, N, R, cols, hidden, device):
-        """The workspace of bbx_pmlp_grad, kept between calls (it grows only; calls on one stream run in order)."""
-        nfl = _ffi.lib().bbx_pmlp_grad_workspace_floats(N, R, cols, hidden)
-        _ffi.check(min(nfl, 0))
-        ws = self.__dict__.get("_grad_ws")
-        if ws is None or ws.numel() < nfl or ws.device != device:
-            ws = torch.empty(nfl, dtype=torch.float32, device=device)
-            self.__dict__["_grad_ws"] = ws
-        return ws
-
-    def _grad2_workspace(self, N, R, cols, h1, h2, device):
-        """The workspace of bbx_pmlp2_grad, kept between calls (it grows only; calls on one stream run in order)."""
-        nfl = _ffi.lib().bbx_pmlp2_grad_workspace_floats(N, R, cols, h1, h2)
-        _ffi.check(min(nfl, 0))
-        ws = self.__dict__.get("_grad2_ws")
-        if ws is None or ws.numel() < nfl or ws.device != device:
-            ws = torch.empty(nfl, dtype=torch.float32, device=device)
-            self.__dict__["_grad2_ws"] = ws
-        return ws
-
-    @staticmethod
-    def _row_counts(states, rows):
-        return (states[:, :, -1] != -1).sum(1).to(torch.int32) if rows is None else rows
-
-    def evaluate(self, states, actions, rows=None):
-        """The training-time view of recorded experience (pg.py _fit_policy_model): states int [N, R, cols], actions [N] ->
-        (logprobs float32 [N] of the recorded actions, entropy float32 [N] of the distribution over each state's rows),
-        differentiable with respect to the module's parameters.  rows [N]: the live rows per state (None: those whose last
-        column is not -1, as forward masks).  No live rows: 0.0 and 0.0; an action outside the live rows: NaN.
-        One hidden layer on the GPU: the HIP kernels bbx_pmlp_logprob / bbx_pmlp_grad; two hidden layers of at most 128 units
-        on the GPU with deep_kernels set: bbx_pmlp2_logprob / bbx_pmlp2_grad; otherwise evaluate_torch."""
-        N, R, cols = states.shape
-        lin = self.embedding[0]
-        if (states.is_cuda and len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
-                and self.fused_ok(cols, lin.out_features) and 1 <= R <= 2048):
-            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
-            st = states if states.dtype == torch.int32 else states.to(torch.int32)
-            return _PMLPEvaluate.apply(self, st.contiguous(), rows, actions.to(torch.int32).contiguous(), lin.weight, lin.bias,
-                                       self.deciding.weight, self.deciding.bias)
-        if (self.deep_kernels and states.is_cuda and len(self.embedding) == 2 and self.deep_ok(cols) and 1 <= R <= 2048
-                and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
-            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
-            st = states if states.dtype == torch.int32 else states.to(torch.int32)
-            l2 = self.embedding[1]
-            return _PMLP2Evaluate.apply(self, st.contiguous(), rows, actions.to(torch.int32).contiguous(), lin.weight, lin.bias, l2.weight, l2.bias,
-                                        self.deciding.weight, self.deciding.bias)
-        return self.evaluate_torch(states, actions, rows)
-
-    def evaluate_at(self, states, actions, rows, index):
-        """evaluate() of the recorded states index[k] WITHOUT gathering them: states int [S, R, cols] or [T, B, R, cols] with
-        actions and rows [S] or [T, B] are whole buffers (DeviceTrajectoryBuffer.states / .actions / .rows as the rollout kernels
-        left them), index int [n] holds flat step numbers into them (DeviceTrajectoryBuffer.get_index) -> (logprobs float32 [n],
-        entropy float32 [n]), differentiable with respect to the module's parameters; for an index in range, the numbers of
-        evaluate(states[index], actions[index], rows[index]) bit for bit.  An index outside the buffer on the kernel path: NaN
-        and NaN, nothing for the gradients.
-        The kernels (bbx_pmlp_logprob_at / bbx_pmlp_grad_at, bbx_pmlp2_..._at) read the buffers in place: under evaluate()'s
-        conditions, and only where states, rows and actions ARE contiguous int32 CUDA tensors already — a buffer is never
-        converted or copied as a whole.  Anything else gathers the n states and takes evaluate()."""
-        lin = self.embedding[0]
-        depth = self._in_place_depth(states, actions, rows)
-        if depth:
-            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
-            if depth == 1:
-                return _PMLPEvaluate.apply(self, states, rows, actions, lin.weight, lin.bias, self.deciding.weight, self.deciding.bias, idx)
-            l2 = self.embedding[1]
-            return _PMLP2Evaluate.apply(self, states, rows, actions, lin.weight, lin.bias, l2.weight, l2.bias, self.deciding.weight, self.deciding.bias, idx)
-        j = index.to(device=states.device, dtype=torch.int64)
-        if states.dim() == 4:                                         # (no reshape: a non-contiguous buffer would be copied whole)
-            t, b = j // states.shape[1], j % states.shape[1]
-            return self.evaluate(states[t, b], actions[t, b], rows[t, b])
-        return self.evaluate(states[j], actions[j], rows[j])
-
-    def _in_place_depth(self, states, actions, rows):
-        """1 or 2 where the training kernels of that many hidden layers can read states [..., R, cols], actions and rows where they
-        lie (evaluate()'s conditions, and contiguous int32 CUDA tensors of matching sizes); 0: they cannot."""
-        R, cols = states.shape[-2:]
-        lin = self.embedding[0]
-        S = rows.numel()
-        in_place = (states.is_cuda and 1 <= R <= 2048 and states.numel() == S * R * cols and actions.numel() == S
-                    and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows, actions)))
-        if not in_place:
-            return 0
-        if len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features):
-            return 1
-        if (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
-                and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
-            return 2
-        return 0
-
-    LOSS_MODES = {"pg": 0, "clip": 1, "penalty": 2}
-
-    def ppo_step_at(self, states, actions, rows, index, old_logprobs, advantages, clip=0.2, ent_coef=0.0, mode="clip", c_kl=0.0):
-        """One minibatch of the policy update (pg.py _fit_policy_model) in one library call: from the recorded states index[k] of
-        the buffers states / actions / rows (as evaluate_at takes them), the rollout's log-probabilities old_logprobs [n] and the
-        advantages [n] to the gradients of
-            L = -mean_k u_k - ent_coef mean_k H_k
-            u_k = logprob_k A_k                                         mode "pg"
-                  min(r_k A_k, clamp(r_k, 1 - clip, 1 + clip) A_k)      mode "clip"       (r_k = exp(logprob_k - old_k))
-                  r_k A_k - c_kl (old_k - logprob_k)                    mode "penalty"
-        ADDED to the parameters' .grad as loss.backward() would (None becomes the tensor), in torch.nn.Linear's layouts.  The means
-        are over the n positions (scale 1 / n); a position whose log-probability is NaN (index out of range, action outside the live
-        rows) contributes nothing.  Returns (stats float64 [6] on the device: counted positions, sum u, sum H, sum (old - new),
-        positions clipped, positions not counted; logprobs float32 [n]; entropy float32 [n]) — nothing is read back, nothing waits.
-        Under evaluate_at's conditions for the kernels: bbx_pmlp_ppo_grad_at / bbx_pmlp2_ppo_grad_at (no autograd, no torch op over
-        the n positions); anywhere else the same formulae with torch ops through evaluate_at and backward()."""
-        depth = self._in_place_depth(states, actions, rows)
-        if depth:
-            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
-            return self._ppo_kernels(depth, states, rows, actions, idx, old_logprobs, advantages, clip, ent_coef, mode, c_kl)
-        return self._ppo_torch(self.evaluate_at(states, actions, rows, index), old_logprobs, advantages, clip, ent_coef, mode, c_kl)
-
-    def ppo_step(self, states, actions, rows=None, old_logprobs=None, advantages=None, clip=0.2, ent_coef=0.0, mode="clip", c_kl=0.0):
-        """ppo_step_at for gathered tensors, as evaluate takes them: states int [N, R, cols], actions [N], rows [N] (None: the rows
-        whose last column is not -1) — bbx_pmlp_ppo_grad / bbx_pmlp2_ppo_grad under evaluate()'s conditions for the kernels."""
-        N, R, cols = states.shape
-        lin = self.embedding[0]
-        depth = 0
-        if states.is_cuda and 1 <= R <= 2048:
-            if len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32 and self.fused_ok(cols, lin.out_features):
-                depth = 1
-            elif (self.deep_kernels and len(self.embedding) == 2 and self.deep_ok(cols)
-                  and all(q.is_cuda and q.dtype == torch.float32 for q in self.parameters())):
-                depth = 2
-        if depth:
-            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
-            st = states if states.dtype == torch.int32 else states.to(torch.int32)
-            return self._ppo_kernels(depth, st.contiguous(), rows, actions.to(torch.int32).contiguous(), None, old_logprobs, advantages, clip,
-                                     ent_coef, mode, c_kl)
-        return self._ppo_torch(self.evaluate(states, actions, rows), old_logprobs, advantages, clip, ent_coef, mode, c_kl)
-
-    def _ppo_workspace(self, depth, N, R, cols, hidden, device):
-        """The workspace of bbx_pmlp_ppo_grad / bbx_pmlp2_ppo_grad, kept between calls (it grows only; calls on one stream run in
-        order)."""
-        lib = _ffi.lib()
-        nfl = lib.bbx_pmlp_ppo_workspace_floats(N, R, cols, *hidden) if depth == 1 else lib.bbx_pmlp2_ppo_workspace_floats(N, R, cols, *hidden)
-        _ffi.check(min(nfl, 0))
-        ws = self.__dict__.get("_ppo_ws")
-        if ws is None or ws.numel() < nfl or ws.device != device:
-            ws = torch.empty(nfl, dtype=torch.float32, device=device)
-            self.__dict__["_ppo_ws"] = ws
-        return ws
-
-    def _ppo_kernels(self, depth, states, rows, actions, index, old_logprobs, advantages, clip, ent_coef, mode, c_kl):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        dev = states.device
-        old = old_logprobs.to(device=dev, dtype=torch.float32).contiguous()
-        adv = advantages.to(device=dev, dtype=torch.float32).contiguous()
-        if old.numel() != N or adv.numel() != N:
-            raise ValueError("ppo_step: %d positions, %d old log-probabilities, %d advantages" % (N, old.numel(), adv.numel()))
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        logp, ent, coef = new(N), new(N), new(2 * N)
-        stats = torch.empty(6, dtype=torch.float64, device=dev)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        loss = (self.LOSS_MODES[mode], C.c_float(1.0 / N if N else 0.0), C.c_float(clip), C.c_float(ent_coef), C.c_float(c_kl))
-        lib = _ffi.lib()
-        with torch.cuda.device(dev):
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            src = (p(states), p(rows), p(actions)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
-            if depth == 1:
-                w = self._fused_weights()
-                hidden = (w["hidden"],)
-                grads = [new(cols, hidden[0]), new(hidden[0]), new(hidden[0]), new(1)]
-                fn = lib.bbx_pmlp_ppo_grad if index is None else lib.bbx_pmlp_ppo_grad_at
-            else:
-                w = self._deep_weights()
-                hidden = tuple(w["hidden"])
-                grads = [new(cols, hidden[0]), new(hidden[0]), new(hidden[0], hidden[1]), new(hidden[1]), new(hidden[1]), new(1)]
-                fn = lib.bbx_pmlp2_ppo_grad if index is None else lib.bbx_pmlp2_ppo_grad_at
-            ws = self._ppo_workspace(depth, N, R, cols, hidden, dev)
-            _ffi.check(fn(*src, w["prepared"], *hidden, p(old), p(adv), *loss, p(logp), p(ent), p(coef), p(stats), p(ws), *[p(g) for g in grads], s))
-        # torch.nn.Linear's layouts, added as backward() would
-        lin = self.embedding[0]
-        if depth == 1:
-            params = (lin.weight, lin.bias, self.deciding.weight, self.deciding.bias)
-            shaped = (grads[0].t(), grads[1], grads[2].view(1, -1), grads[3])
-        else:
-            l2 = self.embedding[1]
-            params = (lin.weight, lin.bias, l2.weight, l2.bias, self.deciding.weight, self.deciding.bias)
-            shaped = (grads[0].t(), grads[1], grads[2].t(), grads[3], grads[4].view(1, -1), grads[5])
-        for q, g in zip(params, shaped):
-            if q.grad is None:
-                q.grad = g.contiguous()
-            else:
-                q.grad.add_(g)
-        return stats, logp, ent
-
-    def _ppo_torch(self, evaluated, old_logprobs, advantages, clip, ent_coef, mode, c_kl):
-        """The loss epilogue of the kernels with torch ops, float32 in the same order, and backward() through `evaluated`."""
-        logp, ent = evaluated
-        kind = self.LOSS_MODES[mode]
-        n = logp.numel()
-        old = old_logprobs.to(device=logp.device, dtype=torch.float32)
-        A = advantages.to(device=logp.device, dtype=torch.float32)
-        counted = ~torch.isnan(logp)
-        new = torch.where(counted, logp, old.detach())               # (a NaN must not reach exp: 0 * NaN in its backward)
-        r = torch.exp(new - old)
-        clipped = torch.zeros_like(counted)
-        if kind == 0:
-            u = new * A
-        elif kind == 1:
-            a, b = r * A, torch.clamp(r, 1.0 - clip, 1.0 + clip) * A
-            u = torch.min(a, b)
-            clipped = (a > b) & counted
-        else:
-            u = r * A - c_kl * (old - new)
-        zero = torch.zeros_like(u)
-        u = torch.where(counted, u, zero); H = torch.where(counted, ent, zero)
-        if n:
-            loss = -u.mean() - ent_coef * H.mean()
-            if loss.requires_grad:
-                loss.backward()
-        d = lambda x: x.detach().to(torch.float64).sum()
-        stats = torch.stack([d(counted), d(u), d(H), d(torch.where(counted, old - new, zero)), d(clipped), d(~counted)])
-        return stats, logp.detach(), ent.detach()
-
-    def evaluate_torch(self, states, actions, rows=None):
-        """evaluate with torch ops and autograd (any depth, any device; the baseline of the kernels): forward, gather, and
-        -(exp(lp) lp) summed over the live rows."""
-        N, R, _ = states.shape
-        if rows is None:
-            lp = self.forward(states)
-            live = states[:, :, -1] != -1
-        else:                                                         # (the count masks, whatever the rows beyond it hold)
-            live = torch.arange(R, device=states.device)[None, :] < torch.clamp(rows.to(torch.int64), 0, R)[:, None]
-            lg = self._logits(states)
-            lp = torch.log_softmax(torch.where(live, lg, torch.full_like(lg, -1e9)), dim=-1)
-        n = live.sum(1)
-        a = actions.to(torch.int64)
-        ok = (a >= 0) & (a < n)
-        picked = lp.gather(1, torch.where(ok, a, torch.zeros_like(a))[:, None]).squeeze(1)
-        zero = torch.zeros_like(picked)
-        logp = torch.where(n > 0, torch.where(ok, picked, torch.full_like(picked, float("nan"))), zero)
-        lpl = torch.where(live, lp, torch.zeros_like(lp))
-        ent = torch.where(n > 0, -(torch.exp(lpl) * lpl * live.to(lp.dtype)).sum(dim=1), zero)
-        return logp, ent
-
-    def _logits(self, batch):
-        x = batch.to(self.deciding.weight.dtype)
-        for layer in self.embedding:
-            x = torch.relu(layer(x))
-        return self.deciding(x).squeeze(-1)
-
-    def act_torch(self, obs, rows, u, actions=None, logprobs=None, greedy=False):
-        """The same draw with torch ops (the reference of the fused kernel; any depth).  greedy=True: the argmax over the live
-        rows, the first index on ties (u unused, may be None)."""
-        lp = self.forward(obs)
-        n = torch.clamp(rows, max=obs.shape[1]).to(torch.int64)
-        valid = torch.arange(obs.shape[1], device=obs.device)[None, :] < n[:, None]
-        if greedy:
-            best = torch.where(valid, lp, torch.full_like(lp, float("-inf")))
-            top = best.max(dim=1, keepdim=True).values
-            a = ((best == top) & valid).to(torch.int64).argmax(dim=1)   # (0 / 1 flags: argmax returns the first 1; no live row: 0)
-        else:
-            p = torch.where(valid, torch.exp(lp - lp.max(dim=1, keepdim=True).values), torch.zeros_like(lp))
-            cdf = torch.cumsum(p, dim=1)
-            target = u * cdf[:, -1]
-            a = torch.minimum((cdf <= target[:, None]).sum(dim=1), n - 1).clamp(min=0)
-        out_a = a.to(torch.int32)
-        out_l = lp.gather(1, a[:, None]).squeeze(1)
-        if actions is not None:
-            actions.copy_(out_a); out_a = actions
-        if logprobs is not None:
-            logprobs.copy_(out_l); out_l = logprobs
-        return out_a, out_l
-
-
-class _PMLPValueEvaluate(torch.autograd.Function):
-    """The values of a one-hidden-layer PMLPValue through bbx_pmlp_value, differentiable with respect to the four parameter tensors
-    through bbx_pmlp_value_grad (the hidden activations are recomputed there).  No gradient for states or rows.
-    index (int32 [n], optional): as in _PMLPEvaluate — states and rows are whole buffers read in place (bbx_pmlp_value_at /
-    bbx_pmlp_value_grad_at), the output has length n."""
-
-    @staticmethod
-    def forward(ctx, critic, states, rows, w1, b1, w2, b2, index=None):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        values = torch.empty(N, dtype=torch.float32, device=states.device)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(states.device):
-            w = critic._fused_weights()
-            # (the prepared buffer is refilled in place when the weights change: backward reads THIS forward pass's weights from a
-            # copy of its own, made on the stream behind the fill)
-            prep = w["keep"].clone()
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
-            fn = _ffi.lib().bbx_pmlp_value if index is None else _ffi.lib().bbx_pmlp_value_at
-            _ffi.check(fn(*src, p(prep), w["hidden"], critic.pool_id, p(values), None, s))
-        ctx.critic, ctx.prep, ctx.hidden, ctx.pool = critic, prep, w["hidden"], critic.pool_id
-        ctx.save_for_backward(states, rows, w1, b1, w2, b2, index)
-        return values
-
-    @staticmethod
-    def backward(ctx, gvalue):
-        states, rows, w1, b1, w2, b2, index = ctx.saved_tensors
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        hidden = ctx.hidden
-        dev = states.device
-        gvalue = gvalue.contiguous().float()
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        gw1, gb1, gw2, gb2 = new(cols, hidden), new(hidden), new(hidden), new(1)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with torch.cuda.device(dev):
-            ws = ctx.critic._workspace("grad", N, R, cols, hidden, dev)
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
-            fn = _ffi.lib().bbx_pmlp_value_grad if index is None else _ffi.lib().bbx_pmlp_value_grad_at
-            _ffi.check(fn(*src, p(ctx.prep), hidden, ctx.pool, p(gvalue), p(ws), p(gw1), p(gb1), p(gw2), p(gb2), s))
-        return None, None, None, gw1.t().to(w1.dtype), gb1.to(b1.dtype), gw2.view(1, -1).to(w2.dtype), gb2.to(b2.dtype), None
-
-
-class PMLPValue(torch.nn.Module):
-    """A learned value baseline (critic) over the observation block: the row embedding of PMLPPolicy (`embedding`, relu), one
-    linear unit per row (`head`), and a pool over a state's live rows in place of the softmax:
-        pool="sum"   V = sum_r z_r        pool="mean"   V = that sum / n        pool="lse"   V = log sum_r exp z_r
-    A state without live rows is worth 0.  One hidden layer of at most 256 units over at most 64 columns, float32 on the GPU: the
-    HIP kernels (bbx_pmlp_value / bbx_pmlp_value_grad / bbx_pmlp_value_fit and their _at forms, which read a trajectory buffer in
-    place); CPU tensors, more hidden layers or wider ones: the torch path (forward, values_torch, evaluate_torch).  `last_path`
-    names the path the last call took ("kernels" or "torch")."""
-
-    POOLS = {"sum": 0, "mean": 1, "lse": 2}                           # BBX_POOL_* of include/bbx.h
-
-    def __init__(self, cols, hidden_layers=(128,), pool="sum"):
-        super().__init__()
-        if pool not in self.POOLS:
-            raise ValueError("PMLPValue: pool is one of %s (got %r)" % (sorted(self.POOLS), pool))
-        dims = [cols] + list(hidden_layers)
-        self.embedding = torch.nn.ModuleList([torch.nn.Linear(a, b) for a, b in zip(dims[:-1], dims[1:])])
-        self.head = torch.nn.Linear(dims[-1], 1)
-        self.cols, self.pool, self.pool_id = cols, pool, self.POOLS[pool]
-        self.last_path = None
-
-    # ---- the torch path
-    def _scores(self, batch):
-        x = batch.to(self.head.weight.dtype)
-        for layer in self.embedding:
-            x = torch.relu(layer(x))
-        return self.head(x).squeeze(-1)
-
-    def evaluate_torch(self, states, rows=None):
-        """Values float [N] of states int [N, R, cols] with torch ops and autograd (any depth, any device; the baseline of the
-        kernels).  rows [N]: the live rows per state (None: those whose last column is not -1)."""
-        self.last_path = "torch"
-        N, R, _ = states.shape
-        if rows is None:
-            live = states[:, :, -1] != -1
-        else:                                                         # (the count masks, whatever the rows beyond it hold)
-            live = torch.arange(R, device=states.device)[None, :] < torch.clamp(rows.to(torch.int64), 0, R)[:, None]
-        z = self._scores(states)
-        n = live.sum(1)
-        zero = torch.zeros_like(z)
-        if self.pool == "lse":
-            v = torch.logsumexp(torch.where(live, z, torch.full_like(z, -1e9)), dim=1)
-        else:
-            v = torch.where(live, z, zero).sum(dim=1)
-            if self.pool == "mean":
-                v = v / torch.clamp(n, min=1).to(v.dtype)
-        return torch.where(n > 0, v, torch.zeros_like(v))
-
-    def forward(self, batch):
-        """int [B, R, cols] with -1 padding -> values [B]."""
-        return self.evaluate_torch(batch)
-
-    @torch.no_grad()
-    def values_torch(self, states, rows=None, out=None, out64=None):
-        R, cols = states.shape[-2:]
-        v = self.evaluate_torch(states.reshape(-1, R, cols), None if rows is None else rows.reshape(-1))
-        return self._deliver(v, out, out64)
-
-    @staticmethod
-    def _deliver(v, out, out64):
-        if out64 is not None:
-            out64.view(-1).copy_(v.to(torch.float64))
-        if out is not None:
-            out.view(-1).copy_(v)
-        return out if out is not None else (out64 if out64 is not None else v)
-
-    # ---- the kernels
-    def kernels_ok(self, states):
-        """Whether the HIP kernels take states [..., R, cols] with this module's weights (otherwise: the torch path)."""
-        R, cols = states.shape[-2:]
-        lin = self.embedding[0]
-        return (states.is_cuda and len(self.embedding) == 1 and lin.weight.is_cuda and lin.weight.dtype == torch.float32
-                and PMLPPolicy.fused_ok(cols, lin.out_features) and 1 <= R <= 2048)
-
-    def _in_place(self, states, rows):
-        """Whether the _at kernels can read states [..., R, cols] and rows where they lie (contiguous int32 CUDA tensors of
-        matching sizes): a buffer is never converted or copied as a whole."""
-        R, cols = states.shape[-2:]
-        return (self.kernels_ok(states) and states.numel() == rows.numel() * R * cols
-                and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in (states, rows)))
-
-    def _fused_weights(self):
-        """The kernels' view of the weights (bbx_pmlp_prepare, the one-layer policy's layout), rebuilt only when a parameter
-        changed (an optimiser step bumps the tensors' version counters), in the same buffer."""
-        if len(self.embedding) != 1:
-            raise ValueError("_fused_weights: the kernels take one hidden layer (this critic has %d)" % len(self.embedding))
-        lin = self.embedding[0]
-        key = tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        c = self.__dict__.get("_fused_cache")
-        if c is None or c["key"] != key:
-            cols, hidden = lin.in_features, lin.out_features
-            w1 = lin.weight.detach().t().contiguous().float()
-            b1 = lin.bias.detach().contiguous().float()
-            w2 = self.head.weight.detach().reshape(-1).contiguous().float()
-            nfl = _ffi.lib().bbx_pmlp_prepared_floats(cols, hidden)
-            _ffi.check(min(nfl, 0))
-            prep = c["keep"] if c is not None and c["keep"].numel() == nfl and c["keep"].device == w1.device else \
-                torch.empty(nfl, dtype=torch.float32, device=w1.device)
-            # (b2 travels by value in the C call; reading it back would make every optimiser step wait for the device: the call gets
-            # 0 and the bias is copied on the device into its place, the first of the layout's last four floats)
-            _ffi.check(_ffi.lib().bbx_pmlp_prepare(C.c_void_p(w1.data_ptr()), C.c_void_p(b1.data_ptr()), C.c_void_p(w2.data_ptr()),
-                                                   C.c_float(0.0), cols, hidden, C.c_void_p(prep.data_ptr()),
-                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            prep[nfl - 4:nfl - 3].copy_(self.head.bias.detach().reshape(1))
-            c = {"key": key, "keep": prep, "prepared": C.c_void_p(prep.data_ptr()), "hidden": hidden}
-            self.__dict__["_fused_cache"] = c
-        return c
-
-    def _workspace(self, kind, N, R, cols, hidden, device):
-        """The workspace of bbx_pmlp_value_grad ("grad") / bbx_pmlp_value_fit ("fit"), kept between calls (it grows only; calls on
-        one stream run in order)."""
-        lib = _ffi.lib()
-        nfl = (lib.bbx_pmlp_value_fit_workspace_floats if kind == "fit" else lib.bbx_pmlp_value_grad_workspace_floats)(N, R, cols, hidden)
-        _ffi.check(min(nfl, 0))
-        ws = self.__dict__.get("_ws")
-        if ws is None or ws.numel() < nfl or ws.device != device:
-            ws = torch.empty(nfl, dtype=torch.float32, device=device)
-            self.__dict__["_ws"] = ws
-        return ws
-
-    @staticmethod
-    def _row_counts(states, rows):
-        return (states[:, :, -1] != -1).sum(1).to(torch.int32) if rows is None else rows
-
-    def _value_call(self, states, rows, index, out, out64):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        dev = states.device
-        if out is None and out64 is None:
-            out = torch.empty(N, dtype=torch.float32, device=dev)
-        for o, dt in ((out, torch.float32), (out64, torch.float64)):
-            if o is not None and not (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() == N):
-                raise ValueError("PMLPValue.values: out / out64 are contiguous float32 / float64 CUDA tensors of %d elements" % N)
-        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        with torch.cuda.device(dev):
-            w = self._fused_weights()
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
-            fn = _ffi.lib().bbx_pmlp_value if index is None else _ffi.lib().bbx_pmlp_value_at
-            _ffi.check(fn(*src, w["prepared"], w["hidden"], self.pool_id, p(out), p(out64), s))
-        self.last_path = "kernels"
-        return out if out is not None else out64
-
-    @torch.no_grad()
-    def values(self, states, rows, out=None, out64=None):
-        """Values of states int [..., R, cols] with rows [...] live rows each, no autograd: float32 into `out` and / or the same
-        numbers widened into `out64` (float64: what DeviceTrajectoryBuffer.values holds), each of rows.numel() elements; neither:
-        a new float32 tensor.  Returns out (out64 where only that was given).  On the GPU under kernels_ok: one bbx_pmlp_value
-        call, over the tensors in place where they are contiguous int32; otherwise values_torch."""
-        if not self.kernels_ok(states):
-            return self.values_torch(states, rows, out, out64)
-        R, cols = states.shape[-2:]
-        st = (states if states.dtype == torch.int32 else states.to(torch.int32)).contiguous()
-        rw = self._row_counts(st.view(-1, R, cols), None if rows is None else rows.reshape(-1)).to(torch.int32).contiguous()
-        return self._value_call(st, rw, None, out, out64)
-
-    @torch.no_grad()
-    def values_at(self, states, rows, index, out=None, out64=None):
-        """values() of the recorded states index[k] of the buffers states [S, R, cols] or [T, B, R, cols] and rows, read in place
-        (bbx_pmlp_value_at; an index outside the buffer: NaN); where the kernels cannot read them in place the n states are
-        gathered."""
-        if self._in_place(states, rows):
-            return self._value_call(states, rows, index.to(device=states.device, dtype=torch.int32).contiguous(), out, out64)
-        st, rw = self._gather(states, rows, index)
-        return self.values(st, rw, out, out64)
-
-    @staticmethod
-    def _gather(states, rows, index):
-        R, cols = states.shape[-2:]
-        j = index.to(device=states.device, dtype=torch.int64)
-        if states.dim() == 4:                                         # (no reshape: a non-contiguous buffer would be copied whole)
-            t, b = j // states.shape[1], j % states.shape[1]
-            return states[t, b], rows[t, b]
-        return states[j], rows[j]
-
-    def evaluate(self, states, rows=None):
-        """Values float32 [N] of states int [N, R, cols], differentiable with respect to the module's parameters: under kernels_ok
-        bbx_pmlp_value forward and bbx_pmlp_value_grad backward; otherwise evaluate_torch."""
-        if not self.kernels_ok(states):
-            return self.evaluate_torch(states, rows)
-        rows = self._row_counts(states, rows).to(torch.int32).contiguous()
-        st = states if states.dtype == torch.int32 else states.to(torch.int32)
-        self.last_path = "kernels"
-        lin = self.embedding[0]
-        return _PMLPValueEvaluate.apply(self, st.contiguous(), rows, lin.weight, lin.bias, self.head.weight, self.head.bias)
-
-    def evaluate_at(self, states, rows, index):
-        """evaluate() of the recorded states index[k] without gathering them (bbx_pmlp_value_at / bbx_pmlp_value_grad_at), as
-        PMLPPolicy.evaluate_at; where the kernels cannot read the buffers in place the n states are gathered."""
-        if self._in_place(states, rows):
-            self.last_path = "kernels"
-            lin = self.embedding[0]
-            idx = index.to(device=states.device, dtype=torch.int32).contiguous()
-            return _PMLPValueEvaluate.apply(self, states, rows, lin.weight, lin.bias, self.head.weight, self.head.bias, idx)
-        return self.evaluate(*self._gather(states, rows, index))
-
-    def fit_step_at(self, states, rows, index, targets):
-        """One minibatch of the squared-error fit in one library call (bbx_pmlp_value_fit_at): from the recorded states index[k] of
-        the buffers states / rows and the targets [n] to the gradients of
-            L = 1/2 mean_k (V_k - target_k)^2
-        ADDED to the parameters' .grad as loss.backward() would.  Returns (stats float64 [6] on the device: counted positions,
-        sum d^2, sum V, sum target, sum target^2, positions not counted; values float32 [n]) — nothing is read back, nothing waits.
-        Where the kernels cannot read the buffers in place: fit_step on the gathered states."""
-        if self._in_place(states, rows):
-            return self._fit_kernels(states, rows, index.to(device=states.device, dtype=torch.int32).contiguous(), targets)
-        st, rw = self._gather(states, rows, index)
-        return self.fit_step(st, rw, targets)
-
-    def fit_step(self, states, rows, targets):
-        """fit_step_at for gathered tensors: states int [N, R, cols], rows [N] (None: the rows whose last column is not -1) —
-        bbx_pmlp_value_fit under kernels_ok; otherwise the same formulae with torch ops and backward()."""
-        if self.kernels_ok(states):
-            rows = self._row_counts(states, rows).to(torch.int32).contiguous()
-            st = states if states.dtype == torch.int32 else states.to(torch.int32)
-            return self._fit_kernels(st.contiguous(), rows, None, targets)
-        v = self.evaluate_torch(states, rows)
-        n = v.numel()
-        t = targets.to(device=v.device, dtype=v.dtype)
-        d = v - t
-        if n:
-            loss = 0.5 * (d * d).sum() / n
-            if loss.requires_grad:
-                loss.backward()
-        s = lambda x: x.detach().to(torch.float64).sum()
-        zero = torch.zeros((), dtype=torch.float64, device=v.device)
-        stats = torch.stack([zero + n, s(d * d), s(v), s(t), s(t * t), zero])
-        return stats, v.detach()
-
-    def _fit_kernels(self, states, rows, index, targets):
-        R, cols = states.shape[-2:]
-        S = rows.numel()
-        N = S if index is None else index.numel()
-        dev = states.device
-        tg = targets.to(device=dev, dtype=torch.float32).contiguous()
-        if tg.numel() != N:
-            raise ValueError("fit_step: %d positions, %d targets" % (N, tg.numel()))
-        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        values, coef = new(N), new(N)
-        stats = torch.empty(6, dtype=torch.float64, device=dev)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        lib = _ffi.lib()
-        with torch.cuda.device(dev):
-            w = self._fused_weights()
-            hidden = w["hidden"]
-            grads = [new(cols, hidden), new(hidden), new(hidden), new(1)]
-            ws = self._workspace("fit", N, R, cols, hidden, dev)
-            s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            src = (p(states), p(rows)) + ((N,) if index is None else (S, p(index), N)) + (R, cols)
-            fn = lib.bbx_pmlp_value_fit if index is None else lib.bbx_pmlp_value_fit_at
-            _ffi.check(fn(*src, w["prepared"], hidden, self.pool_id, p(tg), C.c_float(1.0 / N if N else 0.0), p(values), p(coef), p(stats), p(ws),
-                          *[p(g) for g in grads], s))
-        self.last_path = "kernels"
-        lin = self.embedding[0]
-        for q, g in zip((lin.weight, lin.bias, self.head.weight, self.head.bias), (grads[0].t(), grads[1], grads[2].view(1, -1), grads[3])):
-            if q.grad is None:
-                q.grad = g.contiguous()
-            else:
-                q.grad.add_(g)
-        return stats, values
 
 
 class DeviceTrajectoryBuffer:
@@ -1030,6 +222,34 @@ class DeviceTrajectoryBuffer:
         return batches
 
 
+def _epochs(name, buffer, columns, optimizer, epochs, batch_size, shuffle, generator, step):
+    """The epoch loop of ppo_update and value_update, one epoch per iteration: ONE permutation of buffer.get_index()'s steps (shuffle;
+    from `generator`), then per minibatch of batch_size step(index slice, the same slice of each of get_index's `columns`) — which
+    returns the minibatch's six statistics on the device —, optimizer.step() and optimizer.zero_grad().  Yields (the minibatches'
+    stacked statistics float64 [minibatches, 6] — the epoch's one host read —, their sum, the counted positions or 1)."""
+    if buffer.states is None:
+        raise ValueError("%s: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))" % name)
+    whole = buffer.get_index(None)
+    cols = [whole[0]] + [whole[c] for c in columns]
+    n = int(cols[0].numel())
+    optimizer.zero_grad()
+    for _ in range(epochs):
+        if shuffle:
+            perm = torch.randperm(n, device=cols[0].device, generator=generator)
+            e = [x[perm] for x in cols]
+        else:
+            e = cols
+        stats = []
+        for i in range(0, n, batch_size):
+            k = min(i + batch_size, n)
+            stats.append(step(*[x[i:k] for x in e]))
+            optimizer.step()
+            optimizer.zero_grad()
+        st = torch.stack(stats).cpu().numpy() if stats else np.zeros((0, 6))
+        tot = st.sum(axis=0) if len(st) else np.zeros(6)
+        yield st, tot, max(tot[0], 1.0)
+
+
 def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef=0.0, kld_limit=None, mode="clip", shuffle=True, generator=None,
                c_kl=0.0):
     """The policy update of the reference (pg.py _fit_policy_model) over a finished DeviceTrajectoryBuffer with states: `epochs`
@@ -1039,29 +259,9 @@ def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef
     stacked statistics.  With kld_limit the update stops after an epoch whose mean old - new log-probability exceeds it.
     Returns one dict per epoch run: "stats" (float64 [minibatches, 6], ppo_step_at's), and over the epoch's counted positions
     "loss", "entropy", "kl" (mean old - new) and "clip_frac"."""
-    if buffer.states is None:
-        raise ValueError("ppo_update: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
-    idx, _, old, adv, _ = buffer.get_index(None)
-    n = int(idx.numel())
+    step = lambda i, o, a: policy.ppo_step_at(buffer.states, buffer.actions, buffer.rows, i, o, a, clip=clip, ent_coef=ent_coef, mode=mode, c_kl=c_kl)[0]
     out = []
-    optimizer.zero_grad()
-    for _ in range(epochs):
-        if shuffle:
-            perm = torch.randperm(n, device=idx.device, generator=generator)
-            e_idx, e_old, e_adv = idx[perm], old[perm], adv[perm]
-        else:
-            e_idx, e_old, e_adv = idx, old, adv
-        stats = []
-        for i in range(0, n, batch_size):
-            k = min(i + batch_size, n)
-            st, _, _ = policy.ppo_step_at(buffer.states, buffer.actions, buffer.rows, e_idx[i:k], e_old[i:k], e_adv[i:k], clip=clip, ent_coef=ent_coef,
-                                          mode=mode, c_kl=c_kl)
-            optimizer.step()
-            optimizer.zero_grad()
-            stats.append(st)
-        st = torch.stack(stats).cpu().numpy() if stats else np.zeros((0, 6))     # the epoch's one host read
-        tot = st.sum(axis=0) if len(st) else np.zeros(6)
-        cnt = max(tot[0], 1.0)
+    for st, tot, cnt in _epochs("ppo_update", buffer, (2, 3), optimizer, epochs, batch_size, shuffle, generator, step):
         out.append({"stats": st, "loss": -(tot[1] + ent_coef * tot[2]) / cnt, "entropy": tot[2] / cnt, "kl": tot[3] / cnt, "clip_frac": tot[4] / cnt})
         if kld_limit is not None and out[-1]["kl"] > kld_limit:
             break
@@ -1076,28 +276,9 @@ def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, ge
     minibatches' stacked statistics.  Returns one dict per epoch: "stats" (float64 [minibatches, 6], fit_step_at's), and over the
     epoch's counted positions "loss" (1/2 mean (V - target)^2, each minibatch under the weights it saw) and "explained_variance"
     (1 - mean (V - target)^2 / var(target); NaN where the targets do not vary)."""
-    if buffer.states is None:
-        raise ValueError("value_update: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
-    idx, _, _, _, ret = buffer.get_index(None)
-    n = int(idx.numel())
+    step = lambda i, r: critic.fit_step_at(buffer.states, buffer.rows, i, r)[0]
     out = []
-    optimizer.zero_grad()
-    for _ in range(epochs):
-        if shuffle:
-            perm = torch.randperm(n, device=idx.device, generator=generator)
-            e_idx, e_ret = idx[perm], ret[perm]
-        else:
-            e_idx, e_ret = idx, ret
-        stats = []
-        for i in range(0, n, batch_size):
-            k = min(i + batch_size, n)
-            st, _ = critic.fit_step_at(buffer.states, buffer.rows, e_idx[i:k], e_ret[i:k])
-            optimizer.step()
-            optimizer.zero_grad()
-            stats.append(st)
-        st = torch.stack(stats).cpu().numpy() if stats else np.zeros((0, 6))     # the epoch's one host read
-        tot = st.sum(axis=0) if len(st) else np.zeros(6)
-        cnt = max(tot[0], 1.0)
+    for st, tot, cnt in _epochs("value_update", buffer, (4,), optimizer, epochs, batch_size, shuffle, generator, step):
         var = tot[4] / cnt - (tot[3] / cnt) ** 2
         out.append({"stats": st, "loss": 0.5 * tot[1] / cnt, "explained_variance": 1.0 - (tot[1] / cnt) / var if var > 0 else float("nan")})
     return out

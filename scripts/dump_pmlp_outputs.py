@@ -10,7 +10,9 @@ outside its state's rows), and an index list with a repeated index, -1 and n_src
 count NB in {1, 2, 4, 8} and every k-step count KS in {3, 6, 10, 16, 32} of the one-layer kernels, two column blocks (64 columns) and
 more than one unit group (256 units).  Calls: bbx_pmlp_grad[_at] with and without d_gent, bbx_pmlp_value_grad[_at] for the three pools,
 bbx_pmlp_ppo_grad_at and bbx_pmlp_value_fit_at with statistics and workspace tail, bbx_pmlp_act, bbx_pmlp_act_greedy; once:
-bbx_pmlp2_grad, and one bbx_policy_step_device step (the fused step kernel) on 64 environments with 6 and with 12 columns."""
+bbx_pmlp2_grad, and one bbx_policy_step_device step (the fused step kernel) on 64 environments with 6 and with 12 columns.
+A second group, module/..., goes through the Python classes instead (a refactor of deepgroebner_amd/pmlp.py must not move a bit
+either): see module_arrays."""
 import ctypes as C
 import os
 import sys
@@ -31,6 +33,80 @@ def compare(a, b):
     bad += [k for k in A.files if k in B.files and (A[k].dtype != B[k].dtype or A[k].shape != B[k].shape or A[k].tobytes() != B[k].tobytes())]
     print("%d arrays, %d bytes; differing: %s" % (len(A.files), sum(A[k].nbytes for k in A.files), bad or "none"))
     return 1 if bad else 0
+
+
+def module_arrays(keep, device="cuda"):
+    """The second group, module/...: the same kind of cases through the public methods of PMLPPolicy and PMLPValue and through
+    ppo_update / value_update, on the first and third shape of SHAPES and the two-layer case."""
+    import torch
+    from deepgroebner_amd import DeviceTrajectoryBuffer, ppo_update, value_update
+    from tests import policy_cases as pc
+    from tests import value_cases as vc
+    dev = lambda a, dt=None: torch.from_numpy(np.ascontiguousarray(a if dt is None else np.asarray(a, dtype=dt))).to(device)
+    grads = lambda m: [q.grad for q in m.parameters()]
+    for cols, hidden in ((6, (32,)), (12, (128,)), (12, (64, 128))):
+        tag = "module/" + pc.label(cols, hidden)
+        w, obs, rows = vc.value_case(cols, hidden, LIVE, R, 5100 + cols + sum(hidden))
+        rng = np.random.default_rng(88 + cols + len(hidden))
+        N = len(rows)
+        actions = (rng.integers(0, 1 << 30, size=N) % np.maximum(rows, 1)).astype(np.int32)
+        actions[4] = rows[4]                                      # one action outside the live rows
+        dobs, drows, dact, dindex = dev(obs), dev(rows), dev(actions), dev(INDEX, np.int32)
+        n = len(INDEX)
+        per = {m: [dev(rng.normal(size=m), np.float32) for _ in range(3)] for m in (N, n)}
+
+        def policy():
+            pol = pc.to_policy(w, device)
+            pol.deep_kernels = len(hidden) == 2
+            return pol
+
+        for at in (False, True):
+            a, b, c = per[n if at else N]
+            sfx = "_at" if at else ""
+            pol = policy()
+            lp, ent = pol.evaluate_at(dobs, dact, drows, dindex) if at else pol.evaluate(dobs, dact, drows)
+            torch.autograd.backward((lp, ent), (a, b))
+            keep("%s/evaluate%s" % (tag, sfx), lp.detach(), ent.detach(), *grads(pol))
+            for mode in ("pg", "clip", "penalty"):
+                pol = policy()
+                kw = dict(clip=0.2, ent_coef=0.01, mode=mode, c_kl=0.5)
+                res = pol.ppo_step_at(dobs, dact, drows, dindex, a, b, **kw) if at else pol.ppo_step(dobs, dact, drows, a, b, **kw)
+                keep("%s/ppo_step%s/%s" % (tag, sfx, mode), *res, *grads(pol))
+            if len(hidden) != 1:
+                continue
+            for pool in vc.POOLS:
+                what = "%s/%%s%s/%s" % (tag, sfx, pool)
+                cr = vc.to_critic(w, pool, device)
+                keep(what % "values", cr.values_at(dobs, drows, dindex) if at else cr.values(dobs, drows))
+                v = cr.evaluate_at(dobs, drows, dindex) if at else cr.evaluate(dobs, drows)
+                v.backward(c)
+                keep(what % "evaluate", v.detach(), *grads(cr))
+                cr = vc.to_critic(w, pool, device)
+                res = cr.fit_step_at(dobs, drows, dindex, c) if at else cr.fit_step(dobs, drows, c)
+                keep(what % "fit_step", *res, *grads(cr))
+
+        # one epoch of each update loop, in order, with SGD, on a buffer of 6 steps of 4 environments written by hand
+        T, B, RB = 6, 4, 8
+        buf = DeviceTrajectoryBuffer(T, B, obs_shape=(RB, cols), device=device)
+        brows = rng.integers(1, RB + 1, size=(T, B)).astype(np.int32)
+        bobs = pc.fill_padding(pc.random_blocks(T * B, RB, cols, 97 + cols, emax=3), brows.reshape(-1), False).reshape(T, B, RB, cols)
+        dones = rng.random(size=(T, B)) < 0.3
+        dones[T - 1, :3] = True                                   # (the fourth environment's last episode stays incomplete)
+        buf.states.copy_(dev(bobs)); buf.rows.copy_(dev(brows)); buf.dones.copy_(dev(dones))
+        buf.actions.copy_(dev((rng.integers(0, 1 << 30, size=(T, B)) % brows).astype(np.int32)))
+        buf.rewards.copy_(dev(-rng.integers(1, 20, size=(T, B)).astype(np.float64)))
+        buf.logprobs.copy_(dev(-rng.random(size=(T, B)) * 2.0, np.float32))
+        buf.t = T
+        pol = policy()
+        ep = ppo_update(pol, buf, torch.optim.SGD(pol.parameters(), lr=0.01), 1, 5, ent_coef=0.01, shuffle=False)
+        keep("%s/ppo_update" % tag, *[torch.as_tensor(np.asarray(ep[0][k], dtype=np.float64)) for k in ("stats", "loss", "entropy", "kl", "clip_frac")],
+             *[q.detach() for q in pol.parameters()])
+        if len(hidden) == 1:
+            for pool in vc.POOLS:
+                cr = vc.to_critic(w, pool, device)
+                ep = value_update(cr, buf, torch.optim.SGD(cr.parameters(), lr=0.01), 1, 5, shuffle=False)
+                keep("%s/value_update/%s" % (tag, pool), *[torch.as_tensor(np.asarray(ep[0][k], dtype=np.float64)) for k in ("stats", "loss", "explained_variance")],
+                     *[q.detach() for q in cr.parameters()])
 
 
 def main(path):
@@ -127,6 +203,7 @@ def main(path):
         env.policy_step_device(fw["prepared"], fw["hidden"], u, A, L, rew, done, rows, obs, RO, 1, s); env.sync()
         keep("policy_step/k%d" % k, A, L, rew, done, rows, obs)
 
+    module_arrays(keep)
     np.savez(path, **out)
     print("%d arrays, %d bytes -> %s" % (len(out), sum(v.nbytes for v in out.values()), path))
 
