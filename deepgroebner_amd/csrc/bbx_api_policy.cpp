@@ -201,6 +201,47 @@ int pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n_src, const
   if (d_stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, n, d_stats, (hipStream_t)stream))) return rc; }
   return pmlp_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_coef, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
 }
+// ... and over two hidden layers (bbx_pmlp2_value.h): the shape refusals of the two-layer training calls in front, then the
+// argument checks above, in their order
+int pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+                int hidden1, int hidden2, int pool, float* d_values, double* d_values64, void* stream, const PmlpFit* fit = nullptr) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || (!d_values && !d_values64 && !fit))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (int rc = refuse_pool(pool)) return rc;
+  if (n == 0) return BBX_OK;
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_value(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, d_index, n_src, fit,
+                                             di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+int pmlp2_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+                     int hidden1, int hidden2, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
+                     float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows || !d_gvalue)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
+  if (int rc = refuse_pool(pool)) return rc;
+  int dev = 0; DeviceInfo di{};
+  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
+  return launched_lds(bbx_launch_pmlp2_value_grad(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1,
+                                                  d_gw2, d_gb2, d_gw3, d_gb3, d_index, n_src, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+}
+int pmlp2_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
+                    int hidden1, int hidden2, int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats,
+                    float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows)),
+                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
+  if (int rc = refuse_pool(pool)) return rc;
+  if (n > 0 && (!d_targets || !d_coef)) return fail(BBX_E_ARG, "null argument");   // (d_stats null: no statistics wanted)
+  const int gfl = pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
+  if (fit_workspace(n, gfl) < 0) return BBX_E_ARG;
+  const PmlpFit fit{d_targets, d_coef, d_workspace + gfl, n, scale};
+  if (int rc = pmlp2_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, nullptr, stream, &fit)) return rc;
+  if (d_stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, n, d_stats, (hipStream_t)stream))) return rc; }
+  return pmlp2_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_coef, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
+                          d_gw3, d_gb3, stream);
+}
 
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
 int policy_rollout(bbx_batch* b, const float* d_prepared, int hidden, int hidden2, int (*admit)(const bbx_batch*, int cols, int h1, int h2),
@@ -434,6 +475,54 @@ int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int
   return pmlp2_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2,
                    PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
                    d_gw2, d_gb2, d_gw3, d_gb3, stream);
+}
+
+// ---- the critic over two hidden layers (bbx_pmlp2_value.h)
+int bbx_pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, int pool,
+                    float* d_values, double* d_values64, void* stream) {
+  return pmlp2_value(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, stream);
+}
+int bbx_pmlp2_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                       const float* d_prepared, int hidden1, int hidden2, int pool, float* d_values, double* d_values64, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, stream);
+}
+int bbx_pmlp2_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
+  return bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
+}
+int bbx_pmlp2_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                         int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
+                         float* d_gb3, void* stream) {
+  return pmlp2_value_grad(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
+                          d_gw3, d_gb3, stream);
+}
+int bbx_pmlp2_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                            const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1,
+                            float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2,
+                          d_gb2, d_gw3, d_gb3, stream);
+}
+int bbx_pmlp2_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
+  const int gfl = bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
+  return gfl < 0 ? gfl : fit_workspace(n, gfl);
+}
+int bbx_pmlp2_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                        int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
+                        float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  return pmlp2_value_fit(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_targets, scale, d_values, d_coef, d_stats,
+                         d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
+}
+int bbx_pmlp2_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                           const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_targets, float scale, float* d_values,
+                           float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
+                           float* d_gb3, void* stream) {
+  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
+  if (int rc = refuse_index(n_src, d_index, n)) return rc;
+  return pmlp2_value_fit(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_targets, scale, d_values, d_coef, d_stats,
+                         d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
 }
 
 int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,

@@ -60,6 +60,12 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
 extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                      int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
                                      float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
+                                      float* values, double* values64, const int32_t* index, int n_src, const struct PmlpFit* fit, int cus, int max_lds,
+                                      hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
+                                           const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
+                                           const int32_t* index, int n_src, int max_lds, hipStream_t stream);
 
 
 // The call in flight: what finish() waits for, continues and reports on.  Formed in two places only — start_flight() (a

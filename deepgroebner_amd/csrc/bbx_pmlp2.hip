@@ -28,6 +28,7 @@
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 #include "bbx_pmlp2_grad.h"
+#include "bbx_pmlp2_value.h"
 
 // (the prepared layout, pmlp2_hidden and the scoring of a tile, pmlp2_tile, live in bbx_pmlp.h: the policy rollouts inside
 // the step kernels run the same code)
@@ -217,12 +218,27 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
   return rc ? rc : (int)hipGetLastError();
 }
 
-// log-probability / entropy of recorded actions and the weight gradients for two hidden layers (bbx_pmlp2_grad.h);
+// log-probability / entropy of recorded actions and the weight gradients for two hidden layers (bbx_pmlp2_grad.h), and the critic
+// over the same weights (bbx_pmlp2_value.h);
 // BBX_P2G_SHAPES(M): M(HP1, HP2, KS) of the shape.  index != null: the indexed instantiations (position k is about recorded
 // state index[k] of n_src)
 #define BBX_P2G_K(M, N1, N2) do { if (ks == 3) M(N1, N2, 3); else if (ks == 8) M(N1, N2, 8); else M(N1, N2, 16); } while (0)
 #define BBX_P2G_SHAPES(M) do { if (hp1 == 64 && hp2 == 64) BBX_P2G_K(M, 64, 64); else if (hp1 == 64) BBX_P2G_K(M, 64, 128); \
                                else if (hp2 == 64) BBX_P2G_K(M, 128, 64); else BBX_P2G_K(M, 128, 128); } while (0)
+// how the forward kernels of the policy (bbx_pmlp2_logprob_kernel) and the critic (bbx_pmlp2_value_kernel) are launched: 8 waves
+// beside the staged weights, fewer where tall observation blocks (4 bytes of logits per row and wave) leave less room; two
+// workgroups per CU at the most, striding over the positions
+struct Pmlp2ForwardLaunch {
+  int waves, lgcap, blocks;
+  size_t ml;
+  Pmlp2ForwardLaunch(int n, int obs_rows, int hp1, int hp2, int cus, int max_lds) : waves(PMLP2_WAVES), lgcap(pmlp2_logprob_lgcap(obs_rows)) {
+    while (waves > 1 && pmlp2_logprob_lds_bytes(hp1, hp2, waves, obs_rows) > (size_t)max_lds) waves /= 2;
+    ml = pmlp2_logprob_lds_bytes(hp1, hp2, waves, obs_rows);
+    const int max_blocks = 2 * (cus > 0 ? cus : 256);
+    blocks = (n + waves - 1) / waves;
+    blocks = blocks < max_blocks ? blocks : max_blocks;
+  }
+};
 // (hipErrorInvalidValue: the device has less LDS per workgroup than the shape needs)
 extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                         int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss, int cus,
@@ -230,15 +246,10 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
   if (n <= 0) return 0;
   const PmlpLoss ls = loss ? *loss : PmlpLoss{};
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
-  // 8 waves beside the staged weights, fewer where tall observation blocks (4 bytes of logits per row and wave) leave less room
-  int waves = PMLP2_WAVES;
-  while (waves > 1 && pmlp2_logprob_lds_bytes(hp1, hp2, waves, obs_rows) > (size_t)max_lds) waves /= 2;
-  const size_t ml = pmlp2_logprob_lds_bytes(hp1, hp2, waves, obs_rows);
-  if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  const int lgcap = pmlp2_logprob_lgcap(obs_rows);
-  const int max_blocks = 2 * (cus > 0 ? cus : 256);
-  int blocks = (n + waves - 1) / waves;
-  blocks = blocks < max_blocks ? blocks : max_blocks;
+  const Pmlp2ForwardLaunch F(n, obs_rows, hp1, hp2, cus, max_lds);
+  if (F.ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  const int blocks = F.blocks, waves = F.waves, lgcap = F.lgcap;
+  const size_t ml = F.ml;
   int rc = 0;
 #define BBX_P2_LOGPROB_I(N1, N2, K, I, L) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K, I, L>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, \
                                                                                                     cols, wp, logprobs, entropy, lgcap, index, n_src, ls)
@@ -255,6 +266,16 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
 #undef BBX_P2_LOGPROB_I
   return rc ? rc : (int)hipGetLastError();
 }
+// the second kernel of the policy's and the critic's gradients, unless launching the first (rc) has failed: the `groups` slots of
+// every output added in order
+static int pmlp2_grad_reduce(int rc, const float* ws, int groups, int cols, int h1, int h2, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3,
+                             float* gb3, hipStream_t stream) {
+  if (rc) return rc;
+  if ((rc = (int)hipGetLastError())) return rc;
+  const int total = cols * h1 + h1 + h1 * h2 + 2 * h2 + 1;
+  hipLaunchKernelGGL(bbx_pmlp2_grad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3);
+  return (int)hipGetLastError();
+}
 extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
                                      int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
                                      float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream) {
@@ -262,20 +283,64 @@ extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, co
   const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
   const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows);
   if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  const Pmlp2PolicyHead head{actions, glogp, gent, 0};
   int rc = 0;
-#define BBX_P2_GRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I>>(groups, threads, ml, stream, obs, rows, actions, n, obs_rows, cols, wp, glogp, \
-                                                                                        gent, groups, ws, index, n_src)
+#define BBX_P2_GRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I, Pmlp2PolicyHead>>(groups, threads, ml, stream, obs, rows, n, obs_rows, cols, wp, \
+                                                                                                         head, groups, ws, index, n_src)
 #define BBX_P2_GRAD(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, false)
 #define BBX_P2_GRAD_AT(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, true)
   if (groups > 0) { if (index) BBX_P2G_SHAPES(BBX_P2_GRAD_AT); else BBX_P2G_SHAPES(BBX_P2_GRAD); }
 #undef BBX_P2_GRAD_AT
 #undef BBX_P2_GRAD
 #undef BBX_P2_GRAD_I
-  if (rc) return rc;
-  if ((rc = (int)hipGetLastError())) return rc;
-  const int total = cols * h1 + h1 + h1 * h2 + 2 * h2 + 1;
-  hipLaunchKernelGGL(bbx_pmlp2_grad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3);
-  return (int)hipGetLastError();
+  return pmlp2_grad_reduce(rc, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3, stream);
+}
+// the critic: values of n positions (fit != null: with the squared-error epilogue), in the frame of bbx_launch_pmlp2_logprob
+extern "C" int bbx_launch_pmlp2_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
+                                      float* values, double* values64, const int32_t* index, int n_src, const PmlpFit* fit, int cus, int max_lds,
+                                      hipStream_t stream) {
+  if (n <= 0) return 0;
+  const PmlpFit ft = fit ? *fit : PmlpFit{};
+  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
+  const Pmlp2ForwardLaunch F(n, obs_rows, hp1, hp2, cus, max_lds);
+  if (F.ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  const int blocks = F.blocks, waves = F.waves, lgcap = F.lgcap;
+  const size_t ml = F.ml;
+  int rc = 0;
+#define BBX_P2_VALUE_I(N1, N2, K, I, F) rc = launch_lds<bbx_pmlp2_value_kernel<N1, N2, K, I, F>>(blocks, waves * WAVE, ml, stream, obs, rows, n, obs_rows, cols, wp, \
+                                                                                                pool, values, values64, lgcap, index, n_src, ft)
+#define BBX_P2_VALUE(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, false, false)
+#define BBX_P2_VALUE_AT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, true, false)
+#define BBX_P2_FIT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, false, true)
+#define BBX_P2_FIT_AT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, true, true)
+  if (fit) { if (index) BBX_P2G_SHAPES(BBX_P2_FIT_AT); else BBX_P2G_SHAPES(BBX_P2_FIT); }
+  else if (index) BBX_P2G_SHAPES(BBX_P2_VALUE_AT); else BBX_P2G_SHAPES(BBX_P2_VALUE);
+#undef BBX_P2_FIT_AT
+#undef BBX_P2_FIT
+#undef BBX_P2_VALUE_AT
+#undef BBX_P2_VALUE
+#undef BBX_P2_VALUE_I
+  return rc ? rc : (int)hipGetLastError();
+}
+// the critic's weight gradients: the policy's partition, workspace and second kernel
+extern "C" int bbx_launch_pmlp2_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
+                                           const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
+                                           const int32_t* index, int n_src, int max_lds, hipStream_t stream) {
+  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
+  const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
+  const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows, Pmlp2ValueHead::exact_a1);
+  if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  const Pmlp2ValueHead head{gvalue, pool};
+  int rc = 0;
+#define BBX_P2_VGRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I, Pmlp2ValueHead>>(groups, threads, ml, stream, obs, rows, n, obs_rows, cols, wp, \
+                                                                                                         head, groups, ws, index, n_src)
+#define BBX_P2_VGRAD(N1, N2, K) BBX_P2_VGRAD_I(N1, N2, K, false)
+#define BBX_P2_VGRAD_AT(N1, N2, K) BBX_P2_VGRAD_I(N1, N2, K, true)
+  if (groups > 0) { if (index) BBX_P2G_SHAPES(BBX_P2_VGRAD_AT); else BBX_P2G_SHAPES(BBX_P2_VGRAD); }
+#undef BBX_P2_VGRAD_AT
+#undef BBX_P2_VGRAD
+#undef BBX_P2_VGRAD_I
+  return pmlp2_grad_reduce(rc, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3, stream);
 }
 #undef BBX_P2G_SHAPES
 #undef BBX_P2G_K

@@ -9,7 +9,8 @@
 // sum and lg[a] - logz from pmlp_softmax_wave (= pmlp_sample's order): for an action bbx_pmlp2_act has just drawn from the same
 // block and weights the log-probability is that call's, bit for bit.
 //
-// Backward (bbx_pmlp2_grad_kernel + bbx_pmlp2_grad_reduce_kernel): a workgroup of NW = max(HP1, HP2) / 32 waves takes states
+// Backward (bbx_pmlp2_grad_kernel<..., HEAD> + bbx_pmlp2_grad_reduce_kernel; the text describes the policy's head, the critic's
+// differs in the states it skips and in g_r alone): a workgroup of NW = max(HP1, HP2) / 32 waves takes states
 // p, p + groups, ... (pmlp2_grad_groups(n) workgroups: bbx_pmlp_shape.h).  Wave w owns units 32 w .. 32 w + 31 of BOTH layers:
 // the columns dW1[:, slice], dW2[:, slice] (at most 32 + 64 accumulator registers) and the matching db1, db2, dw3.  Per state:
 //   the logits (pmlp2_tile, the tiles dealt to the waves), p_r, H, then g_r = glogp (delta_{r,a} - p_r) - gent p_r (log p_r + H)
@@ -33,7 +34,8 @@
 // caller's workspace and the second kernel adds the slots of every output in a fixed order: no floating-point atomics, and the
 // partition depends on (n, cols, hidden1, hidden2) alone.
 // Every barrier is reached by the whole workgroup: the state loop, the row count, the action and the tile loop are the same
-// for all its threads, and a state that contributes nothing (no row, one row, a bad action) is skipped before its first barrier.
+// for all its threads, and a state that contributes nothing (the head's takes(): no row, one row, a bad action) is skipped before its
+// first barrier.
 //
 // Indexed form (IDX; bbx_pmlp2_logprob_at, bbx_pmlp2_grad_at): position k of the call is about recorded state index[k] — obs, rows
 // and actions are read there, the per-call arrays (logprobs, entropy, glogp, gent) at k.  An index outside [0, n_src): NaN / NaN,
@@ -50,8 +52,9 @@ __host__ __device__ constexpr int pmlp2_logprob_lgcap(int obs_rows) { return ((p
 __host__ __device__ constexpr size_t pmlp2_logprob_lds_bytes(int hp1, int hp2, int waves, int obs_rows) {
   return ((size_t)hp1 * hp2 + 2 * hp2 + (size_t)waves * pmlp2_logprob_lgcap(obs_rows)) * sizeof(float);
 }
-__host__ __device__ constexpr size_t pmlp2_grad_lds_bytes(int hp1, int hp2, int obs_rows) {
-  return ((size_t)hp1 * hp2 + 2 * hp2 + pmlp2_grad_lgcap(obs_rows) + 32 * (hp1 + PMLP2_GRAD_PAD) + 32 * (hp2 + PMLP2_GRAD_PAD)) * sizeof(float);
+// (exact_a1: a head that keeps the low halves of the first layer's activations too — a third tile, behind the other two)
+__host__ __device__ constexpr size_t pmlp2_grad_lds_bytes(int hp1, int hp2, int obs_rows, bool exact_a1 = false) {
+  return ((size_t)hp1 * hp2 + 2 * hp2 + pmlp2_grad_lgcap(obs_rows) + (exact_a1 ? 64 : 32) * (hp1 + PMLP2_GRAD_PAD) + 32 * (hp2 + PMLP2_GRAD_PAD)) * sizeof(float);
 }
 // where W2[k][unit] lies in the permuted A2 [HP2 / 16][S4 = HP1 / 16][64][4] (the inverse of pmlp2_perm, bbx_pmlp2.hip)
 __host__ __device__ constexpr int pmlp2_a2_index(int k, int unit, int S4) {
@@ -135,11 +138,49 @@ __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* _
   }
 }
 
-template <int HP1, int HP2, int KS, bool IDX = false>
-__global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
-                                                                                     const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
-                                                                                     const float* __restrict__ wp, const float* __restrict__ glogp,
-                                                                                     const float* __restrict__ gent, int groups, float* __restrict__ ws,
+// The policy's head of the gradient kernel: which states contribute, and the row coefficients g_r that take the place of the scores
+// in LDS.  A head (the critic's: Pmlp2ValueHead, bbx_pmlp2_value.h) travels by value as a kernel argument and has
+//   state(s)                   what it reads of recorded state s (an index in range), the same in every thread of the workgroup
+//   takes(n)                   whether that state, with n live rows, contributes — workgroup-uniform, asked before the first barrier
+//   coefs(lg, n, k, lane, db3) called by the whole workgroup with the n > 0 scores of position k complete in lg (a barrier lies behind
+//                              them): what it needs of them, ONE barrier, then g_r over the scores, zero up to the next multiple of 32,
+//                              every thread its own entries r = threadIdx.x, + blockDim.x, ..., each added to db3
+//   exact_a1                   whether stage 2 recomputes z2 from a1 = relu(z1) as a float32 PAIR (hi + lo, good to 2^-48) instead of the one
+//                              float32 the tile holds: the critic's sum and mean pools have K_s = 1 in their bound, which takes the
+//                              activations at their exact values, and a second-layer unit that a single row holds active with a z2
+//                              left by cancellation then shows the 2^-24 of sum_k |a1_k W2_ku| a rounded a1 puts into it (measured:
+//                              2646 units of the bound against 64).  The policy's head keeps the single float: its outputs are
+//                              what they were, bit for bit
+struct Pmlp2PolicyHead {
+  static constexpr bool exact_a1 = false;
+  const int32_t* actions;
+  const float* glogp;
+  const float* gent;
+  int a;                                                                      // the action of the state in hand
+  __device__ __forceinline__ void state(int s) { a = uni(actions[s]); }
+  __device__ __forceinline__ bool takes(int n) const { return n > 1 && a >= 0 && a < n; }   // no row, one row (delta - p = 0) or a bad action: nothing
+  __device__ __forceinline__ void coefs(float* lg, int n, int k, int lane, float& db3) const {
+    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);                    // (every wave for itself: the same numbers)
+    const float H = pmlp_entropy_wave(lg, n, lane, sm);
+    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
+    const float rse = 1.f / sm.se;
+    const int n32 = (n + 31) & ~31;
+    __syncthreads();                                                          // (every wave has read the logits)
+    for (int r = (int)threadIdx.x; r < n32; r += (int)blockDim.x) {           // (every thread reads and writes its own entries only)
+      const float g = r < n ? pmlp_policy_coef(lg[r], r == a, sm, H, gl, ge, rse) : 0.f;
+      lg[r] = g; db3 += g;
+    }
+  }
+};
+
+// One kernel for the policy's gradients (HEAD = Pmlp2PolicyHead) and the critic's (Pmlp2ValueHead, bbx_pmlp2_value.h): the staging,
+// the state loop, the scores, then — behind the head — the f64 recomputation of both pre-activations, the three MFMA stages, the
+// accumulators and the partial layout bbx_pmlp2_grad_reduce_kernel reads.  (The body stays in the kernel itself: moved into a
+// device function that two kernels call, it is inlined with other register classes — 32 more AGPRs at 64 units.)
+template <int HP1, int HP2, int KS, bool IDX = false, class HEAD = Pmlp2PolicyHead>
+__global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows, int B,
+                                                                                     int obs_rows, int cols, const float* __restrict__ wp, HEAD head,
+                                                                                     int groups, float* __restrict__ ws,
                                                                                      const int32_t* __restrict__ index, int n_src) {
   constexpr int NB1 = HP1 / 32, NB2 = HP2 / 32, NW = NB1 > NB2 ? NB1 : NB2;  // pmlp2_grad_waves
   constexpr int CB = KS == 16 ? 2 : 1;                                        // pmlp2_grad_cb
@@ -158,6 +199,7 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
   float* lg = a2 + A2F + 2 * HP2;                                             // the state's logits, then its g_r
   float* a1t = lg + pmlp2_grad_lgcap(obs_rows);                               // [32][S1] relu(z1) of the tile
   float* dz2t = a1t + 32 * S1;                                                // [32][S2]
+  [[maybe_unused]] float* a1lo = dz2t + 32 * S2;                              // [32][S1] relu(z1) - (float)relu(z1) (HEAD::exact_a1 only)
   const int lane = lane_id(), w = uni((int)(threadIdx.x / WAVE));
   const int lr = lane & 31, lk = lane >> 5, l15 = lane & 15, l4 = lane >> 4;
   const bool own1 = w < NB1, own2 = w < NB2;                                  // (wave-uniform: does the wave own a slice of the layer)
@@ -180,23 +222,14 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
       if (s < 0 || s >= n_src) continue;                                      // nothing, and nothing read there
     }
     int n = uni(rows[s]);
-    const int a = uni(actions[s]);
+    head.state(s);
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS;
-    if (n <= 1 || a < 0 || a >= n) continue;                                  // no row, one row (delta - p = 0) or a bad action: nothing
+    if (!head.takes(n)) continue;                                          // (the same for the whole workgroup: no barrier is left out)
     const int32_t* ob = obs + (size_t)s * obs_rows * cols;
     // (the previous state's g_r and tiles have been read: the barrier that ends its last tile)
     for (int r0 = 16 * w; r0 < n; r0 += 16 * NW) pmlp2_logits_tile<HP1, HP2, KS>(lg, ob, r0, n, obs_rows, cols, W1p, b1p, a2, b2l, w3l, b3, lane);
     __syncthreads();
-    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);                    // (every wave for itself: the same numbers)
-    const float H = pmlp_entropy_wave(lg, n, lane, sm);
-    const float gl = glogp[k], ge = gent ? gent[k] : 0.f;
-    const float rse = 1.f / sm.se;
-    const int n32 = (n + 31) & ~31;
-    __syncthreads();                                                          // (every wave has read the logits)
-    for (int r = (int)threadIdx.x; r < n32; r += (int)blockDim.x) {           // (every thread reads and writes its own entries only)
-      const float g = r < n ? pmlp_policy_coef(lg[r], r == a, sm, H, gl, ge, rse) : 0.f;
-      lg[r] = g; db3a += g;
-    }
+    head.coefs(lg, n, k, lane, db3a);
     __syncthreads();
     for (int r0 = 0; r0 < n; r0 += 32) {
       bbx_f32x16 D;
@@ -244,7 +277,9 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
 #pragma unroll
             for (int v = 0; v < 4; v++) {
               const double z = Z[rt][ut][v];
-              a1t[(16 * rt + l4 + 4 * v) * S1 + 32 * w + 16 * ut + l15] = z > 0.0 ? (float)z : 0.f;
+              const float hi = z > 0.0 ? (float)z : 0.f;
+              a1t[(16 * rt + l4 + 4 * v) * S1 + 32 * w + 16 * ut + l15] = hi;
+              if constexpr (HEAD::exact_a1) a1lo[(16 * rt + l4 + 4 * v) * S1 + 32 * w + 16 * ut + l15] = z > 0.0 ? (float)(z - (double)hi) : 0.f;
             }
       }
       __syncthreads();
@@ -266,8 +301,12 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
 #pragma unroll 2
           for (int S = 0; S < S4; S++) {
             bbx_f32x4 av[2], bv[2];
+            [[maybe_unused]] bbx_f32x4 al[2];
 #pragma unroll
-            for (int rt = 0; rt < 2; rt++) av[rt] = *(const bbx_f32x4*)(ap + 16 * rt * S1 + 16 * S);
+            for (int rt = 0; rt < 2; rt++) {
+              av[rt] = *(const bbx_f32x4*)(ap + 16 * rt * S1 + 16 * S);
+              if constexpr (HEAD::exact_a1) al[rt] = *(const bbx_f32x4*)(ap + (a1lo - a1t) + 16 * rt * S1 + 16 * S);
+            }
 #pragma unroll
             for (int ut = 0; ut < 2; ut++) bv[ut] = *(const bbx_f32x4*)(bp + (ut * S4 + S) * 256);
 #pragma unroll
@@ -275,7 +314,11 @@ __global__ __launch_bounds__(2 * (HP1 > HP2 ? HP1 : HP2)) void bbx_pmlp2_grad_ke
 #pragma unroll
               for (int rt = 0; rt < 2; rt++)
 #pragma unroll
-                for (int ut = 0; ut < 2; ut++) Z[rt][ut] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[rt][j], (double)bv[ut][j], Z[rt][ut], 0, 0, 0);
+                for (int ut = 0; ut < 2; ut++) {
+                  double a = (double)av[rt][j];
+                  if constexpr (HEAD::exact_a1) a += (double)al[rt][j];
+                  Z[rt][ut] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (double)bv[ut][j], Z[rt][ut], 0, 0, 0);
+                }
           }
 #pragma unroll
           for (int rt = 0; rt < 2; rt++)

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __
 // The second stage: output i of dW1 [cols][hidden] | db1 [hidden] | dw2 [hidden] | db2 is the sum of its nwaves partials —
 // 64 outputs per workgroup, the partials of an output dealt to four threads (partial q, q + 4, ... in order), the four sums
 // added as (s0 + s1) + (s2 + s3).  nwaves = 0: zeros.
-__global__ __launch_bounds__(256) void bbx_pmlp_grad_reduce_kernel(const float* __restrict__ ws, int nwaves, int cols, int hidden,
+static __global__ __launch_bounds__(256) void bbx_pmlp_grad_reduce_kernel(const float* __restrict__ ws, int nwaves, int cols, int hidden,
                                                                    float* __restrict__ gw1, float* __restrict__ gb1, float* __restrict__ gw2,
                                                                    float* __restrict__ gb2) {
   __shared__ float part[4][64];
@@ -311,7 +311,7 @@ __device__ __forceinline__ void pmlp_stats_sum(double (&acc)[6], double* __restr
 // positions, sum u_k, sum H_k, sum (old_k - new_k), positions clipped, positions not counted; the sums in double over the float32
 // terms.  ONE workgroup of PMLP_PPO_STAT_THREADS threads: thread t adds positions t, t + threads, ..., then pmlp_stats_sum.  No
 // atomics, and a partition that depends on n alone.  n == 0: zeros.
-__global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+static __global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
   const size_t n = (size_t)n_;
   const int32_t* flags = (const int32_t*)tail + 3 * n;
   double acc[6] = {0., 0., 0., 0., 0., 0.};

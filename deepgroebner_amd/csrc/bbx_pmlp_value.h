@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_value_grad_kernel(const int32
 // sum V, sum target, sum target^2 (the float32 product target * target), positions not counted; the sums in double over the
 // float32 terms.  ONE workgroup of PMLP_PPO_STAT_THREADS threads in the order of bbx_pmlp_ppo_stats_kernel: thread t adds
 // positions t, t + threads, ..., then pmlp_stats_sum.  n == 0: zeros.
-__global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_value_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+static __global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_value_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
 #pragma clang fp contract(off)
   const size_t n = (size_t)n_;
   const int32_t* flags = (const int32_t*)tail + 3 * n;

@@ -9,7 +9,8 @@ call the hand-written HIP kernels of bbx_api_policy.cpp.
                                call (bbx_pmlp_ppo_grad[_at] / bbx_pmlp2_ppo_grad[_at])           pg.py _fit_policy_model
     PMLPValue                  a learned baseline (--value_model mlp, pg.py _fit_value_model): a critic over the recorded state
                                blocks — one launch for a whole buffer's values (bbx_pmlp_value), one library call per minibatch of the
-                               squared-error fit (bbx_pmlp_value_fit[_at])
+                               squared-error fit (bbx_pmlp_value_fit[_at]); with two hidden layers and deep_kernels set the same through
+                               bbx_pmlp2_value / bbx_pmlp2_value_grad / bbx_pmlp2_value_fit[_at]
 
 The kernel-call layer (_PMLPKernels and the helpers in front of it) holds what every such call needs, once: the prepared weights
 and their cache, the workspaces, the head of an argument list, the decision whether the kernels can take a call, the conversion
@@ -108,6 +109,11 @@ class _PMLPKernels(torch.nn.Module):
         """Shapes the one-layer kernels are built for (bbx_pmlp_prepared_floats >= 0)."""
         return 1 <= hidden <= 256 and 1 <= cols <= 64
 
+    def deep_ok(self, cols):
+        """Two or three hidden layers of at most 128 units: the shapes bbx_pmlp2_act / bbx_pmlp3_act are built for (two: the training
+        kernels' and the critic's too)."""
+        return len(self.embedding) in (2, 3) and all(1 <= l.out_features <= 128 for l in self.embedding) and 1 <= cols <= 64
+
     def _kernel_params(self):
         """The parameters in the kernels' order, which is the order of _grad_arrays (and of parameters())."""
         return [q for l in (*self.embedding, self._last) for q in (l.weight, l.bias)]
@@ -203,7 +209,7 @@ class _PMLPKernels(torch.nn.Module):
         return ws
 
 
-# What tells the three autograd functions apart: the stems of the forward and the backward entry point (the backward's workspace is
+# What tells the four autograd functions apart: the stems of the forward and the backward entry point (the backward's workspace is
 # <backward>_workspace_floats), the module's workspace slot, the hidden layers, whether the critic's pool id travels along (recorded
 # actions do where the function has them), and the number of outputs (the forward entry points have two output arguments: a
 # critic's second stays empty).
@@ -211,10 +217,11 @@ _Kernels = collections.namedtuple("_Kernels", ["forward", "backward", "slot", "d
 _POLICY = _Kernels("bbx_pmlp_logprob", "bbx_pmlp_grad", "_grad_ws", 1, False, 2)
 _POLICY2 = _Kernels("bbx_pmlp2_logprob", "bbx_pmlp2_grad", "_grad2_ws", 2, False, 2)
 _VALUE = _Kernels("bbx_pmlp_value", "bbx_pmlp_value_grad", "_ws", 1, True, 1)
+_VALUE2 = _Kernels("bbx_pmlp2_value", "bbx_pmlp2_value_grad", "_ws", 2, True, 1)
 
 
 def _forward(ctx, kind, module, states, rows, actions, index, params):
-    """The forward pass of the three functions: `kind.outputs` float32 tensors, one element per state (per index)."""
+    """The forward pass of the four functions: `kind.outputs` float32 tensors, one element per state (per index)."""
     fn, head, _, N, _, _ = _call_head(kind.forward, states, rows, actions, index)
     out = [torch.empty(N, dtype=torch.float32, device=states.device) for _ in range(kind.outputs)]
     pool = (module.pool_id,) if kind.pool else ()
@@ -227,7 +234,7 @@ def _forward(ctx, kind, module, states, rows, actions, index, params):
 
 
 def _backward(ctx, kind, *cotangents):
-    """The backward pass of the three functions: the parameters' gradients in torch.nn.Linear's layouts and the parameters' dtypes.
+    """The backward pass of the four functions: the parameters' gradients in torch.nn.Linear's layouts and the parameters' dtypes.
     The hidden activations are recomputed: nothing of size [N, R, hidden] is kept between forward and backward."""
     states, rows, actions, index, *params = ctx.saved_tensors
     fn, head, _, N, R, cols = _call_head(kind.backward, states, rows, actions, index)
@@ -282,6 +289,19 @@ class _PMLPValueEvaluate(torch.autograd.Function):
         return (None,) * 3 + _backward(ctx, _VALUE, gvalue) + (None,)
 
 
+class _PMLP2ValueEvaluate(torch.autograd.Function):
+    """_PMLPValueEvaluate for two hidden layers: bbx_pmlp2_value forward, bbx_pmlp2_value_grad backward, gradients for the six
+    parameter tensors.  index: as in _PMLPEvaluate (bbx_pmlp2_value_at / bbx_pmlp2_value_grad_at)."""
+
+    @staticmethod
+    def forward(ctx, critic, states, rows, w1, b1, w2, b2, w3, b3, index=None):
+        return _forward(ctx, _VALUE2, critic, states, rows, None, index, (w1, b1, w2, b2, w3, b3))[0]
+
+    @staticmethod
+    def backward(ctx, gvalue):
+        return (None,) * 3 + _backward(ctx, _VALUE2, gvalue) + (None,)
+
+
 class PMLPPolicy(_PMLPKernels):
     """ParallelMultilayerPerceptron(hidden_layers) of the reference: every row of the -1-padded [batch, rows, cols] int
     block is embedded by the same MLP (relu), scored by one linear unit, padded rows get -1e9, log-softmax over rows."""
@@ -330,10 +350,6 @@ class PMLPPolicy(_PMLPKernels):
         _ffi.check(fn(_ptr(obs), _ptr(rows), B, R, cols, w["prepared"], *hidden, *(() if greedy else (_ptr(u),)), _ptr(actions), _ptr(logprobs),
                       C.c_void_p(s)))
         return actions, logprobs
-
-    def deep_ok(self, cols):
-        """Two or three hidden layers of at most 128 units: the shapes bbx_pmlp2_act / bbx_pmlp3_act are built for."""
-        return len(self.embedding) in (2, 3) and all(1 <= l.out_features <= 128 for l in self.embedding) and 1 <= cols <= 64
 
     def deep_max_rows(self):
         """Rows per environment the two- / three-layer kernels score: the logits of a wave's environment live in LDS beside the
@@ -520,13 +536,15 @@ class PMLPValue(_PMLPKernels):
         pool="sum"   V = sum_r z_r        pool="mean"   V = that sum / n        pool="lse"   V = log sum_r exp z_r
     A state without live rows is worth 0.  One hidden layer of at most 256 units over at most 64 columns, float32 on the GPU: the
     HIP kernels (bbx_pmlp_value / bbx_pmlp_value_grad / bbx_pmlp_value_fit and their _at forms, which read a trajectory buffer in
-    place); CPU tensors, more hidden layers or wider ones: the torch path (forward, values_torch, evaluate_torch).  `last_path`
-    names the path the last call took ("kernels" or "torch")."""
+    place); two hidden layers of at most 128 units with deep_kernels set: their two-layer counterparts (bbx_pmlp2_value / ..._grad /
+    ..._fit and the _at forms); CPU tensors, two layers without the flag, more hidden layers or wider ones: the torch path (forward,
+    values_torch, evaluate_torch).  `last_path` names the path the last call took ("kernels" or "torch")."""
 
     POOLS = {"sum": 0, "mean": 1, "lse": 2}                           # BBX_POOL_* of include/bbx.h
 
-    def __init__(self, cols, hidden_layers=(128,), pool="sum"):
+    def __init__(self, cols, hidden_layers=(128,), pool="sum", deep_kernels=False):
         super().__init__()
+        self.deep_kernels = deep_kernels                              # two hidden layers: the bbx_pmlp2_value* kernels in place of the torch path
         if pool not in self.POOLS:
             raise ValueError("PMLPValue: pool is one of %s (got %r)" % (sorted(self.POOLS), pool))
         dims = [cols] + list(hidden_layers)
@@ -587,11 +605,28 @@ class PMLPValue(_PMLPKernels):
     # ---- the kernels
     def kernels_ok(self, states):
         """Whether the HIP kernels take states [..., R, cols] with this module's weights (otherwise: the torch path)."""
-        return self._kernel_depth(states) == 1
+        return self._kernel_depth(states) in (1, 2)
 
     def _in_place(self, states, rows):
         """Whether the _at kernels can read states [..., R, cols] and rows where they lie."""
-        return self._kernel_depth(states, rows, in_place=True) == 1
+        return self._kernel_depth(states, rows, in_place=True) in (1, 2)
+
+    def _deep_weights(self):
+        """The two-layer kernels' view of the weights (the two-layer policy's layout), refilled in place (_prepared_weights)."""
+        return self._prepared_weights("_deep_cache", self.embedding, self.head, True)
+
+    def _kernels(self):
+        """(the entry points' stem, the prepared weights, the hidden sizes as a tuple) of this module's depth."""
+        if len(self.embedding) == 1:
+            w = self._fused_weights()
+            return "bbx_pmlp_value", w, (w["hidden"],)
+        w = self._deep_weights()
+        return "bbx_pmlp2_value", w, tuple(w["hidden"])
+
+    def _evaluate_kernels(self, states, rows, index=None):
+        self.last_path = "kernels"
+        fn = _PMLPValueEvaluate if len(self.embedding) == 1 else _PMLP2ValueEvaluate
+        return fn.apply(self, states, rows, *self._kernel_params(), index)
 
     def _fused_weights(self):
         """The kernels' view of the weights (the one-layer policy's layout), refilled in place (_prepared_weights)."""
@@ -600,16 +635,17 @@ class PMLPValue(_PMLPKernels):
         return self._prepared_weights("_fused_cache", self.embedding, self.head, True)
 
     def _value_call(self, states, rows, index, out, out64):
-        fn, head, _, N, _, _ = _call_head("bbx_pmlp_value", states, rows, None, index)
         dev = states.device
+        with torch.cuda.device(dev):
+            stem, w, hidden = self._kernels()
+        fn, head, _, N, _, _ = _call_head(stem, states, rows, None, index)
         if out is None and out64 is None:
             out = torch.empty(N, dtype=torch.float32, device=dev)
         for o, dt in ((out, torch.float32), (out64, torch.float64)):
             if o is not None and not (o.is_cuda and o.dtype == dt and o.is_contiguous() and o.numel() == N):
                 raise ValueError("PMLPValue.values: out / out64 are contiguous float32 / float64 CUDA tensors of %d elements" % N)
         with torch.cuda.device(dev):
-            w = self._fused_weights()
-            _ffi.check(fn(*head, w["prepared"], w["hidden"], self.pool_id, _ptr(out), _ptr(out64), _stream()))
+            _ffi.check(fn(*head, w["prepared"], *hidden, self.pool_id, _ptr(out), _ptr(out64), _stream()))
         self.last_path = "kernels"
         return out if out is not None else out64
 
@@ -618,7 +654,7 @@ class PMLPValue(_PMLPKernels):
         """Values of states int [..., R, cols] with rows [...] live rows each, no autograd: float32 into `out` and / or the same
         numbers widened into `out64` (float64: what DeviceTrajectoryBuffer.values holds), each of rows.numel() elements; neither:
         a new float32 tensor.  Returns out (out64 where only that was given).  On the GPU under kernels_ok: one bbx_pmlp_value
-        call, over the tensors in place where they are contiguous int32; otherwise values_torch."""
+        (two hidden layers: bbx_pmlp2_value) call, over the tensors in place where they are contiguous int32; otherwise values_torch."""
         if not self.kernels_ok(states):
             return self.values_torch(states, rows, out, out64)
         st, rw, _ = _kernel_inputs(states, rows)
@@ -639,15 +675,13 @@ class PMLPValue(_PMLPKernels):
         if not self.kernels_ok(states):
             return self.evaluate_torch(states, rows)
         st, rw, _ = _kernel_inputs(states, rows)
-        self.last_path = "kernels"
-        return _PMLPValueEvaluate.apply(self, st, rw, *self._kernel_params())
+        return self._evaluate_kernels(st, rw)
 
     def evaluate_at(self, states, rows, index):
         """evaluate() of the recorded states index[k] without gathering them (bbx_pmlp_value_at / bbx_pmlp_value_grad_at), as
         PMLPPolicy.evaluate_at; where the kernels cannot read the buffers in place the n states are gathered."""
         if self._in_place(states, rows):
-            self.last_path = "kernels"
-            return _PMLPValueEvaluate.apply(self, states, rows, *self._kernel_params(), _index32(index, states))
+            return self._evaluate_kernels(states, rows, _index32(index, states))
         return self.evaluate(*_gather(index, states, rows))
 
     def fit_step_at(self, states, rows, index, targets):
@@ -681,19 +715,19 @@ class PMLPValue(_PMLPKernels):
         return stats, v.detach()
 
     def _fit_kernels(self, states, rows, index, targets):
-        fn, head, _, N, R, cols = _call_head("bbx_pmlp_value_fit", states, rows, None, index)
         dev = states.device
+        with torch.cuda.device(dev):
+            stem, w, hidden = self._kernels()
+        fn, head, _, N, R, cols = _call_head(stem + "_fit", states, rows, None, index)
         tg = targets.to(device=dev, dtype=torch.float32).contiguous()
         if tg.numel() != N:
             raise ValueError("fit_step: %d positions, %d targets" % (N, tg.numel()))
         values, coef = (torch.empty(N, dtype=torch.float32, device=dev) for _ in range(2))
         stats = torch.empty(6, dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            w = self._fused_weights()
-            hidden = w["hidden"]
-            grads = _grad_arrays(cols, (hidden,), dev)
-            ws = self._workspace("_ws", _ffi.lib().bbx_pmlp_value_fit_workspace_floats(N, R, cols, hidden), dev)
-            _ffi.check(fn(*head, w["prepared"], hidden, self.pool_id, _ptr(tg), C.c_float(1.0 / N if N else 0.0), _ptr(values), _ptr(coef),
+            grads = _grad_arrays(cols, hidden, dev)
+            ws = self._workspace("_ws", getattr(_ffi.lib(), stem + "_fit_workspace_floats")(N, R, cols, *hidden), dev)
+            _ffi.check(fn(*head, w["prepared"], *hidden, self.pool_id, _ptr(tg), C.c_float(1.0 / N if N else 0.0), _ptr(values), _ptr(coef),
                           _ptr(stats), _ptr(ws), *[_ptr(g) for g in grads], _stream()))
         self.last_path = "kernels"
         _add_to_grad(self._kernel_params(), _linear_layouts(grads))

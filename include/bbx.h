@@ -403,6 +403,42 @@ int bbx_pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int o
 int bbx_pmlp_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                           const float* d_prepared, int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef,
                           double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+/* The critic over TWO hidden layers: the block above word for word — pools, live rows n_s = clamp(d_rows[s], 0, min(obs_rows, 2048)),
+ * n_s <= 0: V = 0.0f and no gradient, ONE live row contributes, rows beyond the live ones play no part, _at: an index outside
+ * [0, n_src) gives NaN, reads nothing there and contributes nothing, n == 0 legal, the fit's float32 recipe, d_stats and workspace
+ * tail — with the parameters, layouts and prepared weights of the two-layer policy (bbx_pmlp2_prepare, unchanged:
+ * bbx_pmlp2_prepared_floats) and the shapes of bbx_pmlp2_logprob (1 <= cols <= 64, 1 <= hidden1, hidden2 <= 128, 1 <= obs_rows <=
+ * BBX_POLICY_MAX_ROWS; anything else: BBX_E_UNSUPPORTED before a device is asked for anything; a device with too little LDS per
+ * workgroup: BBX_E_UNSUPPORTED as well).  The row score z_r = w3 . relu(W2^T relu(W1^T x_r + b1) + b2) + b3 comes from the two-layer
+ * policy kernels' tile code: for the same block and weights, the bits of their logits.
+ * bbx_pmlp2_value[_at]: d_values / d_values64 as bbx_pmlp_value's (either may be NULL, both NULL with n > 0: BBX_E_ARG).
+ * bbx_pmlp2_value_grad[_at]: the gradients of L = sum_k d_gvalue[k] V_k in the six layouts bbx_pmlp2_prepare reads; d_workspace holds
+ *   bbx_pmlp2_value_grad_workspace_floats(n, ...) = bbx_pmlp2_grad_workspace_floats(n, ...) floats: the partition, the float64
+ *   recomputation of both pre-activations and the second kernel are bbx_pmlp2_grad's (no floating-point atomics; the partition
+ *   depends on n and the shape alone).  A state without live rows or an index out of range: its d_gvalue is not read.
+ * bbx_pmlp2_value_fit[_at]: forward with the squared-error epilogue, statistics, gradients; THE GRADIENTS ARE, BIT FOR BIT, THOSE OF
+ *   bbx_pmlp2_value_grad[_at] CALLED WITH d_gvalue = d_coef, d_values (may be NULL) that of bbx_pmlp2_value[_at].  d_workspace holds
+ *   bbx_pmlp2_value_fit_workspace_floats(n, ...) floats (16-byte aligned): the gradient workspace, then d^2 | V | target | flags, n
+ *   each.  d_targets or d_coef NULL with n > 0: BBX_E_ARG; d_stats may be NULL (no statistics kernel is queued; everything else as with it). */
+int bbx_pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                    int pool, float* d_values, double* d_values64, void* stream);
+int bbx_pmlp2_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                       const float* d_prepared, int hidden1, int hidden2, int pool, float* d_values, double* d_values64, void* stream);
+int bbx_pmlp2_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2);   /* < 0: shape not supported */
+int bbx_pmlp2_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                         int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
+                         float* d_gb3, void* stream);
+int bbx_pmlp2_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                            const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1,
+                            float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+int bbx_pmlp2_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2);   /* < 0: shape not supported */
+int bbx_pmlp2_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
+                        int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
+                        float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+int bbx_pmlp2_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                           const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_targets, float scale, float* d_values,
+                           float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
+                           float* d_gb3, void* stream);
 /* ... and for three hidden layers (hidden_layers=[hidden1, hidden2, hidden3], each <= 128): the same kernel with a middle layer
  * whose output stays in registers as the next layer's B operands; d_w3 [hidden2][hidden3], d_b3 [hidden3], d_w4 [hidden3],
  * d_b4 [1].  All three layers are padded to the widest one's tile size (64 or 128 units). */

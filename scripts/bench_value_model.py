@@ -1,10 +1,13 @@
-"""The learned value baseline (PMLPValue, bbx_pmlp_value / bbx_pmlp_value_fit) measured three ways; one JSON line per part.
+"""The learned value baseline (PMLPValue, bbx_pmlp_value / bbx_pmlp_value_fit; two hidden layers: bbx_pmlp2_value / bbx_pmlp2_value_fit
+through deep_kernels=True) measured three ways; one JSON line per part.
 
-    python scripts/bench_value_model.py [--part all|values|fit|rollout] [--hidden 128] [--pool mean]
+    python scripts/bench_value_model.py [--part all|values|fit|rollout] [--hidden 128 | 128,128 | 64,64] [--pool mean]
 
 values   values/s of DeviceTrajectoryBuffer.fill_values over a recorded block of --T 128 x --B 2048 states of --rows 128 rows (live
          rows uniform in [2, rows]): ONE bbx_pmlp_value call over the block in place, float64 straight into buffer.values.  Each
-         repetition timed with device events; the rate is states over the MEDIAN repetition (--reps, at least 20).
+         repetition timed with device events; the rate is states over the MEDIAN repetition (--reps, at least 20).  Beside it,
+         alternating in blocks of --block repetitions, values_torch of the SAME module over the first --torch-states 8192 states of
+         the block (the torch path holds [states, rows, hidden] tensors: the whole block does not fit).
 fit      one minibatch of the critic's update on --states 4096 positions of that block, two ways on identical tensors,
          alternating in blocks of --block repetitions:
              kernel   PMLPValue.fit_step_at: forward, squared error, statistics and gradients in one library call, the block
@@ -36,7 +39,9 @@ ap.add_argument("--T", type=int, default=128)
 ap.add_argument("--B", type=int, default=2048)
 ap.add_argument("--rows", type=int, default=128)
 ap.add_argument("--cols", type=int, default=12)
-ap.add_argument("--hidden", type=int, default=128)
+ap.add_argument("--hidden", type=lambda t: [int(h) for h in t.split(",")], default=[128],
+                help="units of the hidden layer, or of two: 128,128 (the critic then has deep_kernels=True)")
+ap.add_argument("--torch-states", type=int, default=8192, help="values: states of the block the torch path is timed on")
 ap.add_argument("--pool", default="mean", choices=sorted(PMLPValue.POOLS))
 ap.add_argument("--states", type=int, default=4096, help="fit: positions per minibatch")
 ap.add_argument("--warmup", type=int, default=5)
@@ -53,6 +58,8 @@ if a.reps < 20:
     ap.error("--reps must be at least 20")
 if a.pairs < 5:
     ap.error("--pairs must be at least 5")
+if len(a.hidden) not in (1, 2):
+    ap.error("--hidden takes one or two layer sizes")
 if not torch.cuda.is_available():
     sys.exit("bench_value_model: no GPU (there is no CPU fall-back for a measurement)")
 dev = torch.device("cuda", torch.cuda.current_device())
@@ -93,10 +100,23 @@ def part_values(buf, critic):
         fill()
     torch.cuda.synchronize()
     assert critic.last_path == "kernels"
-    times = event_times(fill, a.reps)
+    m = min(a.torch_states, n)
+    st, rw = buf.states.view(-1, a.rows, a.cols)[:m], buf.rows.view(-1)[:m]
+    out32 = torch.empty(m, dtype=torch.float32, device="cuda")
+    fill_torch = lambda: critic.values_torch(st, rw, out=out32)
+    for _ in range(a.warmup):
+        fill_torch()
+    torch.cuda.synchronize()
+    times, times_torch, done = [], [], 0
+    while done < a.reps:
+        k = min(a.block, a.reps - done)
+        times += event_times(fill, k); times_torch += event_times(fill_torch, k)
+        done += k
     live = float(buf.rows.float().mean())
     out = {"bench": "value_model_values", "device": name, "T": a.T, "B": a.B, "rows": a.rows, "cols": a.cols, "hidden": a.hidden, "pool": a.pool,
-           "reps": a.reps, "live_rows_mean": live, "block_bytes": buf.states.numel() * 4, "values": summary(times, n)}
+           "reps": a.reps, "live_rows_mean": live, "block_bytes": buf.states.numel() * 4, "values": summary(times, n),
+           "values_torch": dict(summary(times_torch, m), states=m)}
+    out["kernel_over_torch"] = out["values"]["per_s"] / out["values_torch"]["per_s"]
     out["block_GB_per_s"] = out["block_bytes"] / (out["values"]["median_ms"] * 1e-3) / 1e9      # (the whole padded block over the median: an upper
     print(json.dumps(out), flush=True)                                                          # bound on what the kernel reads — it skips dead rows)
 
@@ -150,8 +170,8 @@ def part_rollout():
     B, T, R = a.batch, a.steps, a.obs_rows
     cols = 2 * int(a.dist.split("-")[0]) * 2                     # (cols = 2 nvars k)
     torch.manual_seed(1)
-    policy = PMLPPolicy(cols, (a.hidden,)).to(dev)
-    critic = PMLPValue(cols, (a.hidden,), pool=a.pool).to(dev)
+    policy = PMLPPolicy(cols, a.hidden).to(dev)
+    critic = PMLPValue(cols, a.hidden, pool=a.pool, deep_kernels=len(a.hidden) == 2).to(dev)
 
     def one_run(mode):
         env = VecLeadMonomialsEnv(a.dist, batch=B, k=2)
@@ -189,7 +209,7 @@ def part_rollout():
 
 if a.part in ("all", "values", "fit"):
     torch.manual_seed(a.seed)
-    critic = PMLPValue(a.cols, (a.hidden,), pool=a.pool).cuda()
+    critic = PMLPValue(a.cols, a.hidden, pool=a.pool, deep_kernels=len(a.hidden) == 2).cuda()
     buf, gen = recorded_block()
     if a.part in ("all", "values"):
         part_values(buf, critic)

@@ -2,7 +2,9 @@
 (a refactor of bbx_pmlp.h / bbx_pmlp_grad.h / bbx_pmlp_value.h / bbx_pmlp2_grad.h must not move a bit).
 
     python scripts/dump_pmlp_outputs.py OUT.npz            the tree this file lies in: build it first; needs a GPU; seconds
-    python scripts/dump_pmlp_outputs.py --compare A.npz B.npz     exit status 1 and the names of the arrays that differ
+    python scripts/dump_pmlp_outputs.py --compare A.npz B.npz     exit status 1 and the names of the arrays that differ; arrays of
+                                                                  groups that only the second file has (written by a later tree
+                                                                  with more entry points) are counted, not compared
 
 Cases, from the generators of tests/ (value_cases.grad_case over policy_cases): per shape nine states with 0, 1, 2, 31, 32, 33, 64,
 65 and 129 live rows in blocks of 130 rows (three waves per unit group, each striding over three states; one recorded action
@@ -12,7 +14,9 @@ more than one unit group (256 units).  Calls: bbx_pmlp_grad[_at] with and withou
 bbx_pmlp_ppo_grad_at and bbx_pmlp_value_fit_at with statistics and workspace tail, bbx_pmlp_act, bbx_pmlp_act_greedy; once:
 bbx_pmlp2_grad, and one bbx_policy_step_device step (the fused step kernel) on 64 environments with 6 and with 12 columns.
 A second group, module/..., goes through the Python classes instead (a refactor of deepgroebner_amd/pmlp.py must not move a bit
-either): see module_arrays."""
+either): see module_arrays.  A third, value2/... and module2/..., holds the two-layer critic: bbx_pmlp2_value[_at],
+bbx_pmlp2_value_grad[_at] and bbx_pmlp2_value_fit_at for the three pools on the two-layer case's states and weights, and the public
+methods of a PMLPValue with deep_kernels (value2_arrays)."""
 import ctypes as C
 import os
 import sys
@@ -29,9 +33,12 @@ INDEX = (8, 3, 3, -1, 9, 0, 5, 7, 1, 2, 6, 4)                    # into the nine
 
 def compare(a, b):
     A, B = np.load(a), np.load(b)
-    bad = sorted(set(A.files) ^ set(B.files))
+    group = lambda k: k.split("/")[0]
+    new = sorted(k for k in B.files if group(k) not in {group(x) for x in A.files})
+    bad = sorted((set(A.files) ^ set(B.files)) - set(new))
     bad += [k for k in A.files if k in B.files and (A[k].dtype != B[k].dtype or A[k].shape != B[k].shape or A[k].tobytes() != B[k].tobytes())]
-    print("%d arrays, %d bytes; differing: %s" % (len(A.files), sum(A[k].nbytes for k in A.files), bad or "none"))
+    print("%d arrays, %d bytes; differing: %s%s" % (len(A.files), sum(A[k].nbytes for k in A.files), bad or "none",
+                                                    "; %d arrays of groups only the second file has (%s)" % (len(new), ", ".join(sorted({group(k) for k in new}))) if new else ""))
     return 1 if bad else 0
 
 
@@ -107,6 +114,56 @@ def module_arrays(keep, device="cuda"):
                 ep = value_update(cr, buf, torch.optim.SGD(cr.parameters(), lr=0.01), 1, 5, shuffle=False)
                 keep("%s/value_update/%s" % (tag, pool), *[torch.as_tensor(np.asarray(ep[0][k], dtype=np.float64)) for k in ("stats", "loss", "explained_variance")],
                      *[q.detach() for q in cr.parameters()])
+
+
+def value2_arrays(keep, lib, p, dev, nan, stream):
+    """The third group: the two-layer critic through the C ABI (value2/...) and through PMLPValue(deep_kernels=True) (module2/...)."""
+    import torch
+    from deepgroebner_amd import _ffi
+    from tests import policy_cases as pc
+    from tests import value_cases as vc
+    cols, hidden = 12, (64, 128)
+    w, obs, rows, g = vc.grad_case(cols, hidden, LIVE, R, 6100)
+    N, index = len(rows), np.array(INDEX, dtype=np.int32)
+    n = len(index)
+    rng = np.random.default_rng(6101)
+    dobs, drows, dindex = dev(obs), dev(rows), dev(index)
+    per = {m: [dev(rng.normal(size=m), np.float32) for _ in range(2)] for m in (N, n)}
+    pol = pc.to_policy(w, "cuda")
+    dw = pol._deep_weights()
+    h1, h2 = dw["hidden"]
+    grads = lambda: [nan(cols * h1), nan(h1), nan(h1 * h2), nan(h2), nan(h2), nan(1)]
+    for pool in range(3):
+        for at in (False, True):
+            m, sfx = (n, "_at") if at else (N, "")
+            cnt = (N, p(dindex), n) if at else (N,)
+            c, d = per[m]
+            v32, v64 = nan(m), nan(m, torch.float64)
+            _ffi.check(getattr(lib, "bbx_pmlp2_value" + sfx)(p(dobs), p(drows), *cnt, R, cols, dw["prepared"], h1, h2, pool, p(v32), p(v64), stream()))
+            keep("value2/value%s/pool%d" % (sfx, pool), v32, v64)
+            G, ws = grads(), nan(lib.bbx_pmlp2_value_grad_workspace_floats(m, R, cols, h1, h2))
+            _ffi.check(getattr(lib, "bbx_pmlp2_value_grad" + sfx)(p(dobs), p(drows), *cnt, R, cols, dw["prepared"], h1, h2, pool, p(c), p(ws), *map(p, G), stream()))
+            keep("value2/value_grad%s/pool%d" % (sfx, pool), *G)
+        gfl = lib.bbx_pmlp2_grad_workspace_floats(n, R, cols, h1, h2)
+        G, ws = grads(), nan(lib.bbx_pmlp2_value_fit_workspace_floats(n, R, cols, h1, h2))
+        val, coef, stats = nan(n), nan(n), nan(6, torch.float64)
+        _ffi.check(lib.bbx_pmlp2_value_fit_at(p(dobs), p(drows), N, p(dindex), n, R, cols, dw["prepared"], h1, h2, pool, p(per[n][1]), C.c_float(1.0 / n), p(val),
+                                              p(coef), p(stats), p(ws), *map(p, G), stream()))
+        keep("value2/value_fit_at/pool%d" % pool, val, coef, stats, ws[gfl:], *G)
+    pgrads = lambda m: [q.grad for q in m.parameters()]
+    for pool in vc.POOLS:
+        for at in (False, True):
+            c = per[n if at else N][0]
+            what = "module2/%s/%%s%s/%s" % (pc.label(cols, hidden), "_at" if at else "", pool)
+            new = lambda: vc.to_critic(w, pool, "cuda")
+            cr = new(); cr.deep_kernels = True
+            keep(what % "values", cr.values_at(dobs, drows, dindex) if at else cr.values(dobs, drows))
+            v = cr.evaluate_at(dobs, drows, dindex) if at else cr.evaluate(dobs, drows)
+            v.backward(c)
+            keep(what % "evaluate", v.detach(), *pgrads(cr))
+            cr = new(); cr.deep_kernels = True
+            res = cr.fit_step_at(dobs, drows, dindex, c) if at else cr.fit_step(dobs, drows, c)
+            keep(what % "fit_step", *res, *pgrads(cr))
 
 
 def main(path):
@@ -204,6 +261,7 @@ def main(path):
         keep("policy_step/k%d" % k, A, L, rew, done, rows, obs)
 
     module_arrays(keep)
+    value2_arrays(keep, lib, p, dev, nan, stream)
     np.savez(path, **out)
     print("%d arrays, %d bytes -> %s" % (len(out), sum(v.nbytes for v in out.values()), path))
 
