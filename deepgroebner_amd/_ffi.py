@@ -142,6 +142,9 @@ SIGNATURES = {
     "bbx_alg_get": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "bbx_values_seeded": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp]),
     "bbx_values_device": (C.c_int, [_vp, C.c_char_p, C.c_double, _vp, _vp, _vp]),
+    "bbx_action_values": (C.c_int, [_vp, C.c_char_p, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
+    "bbx_action_values_chunk": (C.c_int, [_vp, C.c_int]),
+    "bbx_action_values_plan": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "bbx_gae_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
     "bbx_pmlp_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp2_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),

@@ -224,6 +224,35 @@ class VecLeadMonomialsEnv:
             return None if x is None else C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
         _ffi.check(_ffi.lib().bbx_values_device(self._h, strategy.encode(), float(gamma), dp(seeds), dp(values), C.c_void_p(int(stream))))
 
+    def action_values(self, strategy="degree", gamma=0.99, max_rows=None, with_steps=False):
+        """What every pair of every environment is worth (bbx_action_values): q[e, a] = r + gamma * value(strategy) of a copy
+        of environment e stepped with action a — the node expansion of a tree search, a one-step lookahead, exact Q targets.
+        float64 [batch, R], NaN where a >= the environment's pair count; R = max_rows, or the tallest pair set (None).
+        with_steps: (q, rewards [batch, R] of the forced step, dones [batch, R]).  The batch itself, self.rows included, is
+        untouched.  "random" / "sample" raise BbxError (BBX_E_UNSUPPORTED)."""
+        L = _ffi.lib()
+        rows = np.zeros(self.batch, dtype=np.int32)
+        R = max(1, int(self.rows.max())) if max_rows is None else int(max_rows)
+        while True:
+            q = np.empty((self.batch, R), dtype=np.float64)
+            rew = np.empty((self.batch, R), dtype=np.float64) if with_steps else None
+            done = np.empty((self.batch, R), dtype=np.uint8) if with_steps else None
+            _ffi.check(L.bbx_action_values(self._h, strategy.encode(), float(gamma), R, _ffi.ptr(q), _ffi.ptr(rew), _ffi.ptr(done), _ffi.ptr(rows)))
+            if max_rows is not None or int(rows.max()) <= R:
+                break
+            R = int(rows.max())                                  # (self.rows was behind the device: asynchronous calls do not keep it)
+        if max_rows is None:
+            R = max(1, int(rows.max()))
+            q, rew, done = q[:, :R], (rew[:, :R] if with_steps else None), (done[:, :R] if with_steps else None)
+        return (q, rew, done.astype(bool)) if with_steps else q
+
+    def action_values_chunk(self, clones=0):
+        """Clones in flight per pass of action_values (<= 0: the default); returns the previous value."""
+        rc = _ffi.lib().bbx_action_values_chunk(self._h, int(clones))
+        if rc < 0:
+            _ffi.check(rc)
+        return rc
+
     def copy(self):
         h = C.c_void_p()
         _ffi.check(_ffi.lib().bbx_copy(self._h, C.byref(h)))
@@ -425,6 +454,11 @@ class CLeadMonomialsEnv:
     def value(self, strategy="degree", gamma=0.99):
         return self._vec.value(0, strategy, gamma)
 
+    def action_values(self, strategy="degree", gamma=0.99):
+        """float64 [pairs]: entry a = the reward of step(a) + gamma * value(strategy) of the state behind it, on copies (what
+        mcts.py:78-102 computes per expanded node); the environment is untouched."""
+        return _action_values_one(self._vec, strategy, gamma)
+
     def copy(self):
         return type(self)(_vec=self._vec.copy())
 
@@ -437,6 +471,15 @@ class LeadMonomialsEnv(CLeadMonomialsEnv):
 
     def value(self, gamma=0.99):
         return self._vec.value(0, "degree", gamma)
+
+    def action_values(self, gamma=0.99):
+        return _action_values_one(self._vec, "degree", gamma)
+
+
+def _action_values_one(vec, strategy, gamma):
+    """The action values of a one-environment batch as a vector whose length is its pair count."""
+    q = vec.action_values(strategy, gamma)
+    return q[0, :int((~np.isnan(q[0])).sum())].copy()
 
 
 P_MOD = 32003
@@ -496,6 +539,10 @@ class BuchbergerEnv:
 
     def value(self, gamma=0.99):
         return self._vec.value(0, "degree", gamma)
+
+    def action_values(self, gamma=0.99):
+        """float64 [len(P)], in the order of P: the reward of step(P[a]) + gamma * value() of the state behind it."""
+        return _action_values_one(self._vec, "degree", gamma)
 
     def copy(self):
         other = BuchbergerEnv.__new__(BuchbergerEnv)
@@ -782,6 +829,29 @@ class LeadMonomialsAgent:
     def act(self, state):
         rule = self._RULES.get(self.strategy)
         return None if rule is None else rule(self, state)   # (the reference falls through to None for anything else)
+
+
+def best_actions(q):
+    """Per row of an action-value block (NaN padding): the first index of the largest entry, 0 for an all-NaN row -> int32."""
+    q = np.atleast_2d(np.asarray(q, dtype=np.float64))
+    return np.where(np.isnan(q), -np.inf, q).argmax(axis=1).astype(np.int32)
+
+
+class LookaheadAgent:
+    """One-step lookahead over the ENVIRONMENT, not its observation: takes the pair with the largest action value
+    r + gamma * value(strategy) (action_values; the first one on ties).  act(env) -> int32 [batch] for a VecLeadMonomialsEnv
+    (0 where an environment has no pair), the row index for a CLeadMonomialsEnv / LeadMonomialsEnv, the pair for a
+    BuchbergerEnv."""
+
+    def __init__(self, strategy="degree", gamma=0.99):
+        self.strategy = strategy
+        self.gamma = gamma
+
+    def act(self, env):
+        if isinstance(env, VecLeadMonomialsEnv):
+            return best_actions(env.action_values(self.strategy, self.gamma))
+        a = int(best_actions(env._vec.action_values(self.strategy, self.gamma))[0])
+        return env.P[a] if isinstance(env, BuchbergerEnv) else a
 
 
 def strategy_stats(ideals, strategy="degree", elimination="gebauermoeller", sort_reducers=True, device=0, caps=None,

@@ -47,6 +47,7 @@ bbx_batch::~bbx_batch() {
   if (ps_ctl_stream) (void)hipStreamDestroy(ps_ctl_stream);
   if (d_clone_idx) (void)hipFree(d_clone_idx);
   bbx_host::value_ring_free(this);
+  bbx_host::action_values_free(this);
   if (v_stream) (void)hipStreamDestroy(v_stream);
   if (d_vident) (void)hipFree(d_vident);
   if (d_vwords) (void)hipFree(d_vwords);

@@ -1,5 +1,6 @@
 // libbbx.so — LeadMonomialsEnv::value (buchberger.cpp:332-351): discounted returns of full Buchberger rollouts from clones of
-// the current states (bbx_value, bbx_values, bbx_values_seeded of include/bbx.h).
+// the current states (bbx_value, bbx_values, bbx_values_seeded of include/bbx.h), their asynchronous form (bbx_values_device)
+// and the same rollouts behind every pair of every environment (bbx_action_values).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -35,21 +36,27 @@ uint32_t minstd_state_of_seed(long long seed) {
 // environments that outgrow it and every other batch on the HBM-resident class of the batch, long-polynomial
 // environments one workgroup per clone.  A clone that runs out of room enlarges the records of the whole batch
 // (grow_records) and the rollouts start again.
+// the clone arrays of value() and bbx_action_values: room for n clones in the batch's current layout (kept between calls;
+// grow_records frees them, so a call after the records were enlarged makes them again)
+int value_scratch_ensure(bbx_batch* b, int n) {
+  if (n <= b->vcap) return BBX_OK;
+  void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};
+  for (void* q : old) (void)hipFree(q);
+  b->d_vrecs = nullptr; b->d_vhdr = nullptr; b->d_vsrc = nullptr; b->d_vseeds = nullptr; b->d_vvals = nullptr; b->vcap = 0;
+  HIPCHK(hipMalloc((void**)&b->d_vrecs, (size_t)n * b->L.rec_bytes));
+  HIPCHK(hipMalloc((void**)&b->d_vhdr, (size_t)n));                        // clone flags (u8)
+  HIPCHK(hipMalloc((void**)&b->d_vsrc, (size_t)n * sizeof(int32_t)));
+  HIPCHK(hipMalloc((void**)&b->d_vseeds, (size_t)n * sizeof(uint32_t)));
+  HIPCHK(hipMalloc((void**)&b->d_vvals, (size_t)n * 2 * sizeof(double)));  // {value, completion mark} per clone
+  b->vcap = n;
+  return BBX_OK;
+}
+
 int value_rollouts(bbx_batch* b, const std::vector<int32_t>& src, int agent, const std::vector<uint32_t>* seeds, double gamma, double* out) {
   const int n = (int)src.size();
   if (int rc = settle(b)) return rc;
   for (int attempt = 0; attempt < 40; attempt++) {
-    if (n > b->vcap) {
-      void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};
-      for (void* q : old) (void)hipFree(q);
-      b->d_vrecs = nullptr; b->d_vhdr = nullptr; b->d_vsrc = nullptr; b->d_vseeds = nullptr; b->d_vvals = nullptr; b->vcap = 0;
-      HIPCHK(hipMalloc((void**)&b->d_vrecs, (size_t)n * b->L.rec_bytes));
-      HIPCHK(hipMalloc((void**)&b->d_vhdr, (size_t)n));                        // clone flags (u8)
-      HIPCHK(hipMalloc((void**)&b->d_vsrc, (size_t)n * sizeof(int32_t)));
-      HIPCHK(hipMalloc((void**)&b->d_vseeds, (size_t)n * sizeof(uint32_t)));
-      HIPCHK(hipMalloc((void**)&b->d_vvals, (size_t)n * 2 * sizeof(double)));  // {value, completion mark} per clone
-      b->vcap = n;
-    }
+    if (int rc = value_scratch_ensure(b, n)) return rc;
     HIPCHK(hipMemcpyAsync(b->d_vsrc, src.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, 0));
     if (seeds) HIPCHK(hipMemcpyAsync(b->d_vseeds, seeds->data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, 0));
     const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
@@ -244,6 +251,125 @@ int value_carry_over(bbx_batch* b, const bbx_vjob& j, size_t jix, const uint32_t
   return rc;
 }
 
+// ---- bbx_action_values: Q[e][a] = r + gamma * value of the state behind action a, for every pair of every environment ----
+// What the reference's tree search does per expanded node (mcts.py:78-102,147; az.py:81-86: env.copy(), step(a), a rollout),
+// for the whole batch: one clone per (environment, pair), the flat list cut into passes of at most av.chunk clones.  A pass
+// is clone -> ONE step with the clone's own action -> resort -> the strategy's rollouts -> collect into [B][max_rows]
+// staging blocks, all on the default stream; the host reads the offsets once before the first pass and the status word and
+// the blocks once behind the last.
+
+// the per-clone arrays of a pass and the staging blocks of a call (neither depends on the record layout)
+int av_ensure(bbx_batch* b, int n, size_t cells) {
+  bbx_avscratch& s = b->av;
+  if (n > s.cap) {
+    void* old[] = {s.d_act, s.d_rew, s.d_done};
+    for (void* q : old) if (q) (void)hipFree(q);
+    s.d_act = nullptr; s.d_rew = nullptr; s.d_done = nullptr; s.cap = 0;
+    HIPCHK(hipMalloc((void**)&s.d_act, (size_t)n * sizeof(int32_t)));
+    HIPCHK(hipMalloc((void**)&s.d_rew, (size_t)n * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&s.d_done, (size_t)n));
+    s.cap = n;
+  }
+  if (cells > s.cells) {
+    void* old[] = {s.d_q, s.d_r, s.d_d};
+    for (void* q : old) if (q) (void)hipFree(q);
+    s.d_q = nullptr; s.d_r = nullptr; s.d_d = nullptr; s.cells = 0;
+    HIPCHK(hipMalloc((void**)&s.d_q, cells * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&s.d_r, cells * sizeof(double)));
+    HIPCHK(hipMalloc((void**)&s.d_d, cells));
+    s.cells = cells;
+  }
+  if (!s.d_word) HIPCHK(hipMalloc((void**)&s.d_word, 2 * sizeof(uint32_t)));
+  return BBX_OK;
+}
+
+// The forced first step on the clones in `recs`: one step with the actions of d_act, no auto-reset, no observation, rewards
+// and done flags into per-clone arrays.  The kernels are those plan_launch gives a rollout of the class — the first kernel and
+// the one that takes over what it hands on: a clone that outgrows the LDS-resident class in this very step is continued, not
+// left waiting for a host that polls —, each with a budget of one step.
+int av_launch_first_step(bbx_batch* b, char* recs, int n) {
+  BbxParams p; fill_params(b, &p);
+  p.recs = recs; p.B = n; p.nsteps = 2; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 0;
+  p.actions = b->av.d_act; p.rewards = b->av.d_rew; p.dones = b->av.d_done;
+  p.trace = nullptr; p.accounting = 0;
+  p.lite = nullptr;                                           // the clones are not the batch's environments
+  LaunchPlan pl = plan_launch(b, p, false, true);
+  int lrc = 0;
+  for (int i = 0; i < pl.n && !lrc; i++) { pl.pass[i].nsteps = 1; lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], 0); }
+  if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  return BBX_OK;
+}
+
+// one pass: positions [first, first + n) of the flat list
+int av_pass(bbx_batch* b, int first, int n, int agent, double gamma, int max_rows) {
+  bbx_avscratch& s = b->av;
+  if (int rc = value_scratch_ensure(b, n)) return rc;
+  int lrc = bbx_launch_av_expand(s.d_off, b->B, first, n, b->d_vsrc, s.d_act, 0);
+  if (lrc) return fail(BBX_E_DEVICE, "expand launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
+  uint8_t* d_flags = (uint8_t*)b->d_vhdr;
+  lrc = bbx_launch_clone(b->d_recs, b->d_vrecs, &b->L, b->d_vsrc, nullptr, n, nullptr, 0, 1, ngen, d_flags, 0);
+  if (lrc) return fail(BBX_E_DEVICE, "clone launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (int rc = av_launch_first_step(b, b->d_vrecs, n)) return rc;
+  // (behind the step: value() re-sorts the state it is called on; the flags are the clone's — a step leaves the generators alone)
+  lrc = bbx_launch_value_resort(b->d_vrecs, &b->L, n, d_flags, 0);
+  if (lrc) return fail(BBX_E_DEVICE, "resort launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (int rc = value_launch_rollouts(b, b->d_vrecs, n, agent, gamma, false, 0)) return rc;
+  lrc = bbx_launch_av_collect(b->d_vrecs, b->L.rec_bytes, n, b->d_vsrc, s.d_act, s.d_rew, s.d_done, gamma, max_rows, s.d_q, s.d_r, s.d_d, s.d_word, 0);
+  if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  return BBX_OK;
+}
+
+int action_values(bbx_batch* b, int agent, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, int32_t* rows) {
+  const int B = b->B;
+  const size_t cells = (size_t)B * (size_t)max_rows;
+  if (cells > 0x7fffffffull) return fail(BBX_E_ARG, "batch x max_rows = %zu: the flat clone list is indexed with 32 bits", cells);
+  if (int rc = settle(b)) return rc;
+  bbx_avscratch& s = b->av;
+  if (!s.d_off) HIPCHK(hipMalloc((void**)&s.d_off, (2 * (size_t)B + 3) * sizeof(int32_t)));
+  int lrc = bbx_launch_av_offsets(b->d_recs, b->L.rec_bytes, B, max_rows, s.d_off, 0);
+  if (lrc) return fail(BBX_E_DEVICE, "offsets launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  std::vector<int32_t> h(2 * (size_t)B + 3);
+  HIPCHK(hipMemcpy(h.data(), s.d_off, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));   // all that visits the host of the states
+  if (h[B + 1]) return fail(BBX_E_CAPACITY, "action values of environment %d: it is in an error state: %s", h[B + 1] - 1, status_name(h[B + 2]));
+  memcpy(rows, &h[B + 3], (size_t)B * sizeof(int32_t));
+  const int total = h[B];
+  if (total == 0) {                                           // nothing to value: nothing launched
+    for (size_t i = 0; i < cells; i++) q[i] = __builtin_nan("");
+    if (rewards) for (size_t i = 0; i < cells; i++) rewards[i] = __builtin_nan("");
+    if (dones) memset(dones, 0, cells);
+    return BBX_OK;
+  }
+  std::vector<int32_t> counts(B), first((size_t)total / (size_t)s.chunk + 3);
+  for (int e = 0; e < B; e++) counts[e] = h[e + 1] - h[e];
+  int32_t npasses = 0;
+  if (int rc = bbx_action_values_plan(counts.data(), B, s.chunk, first.data(), (int)first.size(), &npasses)) return rc;
+  const unsigned capmask = (1u << BBX_ST_G_FULL) | (1u << BBX_ST_P_FULL) | (1u << BBX_ST_ARENA_FULL) | (1u << BBX_ST_POLY_TOO_LONG);
+  for (int attempt = 0; attempt < 40; attempt++) {
+    if (int rc = av_ensure(b, std::min(total, s.chunk), cells)) return rc;
+    lrc = bbx_launch_av_fill(s.d_q, s.d_r, s.d_d, cells, s.d_word, 0);
+    if (lrc) return fail(BBX_E_DEVICE, "fill launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    for (int p = 0; p < npasses; p++)
+      if (int rc = av_pass(b, first[p], first[p + 1] - first[p], agent, gamma, max_rows)) return rc;
+    uint32_t w[2] = {0, 0};
+    HIPCHK(hipMemcpy(w, s.d_word, sizeof w, hipMemcpyDeviceToHost));   // the wait of the call
+    if (!w[0]) {
+      HIPCHK(hipMemcpy(q, s.d_q, cells * sizeof(double), hipMemcpyDeviceToHost));
+      if (rewards) HIPCHK(hipMemcpy(rewards, s.d_r, cells * sizeof(double), hipMemcpyDeviceToHost));
+      if (dones) HIPCHK(hipMemcpy(dones, s.d_d, cells, hipMemcpyDeviceToHost));
+      return BBX_OK;
+    }
+    const int env = (int)w[1] - 1;
+    if ((w[0] & ~capmask) || b->no_growth)
+      return fail(BBX_E_CAPACITY, "action-value rollout of environment %d did not finish: %s", env,
+                  (w[0] & capmask) ? status_name(__builtin_ctz(w[0] & capmask)) : "pairs left or a clone in an error state");
+    // a clone's forced step or rollout outgrew the records: those of the whole batch are enlarged (the clone arrays go with
+    // the old layout) and the passes run again — the results are those of a handle created with room to spare
+    if (int rc = grow_records(b, w[0] & capmask, env, 0)) return rc;
+  }
+  return fail(BBX_E_CAPACITY, "action-value rollouts kept outgrowing the records");
+}
+
 }  // namespace
 
 int bbx_value_ring_from_env() {
@@ -283,6 +409,14 @@ void value_ring_free(bbx_batch* b) {
     if (s.done) (void)hipEventDestroy(s.done);
   }
   b->v_ring.clear();
+}
+
+void action_values_free(bbx_batch* b) {
+  bbx_avscratch& s = b->av;
+  void* dev[] = {s.d_off, s.d_act, s.d_rew, s.d_done, s.d_q, s.d_r, s.d_d, s.d_word};
+  for (void* q : dev) if (q) (void)hipFree(q);
+  const int chunk = s.chunk;
+  s = bbx_avscratch{}; s.chunk = chunk;
 }
 }  // namespace bbx_host
 
@@ -331,6 +465,40 @@ extern "C" int bbx_values_seeded(bbx_batch* b, const char* strategy, double gamm
   std::vector<int32_t> envs(b->B);
   for (int e = 0; e < b->B; e++) envs[e] = e;
   return values_for(b, envs, strategy, gamma, seeds, out);
+}
+
+// The pass plan of bbx_action_values, on the host alone: the flat (environment, action) list — environment e contributes
+// counts[e] positions — cut into contiguous ranges of at most `chunk`; first[p] is where pass p begins, first[npasses] the total
+extern "C" int bbx_action_values_plan(const int32_t* counts, int B, int chunk, int32_t* first, int cap, int32_t* npasses) {
+  if (!counts || !first || !npasses || B < 0 || chunk < 1 || cap < 0) return fail(BBX_E_ARG, "bad arguments");
+  long long total = 0;
+  for (int e = 0; e < B; e++) {
+    if (counts[e] < 0) return fail(BBX_E_ARG, "counts[%d] = %d is negative", e, counts[e]);
+    total += counts[e];
+  }
+  if (total > 0x7fffffffll) return fail(BBX_E_ARG, "%lld clones: the flat list is indexed with 32 bits", total);
+  const long long n = (total + chunk - 1) / chunk;
+  if (n + 1 > cap) return fail(BBX_E_CAPACITY, "%lld passes need %lld elements in first[], cap = %d", n, n + 1, cap);
+  for (long long p = 0; p < n; p++) first[p] = (int32_t)(p * chunk);
+  first[n] = (int32_t)total;
+  *npasses = (int32_t)n;
+  return BBX_OK;
+}
+
+extern "C" int bbx_action_values_chunk(bbx_batch* b, int clones) {
+  if (!b) return fail(BBX_E_ARG, "null argument");
+  const int before = b->av.chunk;
+  b->av.chunk = clones <= 0 ? BBX_AV_CHUNK_DEFAULT : clones;
+  return before;
+}
+
+extern "C" int bbx_action_values(bbx_batch* b, const char* strategy, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones,
+                                 int32_t* rows) {
+  if (!b || !strategy || !q || !rows || max_rows < 1) return fail(BBX_E_ARG, "bad arguments");
+  if (!strcmp(strategy, "random") || !strcmp(strategy, "sample"))
+    return fail(BBX_E_UNSUPPORTED, "action values under \"%s\" need a seed stream per clone: not built (degree, normal, sugar, first)", strategy);
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  return action_values(b, agent_of_strategy(strategy), gamma, max_rows, q, rewards, dones, rows);
 }
 
 extern "C" int bbx_values(bbx_batch* b, const char* strategy, double gamma, double* out) {

@@ -1,5 +1,5 @@
-// Housekeeping kernels of libbbx (initialisation, queue refill, ragged observations, clones, record growth, header
-// gathers), the stand-alone PMLP policy launchers and the launcher that picks a kernel class (bbx_launch_step).
+// Housekeeping kernels of libbbx (initialisation, queue refill, ragged observations, clones, value() and action-value
+// bookkeeping, record growth, header gathers), the stand-alone PMLP policy launchers and the launcher that picks a kernel class (bbx_launch_step).
 #include "bbx_device.h"
 #include "bbx_pmlp.h"
 #include "bbx_pmlp_grad.h"
@@ -235,6 +235,110 @@ __global__ void bbx_value_collect_device_kernel(const char* recs, uint32_t rec_b
 }
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream) {
   hipLaunchKernelGGL(bbx_value_collect_device_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, values, word, only_nan);
+  return (int)hipGetLastError();
+}
+
+// ---- bbx_action_values: one clone per (environment, pair), a forced first step, then value() (bbx_api_value.cpp) ----------
+// The flat list of clones: environment e contributes its actions 0 .. count[e] - 1, count[e] = min(nP, max_rows) — 0 for an
+// environment without pairs or one that awaits its reset.  Kernel 1 (one workgroup, the scan of bbx_obs_offsets_kernel, from
+// the record headers): out[0 .. B] = the exclusive scan of the counts; out[B + 1], out[B + 2] = 1 + the first environment in
+// an error state and its status (0: none); out[B + 3 + e] = the FULL pair count of environment e.  All the host reads of the states.
+__global__ __launch_bounds__(1024) void bbx_av_offsets_kernel(const char* recs, uint32_t rec_bytes, int B, int max_rows, int32_t* out) {
+  __shared__ int part[1024];
+  __shared__ int bad;
+  const int t = threadIdx.x, per = (B + 1023) / 1024;
+  if (t == 0) bad = B;
+  __syncthreads();
+  int s = 0;
+  for (int i = 0; i < per; i++) {
+    const int e = t * per + i;
+    if (e >= B) break;
+    const BbxHdr* h = (const BbxHdr*)(recs + (size_t)e * rec_bytes);
+    const int full = h->need_reset ? 0 : h->nP;
+    out[B + 3 + e] = full;
+    s += full < max_rows ? full : max_rows;
+    if (h->status != BBX_ST_OK) atomicMin(&bad, e);
+  }
+  part[t] = s;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {                     // inclusive scan (Hillis-Steele)
+    const int v = t >= d ? part[t - d] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int base = t ? part[t - 1] : 0;
+  for (int i = 0; i < per; i++) {
+    const int e = t * per + i;
+    if (e < B) { out[e] = base; const int full = out[B + 3 + e]; base += full < max_rows ? full : max_rows; }   // (this thread's own store)
+  }
+  if (t == 1023) out[B] = part[1023];
+  if (t == 0) {
+    out[B + 1] = bad < B ? bad + 1 : 0;
+    out[B + 2] = bad < B ? ((const BbxHdr*)(recs + (size_t)bad * rec_bytes))->status : 0;
+  }
+}
+// Kernel 2: positions [first, first + n) of the flat list -> src[k] = the environment, act[k] = its action.  The environment
+// is the last one whose offset is <= the position (empty environments share their successor's offset and are passed over);
+// the caller keeps first + n <= off[B].
+__global__ void bbx_av_expand_kernel(const int32_t* off, int B, int first, int n, int32_t* src, int32_t* act) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int flat = first + k;
+  int lo = 0, hi = B;                                       // off[lo] <= flat < off[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= flat) lo = mid; else hi = mid;
+  }
+  src[k] = lo; act[k] = flat - off[lo];
+}
+// the [B][max_rows] staging blocks before the passes: NaN / NaN / 0 padding, the status word pair cleared
+__global__ void bbx_av_fill_kernel(double* q, double* rewards, uint8_t* dones, size_t cells, uint32_t* word) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 2) word[i] = 0u;
+  if (i >= cells) return;
+  q[i] = __builtin_nan(""); rewards[i] = __builtin_nan(""); dones[i] = 0;
+}
+// Kernel 3, after the forced step and the rollouts of a pass: clone k writes Q = r + gamma * value at [src[k]][act[k]] — in
+// double, one rounded product and one rounded sum (contraction off, as in bbx_gae_kernel: what the host forms from
+// bbx_step's reward and bbx_values' value) —, the step's reward and done flag beside it.  A clone that did not run to the end
+// leaves its cells as they are and is folded into the word pair like bbx_value_collect_device_kernel's: word[0] |= 1 << status
+// for one that waits for room, bit 31 for anything else; word[1] = 1 + the largest such environment.
+__global__ void bbx_av_collect_kernel(const char* recs, uint32_t rec_bytes, int n, const int32_t* src, const int32_t* act, const double* rew,
+                                      const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word) {
+#pragma clang fp contract(off)
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const BbxHdr* h = (const BbxHdr*)(recs + (size_t)k * rec_bytes);
+  const int st = h->status;
+  if (!(st == BBX_ST_OK && h->nP == 0)) {
+    atomicOr(&word[0], bbx_st_capacity(st) ? 1u << st : 1u << 31);
+    atomicMax(&word[1], (uint32_t)src[k] + 1u);
+    return;
+  }
+  const size_t at = (size_t)src[k] * max_rows + act[k];
+  const double r = rew[k];
+  const double tail = gamma * h->vret;
+  q[at] = r + tail; rewards[at] = r; dones[at] = done[k];
+}
+extern "C" int bbx_launch_av_offsets(const char* recs, uint32_t rec_bytes, int B, int max_rows, int32_t* out, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_av_offsets_kernel, dim3(1), dim3(1024), 0, stream, recs, rec_bytes, B, max_rows, out);
+  return (int)hipGetLastError();
+}
+extern "C" int bbx_launch_av_expand(const int32_t* off, int B, int first, int n, int32_t* src, int32_t* act, hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_av_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, off, B, first, n, src, act);
+  return (int)hipGetLastError();
+}
+extern "C" int bbx_launch_av_fill(double* q, double* rewards, uint8_t* dones, size_t cells, uint32_t* word, hipStream_t stream) {
+  const size_t m = cells > 2 ? cells : 2;
+  hipLaunchKernelGGL(bbx_av_fill_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, q, rewards, dones, cells, word);
+  return (int)hipGetLastError();
+}
+extern "C" int bbx_launch_av_collect(const char* recs, uint32_t rec_bytes, int n, const int32_t* src, const int32_t* act, const double* rew,
+                                     const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(bbx_av_collect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, src, act, rew, done, gamma, max_rows,
+                     q, rewards, dones, word);
   return (int)hipGetLastError();
 }
 

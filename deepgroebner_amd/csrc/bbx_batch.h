@@ -22,6 +22,12 @@ extern "C" int bbx_launch_value_collect(const char* recs, uint32_t rec_bytes, in
 extern "C" int bbx_launch_value_iota(int32_t* idx, int n, hipStream_t stream);
 extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, int n, hipStream_t stream);
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream);
+extern "C" int bbx_launch_av_offsets(const char* recs, uint32_t rec_bytes, int B, int max_rows, int32_t* out, hipStream_t stream);
+extern "C" int bbx_launch_av_expand(const int32_t* off, int B, int first, int n, int32_t* src, int32_t* act, hipStream_t stream);
+extern "C" int bbx_launch_av_fill(double* q, double* rewards, uint8_t* dones, size_t cells, uint32_t* word, hipStream_t stream);
+extern "C" int bbx_launch_av_collect(const char* recs, uint32_t rec_bytes, int n, const int32_t* src, const int32_t* act, const double* rew,
+                                     const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word,
+                                     hipStream_t stream);
 extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
                               double* returns, double* advantages, uint8_t* complete, hipStream_t stream);
 extern "C" int bbx_launch_episodes(const double* rewards, const uint8_t* dones, int T, int B, double* carry_return, int32_t* carry_len, int32_t* ep_count,
@@ -101,6 +107,17 @@ constexpr int BBX_VALUE_RING_DEFAULT = 2;   // measured: 2, 4 and 8 are equal, 1
 constexpr int BBX_VALUE_MAX_JOBS = 8192;    // calls between two waits (a word pair each)
 int bbx_value_ring_from_env();        // BBX_VALUE_RING, clamped to 1..16
 
+// bbx_action_values (bbx_api_value.cpp): what it keeps between calls besides the clone arrays it shares with value()
+// (d_vrecs, d_vhdr, d_vsrc: sized by the record layout, freed by grow_records).  Nothing here depends on the layout.
+constexpr int BBX_AV_CHUNK_DEFAULT = 65536;   // clones in flight per pass (bbx_action_values_chunk)
+struct bbx_avscratch {
+  int chunk = BBX_AV_CHUNK_DEFAULT;
+  int32_t* d_off = nullptr;           // [2 B + 3]: offsets, error pair, full pair counts (bbx_av_offsets_kernel)
+  int32_t* d_act = nullptr; double* d_rew = nullptr; uint8_t* d_done = nullptr; int cap = 0;   // per clone: forced action, its reward and done flag
+  double* d_q = nullptr; double* d_r = nullptr; uint8_t* d_d = nullptr; size_t cells = 0;      // [B][max_rows] staging blocks
+  uint32_t* d_word = nullptr;         // the status word pair of the call (bbx_av_collect_kernel)
+};
+
 struct bbx_gen {
   std::unique_ptr<bbx::IdealGen> g;
   bbx::HIdeal last;
@@ -178,6 +195,7 @@ struct bbx_batch : bbx_config {
   int32_t* d_vident = nullptr; uint32_t* d_vwords = nullptr;
   std::vector<bbx_vjob> v_jobs;
   long long v_calls = 0;              // calls so far (slot = v_calls % v_depth)
+  bbx_avscratch av;                   // bbx_action_values
   // HIP-event timing of the step-kernel launches (bbx_timing)
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_open;
@@ -269,6 +287,7 @@ int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8
 int value_wait(bbx_batch* b);
 int value_resolve(bbx_batch* b);
 void value_ring_free(bbx_batch* b);
+void action_values_free(bbx_batch* b);   // what bbx_action_values keeps between calls (the device must be idle)
 // bbx_api_session.cpp
 int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external = false, bool device_async = false);
 void start_flight(bbx_batch* b, const BbxParams& p, hipStream_t stream, bool obs_external, bool device_async);

@@ -166,6 +166,31 @@ int bbx_values(bbx_batch* b, const char* strategy, double gamma, double* out);
  * Random rollouts of environment e; its Degree rollout needs none); other strategies ignore them.  Equal to the
  * reference's buchberger(G, P, Random, ..., seed).discounted_return per rollout, bit for bit. */
 int bbx_values_seeded(bbx_batch* b, const char* strategy, double gamma, const int64_t* seeds, double* out);
+/* Action values: what each pair of each environment is worth under a fixed strategy — the node expansion of the reference's
+ * tree search (mcts.py:78-102,147; az.py:81-86: env.copy(), step(a), a rollout, once per action) for the whole batch in one
+ * call.  For environment e with n_e pairs and a < n_e:
+ *     c = copy of environment e;  (r, done) = c.step(a)      (no auto-reset; rewards as the handle was created)
+ *     q[e][a] = r + gamma * c.value(strategy, gamma)          (the value of a finished environment is 0.0)
+ * formed in double with one rounded product and one rounded sum: == on doubles to bbx_copy, bbx_step and bbx_values done one
+ * after another (NOT the single-rollout sum r0 + gamma r1 + ..., which rounds differently).
+ *   q [batch][max_rows], NaN at a >= min(rows[e], max_rows); rewards (or NULL) the same shape: r, NaN padding; dones (or NULL):
+ *   the forced step ended the episode, 0 padding; rows [batch]: the FULL pair count — an environment with more than max_rows
+ *   pairs has its first max_rows actions valued and shows the cut here.  An environment without pairs (finished, or waiting
+ *   for its reset): rows[e] = 0 and an all-NaN row; a batch with nothing to value launches nothing.
+ *   "random" / "sample": BBX_E_UNSUPPORTED (per-clone seed streams are not built); any other unknown name selects First, as in
+ *   bbx_values.  NULL b / strategy / q / rows or max_rows < 1: BBX_E_ARG.  An environment in an error state fails the call
+ *   like bbx_values.  Waits on the host; the call in flight, sessions and queued bbx_values_device calls are settled first.
+ *   The handle's environments, counters, bbx_stats and pinned outputs are untouched.
+ * One clone per (environment, action), bbx_action_values_chunk of them in flight per pass (default 65536; <= 0 restores it;
+ * returns the previous value); a pass is clone, one forced step, resort, the strategy's rollouts, collect.  Clones that
+ * outgrow the records enlarge those of the batch (bbx_capacities) and the passes run again: same doubles.
+ * bbx_action_values_plan is the pass plan, on the host alone: the flat (environment, action) list with counts[e] positions
+ * for environment e, cut into contiguous ranges of at most chunk; first[p] = where pass p begins, first[*npasses] = the
+ * total; cap = elements first[] holds (too few: BBX_E_CAPACITY). */
+int bbx_action_values(bbx_batch* b, const char* strategy, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones,
+                      int32_t* rows);
+int bbx_action_values_chunk(bbx_batch* b, int clones);
+int bbx_action_values_plan(const int32_t* counts, int B, int chunk, int32_t* first, int cap, int32_t* npasses);
 
 /* ---- same calls on caller-owned DEVICE buffers (e.g. torch tensors), asynchronous on `stream` ----
  * (hipStream_t passed as void*; NULL = the default stream).  obs may be NULL.
