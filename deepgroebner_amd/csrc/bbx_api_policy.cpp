@@ -1,5 +1,5 @@
 // libbbx.so — the PMLP policy calls of include/bbx.h: prepared weights, the stand-alone act kernels (one, two and three hidden
-// layers), policy + step in one call, and policy rollouts inside the step kernels.  Which shapes the kernels are built for is
+// layers), the training calls of policy and critic, policy + step in one call, and policy rollouts inside the step kernels.  Which shapes the kernels are built for is
 // stated once, in bbx_pmlp_shape.h: a call is admitted here by the predicates the launchers pick an instantiation with.
 #include "bbx_batch.h"
 #include "bbx_pmlp_shape.h"
@@ -19,6 +19,17 @@ int refuse_args(bool null_arg, bool bad, const char* bad_text, int obs_rows) {
 
 int launched(int lrc) { return lrc ? fail(BBX_E_DEVICE, "policy launch failed: %s", hipGetErrorString((hipError_t)lrc)) : BBX_OK; }
 
+// the current device, with what the launchers of the deep kernels size themselves by: its CU count and its LDS per workgroup
+// (cached: this sits on the per-step path of a policy rollout)
+struct Device { int id = 0; DeviceInfo info{}; };
+int current_device(Device* d) { HIPCHK(hipGetDevice(&d->id)); HIPCHK(device_info(d->id, &d->info)); return BBX_OK; }
+// (hipErrorInvalidValue from such a launcher: the shape needs more LDS than the device has)
+int launched_lds(int lrc, const Device& d) {
+  if (lrc == (int)hipErrorInvalidValue)
+    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", d.id, d.info.max_lds);
+  return launched(lrc);
+}
+
 int pmlp_deep_floats(int cols, int h1, int hm, int h2, bool three) {
   if (cols < 1 || cols > 64 || h1 < 1 || h1 > 128 || h2 < 1 || h2 > 128 || (three && (hm < 1 || hm > 128)))
     return three ? fail(BBX_E_UNSUPPORTED, "policy shape %d x %d x %d x %d is not built into the three-layer policy kernel", cols, h1, hm, h2)
@@ -32,12 +43,10 @@ int pmlp_deep_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int ob
   // (greedy: the argmax in place of the draw — d_u is not read)
   if (int rc = refuse_args(!d_obs || !d_rows || !d_prepared || (!d_u && !greedy) || !d_actions || !d_logprobs, batch < 1 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
   if (pmlp_deep_floats(cols, h1, hm, h2, three) < 0) return BBX_E_UNSUPPORTED;
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));   // (cached: this sits on the per-step path of a policy rollout)
-  int lrc = bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, greedy ? 1 : 0, di.cus, di.max_lds, (hipStream_t)stream);
-  if (lrc == (int)hipErrorInvalidValue)
-    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, di.max_lds);
-  return launched(lrc);
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, h1, three ? hm : 0, h2, d_u, d_actions, d_logprobs, greedy ? 1 : 0,
+                                           d.info.cus, d.info.max_lds, (hipStream_t)stream), d);
 }
 
 int pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_rows, int cols, const float* d_prepared, int hidden, const float* d_u,
@@ -47,68 +56,87 @@ int pmlp_act(const int32_t* d_obs, const int32_t* d_rows, int batch, int obs_row
   return launched(bbx_launch_pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, d_u, d_actions, d_logprobs, greedy ? 1 : 0, (hipStream_t)stream));
 }
 
-// the training calls for two hidden layers: the shape first (it needs no device and outranks a null pointer: a caller sizing
-// buffers asks with none), naming the number that is out of range
-bool pmlp2_shape_refused(int cols, int h1, int h2) { return cols < 1 || cols > 64 || h1 < 1 || h1 > 128 || h2 < 1 || h2 > 128; }
-int refuse_pmlp2(int obs_rows, int cols, int h1, int h2) {
+// ---- the training calls of policy and critic: one body per call, for one hidden layer and two, plain and indexed.  What a call
+// is about comes as the records of bbx_pmlp_shape.h (PmlpStates, PmlpNet, PmlpGrads); net.layers picks the launcher.
+
+// the shape of a two-layer training call, naming the number that is out of range, then its rows
+int refuse_pmlp2_shape(int obs_rows, int cols, int h1, int h2) {
   if (cols < 1 || cols > 64) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..64 columns (cols = %d)", cols);
   if (h1 < 1 || h1 > 128) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..128 units per layer (hidden1 = %d)", h1);
   if (h2 < 1 || h2 > 128) return fail(BBX_E_UNSUPPORTED, "the two-layer policy kernels take 1..128 units per layer (hidden2 = %d)", h2);
   return refuse_args(false, false, "", obs_rows);
 }
-int launched_lds(int lrc, int dev, int max_lds) {
-  if (lrc == (int)hipErrorInvalidValue)
-    return fail(BBX_E_UNSUPPORTED, "the policy kernel needs more LDS than device %d has (%d bytes per workgroup)", dev, max_lds);
-  return launched(lrc);
+static_assert(BBX_POOL_SUM == PMLP_POOL_SUM && BBX_POOL_MEAN == PMLP_POOL_MEAN && BBX_POOL_LSE == PMLP_POOL_LSE, "include/bbx.h and bbx_pmlp_shape.h disagree");
+// What every training call and workspace query refuses, and in which order: the one statement of it.  null_arg: a pointer the
+// call cannot do without is null (its own expression: the arrays of length n may be null when n == 0); pool: a critic's.
+//   two layers: the shape — rows above BBX_POLICY_MAX_ROWS, or a cols / hidden1 / hidden2 out of range, the message naming the number:
+//               it needs no device and outranks a null pointer, since a caller sizing buffers asks with none; then the index of an
+//               _at call (n_src < 0; no index with n > 0); a null argument; "bad policy shape" (n < 0, obs_rows < 1); the pool
+//   one layer:  the index of an _at call; a null argument; "bad policy shape"; rows above the limit; the shape
+//               (bbx_pmlp_prepared_floats' message); the pool
+// so the one-layer workspace query looks at n and obs_rows before the shape, the two-layer one at the shape first.  The PPO and fit
+// calls go on from here, alike for both depths: the PPO arguments (refuse_ppo: mode, eps, then the epilogue's null arrays), the
+// fit's null arrays, a workspace that would not fit an int.  Nothing is queued before all of it has passed.
+int refuse_training(const PmlpStates& s, const PmlpNet& net, bool null_arg, int pool = BBX_POOL_SUM) {
+  const bool two = net.layers == 2;
+  if (two) { if (int rc = refuse_pmlp2_shape(s.obs_rows, s.cols, net.h1, net.h2)) return rc; }
+  if (s.at && s.n_src < 0) return fail(BBX_E_ARG, "bad policy shape (n_src = %d)", s.n_src);
+  if (s.at && s.n > 0 && !s.index) return fail(BBX_E_ARG, "null argument");
+  if (int rc = refuse_args(null_arg, s.n < 0 || s.obs_rows < 1, "bad policy shape", s.obs_rows)) return rc;
+  if (!two && bbx_pmlp_prepared_floats(s.cols, net.h1) < 0) return BBX_E_UNSUPPORTED;
+  return pool < BBX_POOL_SUM || pool > BBX_POOL_LSE ? fail(BBX_E_ARG, "bad pool %d (0: sum, 1: mean, 2: log-sum-exp)", pool) : BBX_OK;
+}
+// the null-argument expressions the calls are made of: the weights and the states' arrays, the gradient outputs
+bool no_inputs(const PmlpStates& s, const PmlpNet& net) { return !net.prepared || (s.n > 0 && (!s.obs || !s.rows)); }
+bool no_grads(const PmlpNet& net, const PmlpGrads& g) {
+  return !g.workspace || !g.gw1 || !g.gb1 || !g.gw2 || !g.gb2 || (net.layers == 2 && (!g.gw3 || !g.gb3));
+}
+// the floats of the gradient kernels' workspace: of an admitted call, and as the workspace queries answer (or refuse)
+int grad_floats(const PmlpStates& s, const PmlpNet& net) {
+  return net.layers == 2 ? pmlp2_grad_workspace_floats(s.n, s.cols, net.h1, net.h2) : pmlp_grad_workspace_floats(s.n, s.cols, net.h1);
+}
+int grad_workspace(int n, int obs_rows, int cols, const PmlpNet& net) {
+  const PmlpStates s{nullptr, nullptr, n, nullptr, n, obs_rows, cols, false};
+  if (int rc = refuse_training(s, net, false)) return rc;
+  return grad_floats(s, net);
 }
 
-// ---- the training calls, plain and indexed in one body each.  d_index == null: position k of the call is recorded state k
-// (n_src == n); otherwise it is state d_index[k] of n_src recorded ones (the _at entries: refuse_index first)
-int refuse_index(int n_src, const int32_t* d_index, int n) {
-  if (n_src < 0) return fail(BBX_E_ARG, "bad policy shape (n_src = %d)", n_src);
-  if (n > 0 && !d_index) return fail(BBX_E_ARG, "null argument");
-  return BBX_OK;
+// The forward and the gradient calls.  Two layers ask for the device (their launchers size themselves by it), and their forward
+// calls with n == 0 return before they do; the gradient calls with n == 0 still zero their outputs.
+// (loss: the forward kernel of a PPO call, which may leave d_logprobs out)
+int pmlp_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, void* stream, const PmlpLoss* loss = nullptr) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || (s.n > 0 && (!actions || (!logprobs && !loss))))) return rc;
+  if (net.layers == 1) return launched(bbx_launch_pmlp_logprob(s, net, actions, logprobs, entropy, loss, (hipStream_t)stream));
+  if (s.n == 0) return BBX_OK;
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_logprob(s, net, actions, logprobs, entropy, loss, d.info.cus, d.info.max_lds, (hipStream_t)stream), d);
 }
-int pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-                 const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream, const PmlpLoss* loss = nullptr) {
-  // (loss: the forward kernel of a PPO call, which may leave d_logprobs out)
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || (!d_logprobs && !loss))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, d_index, n_src, loss,
-                                          (hipStream_t)stream));
+int pmlp_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || no_grads(net, g) || (s.n > 0 && (!actions || !glogp)))) return rc;
+  if (net.layers == 1) return launched(bbx_launch_pmlp_grad(s, net, actions, glogp, gent, g, (hipStream_t)stream));
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_grad(s, net, actions, glogp, gent, g, d.info.max_lds, (hipStream_t)stream), d);
 }
-int pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-              const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
-              float* d_gb2, void* stream) {
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return launched(bbx_launch_pmlp_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
-                                       d_gw2, d_gb2, d_index, n_src, (hipStream_t)stream));
+// (fit: the forward kernel of a fit call, which may leave both value outputs out)
+int pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, void* stream, const PmlpFit* fit = nullptr) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || (s.n > 0 && !values && !values64 && !fit), pool)) return rc;
+  if (net.layers == 1) return launched(bbx_launch_pmlp_value(s, net, pool, values, values64, fit, (hipStream_t)stream));
+  if (s.n == 0) return BBX_OK;
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_value(s, net, pool, values, values64, fit, d.info.cus, d.info.max_lds, (hipStream_t)stream), d);
 }
-int pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-                  const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream, const PmlpLoss* loss = nullptr) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || !d_actions || (!d_logprobs && !loss))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (n == 0) return BBX_OK;
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_logprob(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, d_index,
-                                               n_src, loss, di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
-}
-int pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-               const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1,
-               float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 ||
-                           (n > 0 && (!d_obs || !d_rows || !d_actions || !d_glogp)), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_grad(d_obs, d_rows, d_actions, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1,
-                                            d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, d_index, n_src, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
+int pmlp_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || no_grads(net, g) || (s.n > 0 && !gvalue), pool)) return rc;
+  if (net.layers == 1) return launched(bbx_launch_pmlp_value_grad(s, net, pool, gvalue, g, (hipStream_t)stream));
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_value_grad(s, net, pool, gvalue, g, d.info.max_lds, (hipStream_t)stream), d);
 }
 
-// ---- the PPO calls: the forward body with the loss epilogue, the statistics kernel, the gradient body on the coefficients the
+// ---- the PPO call: the forward body with the loss epilogue, the statistics kernel, the gradient body on the coefficients the
 // epilogue wrote.  Everything either body would refuse is refused here first, before anything is queued
 struct PpoArgs {
   const float* old_logprobs; const float* advantages; int mode; float scale, eps, ent_coef, c_kl;
@@ -124,123 +152,34 @@ int ppo_workspace(int n, int grad_floats) {
   const int fl = pmlp_ppo_workspace_floats(n, grad_floats);
   return fl < 0 ? fail(BBX_E_ARG, "bad policy shape (n = %d: the workspace would not fit an int)", n) : fl;
 }
-int ppo_stats(const float* tail, int n, double* d_stats, void* stream) {
-  if (!d_stats) return BBX_OK;                                        // (n == 0 and no statistics wanted)
-  return launched(bbx_launch_pmlp_ppo_stats(tail, n, d_stats, (hipStream_t)stream));
-}
-int pmlp_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-             const float* d_prepared, int hidden, const PpoArgs& a, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_actions)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  if (int rc = refuse_ppo(a, n)) return rc;
-  const int gfl = pmlp_grad_workspace_floats(n, cols, hidden);
-  if (ppo_workspace(n, gfl) < 0) return BBX_E_ARG;
-  const PmlpLoss loss{a.old_logprobs, a.advantages, a.coef, d_workspace + gfl, n, a.mode, a.scale, a.eps, a.ent_coef, a.c_kl};
-  if (int rc = pmlp_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, a.logprobs, a.entropy, stream, &loss)) return rc;
-  if (int rc = ppo_stats(loss.tail, n, a.stats, stream)) return rc;
-  return pmlp_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, a.coef, a.coef ? a.coef + n : nullptr, d_workspace, d_gw1,
-                   d_gb1, d_gw2, d_gb2, stream);
-}
-int pmlp2_ppo(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
-              const float* d_prepared, int hidden1, int hidden2, const PpoArgs& a, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
-              float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows || !d_actions)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (int rc = refuse_ppo(a, n)) return rc;
-  const int gfl = pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
-  if (ppo_workspace(n, gfl) < 0) return BBX_E_ARG;
-  const PmlpLoss loss{a.old_logprobs, a.advantages, a.coef, d_workspace + gfl, n, a.mode, a.scale, a.eps, a.ent_coef, a.c_kl};
-  if (int rc = pmlp2_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, a.logprobs, a.entropy, stream, &loss)) return rc;
-  if (int rc = ppo_stats(loss.tail, n, a.stats, stream)) return rc;
-  return pmlp2_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, a.coef, a.coef ? a.coef + n : nullptr, d_workspace,
-                    d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
+int pmlp_ppo(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const PpoArgs& a, const PmlpGrads& g, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || no_grads(net, g) || (s.n > 0 && !actions))) return rc;
+  if (int rc = refuse_ppo(a, s.n)) return rc;
+  const int gfl = grad_floats(s, net);
+  if (ppo_workspace(s.n, gfl) < 0) return BBX_E_ARG;
+  const PmlpLoss loss{a.old_logprobs, a.advantages, a.coef, g.workspace + gfl, s.n, a.mode, a.scale, a.eps, a.ent_coef, a.c_kl};
+  if (int rc = pmlp_logprob(s, net, actions, a.logprobs, a.entropy, stream, &loss)) return rc;
+  if (a.stats) { if (int rc = launched(bbx_launch_pmlp_ppo_stats(loss.tail, s.n, a.stats, (hipStream_t)stream))) return rc; }   // (null: n == 0 and none wanted)
+  return pmlp_grad(s, net, actions, a.coef, a.coef ? a.coef + s.n : nullptr, g, stream);
 }
 
-// ---- the critic (bbx_pmlp_value.h): values, their weight gradients, and the fit call — the forward body with the squared-error
-// epilogue, the statistics kernel, the gradient body on the coefficients the epilogue wrote.  The refusals of the policy's
-// training calls, in their order; everything either body would refuse is refused by the fit call first
-static_assert(BBX_POOL_SUM == PMLP_POOL_SUM && BBX_POOL_MEAN == PMLP_POOL_MEAN && BBX_POOL_LSE == PMLP_POOL_LSE, "include/bbx.h and bbx_pmlp_shape.h disagree");
-int refuse_pool(int pool) {
-  return pool < BBX_POOL_SUM || pool > BBX_POOL_LSE ? fail(BBX_E_ARG, "bad pool %d (0: sum, 1: mean, 2: log-sum-exp)", pool) : BBX_OK;
-}
-int pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-               int hidden, int pool, float* d_values, double* d_values64, void* stream, const PmlpFit* fit = nullptr) {
-  // (fit: the forward kernel of a fit call, which may leave both value outputs out)
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || (!d_values && !d_values64 && !fit))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  if (int rc = refuse_pool(pool)) return rc;
-  return launched(bbx_launch_pmlp_value(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, d_index, n_src, fit, (hipStream_t)stream));
-}
-int pmlp_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-                    int hidden, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows || !d_gvalue)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  if (int rc = refuse_pool(pool)) return rc;
-  return launched(bbx_launch_pmlp_value_grad(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
-                                             d_index, n_src, (hipStream_t)stream));
-}
+// ---- the critic's fit call: the forward body with the squared-error epilogue, the statistics kernel, the gradient body on the
+// coefficients the epilogue wrote; everything either body would refuse is refused here first
 int fit_workspace(int n, int grad_floats) {
   const int fl = pmlp_fit_workspace_floats(n, grad_floats);
   return fl < 0 ? fail(BBX_E_ARG, "bad policy shape (n = %d: the workspace would not fit an int)", n) : fl;
 }
-int pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-                   int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace,
-                   float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || (n > 0 && (!d_obs || !d_rows)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  if (int rc = refuse_pool(pool)) return rc;
-  if (n > 0 && (!d_targets || !d_coef || !d_stats)) return fail(BBX_E_ARG, "null argument");
-  const int gfl = pmlp_grad_workspace_floats(n, cols, hidden);
-  if (fit_workspace(n, gfl) < 0) return BBX_E_ARG;
-  const PmlpFit fit{d_targets, d_coef, d_workspace + gfl, n, scale};
-  if (int rc = pmlp_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_values, nullptr, stream, &fit)) return rc;
-  if (d_stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, n, d_stats, (hipStream_t)stream))) return rc; }
-  return pmlp_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_coef, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
-}
-// ... and over two hidden layers (bbx_pmlp2_value.h): the shape refusals of the two-layer training calls in front, then the
-// argument checks above, in their order
-int pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-                int hidden1, int hidden2, int pool, float* d_values, double* d_values64, void* stream, const PmlpFit* fit = nullptr) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || (n > 0 && (!d_obs || !d_rows || (!d_values && !d_values64 && !fit))), n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (int rc = refuse_pool(pool)) return rc;
-  if (n == 0) return BBX_OK;
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_value(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, d_index, n_src, fit,
-                                             di.cus, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
-}
-int pmlp2_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-                     int hidden1, int hidden2, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
-                     float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows || !d_gvalue)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;   // (n == 0: the arrays of length n may be null)
-  if (int rc = refuse_pool(pool)) return rc;
-  int dev = 0; DeviceInfo di{};
-  HIPCHK(hipGetDevice(&dev)); HIPCHK(device_info(dev, &di));
-  return launched_lds(bbx_launch_pmlp2_value_grad(d_obs, d_rows, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1,
-                                                  d_gw2, d_gb2, d_gw3, d_gb3, d_index, n_src, di.max_lds, (hipStream_t)stream), dev, di.max_lds);
-}
-int pmlp2_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols, const float* d_prepared,
-                    int hidden1, int hidden2, int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats,
-                    float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_args(!d_prepared || !d_workspace || !d_gw1 || !d_gb1 || !d_gw2 || !d_gb2 || !d_gw3 || !d_gb3 || (n > 0 && (!d_obs || !d_rows)),
-                           n < 0 || obs_rows < 1, "bad policy shape", obs_rows)) return rc;
-  if (int rc = refuse_pool(pool)) return rc;
-  if (n > 0 && (!d_targets || !d_coef)) return fail(BBX_E_ARG, "null argument");   // (d_stats null: no statistics wanted)
-  const int gfl = pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
-  if (fit_workspace(n, gfl) < 0) return BBX_E_ARG;
-  const PmlpFit fit{d_targets, d_coef, d_workspace + gfl, n, scale};
-  if (int rc = pmlp2_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, nullptr, stream, &fit)) return rc;
-  if (d_stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, n, d_stats, (hipStream_t)stream))) return rc; }
-  return pmlp2_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_coef, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
-                          d_gw3, d_gb3, stream);
+int pmlp_value_fit(const PmlpStates& s, const PmlpNet& net, int pool, const float* targets, float scale, float* values, float* coef, double* stats,
+                   const PmlpGrads& g, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || no_grads(net, g), pool)) return rc;
+  // (one layer owes d_stats; two take a null one for "no statistics wanted" and skip the statistics kernel: include/bbx.h)
+  if (s.n > 0 && (!targets || !coef || (net.layers == 1 && !stats))) return fail(BBX_E_ARG, "null argument");
+  const int gfl = grad_floats(s, net);
+  if (fit_workspace(s.n, gfl) < 0) return BBX_E_ARG;
+  const PmlpFit fit{targets, coef, g.workspace + gfl, s.n, scale};
+  if (int rc = pmlp_value(s, net, pool, values, nullptr, stream, &fit)) return rc;
+  if (stats) { if (int rc = launched(bbx_launch_pmlp_value_stats(fit.tail, s.n, stats, (hipStream_t)stream))) return rc; }
+  return pmlp_value_grad(s, net, pool, coef, g, stream);
 }
 
 // A policy rollout inside the step kernels, one hidden layer (hidden2 == 0) or two; admit: the call's shape test and its refusals
@@ -307,38 +246,33 @@ int bbx_pmlp_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch, 
   return pmlp_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden, nullptr, d_actions, d_logprobs, stream, true);
 }
 
-// ---- the policy as a differentiable function of its weights (bbx_pmlp_grad.h)
+// ---- the training calls, one hidden layer: fill the records, call the body.  A plain call is about its n states in order; an _at
+// call about state d_index[k] of n_src at position k
+// the policy as a differentiable function of its weights (bbx_pmlp_grad.h)
 int bbx_pmlp_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                      int hidden, float* d_logprobs, float* d_entropy, void* stream) {
-  return pmlp_logprob(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, stream);
+  return pmlp_logprob(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, d_actions, d_logprobs, d_entropy, stream);
 }
 int bbx_pmlp_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                         int cols, const float* d_prepared, int hidden, float* d_logprobs, float* d_entropy, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, d_logprobs, d_entropy, stream);
+  return pmlp_logprob(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, d_actions, d_logprobs, d_entropy,
+                      stream);
 }
-
-int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) {
-  if (n < 0 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
-  if (int rc = refuse_args(false, false, "", obs_rows)) return rc;
-  if (bbx_pmlp_prepared_floats(cols, hidden) < 0) return BBX_E_UNSUPPORTED;
-  return pmlp_grad_workspace_floats(n, cols, hidden);
-}
-
+int bbx_pmlp_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) { return grad_workspace(n, obs_rows, cols, PmlpNet{nullptr, 1, hidden}); }
 int bbx_pmlp_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                   int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
                   void* stream) {
-  return pmlp_grad(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+  return pmlp_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, d_actions, d_glogp, d_gent,
+                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 int bbx_pmlp_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                      int cols, const float* d_prepared, int hidden, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1,
                      float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
-                   stream);
+  return pmlp_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, d_actions, d_glogp, d_gent,
+                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 
-// ---- forward, PPO loss and gradients in one call
+// forward, PPO loss and gradients in one call
 int bbx_pmlp_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden) {
   const int gfl = bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden);
   return gfl < 0 ? gfl : ppo_workspace(n, gfl);
@@ -347,40 +281,39 @@ int bbx_pmlp_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t
                       int hidden, const float* d_old_logprobs, const float* d_advantages, int mode, float scale, float eps, float ent_coef, float c_kl,
                       float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
                       float* d_gb2, void* stream) {
-  return pmlp_ppo(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden,
-                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
-                  d_gw2, d_gb2, stream);
+  return pmlp_ppo(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, d_actions,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats},
+                  PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 int bbx_pmlp_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                          int cols, const float* d_prepared, int hidden, const float* d_old_logprobs, const float* d_advantages, int mode, float scale,
                          float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace,
                          float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden,
-                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
-                  d_gw2, d_gb2, stream);
+  return pmlp_ppo(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, d_actions,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats},
+                  PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 
-// ---- the critic: a pooled value of the row scores, its weight gradients, the squared-error fit (bbx_pmlp_value.h)
+// the critic: a pooled value of the row scores, its weight gradients, the squared-error fit (bbx_pmlp_value.h)
 int bbx_pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
                    float* d_values, double* d_values64, void* stream) {
-  return pmlp_value(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, stream);
+  return pmlp_value(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, pool, d_values, d_values64, stream);
 }
 int bbx_pmlp_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                       const float* d_prepared, int hidden, int pool, float* d_values, double* d_values64, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_values, d_values64, stream);
+  return pmlp_value(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, pool, d_values, d_values64, stream);
 }
 int bbx_pmlp_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden) { return bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden); }
 int bbx_pmlp_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
                         const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  return pmlp_value_grad(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+  return pmlp_value_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, pool, d_gvalue,
+                         PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 int bbx_pmlp_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                            const float* d_prepared, int hidden, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1,
                            float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, stream);
+  return pmlp_value_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, pool, d_gvalue,
+                         PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 int bbx_pmlp_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden) {
   const int gfl = bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden);
@@ -389,15 +322,14 @@ int bbx_pmlp_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidde
 int bbx_pmlp_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
                        const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
                        float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  return pmlp_value_fit(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden, pool, d_targets, scale, d_values, d_coef, d_stats, d_workspace,
-                        d_gw1, d_gb1, d_gw2, d_gb2, stream);
+  return pmlp_value_fit(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden}, pool, d_targets, scale, d_values,
+                        d_coef, d_stats, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 int bbx_pmlp_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                           const float* d_prepared, int hidden, int pool, const float* d_targets, float scale, float* d_values, float* d_coef,
                           double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp_value_fit(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden, pool, d_targets, scale, d_values, d_coef, d_stats, d_workspace,
-                        d_gw1, d_gb1, d_gw2, d_gb2, stream);
+  return pmlp_value_fit(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden}, pool, d_targets, scale, d_values,
+                        d_coef, d_stats, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 
 // ---- two and three hidden layers (bbx_pmlp2.hip)
@@ -420,38 +352,31 @@ int bbx_pmlp2_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch,
   return pmlp_deep_act(d_obs, d_rows, batch, obs_rows, cols, d_prepared, hidden1, 0, hidden2, false, nullptr, d_actions, d_logprobs, stream, true);
 }
 
-// ---- two hidden layers as a differentiable function of the weights (bbx_pmlp2_grad.h).  Shapes: those of bbx_pmlp2_act,
-// refused before a device is asked for anything
+// ---- the training calls, two hidden layers (bbx_pmlp2_grad.h, bbx_pmlp2_value.h): the same bodies on the weights
+// bbx_pmlp2_prepare leaves.  Shapes: those of bbx_pmlp2_act, refused before a device is asked for anything
 int bbx_pmlp2_logprob(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                       int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
-  return pmlp2_logprob(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, stream);
+  return pmlp_logprob(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions, d_logprobs, d_entropy, stream);
 }
 int bbx_pmlp2_logprob_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                          int cols, const float* d_prepared, int hidden1, int hidden2, float* d_logprobs, float* d_entropy, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_logprob(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_logprobs, d_entropy, stream);
+  return pmlp_logprob(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions, d_logprobs,
+                      d_entropy, stream);
 }
-
 int bbx_pmlp2_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (n < 0 || obs_rows < 1) return fail(BBX_E_ARG, "bad policy shape");
-  return pmlp2_grad_workspace_floats(n, cols, hidden1, hidden2);
+  return grad_workspace(n, obs_rows, cols, PmlpNet{nullptr, 2, hidden1, hidden2});
 }
-
 int bbx_pmlp2_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n, int obs_rows, int cols, const float* d_prepared,
                    int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
                    float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  return pmlp2_grad(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1, d_gb1, d_gw2,
-                    d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions, d_glogp, d_gent,
+                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 int bbx_pmlp2_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                       int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_glogp, const float* d_gent, float* d_workspace,
                       float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_grad(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, d_glogp, d_gent, d_workspace, d_gw1, d_gb1,
-                    d_gw2, d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions, d_glogp, d_gent,
+                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 
 int bbx_pmlp2_ppo_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
@@ -462,31 +387,27 @@ int bbx_pmlp2_ppo_grad(const int32_t* d_obs, const int32_t* d_rows, const int32_
                        int hidden1, int hidden2, const float* d_old_logprobs, const float* d_advantages, int mode, float scale, float eps, float ent_coef,
                        float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1,
                        float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  return pmlp2_ppo(d_obs, d_rows, d_actions, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2,
-                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
-                   d_gw2, d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_ppo(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats},
+                  PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int32_t* d_actions, int n_src, const int32_t* d_index, int n, int obs_rows,
                           int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_old_logprobs, const float* d_advantages, int mode,
                           float scale, float eps, float ent_coef, float c_kl, float* d_logprobs, float* d_entropy, float* d_coef, double* d_stats,
                           float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_ppo(d_obs, d_rows, d_actions, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2,
-                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats}, d_workspace, d_gw1, d_gb1,
-                   d_gw2, d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_ppo(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions,
+                  PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats},
+                  PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 
-// ---- the critic over two hidden layers (bbx_pmlp2_value.h)
 int bbx_pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, int pool,
                     float* d_values, double* d_values64, void* stream) {
-  return pmlp2_value(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, stream);
+  return pmlp_value(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_values, d_values64, stream);
 }
 int bbx_pmlp2_value_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                        const float* d_prepared, int hidden1, int hidden2, int pool, float* d_values, double* d_values64, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_value(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_values, d_values64, stream);
+  return pmlp_value(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_values, d_values64,
+                    stream);
 }
 int bbx_pmlp2_value_grad_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
   return bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
@@ -494,16 +415,14 @@ int bbx_pmlp2_value_grad_workspace_floats(int n, int obs_rows, int cols, int hid
 int bbx_pmlp2_value_grad(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
                          int pool, const float* d_gvalue, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
                          float* d_gb3, void* stream) {
-  return pmlp2_value_grad(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2, d_gb2,
-                          d_gw3, d_gb3, stream);
+  return pmlp_value_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_gvalue,
+                         PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 int bbx_pmlp2_value_grad_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                             const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_gvalue, float* d_workspace, float* d_gw1,
                             float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_value_grad(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_gvalue, d_workspace, d_gw1, d_gb1, d_gw2,
-                          d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_value_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_gvalue,
+                         PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 int bbx_pmlp2_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
   const int gfl = bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
@@ -512,17 +431,15 @@ int bbx_pmlp2_value_fit_workspace_floats(int n, int obs_rows, int cols, int hidd
 int bbx_pmlp2_value_fit(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2,
                         int pool, const float* d_targets, float scale, float* d_values, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1,
                         float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
-  return pmlp2_value_fit(d_obs, d_rows, n, nullptr, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_targets, scale, d_values, d_coef, d_stats,
-                         d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_value_fit(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_targets, scale, d_values,
+                        d_coef, d_stats, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 int bbx_pmlp2_value_fit_at(const int32_t* d_obs, const int32_t* d_rows, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
                            const float* d_prepared, int hidden1, int hidden2, int pool, const float* d_targets, float scale, float* d_values,
                            float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
                            float* d_gb3, void* stream) {
-  if (obs_rows > BBX_POLICY_MAX_ROWS || pmlp2_shape_refused(cols, hidden1, hidden2)) return refuse_pmlp2(obs_rows, cols, hidden1, hidden2);
-  if (int rc = refuse_index(n_src, d_index, n)) return rc;
-  return pmlp2_value_fit(d_obs, d_rows, n_src, d_index, n, obs_rows, cols, d_prepared, hidden1, hidden2, pool, d_targets, scale, d_values, d_coef, d_stats,
-                         d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3, stream);
+  return pmlp_value_fit(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, pool, d_targets, scale,
+                        d_values, d_coef, d_stats, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 
 int bbx_pmlp3_prepare(const float* d_w1, const float* d_b1, const float* d_w2, const float* d_b2, const float* d_w3, const float* d_b3,

@@ -501,9 +501,11 @@ extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int 
                                        else BBX_PMLP_DISPATCH_IE(M, N, 32); } while (0)
 #define BBX_PMLP_DISPATCH(M) do { if (nb == 1) BBX_PMLP_DISPATCH_K(M, 1); else if (nb == 2) BBX_PMLP_DISPATCH_K(M, 2); \
                                   else if (nb == 4) BBX_PMLP_DISPATCH_K(M, 4); else BBX_PMLP_DISPATCH_K(M, 8); } while (0)
-extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss,
+// (the launchers take the records of bbx_pmlp_shape.h and name the fields as the kernels name their parameters)
+extern "C" int bbx_launch_pmlp_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
                                        hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
@@ -534,14 +536,16 @@ struct PmlpGradLaunch {
         grid((nw + waves - 1) / waves, ng), lds(pmlp_grad_lds_bytes(waves, obs_rows)) {}
 };
 // the second kernel of either, unless launching the first has failed: the nw partial sums of every output added in order
-static int pmlp_grad_reduce(const float* ws, int nw, int cols, int hidden, float* gw1, float* gb1, float* gw2, float* gb2, hipStream_t stream) {
+static int pmlp_grad_reduce(const PmlpGrads& g, int nw, int cols, int hidden, hipStream_t stream) {
   if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, ws, nw, cols, hidden, gw1, gb1, gw2, gb2);
+  hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, g.workspace, nw, cols, hidden,
+                     g.gw1, g.gb1, g.gw2, g.gb2);
   return (int)hipGetLastError();
 }
-extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                    int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                    const int32_t* index, int n_src, hipStream_t stream) {
+extern "C" int bbx_launch_pmlp_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
+                                    hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
   const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const bool epi = false;
   const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
@@ -549,11 +553,12 @@ extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, con
                                                       cols, wp, glogp, gent, L.nw, ws, index, n_src)
   if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_GRAD);
 #undef BBX_PMLP_GRAD
-  return pmlp_grad_reduce(ws, L.nw, cols, hidden, gw1, gb1, gw2, gb2, stream);
+  return pmlp_grad_reduce(g, L.nw, cols, hidden, stream);
 }
 // the critic: values of n positions (fit != null: with the squared-error epilogue)
-extern "C" int bbx_launch_pmlp_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
-                                     float* values, double* values64, const int32_t* index, int n_src, const PmlpFit* fit, hipStream_t stream) {
+extern "C" int bbx_launch_pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
   if (n <= 0) return 0;
   const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const size_t ml = pmlp_lds_bytes(waves, obs_rows);
@@ -571,9 +576,9 @@ extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* sta
   return (int)hipGetLastError();
 }
 // the critic's weight gradients
-extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
-                                          const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, const int32_t* index, int n_src,
-                                          hipStream_t stream) {
+extern "C" int bbx_launch_pmlp_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
   const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
   const bool epi = false;
   const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
@@ -581,7 +586,7 @@ extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* row
                                                        wp, pool, gvalue, L.nw, ws, index, n_src)
   if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_VGRAD);
 #undef BBX_PMLP_VGRAD
-  return pmlp_grad_reduce(ws, L.nw, cols, hidden, gw1, gb1, gw2, gb2, stream);
+  return pmlp_grad_reduce(g, L.nw, cols, hidden, stream);
 }
 #undef BBX_PMLP_DISPATCH
 #undef BBX_PMLP_DISPATCH_K

@@ -1,7 +1,9 @@
 // The batch handle of libbbx's C ABI and the internals its translation units share (bbx_api.cpp: creation, kernels of a
 // launch, waits, stepping; bbx_api_session.cpp: what a call becomes — persistent / mailbox sessions, recorded steps;
-// bbx_api_value.cpp: value(); bbx_api_policy.cpp: the PMLP policy calls — prepare, act, policy step, policy rollouts;
-// bbx_api_state.cpp: introspection, generators, text format).
+// bbx_api_value.cpp: value(); bbx_api_policy.cpp: the PMLP policy calls — prepare, act, policy step, policy rollouts, and the
+// training calls of policy and critic, one body per call for both depths; bbx_api_state.cpp: introspection, generators, text
+// format), and the launchers of the kernel files.  The PMLP training launchers take what a call is about as the records of
+// bbx_pmlp_shape.h (PmlpStates, PmlpNet, PmlpGrads), not as positional lists.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,7 @@
 
 #include "bbx_host.h"
 #include "bbx_ideals.h"
+#include "bbx_pmlp_shape.h"
 
 extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_block, hipStream_t stream);
 extern "C" int bbx_launch_clone(const char* src_recs, char* dst_recs, const BbxLayout* L, const int32_t* src, const int32_t* dst, int n,
@@ -43,36 +46,29 @@ extern "C" int bbx_launch_mark_reset(char* recs, uint32_t rec_bytes, int B, cons
 extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const float* w2, float b2, int cols, int hidden, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, int greedy, hipStream_t stream);   // (greedy: the argmax, u unread)
-extern "C" int bbx_launch_pmlp_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                       int hidden, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss,
-                                       hipStream_t stream);   // (index: null, or position k is about state index[k] of n_src; loss: null, or the loss epilogue's arguments)
+// the training launchers take the records of bbx_pmlp_shape.h (states, network, gradient outputs) and their head's own arguments
+// (loss / fit: null, or the arguments of the forward kernel's epilogue)
+extern "C" int bbx_launch_pmlp_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
+                                       hipStream_t stream);
 extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats, hipStream_t stream);
-extern "C" int bbx_launch_pmlp_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                    int hidden, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                    const int32_t* index, int n_src, hipStream_t stream);
-extern "C" int bbx_launch_pmlp_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
-                                     float* values, double* values64, const int32_t* index, int n_src, const struct PmlpFit* fit, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
+                                    hipStream_t stream);
+extern "C" int bbx_launch_pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* stats, hipStream_t stream);
-extern "C" int bbx_launch_pmlp_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int hidden, int pool,
-                                          const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, const int32_t* index, int n_src,
-                                          hipStream_t stream);
+extern "C" int bbx_launch_pmlp_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
                                     const float* u, int32_t* actions, float* logprobs, int greedy, int cus, int max_lds, hipStream_t stream);   // (hm = 0: no middle layer)
-extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const struct PmlpLoss* loss, int cus,
-                                        int max_lds, hipStream_t stream);
-extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                     int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                     float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream);
-extern "C" int bbx_launch_pmlp2_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
-                                      float* values, double* values64, const int32_t* index, int n_src, const struct PmlpFit* fit, int cus, int max_lds,
-                                      hipStream_t stream);
-extern "C" int bbx_launch_pmlp2_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
-                                           const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
-                                           const int32_t* index, int n_src, int max_lds, hipStream_t stream);
-
+// ... with two hidden layers, which size their launch by the device (cus, max_lds: bbx_host::DeviceInfo)
+extern "C" int bbx_launch_pmlp2_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
+                                        int cus, int max_lds, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
+                                     int max_lds, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, int cus,
+                                      int max_lds, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, int max_lds,
+                                           hipStream_t stream);
 
 // The call in flight: what finish() waits for, continues and reports on.  Formed in two places only — start_flight() (a
 // call begins) and continue_session() (a closed session's closing kernels, bbx_api_session.cpp); grow_records moves its

@@ -240,9 +240,11 @@ struct Pmlp2ForwardLaunch {
   }
 };
 // (hipErrorInvalidValue: the device has less LDS per workgroup than the shape needs)
-extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                        int h1, int h2, float* logprobs, float* entropy, const int32_t* index, int n_src, const PmlpLoss* loss, int cus,
-                                        int max_lds, hipStream_t stream) {
+// (the launchers take the records of bbx_pmlp_shape.h and name the fields as the kernels name their parameters)
+extern "C" int bbx_launch_pmlp2_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
+                                        int cus, int max_lds, hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
   if (n <= 0) return 0;
   const PmlpLoss ls = loss ? *loss : PmlpLoss{};
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
@@ -268,17 +270,18 @@ extern "C" int bbx_launch_pmlp2_logprob(const int32_t* obs, const int32_t* rows,
 }
 // the second kernel of the policy's and the critic's gradients, unless launching the first (rc) has failed: the `groups` slots of
 // every output added in order
-static int pmlp2_grad_reduce(int rc, const float* ws, int groups, int cols, int h1, int h2, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3,
-                             float* gb3, hipStream_t stream) {
+static int pmlp2_grad_reduce(int rc, const PmlpGrads& g, int groups, int cols, int h1, int h2, hipStream_t stream) {
   if (rc) return rc;
   if ((rc = (int)hipGetLastError())) return rc;
   const int total = cols * h1 + h1 + h1 * h2 + 2 * h2 + 1;
-  hipLaunchKernelGGL(bbx_pmlp2_grad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3);
+  hipLaunchKernelGGL(bbx_pmlp2_grad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, g.workspace, groups, cols, h1, h2, g.gw1, g.gb1, g.gw2,
+                     g.gb2, g.gw3, g.gb3);
   return (int)hipGetLastError();
 }
-extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, const int32_t* actions, int n, int obs_rows, int cols, const float* wp,
-                                     int h1, int h2, const float* glogp, const float* gent, float* ws, float* gw1, float* gb1, float* gw2, float* gb2,
-                                     float* gw3, float* gb3, const int32_t* index, int n_src, int max_lds, hipStream_t stream) {
+extern "C" int bbx_launch_pmlp2_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
+                                     int max_lds, hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
   const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
   const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows);
@@ -293,12 +296,13 @@ extern "C" int bbx_launch_pmlp2_grad(const int32_t* obs, const int32_t* rows, co
 #undef BBX_P2_GRAD_AT
 #undef BBX_P2_GRAD
 #undef BBX_P2_GRAD_I
-  return pmlp2_grad_reduce(rc, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3, stream);
+  return pmlp2_grad_reduce(rc, g, groups, cols, h1, h2, stream);
 }
 // the critic: values of n positions (fit != null: with the squared-error epilogue), in the frame of bbx_launch_pmlp2_logprob
-extern "C" int bbx_launch_pmlp2_value(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
-                                      float* values, double* values64, const int32_t* index, int n_src, const PmlpFit* fit, int cus, int max_lds,
-                                      hipStream_t stream) {
+extern "C" int bbx_launch_pmlp2_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, int cus,
+                                      int max_lds, hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
   if (n <= 0) return 0;
   const PmlpFit ft = fit ? *fit : PmlpFit{};
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
@@ -323,9 +327,10 @@ extern "C" int bbx_launch_pmlp2_value(const int32_t* obs, const int32_t* rows, i
   return rc ? rc : (int)hipGetLastError();
 }
 // the critic's weight gradients: the policy's partition, workspace and second kernel
-extern "C" int bbx_launch_pmlp2_value_grad(const int32_t* obs, const int32_t* rows, int n, int obs_rows, int cols, const float* wp, int h1, int h2, int pool,
-                                           const float* gvalue, float* ws, float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3,
-                                           const int32_t* index, int n_src, int max_lds, hipStream_t stream) {
+extern "C" int bbx_launch_pmlp2_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, int max_lds,
+                                           hipStream_t stream) {
+  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
+  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
   const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
   const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
   const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows, Pmlp2ValueHead::exact_a1);
@@ -340,7 +345,7 @@ extern "C" int bbx_launch_pmlp2_value_grad(const int32_t* obs, const int32_t* ro
 #undef BBX_P2_VGRAD_AT
 #undef BBX_P2_VGRAD
 #undef BBX_P2_VGRAD_I
-  return pmlp2_grad_reduce(rc, ws, groups, cols, h1, h2, gw1, gb1, gw2, gb2, gw3, gb3, stream);
+  return pmlp2_grad_reduce(rc, g, groups, cols, h1, h2, stream);
 }
 #undef BBX_P2G_SHAPES
 #undef BBX_P2G_K

@@ -108,6 +108,25 @@ BBX_HD constexpr int pmlp_fit_workspace_floats(int n, int grad_floats) {   // -1
   return t > 0x7fffffffLL ? -1 : (int)t;
 }
 
+// ---- what a training call is about (bbx_pmlp[2]_{logprob, grad, ppo_grad, value, value_grad, value_fit}[_at] of include/bbx.h):
+// host-side records, filled by the entry points (bbx_api_policy.cpp) and taken by the training launchers (bbx_aux.hip,
+// bbx_pmlp2.hip) — a field has a name where a place in a list of eight float* had none.  What belongs to one head stays an
+// argument: actions, glogp, gent (policy); pool, gvalue (critic); PmlpLoss, PmlpFit
+struct PmlpStates {                                // the recorded states
+  const int32_t* obs; const int32_t* rows;         // [n_src] blocks of obs_rows x cols, and their row counts
+  int n_src; const int32_t* index;                 // index == null: position k of the call is state k and n_src == n; else state index[k]
+  int n, obs_rows, cols;                           // n positions
+  bool at;                                         // an _at call, which owes an index when n > 0 (what is refused, never what is launched)
+};
+struct PmlpNet {                                   // the network: bbx_pmlp_prepare's weights, or bbx_pmlp2_prepare's
+  const float* prepared;
+  int layers, h1, h2;                              // layers: 1 or 2 (stated, not read off h2: hidden2 = 0 is a two-layer shape to refuse); one layer: h2 = 0
+};
+struct PmlpGrads {                                 // the gradient outputs
+  float* workspace;                                // the partial sums (pmlp[2]_grad_workspace_floats)
+  float *gw1, *gb1, *gw2, *gb2, *gw3, *gb3;        // (gw3, gb3: null with one layer)
+};
+
 // ---- the policies built into the step kernels
 // a rollout with one hidden layer, step kernels of W-word monomials (bbx_binom_policy_kernel; 8-byte monomials with 3 variables
 // and k = 2 also bbx_fast_policy_rollout_kernel): 33..128 hidden units, 6 k-steps, or 10 with 16-byte monomials
