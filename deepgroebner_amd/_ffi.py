@@ -146,6 +146,7 @@ SIGNATURES = {
     "bbx_action_values_chunk": (C.c_int, [_vp, C.c_int]),
     "bbx_action_values_plan": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "bbx_gae_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp]),
+    "bbx_gae_bootstrap_device": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_pmlp_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp2_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp3_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),

@@ -432,13 +432,20 @@ extern "C" int bbx_values_device(bbx_batch* b, const char* strategy, double gamm
   return values_device(b, agent, gamma, agent == BBX_AGENT_STDRANDOM ? d_seeds : nullptr, d_values, (hipStream_t)stream);
 }
 
-extern "C" int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
-                              double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream) {
+extern "C" int bbx_gae_bootstrap_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
+                                        double gam, double lam, const double* d_last_values, double* d_returns, double* d_advantages,
+                                        uint8_t* d_complete, double* d_lambda_returns, void* stream) {
   if (!d_rewards || !d_values || !d_dones || !d_returns || !d_advantages || !d_complete || nsteps < 0 || batch < 0) return fail(BBX_E_ARG, "bad arguments");
   if (nsteps == 0 || batch == 0) return BBX_OK;
-  const int lrc = bbx_launch_gae(d_rewards, d_values, d_dones, nsteps, batch, gam, gam * lam, d_returns, d_advantages, d_complete, (hipStream_t)stream);
+  const int lrc = bbx_launch_gae(d_rewards, d_values, d_dones, nsteps, batch, gam, gam * lam, d_last_values, d_returns, d_advantages, d_complete,
+                                 d_lambda_returns, (hipStream_t)stream);
   if (lrc) return fail(BBX_E_DEVICE, "GAE launch failed: %s", hipGetErrorString((hipError_t)lrc));
   return BBX_OK;
+}
+
+extern "C" int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
+                              double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream) {
+  return bbx_gae_bootstrap_device(d_rewards, d_values, d_dones, nsteps, batch, gam, lam, nullptr, d_returns, d_advantages, d_complete, nullptr, stream);
 }
 
 // per-episode returns and lengths of a [nsteps][batch] block of rewards and dones (bbx_episodes_kernel): no handle, asynchronous.

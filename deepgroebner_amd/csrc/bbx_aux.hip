@@ -346,15 +346,21 @@ extern "C" int bbx_launch_av_collect(const char* recs, uint32_t rec_bytes, int n
 // One thread per environment, reverse scan over t; consecutive threads read consecutive elements of every row.  The
 // arithmetic is the torch loop's, operation for operation: every product is rounded before it is added (no fused
 // multiply-add: contraction is off in the kernel body), gl = gam * lam was formed once in double by the caller.
+// last_values (or NULL): the value of the state behind step T - 1 of every environment, where the scan starts instead of at
+// zero (truncated-horizon GAE: an episode cut by the end of the block is bootstrapped, and every step counts as complete); a
+// done flag clears the carries before anything reads them, so the entry of an environment whose last step ended its episode
+// is never used.  LAM: lambda_returns[i] = adv + v, the TD(lambda) value target, one rounded sum.
+template <bool LAM>
 __global__ void bbx_gae_kernel(const double* __restrict__ rewards, const double* __restrict__ values, const uint8_t* __restrict__ dones,
-                               int T, int B, double gam, double gl, double* __restrict__ returns, double* __restrict__ advantages,
-                               uint8_t* __restrict__ complete) {
+                               int T, int B, double gam, double gl, const double* __restrict__ last_values, double* __restrict__ returns,
+                               double* __restrict__ advantages, uint8_t* __restrict__ complete, double* __restrict__ lambda_returns) {
 #pragma clang fp contract(off)                              // (the default contracts a * b + c into one rounding; __dmul_rn / __dadd_rn are
                                                             // inline * and + that carry the default with them, so plain operators under this)
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B) return;
   double nret = 0.0, nadv = 0.0, nval = 0.0;
   uint8_t comp = 0;
+  if (last_values) { nret = nval = last_values[e]; comp = 1; }
 #pragma unroll 8                                            // (the loads of a row do not depend on the row above: issued ahead of the chain)
   for (int t = T - 1; t >= 0; t--) {
     const size_t i = (size_t)t * B + e;
@@ -363,12 +369,19 @@ __global__ void bbx_gae_kernel(const double* __restrict__ rewards, const double*
     const double ret = r + gam * nret;
     const double adv = ((r - v) + gam * nval) + gl * nadv;
     returns[i] = ret; advantages[i] = adv; complete[i] = comp;
+    if (LAM) lambda_returns[i] = adv + v;
     nret = ret; nadv = adv; nval = v;
   }
 }
 extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
-                              double* returns, double* advantages, uint8_t* complete, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_gae_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, returns, advantages, complete);
+                              const double* last_values, double* returns, double* advantages, uint8_t* complete, double* lambda_returns,
+                              hipStream_t stream) {
+  if (lambda_returns)
+    hipLaunchKernelGGL(bbx_gae_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, last_values, returns,
+                       advantages, complete, lambda_returns);
+  else
+    hipLaunchKernelGGL(bbx_gae_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, last_values, returns,
+                       advantages, complete, lambda_returns);
   return (int)hipGetLastError();
 }
 

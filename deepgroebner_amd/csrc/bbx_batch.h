@@ -32,7 +32,8 @@ extern "C" int bbx_launch_av_collect(const char* recs, uint32_t rec_bytes, int n
                                      const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word,
                                      hipStream_t stream);
 extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
-                              double* returns, double* advantages, uint8_t* complete, hipStream_t stream);
+                              const double* last_values, double* returns, double* advantages, uint8_t* complete, double* lambda_returns,
+                              hipStream_t stream);
 extern "C" int bbx_launch_episodes(const double* rewards, const uint8_t* dones, int T, int B, double* carry_return, int32_t* carry_len, int32_t* ep_count,
                                    double* ep_return, int32_t* ep_len, hipStream_t stream);
 extern "C" int bbx_launch_relayout(const char* src_recs, char* dst_recs, const BbxLayout* Ls, const BbxLayout* Ld, int B, hipStream_t stream);

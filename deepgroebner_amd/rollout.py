@@ -14,6 +14,8 @@ PMLPValue) and the kernel calls behind them are deepgroebner_amd.pmlp's; both na
     run_rollout_fused          the same with the policy INSIDE the step kernel, 256 vector steps per launch
     run_rollout(value_strategy=...)   env.value(strategy, gamma) before every step as the baseline   pg.py:461-465
                                (bbx_values_device: written on the device beside the steps); finish(): one GAE kernel
+    run_rollout / run_rollout_fused (bootstrap=True)   buffer.last_values: the value of the state the rollout stops in, where finish()
+                               starts its scan (bbx_gae_bootstrap_device) — episodes the buffer's end cuts are kept, not dropped
     act / run_rollout / run_rollout_fused (greedy=True)   the highest-probability pair at every step   pg.py run_episodes(greedy=True)
     episode_returns            one return and one length per episode from a rollout's rewards and dones (bbx_episodes_device)
     evaluate_policy            the first K episodes of every environment under a policy   scripts/eval.py
@@ -83,7 +85,10 @@ class DeviceTrajectoryBuffer:
     environment.  finish() turns rewards into discounted rewards-to-go and values into GAE advantages per EPISODE
     (episodes end where done is set; an episode still running at the end of the buffer is incomplete and left out, like
     the reference's `[:self.start]`); get() returns the training tensors with the reference's filtering (states with a
-    single row are dropped) and advantage normalisation."""
+    single row are dropped) and advantage normalisation.
+    last_values (None, or float64 [B] on the buffer's device: the value of the state every environment was in BEHIND the last
+    stored step; the rollout functions set it with bootstrap=True and clear it otherwise): finish() starts its scan there
+    instead of at zero (truncated-horizon GAE), nothing is incomplete, and get() returns the steps of the cut episodes too."""
 
     def __init__(self, nsteps, batch, gam=0.99, lam=0.97, obs_shape=None, device="cuda"):
         self.T, self.B, self.gam, self.lam = nsteps, batch, gam, lam
@@ -95,7 +100,8 @@ class DeviceTrajectoryBuffer:
         self.rows = torch.zeros((nsteps, batch), dtype=torch.int32, device=device)
         self.states = torch.empty((nsteps, batch) + tuple(obs_shape), dtype=torch.int32, device=device) if obs_shape else None
         self.t = 0
-        self.returns = self.advantages = self.complete = None
+        self.last_values = None
+        self.returns = self.advantages = self.complete = self.lambda_returns = None
 
     def store(self, state, rows, action, reward, logprob, value, done):
         t = self.t
@@ -110,8 +116,8 @@ class DeviceTrajectoryBuffer:
     def fill_values(self, critic, t0=0, t1=None):
         """self.values[t0:t1] (t1 None: the steps stored so far) <- the critic's values of the stored states, float64: a learned
         baseline for GAE after a rollout that recorded none (run_rollout_fused).  On the device one bbx_pmlp_value call over the
-        block in place (PMLPValue.values with out64); CPU buffers take the critic's torch path.  returns / advantages / complete
-        are cleared, so that the next get_index() finishes again.  A buffer that keeps no states: ValueError."""
+        block in place (PMLPValue.values with out64); CPU buffers take the critic's torch path.  returns / advantages / complete /
+        lambda_returns are cleared, so that the next get_index() finishes again.  A buffer that keeps no states: ValueError."""
         if self.states is None:
             raise ValueError("fill_values: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
         t1 = self.t if t1 is None else t1
@@ -119,32 +125,48 @@ class DeviceTrajectoryBuffer:
             raise IndexError("fill_values: steps [%d, %d) of a buffer of %d" % (t0, t1, self.T))
         if t1 > t0:
             critic.values(self.states[t0:t1], self.rows[t0:t1], out64=self.values[t0:t1])
-        self.returns = self.advantages = self.complete = None
+        self.returns = self.advantages = self.complete = self.lambda_returns = None
 
     def finish(self):
         """Reverse scan over time with episode boundaries: ret_t = r_t + gam ret_{t+1}; delta_t = r_t - v_t + gam v_{t+1};
-        adv_t = delta_t + gam lam adv_{t+1}; nothing crosses a done flag (pg.py:20-76 per trajectory).  Tensors on the GPU:
-        one kernel (bbx_gae_device, one thread per environment); on the CPU: the torch loop (_finish_torch), whose results
-        the kernel reproduces bit for bit."""
+        adv_t = delta_t + gam lam adv_{t+1}; nothing crosses a done flag (pg.py:20-76 per trajectory).  With self.last_values
+        the scan starts from that value of the state behind the last step (ret = v = last_values, adv = 0) and every step is
+        complete; an environment whose last step is done never reads its entry.  self.lambda_returns = adv + v, the TD(lambda)
+        target of a value fit.  Tensors on the GPU: one kernel (bbx_gae_bootstrap_device, one thread per environment); on the
+        CPU: the torch loop (_finish_torch), whose results the kernel reproduces bit for bit."""
         T = self.t
         r, v, d = self.rewards[:T], self.values[:T], self.dones[:T]
         if not r.is_cuda:
             return self._finish_torch()
-        ret = torch.empty_like(r); adv = torch.empty_like(r); comp = torch.empty_like(d)
-        p = lambda x: C.c_void_p(x.data_ptr())
+        last = self._last_values()
+        ret = torch.empty_like(r); adv = torch.empty_like(r); comp = torch.empty_like(d); lret = torch.empty_like(r)
+        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         with torch.cuda.device(r.device):
-            _ffi.check(_ffi.lib().bbx_gae_device(p(r), p(v), p(d), T, self.B, float(self.gam), float(self.lam), p(ret), p(adv), p(comp),
-                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        self.returns, self.advantages, self.complete = ret, adv, comp
+            _ffi.check(_ffi.lib().bbx_gae_bootstrap_device(p(r), p(v), p(d), T, self.B, float(self.gam), float(self.lam), p(last), p(ret), p(adv),
+                                                           p(comp), p(lret), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        self.returns, self.advantages, self.complete, self.lambda_returns = ret, adv, comp, lret
         return ret, adv, comp
+
+    def _last_values(self):
+        """self.last_values as the scans read it: None, or a contiguous float64 [B] tensor on the buffer's device (anything else:
+        ValueError — the kernel reads B doubles behind a raw pointer)."""
+        last = self.last_values
+        if last is None:
+            return None
+        if not torch.is_tensor(last) or last.dtype != torch.float64 or tuple(last.shape) != (self.B,) or last.device != self.rewards.device:
+            raise ValueError("last_values: None or a float64 tensor of shape (%d,) on %s" % (self.B, self.rewards.device))
+        return last.contiguous()
 
     def _finish_torch(self):
         """finish() with torch ops, about ten launches per step: CPU tensors, and the reference of the kernel."""
         T = self.t
         r, v, d = self.rewards[:T], self.values[:T], self.dones[:T]
-        ret = torch.zeros_like(r); adv = torch.zeros_like(r); comp = torch.zeros_like(d)
+        boot = self._last_values()
+        ret = torch.zeros_like(r); adv = torch.zeros_like(r); comp = torch.zeros_like(d); lret = torch.zeros_like(r)
         nret = torch.zeros(self.B, dtype=torch.float64, device=r.device); nadv = torch.zeros_like(nret)
         nval = torch.zeros_like(nret); ncomp = torch.zeros(self.B, dtype=torch.bool, device=r.device)
+        if boot is not None:                                         # the state behind step T - 1 is worth boot, and nothing is cut
+            nret = boot.clone(); nval = boot.clone(); ncomp = torch.ones_like(ncomp)
         for t in range(T - 1, -1, -1):
             last = d[t]                                              # step t ends its episode: nothing follows it
             nret = torch.where(last, torch.zeros_like(nret), nret); nadv = torch.where(last, torch.zeros_like(nadv), nadv)
@@ -152,17 +174,21 @@ class DeviceTrajectoryBuffer:
             ret[t] = r[t] + self.gam * nret
             adv[t] = (r[t] - v[t] + self.gam * nval) + self.gam * self.lam * nadv
             comp[t] = ncomp
+            lret[t] = adv[t] + v[t]
             nret, nadv, nval = ret[t], adv[t], v[t]
-        self.returns, self.advantages, self.complete = ret, adv, comp
+        self.returns, self.advantages, self.complete, self.lambda_returns = ret, adv, comp, lret
         return ret, adv, comp
 
-    def get_index(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
+    def get_index(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False, targets="returns"):
         """get() without the state blocks: the same selection, order, advantage normalisation and batching, but the first element
         of every tuple is an int32 tensor of flat step numbers t * B + b — positions in self.states.view(-1, R, cols),
         self.rows.view(-1) and self.actions.view(-1) — for PMLPPolicy.evaluate_at, which reads the states where the rollout
         left them.  With batch_size the tuples hold slices of ONE index tensor (a shuffle of the epoch is a permutation of it);
         nothing of the size of a state block is allocated, nothing waits for the device per batch, and a buffer without states
-        gives the same indices."""
+        gives the same indices.  targets: what the fifth element holds — "returns" (the discounted returns) or "lambda"
+        (lambda_returns, adv + v before normalisation); anything else: ValueError."""
+        if targets not in ("returns", "lambda"):
+            raise ValueError("targets: \"returns\" or \"lambda\" (got %r)" % (targets,))
         if self.returns is None:
             self.finish()
         T = self.t
@@ -181,7 +207,7 @@ class DeviceTrajectoryBuffer:
             idx, adv, rows = idx[order], adv[order], rows[order]
         j = idx.to(torch.int64)
         at = lambda x: x[:T].reshape(-1)[j]
-        out = [idx, at(self.actions), at(self.logprobs), adv, at(self.returns).to(torch.float32)]
+        out = [idx, at(self.actions), at(self.logprobs), adv, at(self.returns if targets == "returns" else self.lambda_returns).to(torch.float32)]
         if with_rows:
             out.append(rows)
         if batch_size is None:
@@ -195,7 +221,7 @@ class DeviceTrajectoryBuffer:
             batches.append(tuple(x[i:k] for x in out))
         return batches
 
-    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False):
+    def get(self, batch_size=None, normalize_advantages=True, sort=False, drop_remainder=False, with_rows=False, targets="returns"):
         """Training data of all complete-episode steps whose state had more than one row (pg.py:162-240): (states or None,
         actions, logprobs, advantages, values-to-fit), advantages normalised by their mean and population std over the
         complete steps (pg.py:176-178: before the single-row filter, like the reference), steps ordered trajectory after
@@ -204,8 +230,9 @@ class DeviceTrajectoryBuffer:
         rows any of its states has (-1 padding beyond a state's own rows, as stored); sort=True orders the steps by their
         number of rows first (less padding); drop_remainder=True leaves a short last batch out.  with_rows=True: every tuple
         carries the states' row counts (int32) as a sixth element (what PMLPPolicy.evaluate takes as `rows`).
+        targets: "returns" or "lambda", the values-to-fit as in get_index.
         The selection is get_index's; the states are gathered here, once."""
-        whole = self.get_index(None, normalize_advantages, sort, False, True)
+        whole = self.get_index(None, normalize_advantages, sort, False, True, targets)
         rows = whole[5]
         st = self.states[:self.t].reshape((-1,) + tuple(self.states.shape[2:]))[whole[0].to(torch.int64)] if self.states is not None else None
         out = [st] + list(whole[1:6 if with_rows else 5])
@@ -222,14 +249,14 @@ class DeviceTrajectoryBuffer:
         return batches
 
 
-def _epochs(name, buffer, columns, optimizer, epochs, batch_size, shuffle, generator, step):
+def _epochs(name, buffer, columns, optimizer, epochs, batch_size, shuffle, generator, step, targets="returns"):
     """The epoch loop of ppo_update and value_update, one epoch per iteration: ONE permutation of buffer.get_index()'s steps (shuffle;
     from `generator`), then per minibatch of batch_size step(index slice, the same slice of each of get_index's `columns`) — which
     returns the minibatch's six statistics on the device —, optimizer.step() and optimizer.zero_grad().  Yields (the minibatches'
     stacked statistics float64 [minibatches, 6] — the epoch's one host read —, their sum, the counted positions or 1)."""
     if buffer.states is None:
         raise ValueError("%s: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))" % name)
-    whole = buffer.get_index(None)
+    whole = buffer.get_index(None, targets=targets)
     cols = [whole[0]] + [whole[c] for c in columns]
     n = int(cols[0].numel())
     optimizer.zero_grad()
@@ -268,9 +295,10 @@ def ppo_update(policy, buffer, optimizer, epochs, batch_size, clip=0.2, ent_coef
     return out
 
 
-def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, generator=None):
+def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, generator=None, targets="returns"):
     """The counterpart of ppo_update for a PMLPValue critic (pg.py _fit_value_model): `epochs` passes over buffer.get_index()'s steps
-    in minibatches of batch_size, the targets its fifth element (the discounted returns) — per epoch ONE permutation of the index
+    in minibatches of batch_size, the targets its fifth element (get_index(targets=...): the discounted returns, or with "lambda"
+    the TD(lambda) targets adv + v) — per epoch ONE permutation of the index
     list (shuffle; from `generator`, which lives on the buffer's device), per minibatch one critic.fit_step_at on the buffers as the
     rollout left them, then optimizer.step() and optimizer.zero_grad(); the optimiser is the caller's.  One host read per epoch: the
     minibatches' stacked statistics.  Returns one dict per epoch: "stats" (float64 [minibatches, 6], fit_step_at's), and over the
@@ -278,15 +306,36 @@ def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, ge
     (1 - mean (V - target)^2 / var(target); NaN where the targets do not vary)."""
     step = lambda i, r: critic.fit_step_at(buffer.states, buffer.rows, i, r)[0]
     out = []
-    for st, tot, cnt in _epochs("value_update", buffer, (4,), optimizer, epochs, batch_size, shuffle, generator, step):
+    for st, tot, cnt in _epochs("value_update", buffer, (4,), optimizer, epochs, batch_size, shuffle, generator, step, targets):
         var = tot[4] / cnt - (tot[3] / cnt) ** 2
         out.append({"stats": st, "loss": 0.5 * tot[1] / cnt, "explained_variance": 1.0 - (tot[1] / cnt) / var if var > 0 else float("nan")})
     return out
 
 
+def _set_last_values(buffer, last):
+    """A rollout's last word on its buffer: the bootstrap of the cut tails (None: there is none), and whatever an earlier
+    finish() left is cleared — it knows neither the new steps nor the new tail."""
+    buffer.last_values = last
+    buffer.returns = buffer.advantages = buffer.complete = buffer.lambda_returns = None
+
+
+def _critic_last_values(env, critic, obs_rows, stream):
+    """The critic's values of the states the environments are in now, float64 [B]: a zero-step launch writes the padded
+    observation block and the row counts (it steps nothing and draws nothing), one critic.values call reads them."""
+    B, dev = env.batch, torch.device("cuda", torch.cuda.current_device())
+    obs = torch.empty((B, obs_rows, env.cols), dtype=torch.int32, device=dev)
+    rew = torch.zeros(B, dtype=torch.float64, device=dev); done = torch.zeros(B, dtype=torch.uint8, device=dev)
+    rows = torch.zeros(B, dtype=torch.int32, device=dev)
+    env.rollout_device("first", 0, False, stream.cuda_stream, rew, done, rows, obs, obs_rows, True, False)
+    env.sync()
+    last = torch.empty(B, dtype=torch.float64, device=dev)
+    critic.values(obs, rows, out64=last)
+    return last
+
+
 @_with_gc_paused
 @torch.no_grad()
-def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False, critic=None):
+def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False, critic=None, bootstrap=False):
     """run_rollout with the policy INSIDE the step kernel: `chunk` vector steps per launch, environments never wait for each
     other between steps.  One hidden layer: bbx_policy_rollout_device; two hidden layers of at most 128 units:
     bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
@@ -302,9 +351,16 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
     critic (a PMLPValue; needs a buffer that keeps states): after the last chunk buffer.fill_values(critic, ...) writes the
     critic's values of the steps recorded here into buffer.values — one launch over the recorded block, nothing per step; the
     rollout itself is the one without a critic, draw for draw.  None: buffer.values is left as it is.  A critic without a
-    state-keeping buffer: ValueError before anything is queued."""
+    state-keeping buffer: ValueError before anything is queued.
+    bootstrap=True (needs a critic): behind fill_values one zero-step launch writes the observation block the environments
+    stopped in, and the critic's values of it become buffer.last_values — finish() then bootstraps the episodes the end of the
+    buffer cut instead of dropping them (truncated-horizon GAE).  The environments are not touched by it.  Every call with a
+    buffer sets buffer.last_values (None without bootstrap) and clears what an earlier finish() left.  bootstrap=True without a
+    critic: ValueError before anything is queued."""
     if critic is not None and (buffer is None or buffer.states is None):
         raise ValueError("run_rollout_fused: a critic reads the recorded states (buffer=DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
+    if bootstrap and critic is None:
+        raise ValueError("run_rollout_fused: bootstrap=True takes the value of the state the rollout stops in from a critic (critic=PMLPValue(...))")
     B, cols = env.batch, env.cols
     depth = len(policy.embedding)
     if not (depth == 1 or (depth == 2 and policy.deep_ok(cols))):
@@ -353,6 +409,11 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
         env.policy_greedy(was_greedy)
     if critic is not None:
         buffer.fill_values(critic, t_start, buffer.t)
+    last = None
+    if bootstrap:
+        last = _critic_last_values(env, critic, obs_rows, stream)
+    if buffer is not None:
+        _set_last_values(buffer, last)
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)
     episodes = torch.tensor(d[:, 2], device=dev)
@@ -362,7 +423,7 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
 @_with_gc_paused
 @torch.no_grad()
 def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, sync_every=64, graph=False,
-                value_strategy=None, value_gamma=None, greedy=False):
+                value_strategy=None, value_gamma=None, greedy=False, critic=None, bootstrap=False):
     """nsteps vector steps of `env` (a VecLeadMonomialsEnv already reset) under `policy`, everything on the device
     (obs_rows: rows of the observation block per environment — a pair set with more rows makes env.sync() raise
     BBX_E_CAPACITY, it is never cut silently; 256 is what the register/LDS-resident class holds):
@@ -379,11 +440,27 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     overlapping the steps that follow; value_gamma defaults to buffer.gam.  No extra host wait.  None: no values, call for call
     what it was.  With graph=True: ValueError.
     greedy=True: the highest-probability pair at every step (policy.act(greedy=True); env.policy_greedy for the duration of the
-    call, restored afterwards); no uniforms are drawn."""
+    call, restored afterwards); no uniforms are drawn.
+    critic (a PMLPValue; needs a buffer that keeps states; not together with value_strategy): behind the loop
+    buffer.fill_values(critic, ...) writes the critic's values of the steps recorded here into buffer.values, as
+    run_rollout_fused does.
+    bootstrap=True (needs a buffer and a value_strategy or a critic): buffer.last_values receives the value of the state the
+    rollout stops in — one more env.values_device before the final wait, or the critic's values of the observation block the
+    loop ends with — and finish() bootstraps the episodes the end of the buffer cut instead of dropping them.  The
+    environments are not touched by it.  Every call with a buffer sets buffer.last_values (None without bootstrap) and clears
+    what an earlier finish() left.  All refusals are ValueError before anything is queued."""
     if value_strategy is not None and graph:
         raise ValueError("run_rollout: value_strategy cannot be recorded into a graph (bbx_values_device keeps host bookkeeping)")
     if value_strategy is not None and buffer is None:
         raise ValueError("run_rollout: value_strategy needs a buffer to write the values to")
+    if critic is not None and value_strategy is not None:
+        raise ValueError("run_rollout: one baseline per rollout, a critic or a value_strategy")
+    if critic is not None and (buffer is None or buffer.states is None):
+        raise ValueError("run_rollout: a critic reads the recorded states (buffer=DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
+    if bootstrap and buffer is None:
+        raise ValueError("run_rollout: bootstrap=True needs a buffer to bootstrap")
+    if bootstrap and critic is None and value_strategy is None:
+        raise ValueError("run_rollout: bootstrap=True takes the value of the state the rollout stops in from a critic or a value_strategy")
     if value_strategy is not None and value_gamma is None:
         value_gamma = buffer.gam
     B, cols = env.batch, env.cols
@@ -401,6 +478,8 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     env.rollout_device("first", 0, False, stream.cuda_stream, rew, done, rows, obs, obs_rows, True, False)
     env.sync()
     keep_states = buffer is not None and buffer.states is not None
+    t_start = buffer.t if buffer is not None else 0
+    by_strategy, last = bootstrap and value_strategy is not None, None
     w = policy._fused_weights() if one_call else None
     nsync = 0
     was_greedy = env.policy_greedy(greedy) if one_call else None
@@ -426,11 +505,25 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
                     buffer.actions[t].copy_(act); buffer.logprobs[t].copy_(logp)
                     buffer.rewards[t].copy_(rew); buffer.dones[t].copy_(done)
                     buffer.t += 1
+            if by_strategy and t0 + n == nsteps:        # the value of the state the rollout stops in, ahead of the last wait
+                last = torch.empty(B, dtype=torch.float64, device=dev)
+                env.values_device(last, value_strategy, value_gamma, None, stream.cuda_stream)
             env.sync()
             nsync += 1
     finally:
         if one_call:
             env.policy_greedy(was_greedy)
+    if by_strategy and last is None:                    # (a rollout of no steps: the state it started in)
+        last = torch.empty(B, dtype=torch.float64, device=dev)
+        env.values_device(last, value_strategy, value_gamma, None, stream.cuda_stream)
+        env.sync()
+    if critic is not None:
+        buffer.fill_values(critic, t_start, buffer.t)
+        if bootstrap:                                   # obs / rows: the block the loop ends with
+            last = torch.empty(B, dtype=torch.float64, device=dev)
+            critic.values(obs, rows, out64=last)
+    if buffer is not None:
+        _set_last_values(buffer, last)
     # totals from the environments' own counters (additions rewards: reward = -additions, buchberger.cpp:328)
     d = env.stats() - st0
     total = torch.tensor(-d[:, 1].astype(np.float64), device=dev)

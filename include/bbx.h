@@ -535,6 +535,21 @@ int bbx_values_device(bbx_batch* b, const char* strategy, double gamma, const in
  * asynchronous on `stream`. */
 int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
                    double gam, double lam, double* d_returns, double* d_advantages, uint8_t* d_complete, void* stream);
+/* bbx_gae_device over a block whose episodes the end of the block may have cut (environments stepping in lockstep for a fixed
+ * nsteps): truncated-horizon GAE, the same scan in the same kernel body, operation for operation, started from a value of the state
+ * BEHIND step nsteps - 1 instead of from zero.
+ *   d_last_values [batch] (or NULL): nret = nval = d_last_values[e], nadv = 0, and every step counts as complete (d_complete all
+ *     ones).  A done flag clears the carries as before, so the entry of an environment whose last recorded step ended its episode
+ *     is never used (under auto-reset its current state belongs to the next episode) — a NaN there reaches no output.  NULL: the
+ *     scan starts from zero and d_complete is bbx_gae_device's.
+ *   d_lambda_returns [nsteps][batch] (or NULL): adv + v, one rounded sum — the TD(lambda) target of a value fit; with bootstrapped
+ *     tails the discounted return d_returns is no longer a pure Monte-Carlo target, and callers have the choice.
+ * bbx_gae_device is this call with both NULL: the same bits.  A NULL among the other pointers, nsteps < 0 or batch < 0: BBX_E_ARG;
+ * nsteps == 0 or batch == 0: BBX_OK, nothing launched.  One kernel, one thread per environment; needs no handle; asynchronous on
+ * `stream`. */
+int bbx_gae_bootstrap_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
+                             double gam, double lam, const double* d_last_values, double* d_returns, double* d_advantages,
+                             uint8_t* d_complete, double* d_lambda_returns, void* stream);
 /* Evaluation (run_episodes(..., greedy=True), pg.py; scripts/eval.py): the policy takes the row of the largest logit at every
  * step instead of drawing one.
  * The greedy forms of bbx_pmlp_act, bbx_pmlp2_act and bbx_pmlp3_act: the same arguments without d_u, the same shape refusals, the
