@@ -47,12 +47,12 @@ bbx_batch::~bbx_batch() {
   if (ps_ctl_stream) (void)hipStreamDestroy(ps_ctl_stream);
   if (d_clone_idx) (void)hipFree(d_clone_idx);
   bbx_host::value_ring_free(this);
+  bbx_host::value_scratch_free(this);
   bbx_host::action_values_free(this);
   if (v_stream) (void)hipStreamDestroy(v_stream);
   if (d_vident) (void)hipFree(d_vident);
   if (d_vwords) (void)hipFree(d_vwords);
-  void* dev[] = {d_recs, d_q, d_tail, d_out, d_actions, d_mask, d_seeds, d_obs, d_trace, d_hdr,
-                 d_vrecs, d_vhdr, d_vsrc, d_vseeds, d_vvals, d_stage, d_obs_off, d_obs_packed};
+  void* dev[] = {d_recs, d_q, d_tail, d_out, d_actions, d_mask, d_seeds, d_obs, d_trace, d_hdr, d_stage, d_obs_off, d_obs_packed};
   for (void* q : dev) if (q) (void)hipFree(q);
   for (void* q : retired) if (q) (void)hipFree(q);
   void* pinned[] = {h_io, h_act, h_stage, h_zobs, h_obs, (void*)h_mbox};
@@ -409,11 +409,7 @@ int grow_records(bbx_batch* b, unsigned need, int env, hipStream_t stream) {
   HIPCHK(hipStreamSynchronize(stream));
   if (int rc = value_wait(b)) return rc;                    // (clones of queued bbx_values_device calls still read the old records;
                                                             // their ring slots are not this scratch and stay: value_resolve needs them)
-  if (b->d_vrecs) {                                         // value() scratch is sized by the old layout: rebuilt on demand
-    void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};
-    for (void* q : old) (void)hipFree(q);
-    b->d_vrecs = nullptr; b->d_vhdr = nullptr; b->d_vsrc = nullptr; b->d_vseeds = nullptr; b->d_vvals = nullptr; b->vcap = 0;
-  }
+  value_scratch_free(b);                                    // (sized by the old layout: rebuilt on demand)
   HIPCHK(hipMemGetInfo(&freeb, &totalb));
   if (bytes + (256u << 20) > freeb)
     return fail(BBX_E_CAPACITY, "environment %d: %s, and the device has no room for larger records (%zu MiB needed, %zu MiB free)",

@@ -1,6 +1,12 @@
 // libbbx.so — LeadMonomialsEnv::value (buchberger.cpp:332-351): discounted returns of full Buchberger rollouts from clones of
 // the current states (bbx_value, bbx_values, bbx_values_seeded of include/bbx.h), their asynchronous form (bbx_values_device)
 // and the same rollouts behind every pair of every environment (bbx_action_values).
+// All three run one pipeline — value_clone, value_resort, value_launch_rollouts, a collect that folds "did not finish" into a
+// word pair — and read that word with one rule (classify).  They differ in three things.  Streams: the synchronous calls and
+// bbx_action_values stay on the NULL stream, bbx_values_device clones on the caller's stream and runs the rest on the library's.
+// The forced step: bbx_action_values steps every clone once with its own action between clone and re-sort.  After growth: both
+// NULL-stream forms restart from fresh clones of the enlarged records (retry_growing), bbx_values_device carries its clones
+// over to them and resumes (value_carry_over).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -11,7 +17,6 @@
 
 using namespace bbx_host;
 
-// ---- value(): discounted return of full Buchberger rollouts from clones of the current states ---------------------
 namespace {
 
 int agent_of_strategy(const char* s) {   // unknown keys select First: std::map::operator[] default (buchberger.cpp:342-349)
@@ -29,68 +34,132 @@ uint32_t minstd_state_of_seed(long long seed) {
   return x ? x : 1u;
 }
 
-// One rollout to completion per entry of src (indices into b), from clones of the current states; seeds != null: the
-// engine states of the clones' seeded Random selection.  Everything runs on the default stream without a copy in between
-// and with one wait: values + completion marks come back in one transfer at the end (clones whose generator lead monomials
-// tie get the reducer order buchberger()'s std::sort would give them from a kernel: bbx_value_resort_kernel).  3-variable binomial batches run on the register/LDS-resident class (bbx_fast_value_kernel),
-// environments that outgrow it and every other batch on the HBM-resident class of the batch, long-polynomial
-// environments one workgroup per clone.  A clone that runs out of room enlarges the records of the whole batch
-// (grow_records) and the rollouts start again.
-// the clone arrays of value() and bbx_action_values: room for n clones in the batch's current layout (kept between calls;
-// grow_records frees them, so a call after the records were enlarged makes them again)
+void free_dev(std::initializer_list<void*> dev) { for (void* q : dev) if (q) (void)hipFree(q); }
+int launched(int lrc, const char* what) {   // what a bbx_launch_* returned -> the return code of the call
+  return lrc ? fail(BBX_E_DEVICE, "%s launch failed: %s", what, hipGetErrorString((hipError_t)lrc)) : BBX_OK;
+}
+
+// the clone arrays of the synchronous calls and bbx_action_values: room for n clones in the batch's current layout (kept
+// between calls; grow_records frees them, so a call after the records were enlarged makes them again)
 int value_scratch_ensure(bbx_batch* b, int n) {
   if (n <= b->vcap) return BBX_OK;
-  void* old[] = {b->d_vrecs, b->d_vhdr, b->d_vsrc, b->d_vseeds, b->d_vvals};
-  for (void* q : old) (void)hipFree(q);
-  b->d_vrecs = nullptr; b->d_vhdr = nullptr; b->d_vsrc = nullptr; b->d_vseeds = nullptr; b->d_vvals = nullptr; b->vcap = 0;
+  value_scratch_free(b);
   HIPCHK(hipMalloc((void**)&b->d_vrecs, (size_t)n * b->L.rec_bytes));
-  HIPCHK(hipMalloc((void**)&b->d_vhdr, (size_t)n));                        // clone flags (u8)
+  HIPCHK(hipMalloc((void**)&b->d_vflags, (size_t)n));
   HIPCHK(hipMalloc((void**)&b->d_vsrc, (size_t)n * sizeof(int32_t)));
   HIPCHK(hipMalloc((void**)&b->d_vseeds, (size_t)n * sizeof(uint32_t)));
-  HIPCHK(hipMalloc((void**)&b->d_vvals, (size_t)n * 2 * sizeof(double)));  // {value, completion mark} per clone
+  HIPCHK(hipMalloc((void**)&b->d_vvals, ((size_t)n + 1) * sizeof(double)));   // the word pair, then a value per clone
+  HIPCHK(hipMemsetAsync(b->d_vvals, 0, sizeof(double), 0));                   // (the word is clear whenever no attempt is under way)
   b->vcap = n;
   return BBX_OK;
 }
 
+// ---- the pipeline: n clones and the flags the clone kernel leaves for the re-sort (the scratch above, or a ring slot; flags
+// may be null for clones that are only rolled out: value_clone writes them, value_resort reads them, nothing else) -----------
+struct ValueClones { char* recs; uint8_t* flags; int n; };
+
+// clones[k] <- environment d_src[k]; d_seeds != null: the engine states of the clones' seeded Random selection
+int value_clone(bbx_batch* b, const ValueClones& c, const int32_t* d_src, const uint32_t* d_seeds, hipStream_t stream) {
+  const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
+  return launched(bbx_launch_clone(b->d_recs, c.recs, &b->L, d_src, nullptr, c.n, d_seeds, 0, 1, ngen, c.flags, stream), "clone");
+}
+
+// clones whose generator lead monomials tie get the reducer order buchberger()'s std::sort would give them (value() re-sorts
+// the state it is called on; the flags are the clone's — a step in between leaves the generators alone)
+int value_resort(bbx_batch* b, const ValueClones& c, hipStream_t stream) {
+  return launched(bbx_launch_value_resort(c.recs, &b->L, c.n, c.flags, stream), "resort");
+}
+
+// what every launch on clones has in common: they are not the batch's environments (no status block, trace or accounting)
+BbxParams clone_params(bbx_batch* b, const ValueClones& c, int nsteps, int agent) {
+  BbxParams p; fill_params(b, &p);
+  p.recs = c.recs; p.B = c.n; p.nsteps = nsteps; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
+  p.trace = nullptr; p.accounting = 0; p.lite = nullptr;
+  return p;
+}
+
+// the kernels plan_launch gives a rollout of the class — the first kernel and those that take over what it hands on —, each
+// with a budget of `budget` steps (0: p's own)
+int launch_on_clones(bbx_batch* b, const BbxParams& p, bool resume, int budget, hipStream_t stream) {
+  LaunchPlan pl = plan_launch(b, p, resume, true);
+  int lrc = 0;
+  for (int i = 0; i < pl.n && !lrc; i++) {
+    if (budget) pl.pass[i].nsteps = budget;
+    lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], stream);
+  }
+  return launched(lrc, "kernel");
+}
+
+// The rollouts to completion (resume: clones carried over to enlarged records continue where they stopped).  3-variable binomial
+// batches run on the register/LDS-resident class (bbx_fast_value_kernel: every selection strategy, f_select_ordered), clones that
+// outgrow it and every other batch on the HBM-resident class of the batch, long-polynomial environments one workgroup per clone.
+int value_launch_rollouts(bbx_batch* b, const ValueClones& c, int agent, double gamma, bool resume, hipStream_t stream) {
+  BbxParams p = clone_params(b, c, 1 << 30, agent);
+  p.value_mode = 1; p.gamma = gamma; p.values = nullptr;
+  return launch_on_clones(b, p, resume, 0, stream);
+}
+
+// ---- a clone that did not finish -------------------------------------------------------------------------------------------
+// The word pair a collect folds (bbx_unfinished_fold, bbx_aux.hip) on the host: bits = 1 << status of every clone that waits
+// for room, bit 31 for anything else; env = the largest index reported (a collect that reports clones: mapped by the caller)
+struct UnfinishedWord { unsigned bits; int env; };
+UnfinishedWord word_of(const void* pair) { uint32_t w[2]; memcpy(w, pair, sizeof w); return {w[0], (int)w[1] - 1}; }
+constexpr unsigned kCapacityBits = BBX_ST_CAPACITY_BITS;   // the statuses a larger record cures
+constexpr int kGrowAttempts = 40;        // enlargements one call goes through before it gives up
+
+// What a word means: nothing unfinished; clones wait for room and the records may grow; or the call fails with BBX_E_CAPACITY
+// (recorded here) — pairs left, an error state, or capacities that are hard limits.  `what` names the call.
+enum class Unfinished { none, grow, fail };
+Unfinished classify(const bbx_batch* b, const UnfinishedWord& w, const char* what) {
+  if (!w.bits) return Unfinished::none;
+  if (!(w.bits & ~kCapacityBits) && !b->no_growth) return Unfinished::grow;
+  fail(BBX_E_CAPACITY, "%s of environment %d did not finish: %s", what, w.env,
+       (w.bits & kCapacityBits) ? status_name(__builtin_ctz(w.bits & kCapacityBits)) : "pairs left or a clone in an error state");
+  return Unfinished::fail;
+}
+int kept_outgrowing(const char* what) { return fail(BBX_E_CAPACITY, "%ss kept outgrowing the records", what); }
+
+// The restart policy: attempt(&w) runs the pipeline from fresh clones, reports its word and delivers its results when the word
+// is clear; clones that wait for room enlarge the records of the whole batch (grow_records frees the clone scratch) and the
+// attempt runs again — the results are those of a handle created with room to spare
+template <class Attempt> int retry_growing(bbx_batch* b, const char* what, Attempt attempt) {
+  for (int i = 0; i < kGrowAttempts; i++) {
+    UnfinishedWord w{0, -1};
+    if (int rc = attempt(&w)) return rc;
+    const Unfinished u = classify(b, w, what);
+    if (u != Unfinished::grow) return u == Unfinished::none ? BBX_OK : BBX_E_CAPACITY;
+    if (int rc = grow_records(b, w.bits & kCapacityBits, w.env, 0)) return rc;
+  }
+  return kept_outgrowing(what);
+}
+
+// ---- bbx_value, bbx_values, bbx_values_seeded ------------------------------------------------------------------------------
+// One rollout to completion per entry of src (indices into b), from clones of the current states; seeds != null: the engine
+// states of the clones' seeded Random selection.  Everything runs on the default stream without a copy in between and with
+// one wait: the word pair and the values behind it come back in one transfer at the end.  The word starts out clear and a call
+// that finds it set clears it for the next (a clear per call costs: profiles/r24_value_calls_ab.txt); it sits in FRONT of the
+// values so that its place does not move with n.
 int value_rollouts(bbx_batch* b, const std::vector<int32_t>& src, int agent, const std::vector<uint32_t>* seeds, double gamma, double* out) {
   const int n = (int)src.size();
   if (int rc = settle(b)) return rc;
-  for (int attempt = 0; attempt < 40; attempt++) {
+  std::vector<double> v((size_t)n + 1);
+  return retry_growing(b, "value rollout", [&](UnfinishedWord* w) -> int {
     if (int rc = value_scratch_ensure(b, n)) return rc;
+    const ValueClones c{b->d_vrecs, b->d_vflags, n};
+    uint32_t* d_word = (uint32_t*)b->d_vvals;
     HIPCHK(hipMemcpyAsync(b->d_vsrc, src.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, 0));
     if (seeds) HIPCHK(hipMemcpyAsync(b->d_vseeds, seeds->data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, 0));
-    const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
-    uint8_t* d_flags = (uint8_t*)b->d_vhdr;
-    int lrc = bbx_launch_clone(b->d_recs, b->d_vrecs, &b->L, b->d_vsrc, nullptr, n, seeds ? b->d_vseeds : nullptr, 0, 1, ngen, d_flags, 0);
-    if (lrc) return fail(BBX_E_DEVICE, "clone launch failed: %s", hipGetErrorString((hipError_t)lrc));
-    lrc = bbx_launch_value_resort(b->d_vrecs, &b->L, n, d_flags, 0);   // (clones whose generators tie: std::sort's order)
-    if (lrc) return fail(BBX_E_DEVICE, "resort launch failed: %s", hipGetErrorString((hipError_t)lrc));
-    BbxParams p; fill_params(b, &p);
-    p.recs = b->d_vrecs; p.B = n; p.nsteps = 1 << 30; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
-    p.value_mode = 1; p.gamma = gamma; p.values = nullptr; p.trace = nullptr; p.accounting = 0;
-    p.lite = nullptr;                                           // the clones are not the batch's environments
-    const LaunchPlan pl = plan_launch(b, p, false, true);      // (the fast class: every selection strategy, bbx_fast.h f_select_ordered)
-    for (int i = 0; i < pl.n && !lrc; i++) lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], 0);
-    if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
-    lrc = bbx_launch_value_collect(b->d_vrecs, b->L.rec_bytes, n, b->d_vvals, 0);
-    if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));
-    std::vector<double> v2((size_t)n * 2);
-    HIPCHK(hipMemcpy(v2.data(), b->d_vvals, v2.size() * sizeof(double), hipMemcpyDeviceToHost));   // the only wait of the call
-    unsigned grow = 0; int grow_k = -1;
-    for (int k = 0; k < n; k++) {
-      const int st = (int)v2[2 * (size_t)k + 1];
-      if (st == 0) continue;
-      if (st > 0 && bbx_st_capacity(st) && !b->no_growth) { grow |= 1u << st; if (grow_k < 0) grow_k = k; continue; }
-      return fail(BBX_E_CAPACITY, "value rollout of environment %d did not finish: %s", src[k], st > 0 ? status_name(st) : "pairs left");
-    }
-    if (!grow) {
-      for (int k = 0; k < n; k++) out[k] = v2[2 * (size_t)k];
-      return BBX_OK;
-    }
-    int rc = grow_records(b, grow, src[grow_k], 0);             // (frees the clones: sized by the old layout)
-    if (rc) return rc;
-  }
-  return fail(BBX_E_CAPACITY, "value rollouts kept outgrowing the records");
+    if (int rc = value_clone(b, c, b->d_vsrc, seeds ? b->d_vseeds : nullptr, 0)) return rc;
+    if (int rc = value_resort(b, c, 0)) return rc;
+    if (int rc = value_launch_rollouts(b, c, agent, gamma, false, 0)) return rc;
+    if (int rc = launched(bbx_launch_value_collect_device(c.recs, b->L.rec_bytes, n, b->d_vvals + 1, d_word, 0, 0), "collect")) return rc;
+    HIPCHK(hipMemcpy(v.data(), b->d_vvals, v.size() * sizeof(double), hipMemcpyDeviceToHost));   // the only wait of the call
+    *w = word_of(&v[0]);
+    if (!w->bits) { memcpy(out, &v[1], (size_t)n * sizeof(double)); return BBX_OK; }
+    w->env = src[(size_t)w->env];                               // (the collect reports a clone: "sample" has 100 per environment)
+    HIPCHK(hipMemsetAsync(d_word, 0, sizeof(double), 0));
+    return BBX_OK;
+  });
 }
 
 // `seeds`: explicit seeds of the Random rollouts — [n] for "random", [n][100] for "sample" — or null: drawn from the
@@ -131,8 +200,7 @@ int value_ring_ensure(bbx_batch* b) {
     HIPCHK(hipMalloc((void**)&b->d_vident, (size_t)b->B * sizeof(int32_t)));
     HIPCHK(hipMalloc((void**)&b->d_vwords, (size_t)BBX_VALUE_MAX_JOBS * 2 * sizeof(uint32_t)));
     HIPCHK(hipMemsetAsync(b->d_vwords, 0, (size_t)BBX_VALUE_MAX_JOBS * 2 * sizeof(uint32_t), b->v_stream));
-    int lrc = bbx_launch_value_iota(b->d_vident, b->B, b->v_stream);
-    if (lrc) return fail(BBX_E_DEVICE, "index launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    if (int rc = launched(bbx_launch_value_iota(b->d_vident, b->B, b->v_stream), "index")) return rc;
   }
   // the records were enlarged since the slots were made (no call is queued then: settle() resolved them all): made again
   if (!b->v_ring.empty() && memcmp(&b->v_L, &b->L, sizeof(BbxLayout)) != 0 && b->v_jobs.empty()) {
@@ -153,19 +221,6 @@ int value_ring_ensure(bbx_batch* b) {
   return BBX_OK;
 }
 
-// the rollout kernels of value() on `recs` (resume: clones carried over to enlarged records continue where they stopped)
-int value_launch_rollouts(bbx_batch* b, char* recs, int n, int agent, double gamma, bool resume, hipStream_t stream) {
-  BbxParams p; fill_params(b, &p);
-  p.recs = recs; p.B = n; p.nsteps = 1 << 30; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
-  p.value_mode = 1; p.gamma = gamma; p.values = nullptr; p.trace = nullptr; p.accounting = 0;
-  p.lite = nullptr;                                           // the clones are not the batch's environments
-  const LaunchPlan pl = plan_launch(b, p, resume, true);
-  int lrc = 0;
-  for (int i = 0; i < pl.n && !lrc; i++) lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], stream);
-  if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
-}
-
 int values_device(bbx_batch* b, int agent, double gamma, const int64_t* d_seeds, double* d_values, hipStream_t stream) {
   if ((int)b->v_jobs.size() >= BBX_VALUE_MAX_JOBS)
     return fail(BBX_E_UNSUPPORTED, "%d bbx_values_device calls are queued on this handle: call bbx_sync before queueing more", BBX_VALUE_MAX_JOBS);
@@ -179,27 +234,17 @@ int values_device(bbx_batch* b, int agent, double gamma, const int64_t* d_seeds,
   const int n = b->B;
   const int slot = (int)(b->v_calls % b->v_depth);
   bbx_vslot& s = b->v_ring[(size_t)slot];
-  if (s.used) HIPCHK(hipStreamWaitEvent(stream, s.done, 0));   // the slot's previous rollouts: a device-side wait
-  else {                                                       // (first use: behind the index array and the cleared words)
-    HIPCHK(hipEventRecord(s.done, b->v_stream));
-    HIPCHK(hipStreamWaitEvent(stream, s.done, 0));
-  }
-  int lrc = 0;
-  if (d_seeds) {
-    lrc = bbx_launch_value_seeds(d_seeds, s.seeds, n, stream);
-    if (lrc) return fail(BBX_E_DEVICE, "seed launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  }
-  const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
-  lrc = bbx_launch_clone(b->d_recs, s.recs, &b->L, b->d_vident, nullptr, n, d_seeds ? s.seeds : nullptr, 0, 1, ngen, s.flags, stream);
-  if (lrc) return fail(BBX_E_DEVICE, "clone launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (!s.used) HIPCHK(hipEventRecord(s.done, b->v_stream));    // (first use: behind the index array and the cleared words)
+  HIPCHK(hipStreamWaitEvent(stream, s.done, 0));               // the slot's previous rollouts: a device-side wait
+  if (int rc = d_seeds ? launched(bbx_launch_value_seeds(d_seeds, s.seeds, n, stream), "seed") : BBX_OK) return rc;
+  const ValueClones c{s.recs, s.flags, n};
+  if (int rc = value_clone(b, c, b->d_vident, d_seeds ? s.seeds : nullptr, stream)) return rc;
   HIPCHK(hipEventRecord(s.cloned, stream));
   HIPCHK(hipStreamWaitEvent(b->v_stream, s.cloned, 0));
-  lrc = bbx_launch_value_resort(s.recs, &b->L, n, s.flags, b->v_stream);
-  if (lrc) return fail(BBX_E_DEVICE, "resort launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  if (int rc = value_launch_rollouts(b, s.recs, n, agent, gamma, false, b->v_stream)) return rc;
+  if (int rc = value_resort(b, c, b->v_stream)) return rc;
+  if (int rc = value_launch_rollouts(b, c, agent, gamma, false, b->v_stream)) return rc;
   uint32_t* word = b->d_vwords + 2 * b->v_jobs.size();
-  lrc = bbx_launch_value_collect_device(s.recs, b->L.rec_bytes, n, d_values, word, 0, b->v_stream);
-  if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (int rc = launched(bbx_launch_value_collect_device(s.recs, b->L.rec_bytes, n, d_values, word, 0, b->v_stream), "collect")) return rc;
   HIPCHK(hipEventRecord(s.done, b->v_stream));
   s.used = true;
   b->v_jobs.push_back(bbx_vjob{slot, d_values, b->L, agent, gamma});
@@ -210,25 +255,23 @@ int values_device(bbx_batch* b, int agent, double gamma, const int64_t* d_seeds,
 // One queued call whose clones did not all finish (word: what its collect folded).  Clones that wait for room are carried over
 // to records of the enlarged layout (bbx_relayout_kernel), finish there and fill the entries the collect left NaN.
 int value_carry_over(bbx_batch* b, const bbx_vjob& j, size_t jix, const uint32_t* word) {
-  const unsigned capmask = (1u << BBX_ST_G_FULL) | (1u << BBX_ST_P_FULL) | (1u << BBX_ST_ARENA_FULL) | (1u << BBX_ST_POLY_TOO_LONG);
-  unsigned bits = word[0]; int env = (int)word[1] - 1;
+  const char* what = "value rollout";
+  UnfinishedWord w = word_of(word);                                  // (clone k is environment k)
   bool owner = true;                                        // a later call has reused the slot: the waiting clones are gone
   for (size_t i = jix + 1; i < b->v_jobs.size(); i++) owner = owner && b->v_jobs[i].slot != j.slot;
-  if ((bits & ~capmask) || b->no_growth)
-    return fail(BBX_E_CAPACITY, "value rollout of environment %d did not finish: %s", env,
-                (bits & capmask) ? status_name(__builtin_ctz(bits & capmask)) : "pairs left or an environment in an error state");
+  if (classify(b, w, what) == Unfinished::fail) return BBX_E_CAPACITY;
   const int n = b->B;
   char* src = b->v_ring[(size_t)j.slot].recs; char* tmp = nullptr;
   BbxLayout Ls = j.L;
   uint32_t* dw = b->d_vwords + 2 * jix;
   int rc = BBX_OK;
-  for (int attempt = 0; attempt < 40 && rc == BBX_OK; attempt++) {
-    if (Ls.rec_bytes == b->L.rec_bytes) rc = grow_records(b, bits & capmask, env, 0);   // (else: an earlier call of this wait enlarged them already)
+  for (int attempt = 0; attempt < kGrowAttempts && rc == BBX_OK; attempt++) {
+    if (Ls.rec_bytes == b->L.rec_bytes) rc = grow_records(b, w.bits & kCapacityBits, w.env, 0);   // (else: an earlier call of this wait enlarged them already)
     if (rc) break;
     if (!owner) {
       rc = fail(BBX_E_CAPACITY, "value rollout of environment %d outgrew its records (%s) and %d later bbx_values_device calls reused its clone "
-                                "before the wait; the records have been enlarged, later calls have room", env,
-                status_name(__builtin_ctz(bits & capmask)), b->v_depth);
+                                "before the wait; the records have been enlarged, later calls have room", w.env,
+                status_name(__builtin_ctz(w.bits & kCapacityBits)), b->v_depth);
       break;
     }
     char* next = nullptr;
@@ -236,16 +279,17 @@ int value_carry_over(bbx_batch* b, const bbx_vjob& j, size_t jix, const uint32_t
     int lrc = bbx_launch_relayout(src, next, &Ls, &b->L, n, 0);
     if (tmp) { (void)hipStreamSynchronize(0); (void)hipFree(tmp); }
     tmp = next; src = next; Ls = b->L;
-    if (lrc) { rc = fail(BBX_E_DEVICE, "relayout launch failed: %s", hipGetErrorString((hipError_t)lrc)); break; }
-    if ((rc = value_launch_rollouts(b, tmp, n, j.agent, j.gamma, true, 0))) break;
-    uint32_t w[2] = {0, 0};
-    if (hipMemsetAsync(dw, 0, sizeof w, 0) != hipSuccess ||
+    if ((rc = launched(lrc, "relayout"))) break;
+    if ((rc = value_launch_rollouts(b, ValueClones{tmp, nullptr, n}, j.agent, j.gamma, true, 0))) break;
+    uint32_t h[2] = {0, 0};
+    if (hipMemsetAsync(dw, 0, sizeof h, 0) != hipSuccess ||
         bbx_launch_value_collect_device(tmp, b->L.rec_bytes, n, j.d_values, dw, 1, 0) != 0 ||
-        hipMemcpy(w, dw, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(BBX_E_DEVICE, "collect of carried-over clones failed"); break; }
-    bits = w[0]; env = (int)w[1] - 1;
-    if (!bits) break;
-    if (bits & ~capmask) rc = fail(BBX_E_CAPACITY, "value rollout of environment %d did not finish: pairs left", env);
-    else if (attempt == 39) rc = fail(BBX_E_CAPACITY, "value rollouts kept outgrowing the records");
+        hipMemcpy(h, dw, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(BBX_E_DEVICE, "collect of carried-over clones failed"); break; }
+    w = word_of(h);
+    const Unfinished u = classify(b, w, what);
+    if (u == Unfinished::none) break;
+    if (u == Unfinished::fail) rc = BBX_E_CAPACITY;
+    else if (attempt == kGrowAttempts - 1) rc = kept_outgrowing(what);
   }
   if (tmp) { (void)hipStreamSynchronize(0); (void)hipFree(tmp); }
   return rc;
@@ -262,8 +306,7 @@ int value_carry_over(bbx_batch* b, const bbx_vjob& j, size_t jix, const uint32_t
 int av_ensure(bbx_batch* b, int n, size_t cells) {
   bbx_avscratch& s = b->av;
   if (n > s.cap) {
-    void* old[] = {s.d_act, s.d_rew, s.d_done};
-    for (void* q : old) if (q) (void)hipFree(q);
+    free_dev({s.d_act, s.d_rew, s.d_done});
     s.d_act = nullptr; s.d_rew = nullptr; s.d_done = nullptr; s.cap = 0;
     HIPCHK(hipMalloc((void**)&s.d_act, (size_t)n * sizeof(int32_t)));
     HIPCHK(hipMalloc((void**)&s.d_rew, (size_t)n * sizeof(double)));
@@ -271,8 +314,7 @@ int av_ensure(bbx_batch* b, int n, size_t cells) {
     s.cap = n;
   }
   if (cells > s.cells) {
-    void* old[] = {s.d_q, s.d_r, s.d_d};
-    for (void* q : old) if (q) (void)hipFree(q);
+    free_dev({s.d_q, s.d_r, s.d_d});
     s.d_q = nullptr; s.d_r = nullptr; s.d_d = nullptr; s.cells = 0;
     HIPCHK(hipMalloc((void**)&s.d_q, cells * sizeof(double)));
     HIPCHK(hipMalloc((void**)&s.d_r, cells * sizeof(double)));
@@ -283,41 +325,27 @@ int av_ensure(bbx_batch* b, int n, size_t cells) {
   return BBX_OK;
 }
 
-// The forced first step on the clones in `recs`: one step with the actions of d_act, no auto-reset, no observation, rewards
-// and done flags into per-clone arrays.  The kernels are those plan_launch gives a rollout of the class — the first kernel and
-// the one that takes over what it hands on: a clone that outgrows the LDS-resident class in this very step is continued, not
-// left waiting for a host that polls —, each with a budget of one step.
-int av_launch_first_step(bbx_batch* b, char* recs, int n) {
-  BbxParams p; fill_params(b, &p);
-  p.recs = recs; p.B = n; p.nsteps = 2; p.set_budget = 1; p.agent = BBX_AGENT_EXTERNAL; p.auto_reset = 0;
+// The forced first step on the clones: one step with the actions of d_act, no auto-reset, no observation, rewards and done
+// flags into per-clone arrays.  Planned as a rollout with a budget of one step: a clone that outgrows the LDS-resident class
+// in this very step is continued by the kernel behind it, not left waiting for a host that polls.
+int av_launch_first_step(bbx_batch* b, const ValueClones& c) {
+  BbxParams p = clone_params(b, c, 2, BBX_AGENT_EXTERNAL);
   p.actions = b->av.d_act; p.rewards = b->av.d_rew; p.dones = b->av.d_done;
-  p.trace = nullptr; p.accounting = 0;
-  p.lite = nullptr;                                           // the clones are not the batch's environments
-  LaunchPlan pl = plan_launch(b, p, false, true);
-  int lrc = 0;
-  for (int i = 0; i < pl.n && !lrc; i++) { pl.pass[i].nsteps = 1; lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], 0); }
-  if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
+  return launch_on_clones(b, p, false, 1, 0);
 }
 
 // one pass: positions [first, first + n) of the flat list
 int av_pass(bbx_batch* b, int first, int n, int agent, double gamma, int max_rows) {
   bbx_avscratch& s = b->av;
   if (int rc = value_scratch_ensure(b, n)) return rc;
-  int lrc = bbx_launch_av_expand(s.d_off, b->B, first, n, b->d_vsrc, s.d_act, 0);
-  if (lrc) return fail(BBX_E_DEVICE, "expand launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  const int ngen = b->sort_reducers ? b->gens[0]->npolys() : 0;
-  uint8_t* d_flags = (uint8_t*)b->d_vhdr;
-  lrc = bbx_launch_clone(b->d_recs, b->d_vrecs, &b->L, b->d_vsrc, nullptr, n, nullptr, 0, 1, ngen, d_flags, 0);
-  if (lrc) return fail(BBX_E_DEVICE, "clone launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  if (int rc = av_launch_first_step(b, b->d_vrecs, n)) return rc;
-  // (behind the step: value() re-sorts the state it is called on; the flags are the clone's — a step leaves the generators alone)
-  lrc = bbx_launch_value_resort(b->d_vrecs, &b->L, n, d_flags, 0);
-  if (lrc) return fail(BBX_E_DEVICE, "resort launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  if (int rc = value_launch_rollouts(b, b->d_vrecs, n, agent, gamma, false, 0)) return rc;
-  lrc = bbx_launch_av_collect(b->d_vrecs, b->L.rec_bytes, n, b->d_vsrc, s.d_act, s.d_rew, s.d_done, gamma, max_rows, s.d_q, s.d_r, s.d_d, s.d_word, 0);
-  if (lrc) return fail(BBX_E_DEVICE, "collect launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
+  const ValueClones c{b->d_vrecs, b->d_vflags, n};
+  if (int rc = launched(bbx_launch_av_expand(s.d_off, b->B, first, n, b->d_vsrc, s.d_act, 0), "expand")) return rc;
+  if (int rc = value_clone(b, c, b->d_vsrc, nullptr, 0)) return rc;
+  if (int rc = av_launch_first_step(b, c)) return rc;
+  if (int rc = value_resort(b, c, 0)) return rc;                // (behind the step: value() re-sorts the state it is called on)
+  if (int rc = value_launch_rollouts(b, c, agent, gamma, false, 0)) return rc;
+  return launched(bbx_launch_av_collect(c.recs, b->L.rec_bytes, n, b->d_vsrc, s.d_act, s.d_rew, s.d_done, gamma, max_rows, s.d_q, s.d_r, s.d_d,
+                                        s.d_word, 0), "collect");
 }
 
 int action_values(bbx_batch* b, int agent, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, int32_t* rows) {
@@ -327,8 +355,7 @@ int action_values(bbx_batch* b, int agent, double gamma, int max_rows, double* q
   if (int rc = settle(b)) return rc;
   bbx_avscratch& s = b->av;
   if (!s.d_off) HIPCHK(hipMalloc((void**)&s.d_off, (2 * (size_t)B + 3) * sizeof(int32_t)));
-  int lrc = bbx_launch_av_offsets(b->d_recs, b->L.rec_bytes, B, max_rows, s.d_off, 0);
-  if (lrc) return fail(BBX_E_DEVICE, "offsets launch failed: %s", hipGetErrorString((hipError_t)lrc));
+  if (int rc = launched(bbx_launch_av_offsets(b->d_recs, b->L.rec_bytes, B, max_rows, s.d_off, 0), "offsets")) return rc;
   std::vector<int32_t> h(2 * (size_t)B + 3);
   HIPCHK(hipMemcpy(h.data(), s.d_off, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));   // all that visits the host of the states
   if (h[B + 1]) return fail(BBX_E_CAPACITY, "action values of environment %d: it is in an error state: %s", h[B + 1] - 1, status_name(h[B + 2]));
@@ -344,30 +371,21 @@ int action_values(bbx_batch* b, int agent, double gamma, int max_rows, double* q
   for (int e = 0; e < B; e++) counts[e] = h[e + 1] - h[e];
   int32_t npasses = 0;
   if (int rc = bbx_action_values_plan(counts.data(), B, s.chunk, first.data(), (int)first.size(), &npasses)) return rc;
-  const unsigned capmask = (1u << BBX_ST_G_FULL) | (1u << BBX_ST_P_FULL) | (1u << BBX_ST_ARENA_FULL) | (1u << BBX_ST_POLY_TOO_LONG);
-  for (int attempt = 0; attempt < 40; attempt++) {
+  // (a forced step or a rollout that outgrows the records: ALL passes run again — one word per call does not say which pass)
+  return retry_growing(b, "action-value rollout", [&](UnfinishedWord* w) -> int {
     if (int rc = av_ensure(b, std::min(total, s.chunk), cells)) return rc;
-    lrc = bbx_launch_av_fill(s.d_q, s.d_r, s.d_d, cells, s.d_word, 0);
-    if (lrc) return fail(BBX_E_DEVICE, "fill launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    if (int rc = launched(bbx_launch_av_fill(s.d_q, s.d_r, s.d_d, cells, s.d_word, 0), "fill")) return rc;
     for (int p = 0; p < npasses; p++)
       if (int rc = av_pass(b, first[p], first[p + 1] - first[p], agent, gamma, max_rows)) return rc;
-    uint32_t w[2] = {0, 0};
-    HIPCHK(hipMemcpy(w, s.d_word, sizeof w, hipMemcpyDeviceToHost));   // the wait of the call
-    if (!w[0]) {
-      HIPCHK(hipMemcpy(q, s.d_q, cells * sizeof(double), hipMemcpyDeviceToHost));
-      if (rewards) HIPCHK(hipMemcpy(rewards, s.d_r, cells * sizeof(double), hipMemcpyDeviceToHost));
-      if (dones) HIPCHK(hipMemcpy(dones, s.d_d, cells, hipMemcpyDeviceToHost));
-      return BBX_OK;
-    }
-    const int env = (int)w[1] - 1;
-    if ((w[0] & ~capmask) || b->no_growth)
-      return fail(BBX_E_CAPACITY, "action-value rollout of environment %d did not finish: %s", env,
-                  (w[0] & capmask) ? status_name(__builtin_ctz(w[0] & capmask)) : "pairs left or a clone in an error state");
-    // a clone's forced step or rollout outgrew the records: those of the whole batch are enlarged (the clone arrays go with
-    // the old layout) and the passes run again — the results are those of a handle created with room to spare
-    if (int rc = grow_records(b, w[0] & capmask, env, 0)) return rc;
-  }
-  return fail(BBX_E_CAPACITY, "action-value rollouts kept outgrowing the records");
+    uint32_t word[2] = {0, 0};
+    HIPCHK(hipMemcpy(word, s.d_word, sizeof word, hipMemcpyDeviceToHost));   // the wait of the call
+    *w = word_of(word);                                  // (this collect reports environments)
+    if (w->bits) return BBX_OK;
+    HIPCHK(hipMemcpy(q, s.d_q, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (rewards) HIPCHK(hipMemcpy(rewards, s.d_r, cells * sizeof(double), hipMemcpyDeviceToHost));
+    if (dones) HIPCHK(hipMemcpy(dones, s.d_d, cells, hipMemcpyDeviceToHost));
+    return BBX_OK;
+  });
 }
 
 }  // namespace
@@ -403,18 +421,21 @@ int value_resolve(bbx_batch* b) {
 
 void value_ring_free(bbx_batch* b) {
   for (bbx_vslot& s : b->v_ring) {
-    void* dev[] = {s.recs, s.flags, s.seeds};
-    for (void* q : dev) if (q) (void)hipFree(q);
+    free_dev({s.recs, s.flags, s.seeds});
     if (s.cloned) (void)hipEventDestroy(s.cloned);
     if (s.done) (void)hipEventDestroy(s.done);
   }
   b->v_ring.clear();
 }
 
+void value_scratch_free(bbx_batch* b) {
+  free_dev({b->d_vrecs, b->d_vflags, b->d_vsrc, b->d_vseeds, b->d_vvals});
+  b->d_vrecs = nullptr; b->d_vflags = nullptr; b->d_vsrc = nullptr; b->d_vseeds = nullptr; b->d_vvals = nullptr; b->vcap = 0;
+}
+
 void action_values_free(bbx_batch* b) {
   bbx_avscratch& s = b->av;
-  void* dev[] = {s.d_off, s.d_act, s.d_rew, s.d_done, s.d_q, s.d_r, s.d_d, s.d_word};
-  for (void* q : dev) if (q) (void)hipFree(q);
+  free_dev({s.d_off, s.d_act, s.d_rew, s.d_done, s.d_q, s.d_r, s.d_d, s.d_word});
   const int chunk = s.chunk;
   s = bbx_avscratch{}; s.chunk = chunk;
 }
@@ -437,10 +458,8 @@ extern "C" int bbx_gae_bootstrap_device(const double* d_rewards, const double* d
                                         uint8_t* d_complete, double* d_lambda_returns, void* stream) {
   if (!d_rewards || !d_values || !d_dones || !d_returns || !d_advantages || !d_complete || nsteps < 0 || batch < 0) return fail(BBX_E_ARG, "bad arguments");
   if (nsteps == 0 || batch == 0) return BBX_OK;
-  const int lrc = bbx_launch_gae(d_rewards, d_values, d_dones, nsteps, batch, gam, gam * lam, d_last_values, d_returns, d_advantages, d_complete,
-                                 d_lambda_returns, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "GAE launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
+  return launched(bbx_launch_gae(d_rewards, d_values, d_dones, nsteps, batch, gam, gam * lam, d_last_values, d_returns, d_advantages, d_complete,
+                                 d_lambda_returns, (hipStream_t)stream), "GAE");
 }
 
 extern "C" int bbx_gae_device(const double* d_rewards, const double* d_values, const uint8_t* d_dones, int nsteps, int batch,
@@ -455,9 +474,8 @@ extern "C" int bbx_episodes_device(const double* d_rewards, const uint8_t* d_don
   if (nsteps < 0 || batch < 1) return fail(BBX_E_ARG, "bad arguments (nsteps = %d, batch = %d)", nsteps, batch);
   if (nsteps == 0) return BBX_OK;
   if (!d_rewards || !d_dones || !d_ep_return || !d_ep_len) return fail(BBX_E_ARG, "null argument");
-  const int lrc = bbx_launch_episodes(d_rewards, d_dones, nsteps, batch, d_carry_return, d_carry_len, d_ep_count, d_ep_return, d_ep_len, (hipStream_t)stream);
-  if (lrc) return fail(BBX_E_DEVICE, "episodes launch failed: %s", hipGetErrorString((hipError_t)lrc));
-  return BBX_OK;
+  return launched(bbx_launch_episodes(d_rewards, d_dones, nsteps, batch, d_carry_return, d_carry_len, d_ep_count, d_ep_return, d_ep_len, (hipStream_t)stream),
+                  "episodes");
 }
 
 extern "C" int bbx_value(bbx_batch* b, int idx, const char* strategy, double gamma, double* out) {
@@ -509,10 +527,6 @@ extern "C" int bbx_action_values(bbx_batch* b, const char* strategy, double gamm
 }
 
 extern "C" int bbx_values(bbx_batch* b, const char* strategy, double gamma, double* out) {
-  if (!b || !strategy || !out) return fail(BBX_E_ARG, "bad arguments");
-  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
-  std::vector<int32_t> envs(b->B);
-  for (int e = 0; e < b->B; e++) envs[e] = e;
-  return values_for(b, envs, strategy, gamma, nullptr, out);
+  return bbx_values_seeded(b, strategy, gamma, nullptr, out);   // (no seeds: drawn from the handle's own stream)
 }
 

@@ -181,17 +181,11 @@ extern "C" int bbx_launch_value_resort(char* recs, const BbxLayout* L, int n, co
   return (int)hipGetLastError();
 }
 
-// value(): per clone {discounted return, 0 when the rollout ran to the end without an error} after the rollouts
-__global__ void bbx_value_collect_kernel(const char* recs, uint32_t rec_bytes, int n, double* out2) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const BbxHdr* h = (const BbxHdr*)(recs + (size_t)k * rec_bytes);
-  out2[2 * (size_t)k] = h->vret;
-  out2[2 * (size_t)k + 1] = (h->status != BBX_ST_OK || h->nP != 0) ? (double)(h->status ? h->status : -1) : 0.0;
-}
-extern "C" int bbx_launch_value_collect(const char* recs, uint32_t rec_bytes, int n, double* out2, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_value_collect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, out2);
-  return (int)hipGetLastError();
+// A clone that did not run to the end (pairs left, or a status other than OK), folded into the word pair the host reads at its next wait:
+// word[0] |= 1 << status if it waits for room (bbx_st_capacity), bit 31 otherwise; word[1] = 1 + the largest `index` so reported
+__device__ inline void bbx_unfinished_fold(uint32_t* word, int st, uint32_t index) {
+  atomicOr(&word[0], bbx_st_capacity(st) ? 1u << st : 1u << 31);
+  atomicMax(&word[1], index + 1u);
 }
 
 // ---- bbx_values_device: the asynchronous form (bbx_api_value.cpp) -------------------------------------------------------
@@ -216,9 +210,8 @@ extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, in
   hipLaunchKernelGGL(bbx_value_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, seeds, states, n);
   return (int)hipGetLastError();
 }
-// per clone: its discounted return into the caller's array, NaN where the rollout did not run to the end; "did not finish"
-// is folded into the job's word pair the host reads at the next wait: word[0] |= 1 << status for a clone that waits for
-// room (bbx_st_capacity), bit 31 for anything else; word[1] = 1 + the largest such environment index.
+// per clone (the synchronous calls use it too): its discounted return into values[k], NaN where the rollout did not run to the
+// end and the clone's index folded into the call's word pair.
 // only_nan != 0 (the carry-over of waiting clones after the records were enlarged): entries that already hold a value stay.
 __global__ void bbx_value_collect_device_kernel(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -228,10 +221,7 @@ __global__ void bbx_value_collect_device_kernel(const char* recs, uint32_t rec_b
   const int st = h->status;
   const bool finished = st == BBX_ST_OK && h->nP == 0;
   values[k] = finished ? h->vret : __builtin_nan("");
-  if (!finished) {
-    atomicOr(&word[0], bbx_st_capacity(st) ? 1u << st : 1u << 31);
-    atomicMax(&word[1], (uint32_t)k + 1u);
-  }
+  if (!finished) bbx_unfinished_fold(word, st, (uint32_t)k);
 }
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream) {
   hipLaunchKernelGGL(bbx_value_collect_device_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, values, word, only_nan);
@@ -302,8 +292,7 @@ __global__ void bbx_av_fill_kernel(double* q, double* rewards, uint8_t* dones, s
 // Kernel 3, after the forced step and the rollouts of a pass: clone k writes Q = r + gamma * value at [src[k]][act[k]] — in
 // double, one rounded product and one rounded sum (contraction off, as in bbx_gae_kernel: what the host forms from
 // bbx_step's reward and bbx_values' value) —, the step's reward and done flag beside it.  A clone that did not run to the end
-// leaves its cells as they are and is folded into the word pair like bbx_value_collect_device_kernel's: word[0] |= 1 << status
-// for one that waits for room, bit 31 for anything else; word[1] = 1 + the largest such environment.
+// leaves its cells as they are and is folded into the call's word pair under its environment's index.
 __global__ void bbx_av_collect_kernel(const char* recs, uint32_t rec_bytes, int n, const int32_t* src, const int32_t* act, const double* rew,
                                       const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word) {
 #pragma clang fp contract(off)
@@ -311,11 +300,7 @@ __global__ void bbx_av_collect_kernel(const char* recs, uint32_t rec_bytes, int 
   if (k >= n) return;
   const BbxHdr* h = (const BbxHdr*)(recs + (size_t)k * rec_bytes);
   const int st = h->status;
-  if (!(st == BBX_ST_OK && h->nP == 0)) {
-    atomicOr(&word[0], bbx_st_capacity(st) ? 1u << st : 1u << 31);
-    atomicMax(&word[1], (uint32_t)src[k] + 1u);
-    return;
-  }
+  if (!(st == BBX_ST_OK && h->nP == 0)) { bbx_unfinished_fold(word, st, (uint32_t)src[k]); return; }
   const size_t at = (size_t)src[k] * max_rows + act[k];
   const double r = rew[k];
   const double tail = gamma * h->vret;

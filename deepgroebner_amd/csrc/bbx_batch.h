@@ -1,9 +1,9 @@
 // The batch handle of libbbx's C ABI and the internals its translation units share (bbx_api.cpp: creation, kernels of a
 // launch, waits, stepping; bbx_api_session.cpp: what a call becomes — persistent / mailbox sessions, recorded steps;
-// bbx_api_value.cpp: value(); bbx_api_policy.cpp: the PMLP policy calls — prepare, act, policy step, policy rollouts, and the
-// training calls of policy and critic, one body per call for both depths; bbx_api_state.cpp: introspection, generators, text
-// format), and the launchers of the kernel files.  The PMLP training launchers take what a call is about as the records of
-// bbx_pmlp_shape.h (PmlpStates, PmlpNet, PmlpGrads), not as positional lists.
+// bbx_api_value.cpp: the value calls — one pipeline, one outgrow policy; bbx_api_policy.cpp: the PMLP policy calls — prepare,
+// act, policy step, policy rollouts, and the training calls of policy and critic, one body per call for both depths;
+// bbx_api_state.cpp: introspection, generators, text format), and the launchers of the kernel files.  The PMLP training
+// launchers take what a call is about as the records of bbx_pmlp_shape.h (PmlpStates, PmlpNet, PmlpGrads), not as lists.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,7 +21,6 @@ extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_
 extern "C" int bbx_launch_clone(const char* src_recs, char* dst_recs, const BbxLayout* L, const int32_t* src, const int32_t* dst, int n,
                                 const uint32_t* seeds, int keep_counters, int seed_std, int ngen, uint8_t* flags, hipStream_t stream);
 extern "C" int bbx_launch_value_resort(char* recs, const BbxLayout* L, int n, const uint8_t* flags, hipStream_t stream);
-extern "C" int bbx_launch_value_collect(const char* recs, uint32_t rec_bytes, int n, double* out2, hipStream_t stream);
 extern "C" int bbx_launch_value_iota(int32_t* idx, int n, hipStream_t stream);
 extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, int n, hipStream_t stream);
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream);
@@ -104,8 +103,8 @@ constexpr int BBX_VALUE_RING_DEFAULT = 2;   // measured: 2, 4 and 8 are equal, 1
 constexpr int BBX_VALUE_MAX_JOBS = 8192;    // calls between two waits (a word pair each)
 int bbx_value_ring_from_env();        // BBX_VALUE_RING, clamped to 1..16
 
-// bbx_action_values (bbx_api_value.cpp): what it keeps between calls besides the clone arrays it shares with value()
-// (d_vrecs, d_vhdr, d_vsrc: sized by the record layout, freed by grow_records).  Nothing here depends on the layout.
+// bbx_action_values (bbx_api_value.cpp): what it keeps between calls besides the clone scratch it shares with value()
+// (sized by the record layout: value_scratch_free).  Nothing here depends on the layout.
 constexpr int BBX_AV_CHUNK_DEFAULT = 65536;   // clones in flight per pass (bbx_action_values_chunk)
 struct bbx_avscratch {
   int chunk = BBX_AV_CHUNK_DEFAULT;
@@ -181,8 +180,9 @@ struct bbx_batch : bbx_config {
   int32_t* d_obs = nullptr; size_t obs_rows_cap = 0;
   BbxTraceRec* d_trace = nullptr; int trace_cap = 0;
   BbxHdr* d_hdr = nullptr;            // compact header copy (bbx_gather_hdr_kernel)
-  // scratch for value(): cloned records, their headers, source indices, agent seeds, results
-  char* d_vrecs = nullptr; BbxHdr* d_vhdr = nullptr; int32_t* d_vsrc = nullptr; uint32_t* d_vseeds = nullptr; double* d_vvals = nullptr;
+  // clone scratch of value() and bbx_action_values, [vcap] each (value_scratch_free): cloned records, the clone kernel's flags
+  // for the re-sort (u8), source indices, agent seeds; [1 + vcap] results: the "did not finish" word pair, then a value per clone
+  char* d_vrecs = nullptr; uint8_t* d_vflags = nullptr; int32_t* d_vsrc = nullptr; uint32_t* d_vseeds = nullptr; double* d_vvals = nullptr;
   int vcap = 0;
   // bbx_values_device: the ring (depth read from BBX_VALUE_RING when the handle is made), the stream its rollouts run on,
   // the identity source indices, a word pair per queued call, and the calls queued since the last wait
@@ -280,10 +280,11 @@ int step_device(bbx_batch* b, const int32_t* d_actions, double* d_rewards, uint8
                 int obs_fill, void* stream, int auto_reset);   // bbx_step_device[_autoreset]
 // bbx_api_value.cpp: the calls bbx_values_device queued — value_wait: the host waits for their device work (before anything
 // moves or frees records); value_resolve: after that, read their words, carry waiting clones over to enlarged records,
-// report; value_ring_free: the ring's memory (the device must be idle)
+// report; value_ring_free, value_scratch_free: the ring's memory, the clone scratch (the device must be idle)
 int value_wait(bbx_batch* b);
 int value_resolve(bbx_batch* b);
 void value_ring_free(bbx_batch* b);
+void value_scratch_free(bbx_batch* b);
 void action_values_free(bbx_batch* b);   // what bbx_action_values keeps between calls (the device must be idle)
 // bbx_api_session.cpp
 int launch(bbx_batch* b, BbxParams& p, hipStream_t stream, bool obs_external = false, bool device_async = false);

@@ -65,6 +65,8 @@ enum {
 // (bbx_api.cpp grow_records) and the environment continues.  A launch that finds an environment waiting like that adds
 // its steps to the environment's budget instead of replacing it, so no step is lost across asynchronous launches.
 static inline BBX_HD int bbx_st_capacity(int st) { return st == BBX_ST_G_FULL || st == BBX_ST_P_FULL || st == BBX_ST_ARENA_FULL || st == BBX_ST_POLY_TOO_LONG; }
+// the same set as bits of a word of `1 << status` (the "did not finish" word of the value calls, bbx_api_value.cpp)
+#define BBX_ST_CAPACITY_BITS ((1u << BBX_ST_G_FULL) | (1u << BBX_ST_P_FULL) | (1u << BBX_ST_ARENA_FULL) | (1u << BBX_ST_POLY_TOO_LONG))
 // Transient statuses say "steps are still owed, somebody else (the host's refill, the follow-up pass, the session's next
 // kernel) has to act first": every step kernel clears them on entry and tries again.
 static inline BBX_HD int bbx_st_transient(int st) { return st == BBX_ST_STARVED || st == BBX_ST_SPILL || st == BBX_ST_TIMESLICE; }
