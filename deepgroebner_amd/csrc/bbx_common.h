@@ -388,6 +388,18 @@ static inline BBX_HD uint32_t bbx_ginfo_hot(uint32_t rec_x, uint32_t inv) {  // 
 // record's word is kept; the function is where a layout that packs the two differently would say so.)
 static inline BBX_HD uint32_t bbx_ginfo_record(uint32_t hot_x, uint32_t kept) { (void)hot_x; return kept; }
 
+// ------------------------------------------------------------------ the fast class's Gebauer-Moeller peel: the key of a candidate
+// A candidate lcm of the peel (add_poly, bbx_fast.h) is named by ONE word, degree above basis index: the wave minimum of the
+// keys is the smallest index among the candidates of minimal degree — which bucket is next and which member stands for it —,
+// and lane and register bank fall out of its low byte.  The lcm's degree is a 16-bit slot and the class holds at most 256
+// basis elements (index = 64 bank + lane), so a key has 24 bits and 0xFFFFFFFF (no candidate) is above every one of them.
+// Stated once, here, for the kernel and for the host check (tests/peel_keyed_min_check.cpp).
+#define BBX_PEEL_NO_KEY 0xFFFFFFFFu
+static inline BBX_HD uint32_t bbx_peel_key(uint32_t deg, uint32_t index) { return (deg << 8) | index; }   // deg < 2^16, index < 2^8
+static inline BBX_HD uint32_t bbx_peel_key_deg(uint32_t key) { return key >> 8; }
+static inline BBX_HD int bbx_peel_key_lane(uint32_t key) { return (int)(key & 63u); }
+static inline BBX_HD int bbx_peel_key_bank(uint32_t key) { return (int)((key >> 6) & 3u); }
+
 // position-keyed commutative hash used for parity traces (same definition in oracle/trace.py)
 static inline BBX_HD uint64_t bbx_mix64(uint64_t idx, uint32_t word) {
   uint64_t z = ((idx << 32) | (uint64_t)word) + 0x9E3779B97F4A7C15ull;

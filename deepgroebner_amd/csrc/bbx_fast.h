@@ -23,10 +23,14 @@
 // ideals are drawn right here at reset (gen_binomial in bbx_device.h).
 //
 // Gebauer-Moeller new pairs without the std::map walk (buchberger.cpp:78-91): the lcms L_i = lcm(LM G_i, LM f) that
-// survive are exactly those minimal under divisibility.  They are peeled by increasing degree: all candidates of
-// minimal degree are minimal (a proper divisor has strictly smaller degree); each such bucket of equal lcms emits the
-// pair of its smallest index unless a member is coprime to f, then every multiple of it is discarded.  Cost is
-// proportional to the number of minimal lcms (a handful) instead of |G|^2/64.
+// survive are exactly those minimal under divisibility.  They are peeled one bucket of equal lcms at a time: a candidate
+// of minimal degree is minimal (a proper divisor has strictly smaller degree), so ONE wave minimum over the keys
+// degree << 8 | basis index (bbx_peel_key, bbx_common.h) names the next bucket and, in its low byte, the bucket's smallest
+// index — every member of the bucket has that degree and is still a candidate (one removed earlier would be a multiple of an
+// earlier minimal lcm, and so would the whole bucket).  The bucket emits the pair of that index unless a member is coprime
+// to f, then every multiple of the lcm is discarded.  Cost is proportional to the number of minimal lcms (3.3 on
+// average on 3-20-10-weighted) instead of |G|^2/64; until round 25 a minimum per degree LEVEL (2.3 per insertion) named the
+// degree only, and a second loop went over the level's buckets with a compare, a ballot and a find-first of its own.
 #pragma once
 
 typedef Mono<2> M2;
@@ -394,7 +398,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   // ---- helpers as lambdas over the state above ----------------------------------------------------------------------
   // The observation of the headline shape (3 variables, k = 2: rows of 4 monomials x 3 exponents = 48 bytes) with
   // everything that depends on the lane decided once per launch: lane -> (row in the sweep, which pair member, lead or
-  // tail) and its output address; per trip two pair gathers, two monomial gathers and two 12-byte stores.
+  // tail) and its output address; per trip of 32 rows two pair gathers, two monomial gathers and two 12-byte stores, and one of
+  // each for a rest of at most 16 rows.
   struct __attribute__((aligned(4))) ObsI3 { int32_t a, b, c; };
   const bool obs32 = HL ? true : (n == 3 && kk == 2 && p.obs != nullptr);
   const int o3_row = lane >> 2, o3_hi = (lane >> 1) & 1;
@@ -415,7 +420,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     int32_t* ob = o3_base + o3_toff;
     asm volatile("" : "+s"(ob));
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)ob, 0, rows * 48, 0x00020000);
-    for (int r0 = 0; r0 < rows; r0 += 32) {
+    int r0 = 0;
+    for (; rows - r0 > 16; r0 += 32) {
       const int ra = r0 + o3_row, rb = ra + 16;
       const uint32_t pa = pairs[ra], pb = pairs[rb];
       const uint32_t ga = (o3_hi ? pa >> 16 : pa) & (uint32_t)(FG - 1), gb = (o3_hi ? pb >> 16 : pb) & (uint32_t)(FG - 1);
@@ -424,6 +430,15 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       const ObsV3 vb = {(int32_t)(mb.w[0] & 0xffffu), (int32_t)(mb.w[0] >> 16), (int32_t)(mb.w[1] & 0xffffu)};
       __builtin_amdgcn_raw_buffer_store_b96(va, rs, r0 * 48 + lane * 12, 0, 0);
       __builtin_amdgcn_raw_buffer_store_b96(vb, rs, r0 * 48 + lane * 12 + 768, 0, 0);
+    }
+    // at most 16 rows are left (half of all steps on 3-20-10-weighted have no more than that in all): one sweep, not a trip
+    // whose second sweep gathers, unpacks and stores rows that do not exist
+    if (r0 < rows) {
+      const uint32_t pa = pairs[r0 + o3_row];
+      const uint32_t ga = (o3_hi ? pa >> 16 : pa) & (uint32_t)(FG - 1);
+      const M2 ma = *(const M2*)(o3_mono + ga * 8);
+      const ObsV3 va = {(int32_t)(ma.w[0] & 0xffffu), (int32_t)(ma.w[0] >> 16), (int32_t)(ma.w[1] & 0xffffu)};
+      __builtin_amdgcn_raw_buffer_store_b96(va, rs, r0 * 48 + lane * 12, 0, 0);
     }
     if (obs_fill) {
       int32_t* out = p.obs + (size_t)env * p.obs_rows * 12;
@@ -504,7 +519,8 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     const uint32_t inv_raw = (uint32_t)p.inv_table[t0.c];
     const M2 f = t0.m;
     const M2 tail = t1.c ? t1.m : m_zero<2>();
-    if (lane == 0) { lm[g] = f; tm[g] = tail; }
+    // (slot g of the basis-order arrays is written further down, all four arrays under one lane-0 mask: nothing in between reads
+    // it — the peel masks lanes >= g with `valid`, the pair filter gathers members of old pairs, all < g)
     // (70-76) drop old pairs (i,j): LM f | lcm_ij and lcm_ij != lcm_if and lcm_ij != lcm_jf.  Only exponents matter,
     // so the lcms are raw v_pk_max words with the degree slot masked out of the comparisons.
     // The gathers of the first 64 pairs are issued here and consumed behind the register-only peel below, which
@@ -515,7 +531,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     // (78-91) new pairs (i, g): minimal lcms by degree peeling
     uint64_t emit[BK];
     {
-      M2 L[BK]; uint64_t valid[BK], cp[BK], cand[BK]; uint32_t d[BK];
+      M2 L[BK]; uint64_t valid[BK], cp[BK], cand[BK]; uint32_t key[BK];
       f_banks<BK>([&](auto b_) {
         constexpr int b = decltype(b_)::value;
         const M2 l = lm[lane + 64 * b];                    // basis order; lanes >= g hold garbage (masked by valid)
@@ -524,42 +540,32 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         L[b] = m_lcm(l, f);
         if constexpr (b == 0) cp[0] = ballot64(m_coprime(l, f)) & valid[0];
         else cp[b] = valid[b] ? (ballot64(m_coprime(l, f)) & valid[b]) : 0ull;
-        d[b] = L[b].w[1] >> 16; cand[b] = valid[b]; emit[b] = 0;
+        key[b] = bbx_peel_key(L[b].w[1] >> 16, (uint32_t)(lane + 64 * b)); cand[b] = valid[b]; emit[b] = 0;
       });
       auto any = [&](const uint64_t (&m)[BK]) { uint64_t o = 0; f_banks<BK>([&](auto b_) { o |= m[decltype(b_)::value]; }); return o; };
       while (any(cand)) {
-        uint32_t dm = f_lane_in(cand[0]) ? d[0] : 0xFFFFFFFFu;
+        uint32_t km = f_lane_in(cand[0]) ? key[0] : BBX_PEEL_NO_KEY;
         f_banks<BK>([&](auto b_) {
           constexpr int b = decltype(b_)::value;
-          if constexpr (b > 0) if (cand[b]) { const uint32_t t = f_lane_in(cand[b]) ? d[b] : 0xFFFFFFFFu; dm = t < dm ? t : dm; }
+          if constexpr (b > 0) if (cand[b]) { const uint32_t t = f_lane_in(cand[b]) ? key[b] : BBX_PEEL_NO_KEY; km = t < km ? t : km; }
         });
-        const uint32_t dmin = f_wave_min(dm);
-        uint64_t surv[BK];
+        const uint32_t kmin = f_wave_min(km);              // the next bucket's degree, and its smallest index: lane s of bank sb
+        const int s = bbx_peel_key_lane(kmin), sb = BK == 1 ? 0 : bbx_peel_key_bank(kmin);
+        M2 Ls = f_readlane(L[0], s);
+        f_banks<BK>([&](auto b_) { constexpr int b = decltype(b_)::value; if constexpr (b > 0) if (sb == b) Ls = f_readlane(L[b], s); });
+        const uint64_t ls = f_u64(Ls);
+        uint64_t eq[BK], dv[BK], bad = 0;
         f_banks<BK>([&](auto b_) {
           constexpr int b = decltype(b_)::value;
-          if constexpr (b == 0) surv[0] = ballot64(f_lane_in(cand[0]) && d[0] == dmin);
-          else surv[b] = cand[b] ? ballot64(f_lane_in(cand[b]) && d[b] == dmin) : 0ull;
+          if constexpr (b == 0) { eq[0] = ballot64(f_u64(L[0]) == ls); dv[0] = ballot64(m_divides(Ls, L[0])); bad |= eq[0] & valid[0] & cp[0]; }
+          else {
+            eq[b] = 0; dv[b] = 0;
+            if (valid[b]) { eq[b] = ballot64(f_u64(L[b]) == ls) & valid[b]; dv[b] = ballot64(m_divides(Ls, L[b])); }
+            bad |= eq[b] & cp[b];
+          }
         });
-        while (any(surv)) {
-          M2 Ls; int s = 0, sb = 0; bool got = false;      // the first survivor: lane s of bank sb
-          f_banks<BK>([&](auto b_) {
-            constexpr int b = decltype(b_)::value;
-            if (!got && (b == BK - 1 || surv[b])) { s = __builtin_ctzll(surv[b]); Ls = f_readlane(L[b], s); sb = b; got = true; }
-          });
-          const uint64_t ls = f_u64(Ls);
-          uint64_t eq[BK], dv[BK], bad = 0;
-          f_banks<BK>([&](auto b_) {
-            constexpr int b = decltype(b_)::value;
-            if constexpr (b == 0) { eq[0] = ballot64(f_u64(L[0]) == ls); dv[0] = ballot64(m_divides(Ls, L[0])); bad |= eq[0] & valid[0] & cp[0]; }
-            else {
-              eq[b] = 0; dv[b] = 0;
-              if (valid[b]) { eq[b] = ballot64(f_u64(L[b]) == ls) & valid[b]; dv[b] = ballot64(m_divides(Ls, L[b])); }
-              bad |= eq[b] & cp[b];
-            }
-          });
-          if (bad == 0) f_banks<BK>([&](auto b_) { constexpr int b = decltype(b_)::value; if (BK == 1 || sb == b) emit[b] |= 1ull << s; });
-          f_banks<BK>([&](auto b_) { constexpr int b = decltype(b_)::value; surv[b] &= ~eq[b]; cand[b] &= ~dv[b]; });
-        }
+        if (bad == 0) f_banks<BK>([&](auto b_) { constexpr int b = decltype(b_)::value; if (BK == 1 || sb == b) emit[b] |= 1ull << s; });
+        f_banks<BK>([&](auto b_) { constexpr int b = decltype(b_)::value; cand[b] &= ~dv[b]; });
       }
     }
     auto stays = [&](uint32_t pr, const M2& li, const M2& lj, int k) {
@@ -612,7 +618,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       }
       const uint32_t inv = (uint32_t)uni((int)inv_raw);        // (the one wait for the table read: every lane read the same entry)
       const uint32_t rec_x = t0.c | (t1.c << 16), hot_x = bbx_ginfo_hot(rec_x, inv);   // tc / lc | (-tc / lc) << 16
-      if (lane == 0) { gi[g] = make_uint2(hot_x, inv | ((uint32_t)sugar << 16)); gc[g] = rec_x; }
+      if (lane == 0) { lm[g] = f; tm[g] = tail; gi[g] = make_uint2(hot_x, inv | ((uint32_t)sugar << 16)); gc[g] = rec_x; }
       const uint2 ns = make_uint2(t1.c | (hot_x & 0xffff0000u), (uint32_t)sugar | ((uint32_t)g << 16));   // .x = tc | (-tc / lc) << 16
       // the overflow order takes the new element (pos beyond the registers) or the reducer that falls out of the last bank
       int ovq = -1; uint32_t ovg = 0;
