@@ -8,20 +8,7 @@
 
 #include "bbx_host.h"
 #include "bbx_ideals.h"
-
-struct AlgParams {                    // (bbx_algebra.hip)
-  char* recs; char* recs2;
-  BbxLayout L;
-  int32_t n, op, elim;
-  const int32_t* args;
-  int32_t* out;
-};
-extern "C" int bbx_launch_alg(const AlgParams* p, hipStream_t stream);
-extern "C" int bbx_launch_relayout(const char* src_recs, char* dst_recs, const BbxLayout* Ls, const BbxLayout* Ld, int B, hipStream_t stream);
-extern "C" int bbx_launch_alg_from_envs(const char* src_recs, const BbxLayout* Ls, const int32_t* idx, int n, char* dst_recs, const BbxLayout* Ld, hipStream_t stream);
-// (bbx_api.cpp) quiesces the batch and reports where its records live
-extern "C" int bbx_internal_records(bbx_batch* b, const char** recs, BbxLayout* L, int* device, int* W, int* batch);
-extern "C" int bbx_launch_gather_hdr(const char* recs, uint32_t rec_bytes, int B, BbxHdr* out, hipStream_t stream);
+#include "bbx_launch.h"
 
 using bbx_host::fail;
 

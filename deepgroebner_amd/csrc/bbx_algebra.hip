@@ -8,16 +8,9 @@
 // appends its result as a new element at the very end (or builds a fresh list in a second record), so a list that runs
 // out of room is left exactly as it was: the host enlarges the records and runs the operation again for those lists.
 #include "bbx_device.h"
+#include "bbx_launch.h"
 
 enum { ALG_ADD = 0, ALG_SUB = 1, ALG_MUL = 2, ALG_SPOLY = 3, ALG_REDUCE = 4, ALG_UPDATE = 5, ALG_MINIMALIZE = 6, ALG_INTERREDUCE = 7 };
-
-struct AlgParams {
-  char* recs; char* recs2;            // the lists; the lists minimalize / interreduce build
-  BbxLayout L;
-  int32_t n, op, elim;
-  const int32_t* args;                // [n][4] operands: element indices i, j (binary operations), dividend index and number of divisors (reduce)
-  int32_t* out;                       // [n][4]: {status (0 = done), reduction steps, -, -}
-};
 
 // G.push_back(polynomial of n terms at sm / sc): arena copy and metadata; false (status set) when the list has no room
 template <int W>
@@ -283,20 +276,14 @@ __global__ void bbx_alg_from_envs_kernel(const char* src_recs, BbxLayout Ls, con
   }
 }
 extern "C" int bbx_launch_alg_from_envs(const char* src_recs, const BbxLayout* Ls, const int32_t* idx, int n, char* dst_recs, const BbxLayout* Ld, hipStream_t stream) {
-  const int blocks = (n + 3) / 4;
-  if (Ls->W == 2) hipLaunchKernelGGL((bbx_alg_from_envs_kernel<2>), dim3(blocks), dim3(256), 0, stream, src_recs, *Ls, idx, n, dst_recs, *Ld);
-  else if (Ls->W == 4) hipLaunchKernelGGL((bbx_alg_from_envs_kernel<4>), dim3(blocks), dim3(256), 0, stream, src_recs, *Ls, idx, n, dst_recs, *Ld);
-  else hipLaunchKernelGGL((bbx_alg_from_envs_kernel<8>), dim3(blocks), dim3(256), 0, stream, src_recs, *Ls, idx, n, dst_recs, *Ld);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick<2, 4, 8>((int)Ls->W, [&](auto W) {
+    return bbx_launch<bbx_alg_from_envs_kernel<W()>>(dim3((n + 3) / 4), 256, 0, stream, src_recs, *Ls, idx, n, dst_recs, *Ld);
+  }));
 }
 
 extern "C" int bbx_launch_alg(const AlgParams* p, hipStream_t stream) {
   const int waves = 4, blocks = (p->n + waves - 1) / waves;
-  const int W = (int)p->L.W;
-  const size_t lds = (size_t)waves * (W == 2 ? merge_lds_bytes<2>() : W == 4 ? merge_lds_bytes<4>() : merge_lds_bytes<8>());
-  const int rc = W == 2 ? launch_lds<bbx_alg_kernel<2>>(blocks, waves * WAVE, lds, stream, *p)
-               : W == 4 ? launch_lds<bbx_alg_kernel<4>>(blocks, waves * WAVE, lds, stream, *p)
-                        : launch_lds<bbx_alg_kernel<8>>(blocks, waves * WAVE, lds, stream, *p);
-  if (rc) return rc;
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick<2, 4, 8>((int)p->L.W, [&](auto W) {
+    return launch_lds<bbx_alg_kernel<W()>>(blocks, waves * WAVE, (size_t)waves * merge_lds_bytes<W()>(), stream, *p);
+  }));
 }

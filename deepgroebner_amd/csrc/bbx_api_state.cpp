@@ -26,7 +26,7 @@ int bbx_stats(bbx_batch* b, int64_t* out8) {
   return BBX_OK;
 }
 
-// (bbx_alg.cpp) where the records of a quiet batch live
+// (bbx_host.h, for bbx_alg.cpp) where the records of a quiet batch live
 int bbx_internal_records(bbx_batch* b, const char** recs, BbxLayout* L, int* device, int* W, int* batch) {
   if (!b) return fail(BBX_E_ARG, "null argument");
   HIPCHK(hipSetDevice(b->device)); b->api_epoch++;

@@ -1,15 +1,12 @@
 // Housekeeping kernels of libbbx (initialisation, queue refill, ragged observations, clones, value() and action-value
-// bookkeeping, record growth, header gathers), the stand-alone PMLP policy launchers and the launcher that picks a kernel class (bbx_launch_step).
+// bookkeeping, record growth, header gathers), the stand-alone PMLP policy launchers and the launcher that picks a kernel class
+// (bbx_launch_step).  Every launcher here and the four class launchers it calls are declared in bbx_launch.h.
 #include "bbx_device.h"
+#include "bbx_launch.h"
 #include "bbx_pmlp.h"
 #include "bbx_pmlp_grad.h"
 #include "bbx_pmlp_value.h"
 #include "bbx_binom.h"
-
-extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream);
-extern "C" int bbx_launch_binom(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream);
-extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int envs_per_block, hipStream_t stream);
-extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream);
 
 // ------------------------------------------------------------------ housekeeping kernels
 // zero the headers and set the per-environment agent seeds
@@ -42,8 +39,7 @@ __global__ void bbx_scatter_queue_kernel(const uint32_t* stage, int n, uint32_t 
   if (threadIdx.x == 0) tail[env] = (int32_t)stage[n + i];
 }
 extern "C" int bbx_launch_scatter_queue(const uint32_t* stage, int n, uint32_t ring_words, uint32_t* q, int32_t* tail, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_scatter_queue_kernel, dim3(n), dim3(256), 0, stream, stage, n, ring_words, q, tail);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_scatter_queue_kernel>(dim3(n), 256, 0, stream, stage, n, ring_words, q, tail));
 }
 // ragged observation: the rows of every environment back to back (what a list of per-environment matrices needs),
 // packed on the device from the padded block a step launch leaves behind.  Kernel 1: off[e] = sum of min(rows, cap)
@@ -77,17 +73,14 @@ __global__ void bbx_obs_pack_kernel(const int32_t* padded, int cap, int cols, co
   for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 extern "C" int bbx_launch_obs_pack(const int32_t* padded, int cap, int cols, const int32_t* rows, int B, int32_t* off, int32_t* packed, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_obs_offsets_kernel, dim3(1), dim3(1024), 0, stream, rows, B, cap, off);
-  hipLaunchKernelGGL(bbx_obs_pack_kernel, dim3(B), dim3(64), 0, stream, padded, cap, cols, off, B, packed);
-  return (int)hipGetLastError();
+  bbx_launch<bbx_obs_offsets_kernel>(dim3(1), 1024, 0, stream, rows, B, cap, off);
+  return bbx_launched(bbx_launch<bbx_obs_pack_kernel>(dim3(B), 64, 0, stream, padded, cap, cols, (const int32_t*)off, B, packed));
 }
 extern "C" int bbx_launch_init(char* recs, uint32_t rec_bytes, int B, const uint32_t* agent_seeds, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_init_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, B, agent_seeds);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_init_kernel>(dim3((B + 255) / 256), 256, 0, stream, recs, rec_bytes, B, agent_seeds));
 }
 extern "C" int bbx_launch_mark_reset(char* recs, uint32_t rec_bytes, int B, const uint8_t* mask, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_mark_reset_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, B, mask);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_mark_reset_kernel>(dim3((B + 255) / 256), 256, 0, stream, recs, rec_bytes, B, mask));
 }
 
 // value(): clone environment src[k] of one record array into slot k of another (live prefixes only), optionally
@@ -125,11 +118,9 @@ __global__ void bbx_clone_kernel(const char* src_recs, char* dst_recs, BbxLayout
 }
 extern "C" int bbx_launch_clone(const char* src_recs, char* dst_recs, const BbxLayout* L, const int32_t* src, const int32_t* dst, int n,
                                 const uint32_t* seeds, int keep_counters, int seed_std, int ngen, uint8_t* flags, hipStream_t stream) {
-  const int blocks = (n + 3) / 4;
-  if (L->W == 2) hipLaunchKernelGGL((bbx_clone_kernel<2>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *L, src, dst, n, seeds, keep_counters, seed_std, ngen, flags);
-  else if (L->W == 4) hipLaunchKernelGGL((bbx_clone_kernel<4>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *L, src, dst, n, seeds, keep_counters, seed_std, ngen, flags);
-  else hipLaunchKernelGGL((bbx_clone_kernel<8>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *L, src, dst, n, seeds, keep_counters, seed_std, ngen, flags);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick<2, 4, 8>((int)L->W, [&](auto W) {
+    return bbx_launch<bbx_clone_kernel<W()>>(dim3((n + 3) / 4), 256, 0, stream, src_recs, dst_recs, *L, src, dst, n, seeds, keep_counters, seed_std, ngen, flags);
+  }));
 }
 // ---- value(): the reducer order buchberger() starts from ---------------------------------------------------------------
 // buchberger() re-sorts its reducers with std::sort (buchberger.cpp:157-158: G_ = F in basis order, sorted by lead
@@ -174,11 +165,9 @@ __global__ void bbx_value_resort_kernel(char* recs, BbxLayout L, int n, const ui
   }
 }
 extern "C" int bbx_launch_value_resort(char* recs, const BbxLayout* L, int n, const uint8_t* flags, hipStream_t stream) {
-  const int blocks = (n + 3) / 4;
-  if (L->W == 2) hipLaunchKernelGGL((bbx_value_resort_kernel<2>), dim3(blocks), dim3(256), 0, stream, recs, *L, n, flags);
-  else if (L->W == 4) hipLaunchKernelGGL((bbx_value_resort_kernel<4>), dim3(blocks), dim3(256), 0, stream, recs, *L, n, flags);
-  else hipLaunchKernelGGL((bbx_value_resort_kernel<8>), dim3(blocks), dim3(256), 0, stream, recs, *L, n, flags);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick<2, 4, 8>((int)L->W, [&](auto W) {
+    return bbx_launch<bbx_value_resort_kernel<W()>>(dim3((n + 3) / 4), 256, 0, stream, recs, *L, n, flags);
+  }));
 }
 
 // A clone that did not run to the end (pairs left, or a status other than OK), folded into the word pair the host reads at its next wait:
@@ -195,8 +184,7 @@ __global__ void bbx_value_iota_kernel(int32_t* idx, int n) {
   if (k < n) idx[k] = k;
 }
 extern "C" int bbx_launch_value_iota(int32_t* idx, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_value_iota_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, idx, n);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_value_iota_kernel>(dim3((n + 255) / 256), 256, 0, stream, idx, n));
 }
 // "random": seed -> engine state of std::default_random_engine::seed(s), minstd_state_of_seed of bbx_api_value.cpp on the
 // device (the int seed converts to the unsigned result type first; x = s mod 2^31 - 1, and 0 becomes 1)
@@ -207,8 +195,7 @@ __global__ void bbx_value_seeds_kernel(const int64_t* seeds, uint32_t* states, i
   states[k] = x ? x : 1u;
 }
 extern "C" int bbx_launch_value_seeds(const int64_t* seeds, uint32_t* states, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_value_seeds_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, seeds, states, n);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_value_seeds_kernel>(dim3((n + 255) / 256), 256, 0, stream, seeds, states, n));
 }
 // per clone (the synchronous calls use it too): its discounted return into values[k], NaN where the rollout did not run to the
 // end and the clone's index folded into the call's word pair.
@@ -224,8 +211,7 @@ __global__ void bbx_value_collect_device_kernel(const char* recs, uint32_t rec_b
   if (!finished) bbx_unfinished_fold(word, st, (uint32_t)k);
 }
 extern "C" int bbx_launch_value_collect_device(const char* recs, uint32_t rec_bytes, int n, double* values, uint32_t* word, int only_nan, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_value_collect_device_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, values, word, only_nan);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_value_collect_device_kernel>(dim3((n + 255) / 256), 256, 0, stream, recs, rec_bytes, n, values, word, only_nan));
 }
 
 // ---- bbx_action_values: one clone per (environment, pair), a forced first step, then value() (bbx_api_value.cpp) ----------
@@ -307,24 +293,20 @@ __global__ void bbx_av_collect_kernel(const char* recs, uint32_t rec_bytes, int 
   q[at] = r + tail; rewards[at] = r; dones[at] = done[k];
 }
 extern "C" int bbx_launch_av_offsets(const char* recs, uint32_t rec_bytes, int B, int max_rows, int32_t* out, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_av_offsets_kernel, dim3(1), dim3(1024), 0, stream, recs, rec_bytes, B, max_rows, out);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_av_offsets_kernel>(dim3(1), 1024, 0, stream, recs, rec_bytes, B, max_rows, out));
 }
 extern "C" int bbx_launch_av_expand(const int32_t* off, int B, int first, int n, int32_t* src, int32_t* act, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_av_expand_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, off, B, first, n, src, act);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_av_expand_kernel>(dim3((n + 255) / 256), 256, 0, stream, off, B, first, n, src, act));
 }
 extern "C" int bbx_launch_av_fill(double* q, double* rewards, uint8_t* dones, size_t cells, uint32_t* word, hipStream_t stream) {
   const size_t m = cells > 2 ? cells : 2;
-  hipLaunchKernelGGL(bbx_av_fill_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, q, rewards, dones, cells, word);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_av_fill_kernel>(dim3((unsigned)((m + 255) / 256)), 256, 0, stream, q, rewards, dones, cells, word));
 }
 extern "C" int bbx_launch_av_collect(const char* recs, uint32_t rec_bytes, int n, const int32_t* src, const int32_t* act, const double* rew,
                                      const uint8_t* done, double gamma, int max_rows, double* q, double* rewards, uint8_t* dones, uint32_t* word,
                                      hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_av_collect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, n, src, act, rew, done, gamma, max_rows,
-                     q, rewards, dones, word);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_av_collect_kernel>(dim3((n + 255) / 256), 256, 0, stream, recs, rec_bytes, n, src, act, rew, done, gamma, max_rows, q, rewards,
+                                                        dones, word));
 }
 
 // ---- GAE over a [T][B] trajectory block (DeviceTrajectoryBuffer.finish(), pg.py:20-76 per trajectory) -------------------
@@ -361,13 +343,10 @@ __global__ void bbx_gae_kernel(const double* __restrict__ rewards, const double*
 extern "C" int bbx_launch_gae(const double* rewards, const double* values, const uint8_t* dones, int T, int B, double gam, double gl,
                               const double* last_values, double* returns, double* advantages, uint8_t* complete, double* lambda_returns,
                               hipStream_t stream) {
-  if (lambda_returns)
-    hipLaunchKernelGGL(bbx_gae_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, last_values, returns,
-                       advantages, complete, lambda_returns);
-  else
-    hipLaunchKernelGGL(bbx_gae_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, values, dones, T, B, gam, gl, last_values, returns,
-                       advantages, complete, lambda_returns);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick_bool(lambda_returns != nullptr, [&](auto LAM) {
+    return bbx_launch<bbx_gae_kernel<LAM()>>(dim3((B + 63) / 64), 64, 0, stream, rewards, values, dones, T, B, gam, gl, last_values, returns, advantages, complete,
+                                             lambda_returns);
+  }));
 }
 
 // ---- per-episode returns and lengths from the [T][B] rewards and dones of a rollout (run_episodes, pg.py: one return and one
@@ -397,8 +376,7 @@ __global__ void bbx_episodes_kernel(const double* __restrict__ rewards, const ui
 }
 extern "C" int bbx_launch_episodes(const double* rewards, const uint8_t* dones, int T, int B, double* carry_return, int32_t* carry_len, int32_t* ep_count,
                                    double* ep_return, int32_t* ep_len, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_episodes_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, rewards, dones, T, B, carry_return, carry_len, ep_count, ep_return, ep_len);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_episodes_kernel>(dim3((B + 63) / 64), 64, 0, stream, rewards, dones, T, B, carry_return, carry_len, ep_count, ep_return, ep_len));
 }
 
 // enlarged records (bbx_api.cpp grow_records): every environment's live state moves from its record in the old layout to
@@ -418,11 +396,9 @@ __global__ void bbx_relayout_kernel(const char* src_recs, char* dst_recs, BbxLay
   }
 }
 extern "C" int bbx_launch_relayout(const char* src_recs, char* dst_recs, const BbxLayout* Ls, const BbxLayout* Ld, int B, hipStream_t stream) {
-  const int blocks = (B + 3) / 4;
-  if (Ls->W == 2) hipLaunchKernelGGL((bbx_relayout_kernel<2>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *Ls, *Ld, B);
-  else if (Ls->W == 4) hipLaunchKernelGGL((bbx_relayout_kernel<4>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *Ls, *Ld, B);
-  else hipLaunchKernelGGL((bbx_relayout_kernel<8>), dim3(blocks), dim3(256), 0, stream, src_recs, dst_recs, *Ls, *Ld, B);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_pick<2, 4, 8>((int)Ls->W, [&](auto W) {
+    return bbx_launch<bbx_relayout_kernel<W()>>(dim3((B + 3) / 4), 256, 0, stream, src_recs, dst_recs, *Ls, *Ld, B);
+  }));
 }
 
 // persistent sessions: the host's hand on the control word (one relaxed agent-scope atomic store: what the waves' polls observe)
@@ -430,8 +406,7 @@ __global__ void bbx_ctl_kernel(unsigned long long* ctl, unsigned long long value
   if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_store(ctl, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 extern "C" int bbx_launch_ctl(unsigned long long* ctl, unsigned long long value, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_ctl_kernel, dim3(1), dim3(64), 0, stream, ctl, value);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_ctl_kernel>(dim3(1), 64, 0, stream, ctl, value));
 }
 
 // compact copy of every header so the host reads them with one contiguous transfer
@@ -448,12 +423,10 @@ __global__ void bbx_gather_lite_kernel(const char* recs, uint32_t rec_bytes, int
   out[env] = make_int4(bbx_lite_word0(h->status, 0, 0), h->q_head, h->budget, h->nP);
 }
 extern "C" int bbx_launch_gather_lite(const char* recs, uint32_t rec_bytes, int B, void* out, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_gather_lite_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, B, (int4*)out);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_gather_lite_kernel>(dim3((B + 255) / 256), 256, 0, stream, recs, rec_bytes, B, (int4*)out));
 }
 extern "C" int bbx_launch_gather_hdr(const char* recs, uint32_t rec_bytes, int B, BbxHdr* out, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_gather_hdr_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, recs, rec_bytes, B, out);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_gather_hdr_kernel>(dim3((B + 255) / 256), 256, 0, stream, recs, rec_bytes, B, out));
 }
 
 // prepared weights of the PMLP policy kernels (layout: bbx_pmlp.h)
@@ -472,53 +445,39 @@ __global__ void bbx_pmlp_prepare_kernel(const float* __restrict__ w1, const floa
   }
 }
 extern "C" int bbx_launch_pmlp_prepare(const float* w1, const float* b1, const float* w2, float b2, int cols, int hidden, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_pmlp_prepare_kernel, dim3(16), dim3(256), 0, stream, w1, b1, w2, b2, cols, hidden, out);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_pmlp_prepare_kernel>(dim3(16), 256, 0, stream, w1, b1, w2, b2, cols, hidden, out));
+}
+// the (NB, KS) table of the one-layer kernels: f(NB, KS) of the network's unit blocks and the columns' k-steps
+template <class F>
+static int pmlp_pick_shape(int hidden, int cols, F&& f) {
+  return bbx_pick<1, 2, 4, 8>(pmlp_nb_for(hidden), [&](auto NB) { return bbx_pick<3, 6, 10, 16, 32>(pmlp_ks_for(cols), [&](auto KS) { return f(NB, KS); }); });
 }
 extern "C" int bbx_launch_pmlp_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int hidden, const float* u,
                                    int32_t* actions, float* logprobs, int greedy, hipStream_t stream) {
-  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const size_t ml = pmlp_lds_bytes(waves, obs_rows);
-#define BBX_PMLP_MFMA(N, K) hipLaunchKernelGGL((bbx_pmlp_act_mfma_kernel<N, K>), dim3((B + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, B, \
-                                                obs_rows, cols, wp, u, actions, logprobs, greedy)
-#define BBX_PMLP_MFMA_K(N) do { if (ks == 3) BBX_PMLP_MFMA(N, 3); else if (ks == 6) BBX_PMLP_MFMA(N, 6); else if (ks == 10) BBX_PMLP_MFMA(N, 10); \
-                                else if (ks == 16) BBX_PMLP_MFMA(N, 16); else BBX_PMLP_MFMA(N, 32); } while (0)
-  if (nb == 1) BBX_PMLP_MFMA_K(1); else if (nb == 2) BBX_PMLP_MFMA_K(2); else if (nb == 4) BBX_PMLP_MFMA_K(4); else BBX_PMLP_MFMA_K(8);
-#undef BBX_PMLP_MFMA_K
-#undef BBX_PMLP_MFMA
-  return (int)hipGetLastError();
+  const int waves = 4;
+  return bbx_launched(pmlp_pick_shape(hidden, cols, [&](auto NB, auto KS) {
+    return bbx_launch<bbx_pmlp_act_mfma_kernel<NB(), KS()>>(dim3((B + waves - 1) / waves), waves * WAVE, pmlp_lds_bytes(waves, obs_rows), stream, obs, rows, B, obs_rows,
+                                                            cols, wp, u, actions, logprobs, greedy);
+  }));
 }
 // log-probability / entropy of recorded actions, the weight gradients (bbx_pmlp_grad.h) and the critic (bbx_pmlp_value.h), all over
-// the same (NB, KS) table.  BBX_PMLP_DISPATCH(M): M(NB, KS, IDX, EPI) of the shape (`nb`, `ks`), of `index` (non-null: the
-// indexed instantiations, position k is about recorded state index[k] of n_src) and of `epi` (the forward kernels' epilogue:
-// LOSS or FIT; the gradient kernels have none and their M ignores it)
-#define BBX_PMLP_DISPATCH_IE(M, N, K) do { if (index) { if (epi) M(N, K, true, true); else M(N, K, true, false); } \
-                                           else if (epi) M(N, K, false, true); else M(N, K, false, false); } while (0)
-#define BBX_PMLP_DISPATCH_K(M, N) do { if (ks == 3) BBX_PMLP_DISPATCH_IE(M, N, 3); else if (ks == 6) BBX_PMLP_DISPATCH_IE(M, N, 6); \
-                                       else if (ks == 10) BBX_PMLP_DISPATCH_IE(M, N, 10); else if (ks == 16) BBX_PMLP_DISPATCH_IE(M, N, 16); \
-                                       else BBX_PMLP_DISPATCH_IE(M, N, 32); } while (0)
-#define BBX_PMLP_DISPATCH(M) do { if (nb == 1) BBX_PMLP_DISPATCH_K(M, 1); else if (nb == 2) BBX_PMLP_DISPATCH_K(M, 2); \
-                                  else if (nb == 4) BBX_PMLP_DISPATCH_K(M, 4); else BBX_PMLP_DISPATCH_K(M, 8); } while (0)
-// (the launchers take the records of bbx_pmlp_shape.h and name the fields as the kernels name their parameters)
+// the same (NB, KS) table, and each for s.index null or not (non-null: the indexed instantiations, position k is about recorded
+// state index[k] of n_src); the forward kernels also with or without their epilogue (loss / fit).
+// (the launchers take the records of bbx_pmlp_shape.h)
 extern "C" int bbx_launch_pmlp_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
                                        hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
-  if (n <= 0) return 0;
-  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const size_t ml = pmlp_lds_bytes(waves, obs_rows);
-  const bool epi = loss != nullptr;
+  if (s.n <= 0) return 0;
+  const int waves = 4;
   const PmlpLoss ls = loss ? *loss : PmlpLoss{};
-#define BBX_PMLP_LOGPROB(N, K, I, L) hipLaunchKernelGGL((bbx_pmlp_logprob_kernel<N, K, I, L>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                         actions, n, obs_rows, cols, wp, logprobs, entropy, index, n_src, ls)
-  BBX_PMLP_DISPATCH(BBX_PMLP_LOGPROB);
-#undef BBX_PMLP_LOGPROB
-  return (int)hipGetLastError();
+  return bbx_launched(pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_pick_bool(loss != nullptr, [&](auto LOSS) {
+      return bbx_launch<bbx_pmlp_logprob_kernel<NB(), KS(), IDX(), LOSS()>>(dim3((s.n + waves - 1) / waves), waves * WAVE, pmlp_lds_bytes(waves, s.obs_rows), stream, s.obs,
+                                                                            s.rows, actions, s.n, s.obs_rows, s.cols, net.prepared, logprobs, entropy, s.index, s.n_src, ls);
+    }); }); }));
 }
 // the statistics of a PPO call, one or two hidden layers, from the tail its forward kernel wrote (n == 0: zeros)
 extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_pmlp_ppo_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_pmlp_ppo_stats_kernel>(dim3(1), PMLP_PPO_STAT_THREADS, 0, stream, tail, n, stats));
 }
 // how the policy's and the critic's gradient kernels are launched: nw waves per unit group (0: no launch, the second kernel writes
 // zeros), ng unit groups
@@ -529,66 +488,52 @@ struct PmlpGradLaunch {
   size_t lds;
   // (indexed with no recorded state at all: every index is out of range, nothing contributes, and the kernel, which reads state 0
   // in place of an index out of range, is not launched)
-  PmlpGradLaunch(int n, int obs_rows, int cols, int hidden, const int32_t* index, int n_src)
-      : nw(n > 0 && !(index && n_src == 0) ? pmlp_grad_waves(n) : 0), ng(pmlp_nb_for(hidden) / pmlp_grad_ubw(cols, hidden)),
-        grid((nw + waves - 1) / waves, ng), lds(pmlp_grad_lds_bytes(waves, obs_rows)) {}
+  PmlpGradLaunch(const PmlpStates& s, int hidden)
+      : nw(s.n > 0 && !(s.index && s.n_src == 0) ? pmlp_grad_waves(s.n) : 0), ng(pmlp_nb_for(hidden) / pmlp_grad_ubw(s.cols, hidden)),
+        grid((nw + waves - 1) / waves, ng), lds(pmlp_grad_lds_bytes(waves, s.obs_rows)) {}
 };
-// the second kernel of either, unless launching the first has failed: the nw partial sums of every output added in order
-static int pmlp_grad_reduce(const PmlpGrads& g, int nw, int cols, int hidden, hipStream_t stream) {
-  if (int rc = (int)hipGetLastError()) return rc;
-  hipLaunchKernelGGL(bbx_pmlp_grad_reduce_kernel, dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), dim3(256), 0, stream, g.workspace, nw, cols, hidden,
-                     g.gw1, g.gb1, g.gw2, g.gb2);
-  return (int)hipGetLastError();
+// the second kernel of either, unless launching the first (rc) has failed: the nw partial sums of every output added in order
+static int pmlp_grad_reduce(int rc, const PmlpGrads& g, int nw, int cols, int hidden, hipStream_t stream) {
+  if (rc) return rc;
+  if ((rc = (int)hipGetLastError())) return rc;
+  return bbx_launched(bbx_launch<bbx_pmlp_grad_reduce_kernel>(dim3((cols * hidden + 2 * hidden + 1 + 63) / 64), 256, 0, stream, (const float*)g.workspace, nw, cols,
+                                                               hidden, g.gw1, g.gb1, g.gw2, g.gb2));
 }
 extern "C" int bbx_launch_pmlp_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
                                     hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
-  const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const bool epi = false;
-  const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
-#define BBX_PMLP_GRAD(N, K, I, E) hipLaunchKernelGGL((bbx_pmlp_grad_kernel<N, K, I>), L.grid, dim3(L.waves * WAVE), L.lds, stream, obs, rows, actions, n, obs_rows, \
-                                                      cols, wp, glogp, gent, L.nw, ws, index, n_src)
-  if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_GRAD);
-#undef BBX_PMLP_GRAD
-  return pmlp_grad_reduce(g, L.nw, cols, hidden, stream);
+  const PmlpGradLaunch L(s, net.h1);
+  int rc = 0;
+  if (L.nw > 0) rc = pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_launch<bbx_pmlp_grad_kernel<NB(), KS(), IDX()>>(L.grid, L.waves * WAVE, L.lds, stream, s.obs, s.rows, actions, s.n, s.obs_rows, s.cols, net.prepared, glogp,
+                                                               gent, L.nw, g.workspace, s.index, s.n_src);
+  }); });
+  return pmlp_grad_reduce(rc, g, L.nw, s.cols, net.h1, stream);
 }
 // the critic: values of n positions (fit != null: with the squared-error epilogue)
 extern "C" int bbx_launch_pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
-  if (n <= 0) return 0;
-  const int waves = 4, nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const size_t ml = pmlp_lds_bytes(waves, obs_rows);
-  const bool epi = fit != nullptr;
+  if (s.n <= 0) return 0;
+  const int waves = 4;
   const PmlpFit ft = fit ? *fit : PmlpFit{};
-#define BBX_PMLP_VALUE(N, K, I, F) hipLaunchKernelGGL((bbx_pmlp_value_kernel<N, K, I, F>), dim3((n + waves - 1) / waves), dim3(waves * WAVE), ml, stream, obs, rows, \
-                                                       n, obs_rows, cols, wp, pool, values, values64, index, n_src, ft)
-  BBX_PMLP_DISPATCH(BBX_PMLP_VALUE);
-#undef BBX_PMLP_VALUE
-  return (int)hipGetLastError();
+  return bbx_launched(pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_pick_bool(fit != nullptr, [&](auto FIT) {
+      return bbx_launch<bbx_pmlp_value_kernel<NB(), KS(), IDX(), FIT()>>(dim3((s.n + waves - 1) / waves), waves * WAVE, pmlp_lds_bytes(waves, s.obs_rows), stream, s.obs,
+                                                                         s.rows, s.n, s.obs_rows, s.cols, net.prepared, pool, values, values64, s.index, s.n_src, ft);
+    }); }); }));
 }
 // the statistics of a fit call from the tail its forward kernel wrote (n == 0: zeros)
 extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* stats, hipStream_t stream) {
-  hipLaunchKernelGGL(bbx_pmlp_value_stats_kernel, dim3(1), dim3(PMLP_PPO_STAT_THREADS), 0, stream, tail, n, stats);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_pmlp_value_stats_kernel>(dim3(1), PMLP_PPO_STAT_THREADS, 0, stream, tail, n, stats));
 }
 // the critic's weight gradients
 extern "C" int bbx_launch_pmlp_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, hidden = net.h1;
-  const int nb = pmlp_nb_for(hidden), ks = pmlp_ks_for(cols);
-  const bool epi = false;
-  const PmlpGradLaunch L(n, obs_rows, cols, hidden, index, n_src);
-#define BBX_PMLP_VGRAD(N, K, I, E) hipLaunchKernelGGL((bbx_pmlp_value_grad_kernel<N, K, I>), L.grid, dim3(L.waves * WAVE), L.lds, stream, obs, rows, n, obs_rows, cols, \
-                                                       wp, pool, gvalue, L.nw, ws, index, n_src)
-  if (L.nw > 0) BBX_PMLP_DISPATCH(BBX_PMLP_VGRAD);
-#undef BBX_PMLP_VGRAD
-  return pmlp_grad_reduce(g, L.nw, cols, hidden, stream);
+  const PmlpGradLaunch L(s, net.h1);
+  int rc = 0;
+  if (L.nw > 0) rc = pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_launch<bbx_pmlp_value_grad_kernel<NB(), KS(), IDX()>>(L.grid, L.waves * WAVE, L.lds, stream, s.obs, s.rows, s.n, s.obs_rows, s.cols, net.prepared, pool,
+                                                                     gvalue, L.nw, g.workspace, s.index, s.n_src);
+  }); });
+  return pmlp_grad_reduce(rc, g, L.nw, s.cols, net.h1, stream);
 }
-#undef BBX_PMLP_DISPATCH
-#undef BBX_PMLP_DISPATCH_K
-#undef BBX_PMLP_DISPATCH_IE
 
 
 // ------------------------------------------------------------------ host-callable launcher
@@ -596,13 +541,11 @@ extern "C" int bbx_launch_pmlp_value_grad(const PmlpStates& s, const PmlpNet& ne
 extern "C" int bbx_launch_step(const BbxParams* p, BbxKernel kind, int envs_per_block, hipStream_t stream) {
   const int threads = envs_per_block * WAVE;
   const int blocks = (p->B + envs_per_block - 1) / envs_per_block;
-  if (kind == BBX_K_FAST) { const int rc = bbx_launch_fast(p, blocks, threads, envs_per_block, stream); return rc ? rc : (int)hipGetLastError(); }
+  if (kind == BBX_K_FAST) return bbx_launched(bbx_launch_fast(p, blocks, threads, envs_per_block, stream));
   if (kind == BBX_K_WIDE) {
     if (p->L.W != 2 && p->L.W != 4 && p->L.W != 8) return (int)hipErrorInvalidValue;
     return bbx_launch_wide(p, envs_per_block, stream);
   }
   const size_t lds = kind == BBX_K_STAGED ? (size_t)envs_per_block * p->LL.rec_bytes : 0;
-  const int rc = p->L.kind == 1 ? bbx_launch_binom(p, kind, blocks, threads, lds, stream) : bbx_launch_general(p, kind, blocks, threads, lds, stream);
-  if (rc) return rc;
-  return (int)hipGetLastError();
+  return bbx_launched(p->L.kind == 1 ? bbx_launch_binom(p, kind, blocks, threads, lds, stream) : bbx_launch_general(p, kind, blocks, threads, lds, stream));
 }

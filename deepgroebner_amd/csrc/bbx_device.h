@@ -23,8 +23,6 @@
 //  * no inter-workgroup communication at all: environments are independent.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <atomic>
-#include <mutex>
 #include <type_traits>
 #include <stdint.h>
 #include <cstdio>
@@ -34,28 +32,6 @@
 #include "bbx_common.h"
 
 #define WAVE 64
-
-// (host) launch Kern with `lds` bytes of dynamic LDS (launch errors: hipGetLastError): the one place that raises a kernel's
-// dynamic-LDS limit, which more than 64 KB needs.  The call is not free and the attribute belongs to the current device's code
-// object: a high-water mark per device and kernel, published once the call has succeeded, and a call only for more than that.
-template <auto Kern, class... A>
-static int launch_lds(int blocks, int threads, size_t lds, hipStream_t stream, A... args) {
-  void (*const kern)(A...) = Kern;                          // (the arguments have the kernel's parameter types exactly)
-  static std::mutex mu; static std::atomic<size_t> mark[64];
-  int dev = 0; (void)hipGetDevice(&dev);
-  std::atomic<size_t>& m = mark[dev & 63];
-  if (m.load(std::memory_order_acquire) < lds) {
-    std::lock_guard<std::mutex> g(mu);                      // (of two threads the smaller request must not lower the limit behind the larger)
-    if (m.load(std::memory_order_relaxed) < lds) {
-      const hipError_t err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (err != hipSuccess) return (int)err;
-      m.store(lds, std::memory_order_release);
-    }
-  }
-  void* argv[] = {(void*)&args...};
-  (void)hipLaunchKernel((const void*)kern, dim3(blocks), dim3(threads), argv, lds, stream);
-  return 0;
-}
 
 // ------------------------------------------------------------------ wave helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }

@@ -1,5 +1,6 @@
 // Hand-tuned register/LDS-resident kernel of the headline class (bbx_fast.h): launcher.
 #include "bbx_device.h"
+#include "bbx_launch.h"
 #include "bbx_pmlp.h"
 #include "bbx_binom.h"
 #include "bbx_fast.h"
@@ -37,7 +38,7 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
   if (getenv("BBX_PROF") && !p->trace) {          // diagnostic: per-phase cycle sums, printed here and summed for bbx_fast_prof_read()
     if (!d_prof) (void)hipMalloc((void**)&d_prof, (size_t)p->B * 8 * sizeof(unsigned long long));
     f.prof = d_prof;
-    hipLaunchKernelGGL(bbx_fast_prof_kernel, dim3(blocks), dim3(threads), lds, stream, f);
+    bbx_launch<bbx_fast_prof_kernel>(dim3(blocks), threads, lds, stream, f);
     (void)hipStreamSynchronize(stream);
     std::vector<unsigned long long> h((size_t)p->B * 8);
     (void)hipMemcpy(h.data(), d_prof, h.size() * 8, hipMemcpyDeviceToHost);
@@ -64,39 +65,28 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
         static_assert((size_t)BBX_POL2_WAVES * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)128 * 128 + 2 * 128 + 4) * sizeof(float) == 156688,
                       "policy2<128,128>: the workgroup's LDS (the CU holds 163,840 bytes)");
         const size_t rl2 = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)h1 * h2 + 2 * h2 + 4) * sizeof(float);
-#define BBX_FP2(A, C) launch_lds<bbx_fast_policy2_rollout_kernel<A, C>>(blocks, threads, rl2, stream, q)
-        return h1 == 64 && h2 == 64 ? BBX_FP2(64, 64) : h1 == 64 ? BBX_FP2(64, 128) : h2 == 64 ? BBX_FP2(128, 64) : BBX_FP2(128, 128);
-#undef BBX_FP2
+        return bbx_pick<64, 128>(h1, [&](auto H1) { return bbx_pick<64, 128>(h2, [&](auto H2) {
+          return launch_lds<bbx_fast_policy2_rollout_kernel<H1(), H2()>>(blocks, threads, rl2, stream, q); }); });
       }
       const size_t rl = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)(2 * 6 + 2) * 32 * pmlp_nb_for(q.pol.hidden) + 4) * sizeof(float);
-      if (p->ctl) {                                        // per-step calls served by a persistent session
-        if (pmlp_nb_for(q.pol.hidden) == 2) hipLaunchKernelGGL((bbx_fast_policy_session_kernel<2>), dim3(blocks), dim3(threads), rl, stream, q);
-        else hipLaunchKernelGGL((bbx_fast_policy_session_kernel<4>), dim3(blocks), dim3(threads), rl, stream, q);
-        return 0;
-      }
-      if (pmlp_nb_for(q.pol.hidden) == 2) hipLaunchKernelGGL((bbx_fast_policy_rollout_kernel<2>), dim3(blocks), dim3(threads), rl, stream, q);
-      else hipLaunchKernelGGL((bbx_fast_policy_rollout_kernel<4>), dim3(blocks), dim3(threads), rl, stream, q);
-      return 0;
+      const int nb = pmlp_nb_for(q.pol.hidden);
+      if (p->ctl)                                          // per-step calls served by a persistent session
+        return bbx_pick<2, 4>(nb, [&](auto NB) { return bbx_launch<bbx_fast_policy_session_kernel<NB()>>(dim3(blocks), threads, rl, stream, q); });
+      return bbx_pick<2, 4>(nb, [&](auto NB) { return bbx_launch<bbx_fast_policy_rollout_kernel<NB()>>(dim3(blocks), threads, rl, stream, q); });
     }
-    const int nb = pmlp_nb_for(q.pol.hidden), ks = pmlp_ks_for(cols);
     const size_t pl = pmlp_lds_bytes(envs_per_block, f.obs_rows), ll = pl > lds_pol ? pl : lds_pol;
-    if (ks == 3) { if (nb == 2) hipLaunchKernelGGL((bbx_fast_policy_kernel<2, 3>), dim3(blocks), dim3(threads), ll, stream, q);
-                   else hipLaunchKernelGGL((bbx_fast_policy_kernel<4, 3>), dim3(blocks), dim3(threads), ll, stream, q); }
-    else { if (nb == 2) hipLaunchKernelGGL((bbx_fast_policy_kernel<2, 6>), dim3(blocks), dim3(threads), ll, stream, q);
-           else hipLaunchKernelGGL((bbx_fast_policy_kernel<4, 6>), dim3(blocks), dim3(threads), ll, stream, q); }
-    return 0;
+    return bbx_pick<3, 6>(pmlp_ks_for(cols), [&](auto KS) { return bbx_pick<2, 4>(pmlp_nb_for(q.pol.hidden), [&](auto NB) {
+      return bbx_launch<bbx_fast_policy_kernel<NB(), KS()>>(dim3(blocks), threads, ll, stream, q); }); });
   }
-  if (p->value_mode) { hipLaunchKernelGGL(bbx_fast_value_kernel, dim3(blocks), dim3(threads), lds, stream, f); return 0; }   // (lean, untraced: bbx_api.cpp)
+  if (p->value_mode) return bbx_launch<bbx_fast_value_kernel>(dim3(blocks), threads, lds, stream, f);   // (lean, untraced: bbx_api.cpp)
+  // the headline shape: what bbx_fast_headline[_persistent]_kernel is specialised for
+  const bool headline = f.agent == BBX_AGENT_HASH && f.nvars == 3 && f.k == 2 && f.obs && f.obs_every_step && !f.obs_fill && f.auto_reset;
   if (p->ctl) {                                            // the kernel of a persistent session (bbx_api.cpp admits lean, untraced launches only)
-    if (f.agent == BBX_AGENT_HASH && f.nvars == 3 && f.k == 2 && f.obs && f.obs_every_step && !f.obs_fill && f.auto_reset)
-      hipLaunchKernelGGL(bbx_fast_headline_persistent_kernel, dim3(blocks), dim3(threads), lds, stream, f);
-    else hipLaunchKernelGGL(bbx_fast_persistent_kernel, dim3(blocks), dim3(threads), lds, stream, f);
-    return 0;
+    if (headline) return bbx_launch<bbx_fast_headline_persistent_kernel>(dim3(blocks), threads, lds, stream, f);
+    return bbx_launch<bbx_fast_persistent_kernel>(dim3(blocks), threads, lds, stream, f);
   }
-  if (p->trace) hipLaunchKernelGGL((bbx_fast_kernel<true, true>), dim3(blocks), dim3(threads), lds, stream, f);
-  else if (p->accounting) hipLaunchKernelGGL((bbx_fast_kernel<false, true>), dim3(blocks), dim3(threads), lds, stream, f);
-  else if (f.agent == BBX_AGENT_HASH && f.nvars == 3 && f.k == 2 && f.obs && f.obs_every_step && !f.obs_fill && f.auto_reset)
-    hipLaunchKernelGGL(bbx_fast_headline_kernel, dim3(blocks), dim3(threads), lds, stream, f);
-  else hipLaunchKernelGGL((bbx_fast_kernel<false, false>), dim3(blocks), dim3(threads), lds, stream, f);
-  return 0;
+  if (p->trace) return bbx_launch<bbx_fast_kernel<true, true>>(dim3(blocks), threads, lds, stream, f);
+  if (p->accounting) return bbx_launch<bbx_fast_kernel<false, true>>(dim3(blocks), threads, lds, stream, f);
+  if (headline) return bbx_launch<bbx_fast_headline_kernel>(dim3(blocks), threads, lds, stream, f);
+  return bbx_launch<bbx_fast_kernel<false, false>>(dim3(blocks), threads, lds, stream, f);
 }

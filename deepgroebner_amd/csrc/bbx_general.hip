@@ -2,6 +2,7 @@
 // (non-binomial random ideals, 8-variable fixed ideals, big batches of fixed ideals).  One wavefront per environment.
 // Reference semantics: buchberger.cpp:18-99, 299-329, 354-408; polynomials.cpp:41-202.
 #include "bbx_device.h"
+#include "bbx_launch.h"
 
 // ------------------------------------------------------------------ the step kernel
 template <int W, bool STAGED, bool TRACE, bool PROF = false>
@@ -235,9 +236,9 @@ __global__ __launch_bounds__(256) void bbx_step_prof_kernel(BbxParams p, unsigne
 template <int W>
 static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
   const bool trace = p->trace != nullptr;
-  if (kind == BBX_K_AUX) { hipLaunchKernelGGL(bbx_aux_kernel<W>, dim3(blocks), dim3(threads), lds, stream, *p); return 0; }
+  if (kind == BBX_K_AUX) return bbx_launch<bbx_aux_kernel<W>>(dim3(blocks), threads, lds, stream, *p);
   if (kind == BBX_K_STAGED)
-    return trace ? launch_lds<bbx_step_kernel<W, true, true>>(blocks, threads, lds, stream, *p) : launch_lds<bbx_step_kernel<W, true, false>>(blocks, threads, lds, stream, *p);
+    return bbx_pick_bool(trace, [&](auto TRACE) { return launch_lds<bbx_step_kernel<W, true, TRACE()>>(blocks, threads, lds, stream, *p); });
 #ifdef BBX_PROF_BUILD   // diagnostic build only (-DBBX_PROF_BUILD): per-phase s_memtime sums, never in the product library
   if (!trace && getenv("BBX_PROF")) {
     static unsigned long long* d_prof = nullptr;
@@ -257,9 +258,8 @@ static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int 
   }
 #endif
   lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();          // merge-path tile scratch, one per wave
-  return trace ? launch_lds<bbx_step_kernel<W, false, true>>(blocks, threads, lds, stream, *p) : launch_lds<bbx_step_kernel<W, false, false>>(blocks, threads, lds, stream, *p);
+  return bbx_pick_bool(trace, [&](auto TRACE) { return launch_lds<bbx_step_kernel<W, false, TRACE()>>(blocks, threads, lds, stream, *p); });
 }
 extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
-  return p->L.W == 2 ? launch_general_w<2>(p, kind, blocks, threads, lds, stream)
-       : p->L.W == 4 ? launch_general_w<4>(p, kind, blocks, threads, lds, stream) : launch_general_w<8>(p, kind, blocks, threads, lds, stream);
+  return bbx_pick<2, 4, 8>((int)p->L.W, [&](auto W) { return launch_general_w<W()>(p, kind, blocks, threads, lds, stream); });
 }

@@ -56,6 +56,8 @@ void pool_synced(bool on);                          // the calling thread has sy
 struct DeviceInfo { int cus, max_lds; };
 hipError_t device_info(int device, DeviceInfo* out);
 }  // namespace bbx_host
+// not part of include/bbx.h: bbx_alg.cpp asks a batch (bbx_api_state.cpp) to settle and say where its records live
+extern "C" int bbx_internal_records(bbx_batch* b, const char** recs, BbxLayout* L, int* device, int* W, int* batch);
 #ifndef BBX_NO_POOL_MACROS
 #define hipMalloc(p, n) bbx_host::pool_malloc((void**)(p), (n))
 #define hipFree(p) bbx_host::pool_free((void*)(p))

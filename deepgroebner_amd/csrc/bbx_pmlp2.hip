@@ -26,6 +26,7 @@
 // distribution of the environments: sorting them by tile count (even loads per wave) and handing them out through a ticket
 // counter (dynamic) were both built; the first changed nothing, the second was slower (same-address atomics from eight XCDs).
 #include "bbx_device.h"
+#include "bbx_launch.h"
 #include "bbx_pmlp.h"
 #include "bbx_pmlp2_grad.h"
 #include "bbx_pmlp2_value.h"
@@ -181,14 +182,13 @@ __global__ __launch_bounds__(NWAVES * WAVE, 16 / NWAVES) void bbx_pmlp2_act_kern
 extern "C" int bbx_launch_pmlp2_prepare(const float* w1, const float* b1, const float* wm, const float* bm, const float* w2, const float* b2,
                                         const float* wd, const float* bd, int cols, int h1, int hm, int h2, float* out, hipStream_t stream) {
   const auto [hp1, hpm, hp2] = pmlp2_pads(h1, hm, h2);
-  hipLaunchKernelGGL(bbx_pmlp2_prepare_kernel, dim3(64), dim3(256), 0, stream, w1, b1, wm, bm, w2, b2, wd, bd, cols, h1, hm, h2, hp1, hpm, hp2, out);
-  return (int)hipGetLastError();
+  return bbx_launched(bbx_launch<bbx_pmlp2_prepare_kernel>(dim3(64), 256, 0, stream, w1, b1, wm, bm, w2, b2, wd, bd, cols, h1, hm, h2, hp1, hpm, hp2, out));
 }
 
 extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int B, int obs_rows, int cols, const float* wp, int h1, int hm, int h2,
                                     const float* u, int32_t* actions, float* logprobs, int greedy, int cus, int max_lds, hipStream_t stream) {
-  const auto [hp1, hpm, hp2] = pmlp2_pads(h1, hm, h2);
-  const int ks = pmlp2_ks_for(cols);
+  const Pmlp2Pads pads = pmlp2_pads(h1, hm, h2);
+  const int hp1 = pads.hp1, hpm = pads.hpm, hp2 = pads.hp2, ks = pmlp2_ks_for(cols);
   // 64 KB of second-layer weights: two workgroups of 8 waves per CU; with a middle layer of that size (128 KB): one workgroup
   // of 16 waves — or of 8 or 4 where tall observation blocks (4 bytes of logits per row and wave) leave less room
   int waves = (hpm == 128) ? 16 : PMLP2_WAVES;
@@ -204,27 +204,23 @@ extern "C" int bbx_launch_pmlp2_act(const int32_t* obs, const int32_t* rows, int
   const int max_blocks = (hpm == 128 ? 1 : 2) * (cus > 0 ? cus : 256);
   int blocks = (B + waves - 1) / waves;
   blocks = blocks < max_blocks ? blocks : max_blocks;
-  int rc = 0;
-#define BBX_P2(N1, NM, N2, K, NW) rc = launch_lds<bbx_pmlp2_act_kernel<N1, NM, N2, K, NW>>(blocks, NW * WAVE, ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions, logprobs, lgcap, greedy)
-#define BBX_P2_K(N1, NM, N2, NW) do { if (ks == 3) BBX_P2(N1, NM, N2, 3, NW); else if (ks == 8) BBX_P2(N1, NM, N2, 8, NW); else BBX_P2(N1, NM, N2, 16, NW); } while (0)
-  if (hpm == 128 && waves == 16) BBX_P2_K(128, 128, 128, 16);
-  else if (hpm == 128 && waves == 8) BBX_P2_K(128, 128, 128, 8);
-  else if (hpm == 128) BBX_P2_K(128, 128, 128, 4);
-  else if (hpm == 64) BBX_P2_K(64, 64, 64, 8);
-  else if (hp1 == 64 && hp2 == 64) BBX_P2_K(64, 0, 64, 8); else if (hp1 == 64) BBX_P2_K(64, 0, 128, 8);
-  else if (hp2 == 64) BBX_P2_K(128, 0, 64, 8); else BBX_P2_K(128, 0, 128, 8);
-#undef BBX_P2_K
-#undef BBX_P2
-  return rc ? rc : (int)hipGetLastError();
+  // built: a middle layer of 128 with 16, 8 or 4 waves, one of 64 and no middle layer with 8
+  return bbx_launched(bbx_pick<128, 64, 0>(hpm, [&](auto HM) { return bbx_pick<16, 8, 4>(waves, [&](auto NW) { return bbx_pick<64, 128>(hp1, [&](auto H1) {
+    return bbx_pick<64, 128>(hp2, [&](auto H2) { return bbx_pick<3, 8, 16>(ks, [&](auto KS) {
+      if constexpr ((HM() != 0 && (H1() != HM() || H2() != HM())) || (HM() != 128 && NW() != 8)) return (int)hipErrorInvalidValue;
+      else return launch_lds<bbx_pmlp2_act_kernel<H1(), HM(), H2(), KS(), NW()>>(blocks, NW() * WAVE, ml, stream, obs, rows, B, obs_rows, cols, wp, u, actions,
+                                                                                 logprobs, lgcap, greedy);
+    }); }); }); }); }));
 }
 
 // log-probability / entropy of recorded actions and the weight gradients for two hidden layers (bbx_pmlp2_grad.h), and the critic
-// over the same weights (bbx_pmlp2_value.h);
-// BBX_P2G_SHAPES(M): M(HP1, HP2, KS) of the shape.  index != null: the indexed instantiations (position k is about recorded
-// state index[k] of n_src)
-#define BBX_P2G_K(M, N1, N2) do { if (ks == 3) M(N1, N2, 3); else if (ks == 8) M(N1, N2, 8); else M(N1, N2, 16); } while (0)
-#define BBX_P2G_SHAPES(M) do { if (hp1 == 64 && hp2 == 64) BBX_P2G_K(M, 64, 64); else if (hp1 == 64) BBX_P2G_K(M, 64, 128); \
-                               else if (hp2 == 64) BBX_P2G_K(M, 128, 64); else BBX_P2G_K(M, 128, 128); } while (0)
+// over the same weights (bbx_pmlp2_value.h).  pmlp2_pick_shape: f(IDX, HP1, HP2, KS) of s.index (non-null: the indexed instantiations,
+// position k is about recorded state index[k] of n_src), of the network's padded layers and of the columns' k-steps
+template <class F>
+static int pmlp2_pick_shape(const PmlpStates& s, const PmlpNet& net, F&& f) {
+  return bbx_pick_bool(s.index != nullptr, [&](auto IDX) { return bbx_pick<64, 128>(pmlp2_hp_for(net.h1), [&](auto H1) {
+    return bbx_pick<64, 128>(pmlp2_hp_for(net.h2), [&](auto H2) { return bbx_pick<3, 8, 16>(pmlp2_ks_for(s.cols), [&](auto KS) { return f(IDX, H1, H2, KS); }); }); }); });
+}
 // how the forward kernels of the policy (bbx_pmlp2_logprob_kernel) and the critic (bbx_pmlp2_value_kernel) are launched: 8 waves
 // beside the staged weights, fewer where tall observation blocks (4 bytes of logits per row and wave) leave less room; two
 // workgroups per CU at the most, striding over the positions
@@ -240,112 +236,53 @@ struct Pmlp2ForwardLaunch {
   }
 };
 // (hipErrorInvalidValue: the device has less LDS per workgroup than the shape needs)
-// (the launchers take the records of bbx_pmlp_shape.h and name the fields as the kernels name their parameters)
 extern "C" int bbx_launch_pmlp2_logprob(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, float* logprobs, float* entropy, const PmlpLoss* loss,
                                         int cus, int max_lds, hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
-  if (n <= 0) return 0;
+  if (s.n <= 0) return 0;
   const PmlpLoss ls = loss ? *loss : PmlpLoss{};
-  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
-  const Pmlp2ForwardLaunch F(n, obs_rows, hp1, hp2, cus, max_lds);
+  const Pmlp2ForwardLaunch F(s.n, s.obs_rows, pmlp2_hp_for(net.h1), pmlp2_hp_for(net.h2), cus, max_lds);
   if (F.ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  const int blocks = F.blocks, waves = F.waves, lgcap = F.lgcap;
-  const size_t ml = F.ml;
-  int rc = 0;
-#define BBX_P2_LOGPROB_I(N1, N2, K, I, L) rc = launch_lds<bbx_pmlp2_logprob_kernel<N1, N2, K, I, L>>(blocks, waves * WAVE, ml, stream, obs, rows, actions, n, obs_rows, \
-                                                                                                    cols, wp, logprobs, entropy, lgcap, index, n_src, ls)
-#define BBX_P2_LOGPROB(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false, false)
-#define BBX_P2_LOGPROB_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true, false)
-#define BBX_P2_LOSS(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, false, true)
-#define BBX_P2_LOSS_AT(N1, N2, K) BBX_P2_LOGPROB_I(N1, N2, K, true, true)
-  if (loss) { if (index) BBX_P2G_SHAPES(BBX_P2_LOSS_AT); else BBX_P2G_SHAPES(BBX_P2_LOSS); }
-  else if (index) BBX_P2G_SHAPES(BBX_P2_LOGPROB_AT); else BBX_P2G_SHAPES(BBX_P2_LOGPROB);
-#undef BBX_P2_LOSS_AT
-#undef BBX_P2_LOSS
-#undef BBX_P2_LOGPROB_AT
-#undef BBX_P2_LOGPROB
-#undef BBX_P2_LOGPROB_I
-  return rc ? rc : (int)hipGetLastError();
+  return bbx_launched(bbx_pick_bool(loss != nullptr, [&](auto LOSS) { return pmlp2_pick_shape(s, net, [&](auto IDX, auto H1, auto H2, auto KS) {
+    return launch_lds<bbx_pmlp2_logprob_kernel<H1(), H2(), KS(), IDX(), LOSS()>>(F.blocks, F.waves * WAVE, F.ml, stream, s.obs, s.rows, actions, s.n, s.obs_rows,
+                                                                                 s.cols, net.prepared, logprobs, entropy, F.lgcap, s.index, s.n_src, ls);
+  }); }));
 }
-// the second kernel of the policy's and the critic's gradients, unless launching the first (rc) has failed: the `groups` slots of
-// every output added in order
-static int pmlp2_grad_reduce(int rc, const PmlpGrads& g, int groups, int cols, int h1, int h2, hipStream_t stream) {
+// the weight gradients of the policy (Pmlp2PolicyHead) and the critic (Pmlp2ValueHead): one partition, one workspace, and the
+// second kernel unless launching the first has failed: the `groups` slots of every output added in order
+template <class Head>
+static int pmlp2_launch_grad(const PmlpStates& s, const PmlpNet& net, Head head, const PmlpGrads& g, int max_lds, hipStream_t stream) {
+  const int hp1 = pmlp2_hp_for(net.h1), hp2 = pmlp2_hp_for(net.h2);
+  const int groups = s.n > 0 ? pmlp2_grad_groups(s.n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
+  const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, s.obs_rows, Head::exact_a1);
+  if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  int rc = 0;
+  if (groups > 0) rc = pmlp2_pick_shape(s, net, [&](auto IDX, auto H1, auto H2, auto KS) {
+    return launch_lds<bbx_pmlp2_grad_kernel<H1(), H2(), KS(), IDX(), Head>>(groups, threads, ml, stream, s.obs, s.rows, s.n, s.obs_rows, s.cols, net.prepared, head,
+                                                                            groups, g.workspace, s.index, s.n_src);
+  });
   if (rc) return rc;
   if ((rc = (int)hipGetLastError())) return rc;
-  const int total = cols * h1 + h1 + h1 * h2 + 2 * h2 + 1;
-  hipLaunchKernelGGL(bbx_pmlp2_grad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, stream, g.workspace, groups, cols, h1, h2, g.gw1, g.gb1, g.gw2,
-                     g.gb2, g.gw3, g.gb3);
-  return (int)hipGetLastError();
+  const int total = s.cols * net.h1 + net.h1 + net.h1 * net.h2 + 2 * net.h2 + 1;
+  return bbx_launched(bbx_launch<bbx_pmlp2_grad_reduce_kernel>(dim3((total + 63) / 64), 256, 0, stream, (const float*)g.workspace, groups, s.cols, net.h1, net.h2, g.gw1, g.gb1,
+                                                                g.gw2, g.gb2, g.gw3, g.gb3));
 }
 extern "C" int bbx_launch_pmlp2_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
                                      int max_lds, hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
-  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
-  const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
-  const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows);
-  if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  const Pmlp2PolicyHead head{actions, glogp, gent, 0};
-  int rc = 0;
-#define BBX_P2_GRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I, Pmlp2PolicyHead>>(groups, threads, ml, stream, obs, rows, n, obs_rows, cols, wp, \
-                                                                                                         head, groups, ws, index, n_src)
-#define BBX_P2_GRAD(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, false)
-#define BBX_P2_GRAD_AT(N1, N2, K) BBX_P2_GRAD_I(N1, N2, K, true)
-  if (groups > 0) { if (index) BBX_P2G_SHAPES(BBX_P2_GRAD_AT); else BBX_P2G_SHAPES(BBX_P2_GRAD); }
-#undef BBX_P2_GRAD_AT
-#undef BBX_P2_GRAD
-#undef BBX_P2_GRAD_I
-  return pmlp2_grad_reduce(rc, g, groups, cols, h1, h2, stream);
+  return pmlp2_launch_grad(s, net, Pmlp2PolicyHead{actions, glogp, gent, 0}, g, max_lds, stream);
 }
 // the critic: values of n positions (fit != null: with the squared-error epilogue), in the frame of bbx_launch_pmlp2_logprob
 extern "C" int bbx_launch_pmlp2_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, int cus,
                                       int max_lds, hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
-  if (n <= 0) return 0;
+  if (s.n <= 0) return 0;
   const PmlpFit ft = fit ? *fit : PmlpFit{};
-  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
-  const Pmlp2ForwardLaunch F(n, obs_rows, hp1, hp2, cus, max_lds);
+  const Pmlp2ForwardLaunch F(s.n, s.obs_rows, pmlp2_hp_for(net.h1), pmlp2_hp_for(net.h2), cus, max_lds);
   if (F.ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  const int blocks = F.blocks, waves = F.waves, lgcap = F.lgcap;
-  const size_t ml = F.ml;
-  int rc = 0;
-#define BBX_P2_VALUE_I(N1, N2, K, I, F) rc = launch_lds<bbx_pmlp2_value_kernel<N1, N2, K, I, F>>(blocks, waves * WAVE, ml, stream, obs, rows, n, obs_rows, cols, wp, \
-                                                                                                pool, values, values64, lgcap, index, n_src, ft)
-#define BBX_P2_VALUE(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, false, false)
-#define BBX_P2_VALUE_AT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, true, false)
-#define BBX_P2_FIT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, false, true)
-#define BBX_P2_FIT_AT(N1, N2, K) BBX_P2_VALUE_I(N1, N2, K, true, true)
-  if (fit) { if (index) BBX_P2G_SHAPES(BBX_P2_FIT_AT); else BBX_P2G_SHAPES(BBX_P2_FIT); }
-  else if (index) BBX_P2G_SHAPES(BBX_P2_VALUE_AT); else BBX_P2G_SHAPES(BBX_P2_VALUE);
-#undef BBX_P2_FIT_AT
-#undef BBX_P2_FIT
-#undef BBX_P2_VALUE_AT
-#undef BBX_P2_VALUE
-#undef BBX_P2_VALUE_I
-  return rc ? rc : (int)hipGetLastError();
+  return bbx_launched(bbx_pick_bool(fit != nullptr, [&](auto FIT) { return pmlp2_pick_shape(s, net, [&](auto IDX, auto H1, auto H2, auto KS) {
+    return launch_lds<bbx_pmlp2_value_kernel<H1(), H2(), KS(), IDX(), FIT()>>(F.blocks, F.waves * WAVE, F.ml, stream, s.obs, s.rows, s.n, s.obs_rows, s.cols,
+                                                                               net.prepared, pool, values, values64, F.lgcap, s.index, s.n_src, ft);
+  }); }));
 }
-// the critic's weight gradients: the policy's partition, workspace and second kernel
 extern "C" int bbx_launch_pmlp2_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, int max_lds,
                                            hipStream_t stream) {
-  const int32_t *obs = s.obs, *rows = s.rows, *index = s.index; const float* wp = net.prepared; float* ws = g.workspace;
-  const int n = s.n, n_src = s.n_src, obs_rows = s.obs_rows, cols = s.cols, h1 = net.h1, h2 = net.h2;
-  const int hp1 = pmlp2_hp_for(h1), hp2 = pmlp2_hp_for(h2), ks = pmlp2_ks_for(cols);
-  const int groups = n > 0 ? pmlp2_grad_groups(n) : 0, threads = pmlp2_grad_waves(hp1, hp2) * WAVE;
-  const size_t ml = pmlp2_grad_lds_bytes(hp1, hp2, obs_rows, Pmlp2ValueHead::exact_a1);
-  if (ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
-  const Pmlp2ValueHead head{gvalue, pool};
-  int rc = 0;
-#define BBX_P2_VGRAD_I(N1, N2, K, I) rc = launch_lds<bbx_pmlp2_grad_kernel<N1, N2, K, I, Pmlp2ValueHead>>(groups, threads, ml, stream, obs, rows, n, obs_rows, cols, wp, \
-                                                                                                         head, groups, ws, index, n_src)
-#define BBX_P2_VGRAD(N1, N2, K) BBX_P2_VGRAD_I(N1, N2, K, false)
-#define BBX_P2_VGRAD_AT(N1, N2, K) BBX_P2_VGRAD_I(N1, N2, K, true)
-  if (groups > 0) { if (index) BBX_P2G_SHAPES(BBX_P2_VGRAD_AT); else BBX_P2G_SHAPES(BBX_P2_VGRAD); }
-#undef BBX_P2_VGRAD_AT
-#undef BBX_P2_VGRAD
-#undef BBX_P2_VGRAD_I
-  return pmlp2_grad_reduce(rc, g, groups, cols, h1, h2, stream);
+  return pmlp2_launch_grad(s, net, Pmlp2ValueHead{gvalue, pool}, g, max_lds, stream);
 }
-#undef BBX_P2G_SHAPES
-#undef BBX_P2G_K

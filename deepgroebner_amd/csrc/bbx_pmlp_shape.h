@@ -1,6 +1,7 @@
 // Shapes of the PMLP policy kernels, stated once: the prepared-weight geometry, and which (columns, hidden units) the step kernels
 // have a policy built in for.  Plain C++: the host API (bbx_api_policy.cpp) admits a call by the functions the launchers
-// (bbx_fast.hip, bbx_binom.hip, bbx_aux.hip, bbx_pmlp2.hip) dispatch behind and the kernels (bbx_pmlp.h) are sized with.
+// (bbx_fast.hip, bbx_binom.hip, bbx_aux.hip, bbx_pmlp2.hip; declared in bbx_launch.h) pick their kernel by (bbx_pick) and the
+// kernels (bbx_pmlp.h) are sized with.
 #pragma once
 #include "bbx_common.h"
 
@@ -109,8 +110,8 @@ BBX_HD constexpr int pmlp_fit_workspace_floats(int n, int grad_floats) {   // -1
 }
 
 // ---- what a training call is about (bbx_pmlp[2]_{logprob, grad, ppo_grad, value, value_grad, value_fit}[_at] of include/bbx.h):
-// host-side records, filled by the entry points (bbx_api_policy.cpp) and taken by the training launchers (bbx_aux.hip,
-// bbx_pmlp2.hip) — a field has a name where a place in a list of eight float* had none.  What belongs to one head stays an
+// host-side records, filled by the entry points (bbx_api_policy.cpp) and taken by the training launchers (bbx_launch.h;
+// bbx_aux.hip, bbx_pmlp2.hip) — a field has a name where a place in a list of eight float* had none.  What belongs to one head stays an
 // argument: actions, glogp, gent (policy); pool, gvalue (critic); PmlpLoss, PmlpFit
 struct PmlpStates {                                // the recorded states
   const int32_t* obs; const int32_t* rows;         // [n_src] blocks of obs_rows x cols, and their row counts

@@ -1,5 +1,6 @@
 // Wide class (one workgroup per environment, bbx_wide.h): launcher.  nw = waves per environment.
 #include "bbx_device.h"
+#include "bbx_launch.h"
 #include "bbx_wide.h"
 
 extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
@@ -31,22 +32,23 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
       q.wide_hc = (int)((budget - fixed) / 20) & ~63;       // a term in LDS: 8-byte sort key + u16 coefficient, two buffers
       while (wide_lds_bytes(W_, q.wide_hc, q.wide_fc, q.wide_rc, q.wide_sc) > budget) q.wide_hc -= 64;
     }
-    p = &q;
     const size_t wl = wide_lds_bytes(W_, q.wide_hc, q.wide_fc, q.wide_rc, q.wide_sc);
-    const bool tr = p->trace != nullptr;
-#define GO(...) launch_lds<__VA_ARGS__>(p->B, nw * WAVE, wl, stream, q)
+    const bool tr = q.trace != nullptr;
+    const int threads = nw * WAVE;
     int rc;
-    if (W_ == 8) rc = tr ? GO(bbx_wide_kernel<8, true, false>) : GO(bbx_wide_kernel<8, false, false>);   // one variant: tier 3 throughout
-    else if (!tr && one_per_cu) {
-      if (W_ == 2) rc = lazy ? GO(bbx_wide_kernel_1cu<2, true, false>) : acct ? GO(bbx_wide_kernel_1cu<2, false, true>) : GO(bbx_wide_kernel_1cu<2, false, false>);
-      else rc = lazy ? GO(bbx_wide_kernel_1cu<4, true, false>) : acct ? GO(bbx_wide_kernel_1cu<4, false, true>) : GO(bbx_wide_kernel_1cu<4, false, false>);
-    } else if (!tr && !lazy && !acct) rc = W_ == 2 ? GO(bbx_wide_eager_kernel<2>) : GO(bbx_wide_eager_kernel<4>);
-    else if (W_ == 2) rc = tr ? (lazy ? GO(bbx_wide_kernel<2, true, true>) : GO(bbx_wide_kernel<2, true, false>))
-                              : (lazy ? GO(bbx_wide_kernel<2, false, true>) : GO(bbx_wide_kernel<2, false, false>));
-    else rc = tr ? (lazy ? GO(bbx_wide_kernel<4, true, true>) : GO(bbx_wide_kernel<4, true, false>))
-                 : (lazy ? GO(bbx_wide_kernel<4, false, true>) : GO(bbx_wide_kernel<4, false, false>));
-#undef GO
-    return rc ? rc : (int)hipGetLastError();
+    if (W_ == 8)                                           // one variant: tier 3 throughout
+      rc = bbx_pick_bool(tr, [&](auto TR) { return launch_lds<bbx_wide_kernel<8, TR(), false>>(q.B, threads, wl, stream, q); });
+    else if (!tr && one_per_cu)                            // lazy, or eager with or without accounting (lazy never counts)
+      rc = bbx_pick<2, 4>(W_, [&](auto W) { return bbx_pick_bool(lazy, [&](auto LAZY) { return bbx_pick_bool(acct, [&](auto ACCT) {
+        if constexpr (LAZY() && ACCT()) return (int)hipErrorInvalidValue;
+        else return launch_lds<bbx_wide_kernel_1cu<W(), LAZY(), ACCT()>>(q.B, threads, wl, stream, q);
+      }); }); });
+    else if (!tr && !lazy && !acct)
+      rc = bbx_pick<2, 4>(W_, [&](auto W) { return launch_lds<bbx_wide_eager_kernel<W()>>(q.B, threads, wl, stream, q); });
+    else
+      rc = bbx_pick<2, 4>(W_, [&](auto W) { return bbx_pick_bool(tr, [&](auto TR) { return bbx_pick_bool(lazy, [&](auto LAZY) {
+        return launch_lds<bbx_wide_kernel<W(), TR(), LAZY()>>(q.B, threads, wl, stream, q); }); }); });
+    return bbx_launched(rc);
 }
 #ifdef BBX_PROF_BUILD
 extern "C" int bbx_wide_prof_read(unsigned long long* out, int reset) {   // diagnostic build only
