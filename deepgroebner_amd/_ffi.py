@@ -151,6 +151,8 @@ SIGNATURES = {
     "bbx_pmlp2_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp3_act_greedy": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bbx_policy_greedy": (C.c_int, [_vp, C.c_int]),
+    "bbx_episode_limit": (C.c_int, [_vp, C.c_int]),
+    "bbx_episode_counts": (C.c_int, [_vp, _vp, _vp]),
     "bbx_episodes_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_persistent": (C.c_int, [_vp, C.c_int]),
     "bbx_join": (C.c_int, [_vp, _vp]),

@@ -34,7 +34,7 @@ class VecLeadMonomialsEnv:
     """
 
     def __init__(self, ideal_dist="3-20-10-weighted", batch=1, elimination="gebauermoeller", rewards="additions",
-                 sort_input=False, sort_reducers=True, k=1, device=0, caps=None, mimic="cpp"):
+                 sort_input=False, sort_reducers=True, k=1, device=0, caps=None, mimic="cpp", max_episode_length=None):
         L = _ffi.lib()
         self._h = C.c_void_p()
         self.batch, self.k = int(batch), int(k)
@@ -78,6 +78,9 @@ class VecLeadMonomialsEnv:
         self.rows = np.zeros(self.batch, dtype=np.int32)
         self._rewards = np.zeros(self.batch, dtype=np.float64)
         self._dones = np.zeros(self.batch, dtype=np.uint8)
+        self._episode_limit = None
+        if max_episode_length is not None:
+            self.episode_limit(max_episode_length)
 
     @classmethod
     def _from_handle(cls, h, src):
@@ -86,6 +89,7 @@ class VecLeadMonomialsEnv:
         self.batch, self.k, self.cols, self.nvars = src.batch, src.k, src.cols, src.nvars
         self.rows = src.rows.copy()
         self._policy_greedy = getattr(src, "_policy_greedy", False)   # (bbx_copy carries the configuration, this switch included)
+        self._episode_limit = getattr(src, "_episode_limit", None)    # (... and the episode step limit)
         self._rewards = np.zeros(self.batch, dtype=np.float64)
         self._dones = np.zeros(self.batch, dtype=np.uint8)
         return self
@@ -175,7 +179,12 @@ class VecLeadMonomialsEnv:
         """auto_reset=True: finished environments start their next episode inside the same call (VecEnv style).
         Returns (list of per-environment int32 [rows_e, cols] matrices, rewards, dones, infos)."""
         flat, off = self._step_obs(actions, auto_reset)
-        return self._as_list(flat, off), self._rewards.copy(), self._dones.astype(bool), [{} for _ in range(self.batch)]
+        dones = self._dones.astype(bool)
+        infos = [{} for _ in range(self.batch)]
+        if self._episode_limit and not auto_reset:           # a cut episode: done with rows left (episode_limit)
+            for e in np.flatnonzero(dones & (self.rows > 0)):
+                infos[e]["truncated"] = True
+        return self._as_list(flat, off), self._rewards.copy(), dones, infos
 
     def step_ragged(self, actions, auto_reset=False):
         """step() for vectorised consumers: (flat int32 [sum rows, cols], offsets int32 [batch + 1], rewards, dones);
@@ -387,6 +396,23 @@ class VecLeadMonomialsEnv:
         self._policy_greedy = bool(enable)
         return before
 
+    def episode_limit(self, n):
+        """The episode step limit of this handle (bbx_episode_limit; the reference's max_episode_length): an episode that has
+        taken n steps and still has pairs is cut — its step reports done, under auto-reset the next episode begins, and
+        episode_counts() counts it as an episode and as a truncation.  None or 0: off.  The value calls ignore it.  Returns
+        the previous value (None: off)."""
+        before = getattr(self, "_episode_limit", None)
+        n = 0 if n is None else int(n)
+        _ffi.check(_ffi.lib().bbx_episode_limit(self._h, n))
+        self._episode_limit = n if n else None
+        return before
+
+    def episode_counts(self):
+        """(episodes, truncations): int64 [batch] each — episodes ended so far, and how many of them the limit cut."""
+        ep, tr = np.zeros(self.batch, dtype=np.int64), np.zeros(self.batch, dtype=np.int64)
+        _ffi.check(_ffi.lib().bbx_episode_counts(self._h, _ffi.ptr(ep), _ffi.ptr(tr)))
+        return ep, tr
+
     def prefetch(self):
         """Generate and upload ideals until every environment's ring is full."""
         _ffi.check(_ffi.lib().bbx_prefetch(self._h))
@@ -429,7 +455,7 @@ class CLeadMonomialsEnv:
     _mimic = "cpp"
 
     def __init__(self, ideal_dist="3-20-10-weighted", elimination="gebauermoeller", rewards="additions",
-                 sort_input=False, sort_reducers=True, k=1, device=0, caps=None, _vec=None):
+                 sort_input=False, sort_reducers=True, k=1, device=0, caps=None, _vec=None, max_episode_length=None):
         if _vec is not None:
             self._vec = _vec
             return
@@ -439,12 +465,16 @@ class CLeadMonomialsEnv:
         # (no algorithmic-byte counting behind the gym surface — the reference has nothing like it —: the lean kernels, and
         # with them the resident kernel that serves a loop of step() calls through a host mailbox, bbx_api.cpp mbox_step)
         self._vec.accounting(False)
+        if max_episode_length is not None:                   # (an extension: the reference caps episodes in its training loop)
+            self._vec.episode_limit(max_episode_length)
 
     def reset(self):
         return self._vec.reset()[0]
 
     def step(self, action):
         obs, r, d = self._vec._step_one(int(action))  # accepts numpy / python scalars like action.numpy()
+        if d and self._vec._episode_limit and len(obs):      # done with rows left: the episode step limit cut it
+            return obs, r, d, {"truncated": True}
         return obs, r, d, {}
 
     def seed(self, seed=None):

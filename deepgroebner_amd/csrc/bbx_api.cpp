@@ -210,6 +210,7 @@ void fill_params(bbx_batch* b, BbxParams* p) {
   p->gen = b->device_gen ? b->d_gen : nullptr;
   p->wide_hc = b->wide_terms;
   p->ctl_stats = b->d_ctl ? b->d_ctl + 8 : nullptr;
+  p->episode_limit = b->episode_limit;
 }
 
 // The kernels of one launch and the parameters of each, for every class and call shape: an aux launch (nsteps == 0), a
@@ -284,6 +285,7 @@ int enqueue(bbx_batch* b, const BbxParams& p0, bool resume, hipStream_t stream) 
     int lrc = bbx_launch_step(&pl.pass[i], pl.kind[i], pl.waves[i], stream);
     if (lrc) return fail(BBX_E_DEVICE, "kernel launch failed: %s", hipGetErrorString((hipError_t)lrc));
     b->step_kernels++;
+    if (pl.kind[i] == BBX_K_FAST && bbx_fast_keeps_no_count(pl.pass[i])) b->steps_uncounted = true;   // (bbx_episode_limit looks at it)
     if (timed) { HIPCHK(hipEventRecord(e1, stream)); b->ev_open.push_back({e0, e1}); }
   }
   return BBX_OK;
@@ -858,7 +860,7 @@ int bbx_copy(const bbx_batch* s, bbx_batch** out) {
   // kernel timing (bbx_timing), persistent sessions (bbx_persistent) or any session state, the trace buffer, or statistics.
   static_cast<bbx_config&>(*b) = *s;
   b->h_q = s->h_q; b->h_tail = s->h_tail; b->h_head = s->h_head; b->q_dirty = true;
-  b->value_rng = s->value_rng;
+  b->value_rng = s->value_rng; b->steps_uncounted = s->steps_uncounted;
   if (s->d_wide_done) HIPCHK(hipMalloc((void**)&b->d_wide_done, 256));
   if (s->device_gen) {
     b->gen_owner = s->gen_owner; b->d_gen = s->d_gen;      // (immutable: shared)

@@ -133,7 +133,7 @@ void continue_session(bbx_batch* b) {
 bool session_same_call(const BbxParams& a, const BbxParams& c) {
   return a.agent == c.agent && a.auto_reset == c.auto_reset && a.rewards == c.rewards && a.dones == c.dones && a.rows == c.rows &&
          a.obs == c.obs && a.obs_rows == c.obs_rows && a.obs_fill == c.obs_fill && a.obs_every_step == c.obs_every_step &&
-         a.actions == c.actions && a.recs == c.recs;
+         a.actions == c.actions && a.recs == c.recs && a.episode_limit == c.episode_limit;
 }
 
 // ---- launch: what a call becomes -------------------------------------------------------------------------------------
@@ -381,6 +381,13 @@ int bbx_graph_replayed(bbx_batch* b, void* stream) {
   if (int rc = settle(b)) return rc;
   b->flight = b->cap; b->flight.stream = (hipStream_t)stream;
   b->flight.async_chain = 2;                            // (any number of replays)
+  // replays of a headline-shaped launch kept no step count per episode (bbx_episode_limit): with a limit set meanwhile the
+  // episodes under way count from here, behind the replays on their stream; without one the next bbx_episode_limit sees to it
+  if (b->cls == BbxClass::FAST && bbx_headline_shape(b->cap.p)) {
+    if (b->episode_limit > 0)
+      HIPCHK(hipMemset2DAsync(b->d_recs + offsetof(BbxHdr, episode_steps), b->L.rec_bytes, 0, sizeof(int32_t), (size_t)b->B, (hipStream_t)stream));
+    else b->steps_uncounted = true;
+  }
   return BBX_OK;
 }
 

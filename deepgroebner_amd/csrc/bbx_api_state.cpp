@@ -26,6 +26,39 @@ int bbx_stats(bbx_batch* b, int64_t* out8) {
   return BBX_OK;
 }
 
+// The episode step limit of every launch the handle makes from here on (bbx_episode_end, bbx_common.h; BbxParams.episode_limit:
+// by value, a recorded graph keeps the limit it was captured with).  A running session was begun with the other limit: it ends
+// here.  The headline-shaped kernels keep no step count per episode: where one has run since the limit was off, the episodes
+// under way count from here.
+int bbx_episode_limit(bbx_batch* b, int limit) {
+  if (limit < 0) return fail(BBX_E_ARG, "the episode step limit must be >= 0 (0: off), got %d", limit);
+  if (!b) return fail(BBX_E_ARG, "null argument");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  if (b->ps_active) { if (int rc = session_close(b, true, nullptr, false)) return rc; }
+  if (limit > 0 && b->steps_uncounted) {
+    if (int rc = settle(b)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemset2D(b->d_recs + offsetof(BbxHdr, episode_steps), b->L.rec_bytes, 0, sizeof(int32_t), (size_t)b->B));
+    HIPCHK(hipDeviceSynchronize());                       // (the next launch may go to a stream the null stream does not order)
+    b->steps_uncounted = false;
+  }
+  b->episode_limit = limit;
+  return BBX_OK;
+}
+
+int bbx_episode_counts(bbx_batch* b, int64_t* episodes, int64_t* truncations) {
+  if (!b) return fail(BBX_E_ARG, "null argument");
+  HIPCHK(hipSetDevice(b->device)); b->api_epoch++;
+  if (int rc = quiesce(b)) return rc;
+  int rc = read_headers(b);
+  if (rc) return rc;
+  for (int e = 0; e < b->B; e++) {
+    if (episodes) episodes[e] = b->h_hdr[e].episodes;
+    if (truncations) truncations[e] = b->h_hdr[e].truncations;
+  }
+  return BBX_OK;
+}
+
 // (bbx_host.h, for bbx_alg.cpp) where the records of a quiet batch live
 int bbx_internal_records(bbx_batch* b, const char** recs, BbxLayout* L, int* device, int* W, int* batch) {
   if (!b) return fail(BBX_E_ARG, "null argument");

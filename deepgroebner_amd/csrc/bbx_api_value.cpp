@@ -75,6 +75,7 @@ BbxParams clone_params(bbx_batch* b, const ValueClones& c, int nsteps, int agent
   BbxParams p; fill_params(b, &p);
   p.recs = c.recs; p.B = c.n; p.nsteps = nsteps; p.set_budget = 1; p.agent = agent; p.auto_reset = 0;
   p.trace = nullptr; p.accounting = 0; p.lite = nullptr;
+  p.episode_limit = 0;                 // the value of a state is the return of the whole computation (bbx_episode_limit)
   return p;
 }
 

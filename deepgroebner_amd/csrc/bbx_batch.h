@@ -88,6 +88,7 @@ struct bbx_config {
   bool no_growth = false;             // bbx_caps.no_growth: the configured capacities are hard limits (BBX_E_CAPACITY)
   bool accounting = true;             // count algorithmic bytes (bbx_accounting)
   bool policy_greedy = false;         // the policy calls on this handle take the argmax instead of drawing (bbx_policy_greedy)
+  int episode_limit = 0;              // the episode step limit of every launch on this handle (bbx_episode_limit; 0: off)
 };
 
 struct bbx_batch : bbx_config {
@@ -169,6 +170,7 @@ struct bbx_batch : bbx_config {
   int32_t* d_clone_idx = nullptr; int clone_cap = 0;   // bbx_clone_envs: source / destination indices on the device
   std::mt19937_64 value_rng;          // seeds of value("random") / value("sample") rollouts when the caller gives none
   int grow_events = 0;                // times the records were enlarged (bbx_capacities)
+  bool steps_uncounted = false;       // a headline-shaped kernel has run since the limit was last set: BbxHdr.episode_steps is out of date
   long long step_kernels = 0;         // kernels enqueue() has launched for this handle (bbx_kernels_launched: what a call costs in launches)
   bbx_batch() = default;
   bbx_batch(const bbx_batch&) = delete;

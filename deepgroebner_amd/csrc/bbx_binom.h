@@ -439,7 +439,9 @@ template <int W> __host__ __device__ constexpr size_t binom_scratch_bytes(int ob
 // POL2 > 0: a policy with TWO hidden layers (bbx_policy2_rollout_device): POL = the first layer's blocks of 16 units, POL2 = the
 // second's, PKS = pmlp2_ks_for(2 n k); tiles of 16 rows through the stand-alone kernel's code (pmlp2_tile, bbx_pmlp.h), every
 // weight read from memory (the second layer's 64 KB stay in L2: this kernel keeps its LDS for the update's scratch).
-template <int W, bool STAGED, bool TRACE, int POL = 0, int PKS = 6, bool AUX = false, int POL2 = 0>
+// LIM: the instantiation that knows the episode step limit (bbx_episode_end, bbx_common.h), launched when one is set; without it
+// the body is what it was before the limit existed.
+template <int W, bool STAGED, bool TRACE, int POL = 0, int PKS = 6, bool AUX = false, int POL2 = 0, bool LIM = false>
 __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem, const BbxPolicy* pol = nullptr) {
   const BbxParams& p = bbx_kparams();                      // (set-up; the step loop and the write-back behind it take their own)
   (void)p_entry;
@@ -759,7 +761,9 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     last_reward = reward;
     if (p.value_mode) value_accumulate(vret, vdisc, reward, p.gamma);
     total_steps++; total_adds += 1 + nsteps_red; t_agent++; episode_steps++; steps_done++;
-    const bool done = nP == 0;
+    int end = 0;                                                        // LIM: how the step ends its episode
+    if constexpr (LIM) end = uni(bbx_episode_end(nP, episode_steps, p.episode_limit));
+    const bool done = LIM ? end != 0 : nP == 0;
 
     BSTAMP(5);
     if (POL == 0 && p.obs_every_step && p.obs) {
@@ -790,7 +794,9 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
     budget--; rollout_pos++;
     done_last = done ? 1 : 0;
     if (done) {
-      episodes++;
+      if constexpr (LIM) {
+        if (bbx_episode_counted(end, episode_steps, p.episode_limit, p.auto_reset)) { episodes++; if (end == 2) count_truncation((BbxHdr*)(p.recs + (size_t)env * p.L.rec_bytes)); }
+      } else episodes++;
       if (p.auto_reset) need_reset = 1;
       // behind a kernel of a persistent session: the episode that outgrew the register/LDS class is over — the next one
       // starts small, so the environment goes back to the session's next kernel with what it still owes
@@ -828,21 +834,21 @@ __device__ __forceinline__ void binom_body(const BbxParams& p_entry, char* smem,
   }
 }
 
-template <int W, bool STAGED, bool TRACE>
+template <int W, bool STAGED, bool TRACE, bool LIM = false>
 __global__ __launch_bounds__(256, 4) void bbx_binom_kernel(BbxParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  binom_body<W, STAGED, TRACE>(p, smem);
+  binom_body<W, STAGED, TRACE, 0, 6, false, 0, LIM>(p, smem);
 }
-template <int W, int NB, int KS>
+template <int W, int NB, int KS, bool LIM = false>
 __global__ __launch_bounds__(256, 4) void bbx_binom_policy_kernel(BbxParams p, BbxPolicy pol) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  binom_body<W, false, false, NB, KS>(p, smem, &pol);
+  binom_body<W, false, false, NB, KS, false, 0, LIM>(p, smem, &pol);
 }
 // the same with a two-hidden-layer policy (binom_body POL2): H1 / H2 = the layers padded to 64 or 128 units, KS = pmlp2_ks_for(2 n k)
-template <int W, int H1, int H2, int KS>
+template <int W, int H1, int H2, int KS, bool LIM = false>
 __global__ __launch_bounds__(256, 4) void bbx_binom_policy2_kernel(BbxParams p, BbxPolicy pol) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  binom_body<W, false, false, H1 / 16, KS, false, H2 / 16>(p, smem, &pol);
+  binom_body<W, false, false, H1 / 16, KS, false, H2 / 16, LIM>(p, smem, &pol);
 }
 template <int W>
 __global__ __launch_bounds__(256) void bbx_binom_aux_kernel(BbxParams p) {

@@ -75,6 +75,30 @@ static inline BBX_HD bool bbx_pass_has_work(int st, int need_reset, int budget, 
 // The `dones` output: the last step taken ended an episode, or the episode is over and no reset is pending (a finished
 // environment stepped without auto-reset stays done)
 static inline BBX_HD int bbx_done_flag(int done_last, int nP, int need_reset) { return (done_last || (nP == 0 && !need_reset)) ? 1 : 0; }
+// The episode step limit (bbx_episode_limit; 0: off), stated once for every step kernel and the host.  How the step that has
+// just been accounted ends its episode — nP, episode_steps: the state and the episode's step count AFTER it:
+//   1  the pair set is empty: an ordinary end (also when this was the limit-th step)
+//   2  pairs are left and the episode has its `limit` steps: it is CUT
+//   0  the episode goes on
+// Wherever a kernel says `done` (dones, done_last, the trace record, the mailbox publication, need_reset under auto-reset, the
+// hand-back to a session) it means end != 0; the bytes it writes stay 0 / 1.
+static inline BBX_HD int bbx_episode_end(int nP, int episode_steps, int limit) { return nP == 0 ? 1 : ((limit > 0 && episode_steps >= limit) ? 2 : 0); }
+// ... and whether that end moves the counters (BbxHdr.episodes, and BbxHdr.truncations when it is a cut).  Without auto-reset a
+// cut environment is left as it is: further steps are taken and each reports done, but only the limit-th one counted.
+static inline BBX_HD bool bbx_episode_counted(int end, int episode_steps, int limit, int auto_reset) {
+  return end == 1 || (end == 2 && (auto_reset || episode_steps == limit));
+}
+// The fast class (bbx_fast.h) counts no steps of an episode: it keeps t_ep0, the agent step count at which the running episode
+// began (episode_steps = t_agent - t_ep0, formed where it is wanted), and tests one event per step, t_agent == t_lim: the agent
+// step count at which the episode is cut.  t_lim as of agent step count t_agent (kernel entry, behind a reset, behind a cut
+// that no reset follows): the episode's limit-th step, or the very next one where it already has them (a limit lowered under a
+// running episode; an environment stepped on without auto-reset) — t_agent + max(limit - episode_steps, 1).  Limit off: a
+// count t_agent, which only goes up, does not reach.
+static inline BBX_HD int bbx_episode_tlim(int t_ep0, int t_agent, int limit) {
+  if (limit <= 0) return (int)((uint32_t)t_agent - 1u);
+  const int left = limit - (int)((uint32_t)t_agent - (uint32_t)t_ep0);
+  return (int)((uint32_t)t_agent + (uint32_t)(left > 1 ? left : 1));
+}
 
 // The user priority (s_setprio, 0..3) of a wave of the register/LDS-resident step kernels (fast_body, bbx_fast.h): a slot of
 // 2^BBX_PRIO_TICK_SHIFT ticks of the 100 MHz clock every wave reads alike (its low 32 bits: 2^32 is a whole number of cycles of
@@ -142,8 +166,10 @@ struct BbxHdr {             // 128 bytes
   int32_t obs_trunc;        // != 0: during the current rollout an observation had more rows than the caller's block holds
                             // (rows beyond obs_rows were not written); reported by bbx_sync as BBX_E_CAPACITY
   int32_t sess_done;        // persistent sessions (bbx_persistent): steps of the session's total this environment has taken
-  int32_t reserved[3];
+  int32_t truncations;      // episodes cut by the episode step limit (bbx_episode_end == 2), counted like `episodes`
+  int32_t reserved[2];
 };
+static_assert(sizeof(BbxHdr) == 128, "BbxHdr: the record arrays start at byte 128");
 
 struct BbxLayout {
   uint32_t W;               // words per monomial (2 or 4)
@@ -266,7 +292,20 @@ struct BbxParams {
   // environment ends with its slowest environments, and those then run at the speed of a workgroup that has a CU to itself
   int32_t wide_tail, wide_ncu;
   int32_t* wide_done;
+  int32_t episode_limit;    // the episode step limit (bbx_episode_end above; 0: off).  By value: a recorded graph keeps the limit
+                            // it was captured with.  The clone pipelines of the value calls run with 0
 };
+// The launch shape bbx_fast_headline[_persistent]_kernel are specialised for (bbx_fast.hip picks them by this; a session's
+// launches, p.ctl, are lean and untraced by admission).  They know no episode limit and do not keep BbxHdr.episode_steps.
+static inline BBX_HD bool bbx_headline_shape(const BbxParams& p) {
+  return !p.policy && !p.value_mode && (p.ctl || (!p.trace && !p.accounting)) && p.agent == BBX_AGENT_HASH && p.nvars == 3 && p.k == 2 &&
+         p.obs && p.obs_every_step && !p.obs_fill && p.auto_reset && p.episode_limit == 0;
+}
+// ... and every launch of the register/LDS-resident class whose kernel leaves BbxHdr.episode_steps alone: those, and the two-layer
+// policy rollout launched without a limit (bbx_fast.h, NOLIM).  The host notes them (bbx_batch::steps_uncounted)
+static inline BBX_HD bool bbx_fast_keeps_no_count(const BbxParams& p) {
+  return bbx_headline_shape(p) || (p.policy && p.policy->rollout && p.policy->hidden2 > 0 && p.episode_limit == 0);
+}
 
 // The step kernels a launch is made of (bbx_launch_step): HBM-resident, LDS-staged, aux (reset / observation only), the
 // hand-tuned register/LDS-resident kernel (bbx_fast.h), wide (one workgroup per environment, bbx_wide.h)

@@ -1321,14 +1321,24 @@ __device__ __forceinline__ void trace_put(const BbxParams& p, int env, int pos, 
   tr.action = action; tr.nP = nP; tr.nG = nG; tr.done = done ? 1 : 0; tr.reward = reward;
   tr.obs_hash = obs_hash; tr.pairs_hash = pairs_hash; tr.newpoly_hash = newpoly_hash;
 }
-// the bookkeeping of a step that has happened (the state is the one after it; done: its pair set is empty)
-__device__ __forceinline__ void step_account(StepState& s, const BbxParams& p, double reward, int nsteps_red, bool done) {
+// how the step that has happened ends its episode (bbx_episode_end, bbx_common.h; nP: the pair set after it), asked BEFORE
+// step_account: the trace record wants it.  limit: the launch's, or the constant 0 in the instantiations launched without one
+// (bbx_general.hip, LIM), where all of this folds to what the kernels did before the limit existed
+__device__ __forceinline__ int step_end(const StepState& s, int limit, int nP) { return bbx_episode_end(nP, s.episode_steps + 1, limit); }
+// an episode the limit cut, counted where it happens — once per episode at most — straight in the header (one lane; the record
+// is this wave's alone): a counter carried through the step loop would cost every step kernel a register for it
+__device__ __forceinline__ void count_truncation(BbxHdr* h) { if (lane_id() == 0) h->truncations += 1; }
+// the bookkeeping of a step that has happened (the state is the one after it; end: step_end of it; h: the record's header)
+__device__ __forceinline__ void step_account(StepState& s, const BbxParams& p, BbxHdr* h, double reward, int nsteps_red, int end, int limit) {
   s.last_reward = reward;
   if (p.value_mode) value_accumulate(s.vret, s.vdisc, reward, p.gamma);
   s.total_steps++; s.total_adds += 1 + nsteps_red; s.t_agent++; s.episode_steps++; s.steps_done++;
   s.budget--; s.rollout_pos++;
-  s.done_last = done ? 1 : 0;
-  if (done) { s.episodes++; if (p.auto_reset) s.need_reset = 1; }
+  s.done_last = end != 0 ? 1 : 0;
+  if (end != 0) {
+    if (bbx_episode_counted(end, s.episode_steps, limit, p.auto_reset)) { s.episodes++; if (end == 2) count_truncation(h); }
+    if (p.auto_reset) s.need_reset = 1;
+  }
 }
 // Exit (one lane): the header back, then what the caller reads.  rewind_rng: the step in progress did not happen and its draw
 // is taken again.  handoff: the environment continues in the follow-up pass of this launch, which reports in its place —

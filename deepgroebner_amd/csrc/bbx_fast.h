@@ -72,6 +72,8 @@ struct BbxFastParams {
   double gamma; double* values;                       // VAL instantiation (value(), buchberger.cpp:332-351): discount, [B] returns
   unsigned long long* ctl_stats;                      // statistics word: steps taken by closing launches
   int32_t mbox;                                       // host mailbox session (BbxParams::mbox)
+  int32_t episode_limit;                              // BbxParams::episode_limit (in what was padding: the argument block is as large
+                                                      // as it was); the HL kernels never read it — the launcher gives them launches with 0
 };
 
 __device__ __forceinline__ uint32_t f_readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
@@ -220,11 +222,12 @@ __device__ __attribute__((noinline)) int f_select_ordered(const uint32_t* pairs,
 // 16 units, POL2 = the second's; tiles of 16 rows through the stand-alone kernel's code (pmlp2_tile, bbx_pmlp.h), the layers
 // behind the first staged in LDS once per workgroup (the launcher gives the kernel workgroups of BBX_POL2_WAVES waves).
 template <bool TRACE, bool ACCT, bool PROF = false, bool HL = false, int POL = 0, bool PERSIST = false, bool VAL = false, int NBK = (POL > 0 ? FNBK_POL : FNBK_WIDE),
-          int POL2 = 0>
+          int POL2 = 0, bool LIM = true>
 __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, int ext_action = -1) {
   typedef FLay<NBK> LY;
   constexpr int FG = LY::G, FP = LY::P, FLDS_BYTES = LY::BYTES;
   constexpr int FOFF_LM = LY::OFF_LM, FOFF_TM = LY::OFF_TM, FOFF_GI = LY::OFF_GI, FOFF_PR = LY::OFF_PR;
+  constexpr bool NOLIM = HL || !LIM;                       // the episode step limit compiled out: no t_lim, BbxHdr.episode_steps left alone
   constexpr bool OVF = LY::OVF > 0;                        // reducers beyond the register banks (their order in LDS)
   unsigned long long prof_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long prof_last = PROF ? __builtin_amdgcn_s_memtime() : 0;
@@ -379,6 +382,17 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
   // step), and the one this launch began with (the first loop top is no 64th-step boundary the loop has crossed)
   int t_done = vzero + (done_in ? t_agent : t_agent - 1);
   const int t_entry = vzero + t_agent;
+  // The episode step limit (bbx_episode_end, bbx_common.h) in the loop's event terms — nothing counts an episode's steps: t_ep0
+  // is the agent step count at which the running episode began (cold: a vector register; episode_steps = t_agent - t_ep0 where
+  // the counters and the write-back want it), t_lim the count at which the episode is cut (bbx_episode_tlim: formed here,
+  // behind every reset, and behind a cut that no reset follows).  The test behind a step is done | (t_agent == t_lim).
+  // NOLIM (the headline kernels; the two-layer policy rollout launched without a limit, whose rate the extra scalar state
+  // cost 1 %): compiled out — those kernels know no limit and leave BbxHdr.episode_steps alone.
+  int t_ep0 = 0, t_lim = 0;
+  if constexpr (!NOLIM) {
+    t_ep0 = vzero + (t_agent - uni(ghdr->episode_steps));
+    t_lim = uni(bbx_episode_tlim(t_agent - uni(ghdr->episode_steps), t_agent, p.episode_limit));
+  }
   const bool tracing = TRACE && p.trace != nullptr;
   const int n = HL ? 3 : p.nvars, kk = HL ? 2 : p.k;
   const int agent = HL ? BBX_AGENT_HASH : p.agent;
@@ -838,6 +852,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
         f_loads_landed();
         if (!ok) { if (status != BBX_ST_STARVED) { nG = 0; nP = 0; } break; }
         need_reset = 0;
+        if constexpr (!NOLIM) { t_ep0 = vzero + t_agent; t_lim = uni(bbx_episode_tlim(t_agent, t_agent, cq->episode_limit)); }   // a new episode: 0 steps
         if constexpr (POL > 0 && PERSIST) {
           // per-step policy calls served by a session (bbx_policy_step_device): the block and the row count the caller finds when
           // the session ends are those of the NEW episode, as after a launch per step — the step that ended the episode wrote the
@@ -1348,7 +1363,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     last_nred = vzero + nred;
     if (VAL) value_accumulate(vret, vdisc, p.rewards_mode == BBX_REW_ADDITIONS ? (-1.0 - (double)nred) : -1.0, p.gamma);
     adds += 1 + nred; t_agent++;
-    const bool done = nP == 0;
+    const bool done = NOLIM ? nP == 0 : ((nP == 0) | (t_agent == t_lim));   // (the pair set is empty, or the episode step limit cuts it)
 
     if (obs_step) { if (obs32) write_obs32(); else write_obs(true, false); note_rows(); }
     if (TRACE && tracing) {
@@ -1392,7 +1407,16 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
       if (f_cold_params()->mbox) { mb_pending = true; t_event = t_agent; }
     }
     if (TRACE) trace_pos++;
+    if constexpr (NOLIM) {
     if (done) { episodes++; t_done = vzero + t_agent; t_event = t_agent; if (auto_reset) need_reset = 1; }   // (the next loop top: reset, or leave)
+    } else if (done) {
+      // which end it is, and whether it counts (bbx_common.h); a cut that no reset follows is met again at the very next step
+      const int lim = f_cold_params()->episode_limit, esteps = t_agent - uni(t_ep0);
+      const int end = bbx_episode_end(nP, esteps, lim);
+      if (bbx_episode_counted(end, esteps, lim, auto_reset ? 1 : 0)) { episodes++; if (end == 2) count_truncation((BbxHdr*)(f_cold_params()->recs + (size_t)env * f_cold_params()->rec_bytes)); }
+      t_done = vzero + t_agent; t_event = t_agent;
+      if (auto_reset) need_reset = 1; else t_lim = uni(bbx_episode_tlim(uni(t_ep0), t_agent, lim));
+    }
     FSTAMP(5);                                             // 5: observation + bookkeeping
   }
   const FColdParams cz = f_cold_params();
@@ -1440,6 +1464,7 @@ __device__ __forceinline__ void fast_body(const BbxFastParams& p, char* smem, in
     if (!HL) h->std_rng = std_rng;
     if (VAL) { h->vret = vret; h->vdisc = vdisc; if (cz->values) cz->values[env] = vret; }
     h->episodes += episodes; h->zero_reductions += zero_red; h->steps_done = steps_done;
+    if constexpr (!NOLIM) h->episode_steps = t_agent - t_ep0;   // (h->truncations: counted where an episode is cut, count_truncation)
     h->budget = budget; h->rollout_pos = rollout_pos; h->done_last = done_last; h->alg_bytes += bytes_total;
     const int trunc_all = (cz->set_budget ? 0 : h->obs_trunc) | obs_trunc;
     h->obs_trunc = trunc_all;
@@ -1519,10 +1544,11 @@ __global__ __launch_bounds__(256, 4) void bbx_fast_policy_rollout_kernel(BbxFast
 // policy rollout with a two-hidden-layer policy (fast_body POL2): H1 / H2 = the layers padded to 64 or 128 units.  Workgroups
 // of BBX_POL2_WAVES = 16 waves, one per CU (four per SIMD, as the one-layer kernel): one LDS copy of the second layer (64 KB
 // at 128 x 128) serves 16 environments.
-template <int H1, int H2>
+// LIM: launched with an episode step limit set; without one the kernel is what it was before the limit existed
+template <int H1, int H2, bool LIM = false>
 __global__ __launch_bounds__(1024, 4) void bbx_fast_policy2_rollout_kernel(BbxFastPolicyParams q) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  fast_body<false, false, false, false, H1 / 16, false, false, FNBK_POL, H2 / 16>(q.f, smem);
+  fast_body<false, false, false, false, H1 / 16, false, false, FNBK_POL, H2 / 16, LIM>(q.f, smem);
 }
 #ifdef BBX_PROF_BUILD
 // diagnostic build with s_memtime stamps between the phases of a step (never timed, never shipped as a result)

@@ -29,6 +29,7 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
   f.sort_input = p->sort_input;
   f.ctl = p->ctl; f.sess_target = p->sess_target; f.ctl_stats = p->ctl_stats; f.slice_ticks = p->slice_ticks; f.mbox = p->mbox;
   f.gamma = p->gamma; f.values = p->values;
+  f.episode_limit = p->episode_limit;
   // (four workgroups of four waves per CU, one wave per SIMD each: 4 x 4 x 9472 = 151,552 of the CU's 163,840 bytes; a layout that
   // no longer fits would lose the fourth workgroup without a word)
   static_assert(4 * 4 * FLay<FNBK_WIDE>::BYTES == 151552 && 4 * 4 * FLay<FNBK_WIDE>::BYTES <= 163840, "fast class: 16 environments per CU");
@@ -66,7 +67,8 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
                       "policy2<128,128>: the workgroup's LDS (the CU holds 163,840 bytes)");
         const size_t rl2 = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)h1 * h2 + 2 * h2 + 4) * sizeof(float);
         return bbx_pick<64, 128>(h1, [&](auto H1) { return bbx_pick<64, 128>(h2, [&](auto H2) {
-          return launch_lds<bbx_fast_policy2_rollout_kernel<H1(), H2()>>(blocks, threads, rl2, stream, q); }); });
+          return bbx_pick_bool(q.f.episode_limit != 0, [&](auto LIM) {
+            return launch_lds<bbx_fast_policy2_rollout_kernel<H1(), H2(), LIM()>>(blocks, threads, rl2, stream, q); }); }); });
       }
       const size_t rl = (size_t)envs_per_block * (FLay<FNBK_POL>::BYTES + 4 * FLay<FNBK_POL>::P) + ((size_t)(2 * 6 + 2) * 32 * pmlp_nb_for(q.pol.hidden) + 4) * sizeof(float);
       const int nb = pmlp_nb_for(q.pol.hidden);
@@ -80,7 +82,8 @@ extern "C" int bbx_launch_fast(const BbxParams* p, int blocks, int threads, int 
   }
   if (p->value_mode) return bbx_launch<bbx_fast_value_kernel>(dim3(blocks), threads, lds, stream, f);   // (lean, untraced: bbx_api.cpp)
   // the headline shape: what bbx_fast_headline[_persistent]_kernel is specialised for
-  const bool headline = f.agent == BBX_AGENT_HASH && f.nvars == 3 && f.k == 2 && f.obs && f.obs_every_step && !f.obs_fill && f.auto_reset;
+  // (bbx_common.h; with an episode step limit set it is the general lean kernel that runs: the headline kernels know none)
+  const bool headline = bbx_headline_shape(*p);
   if (p->ctl) {                                            // the kernel of a persistent session (bbx_api.cpp admits lean, untraced launches only)
     if (headline) return bbx_launch<bbx_fast_headline_persistent_kernel>(dim3(blocks), threads, lds, stream, f);
     return bbx_launch<bbx_fast_persistent_kernel>(dim3(blocks), threads, lds, stream, f);

@@ -5,7 +5,8 @@
 #include "bbx_launch.h"
 
 // ------------------------------------------------------------------ the step kernel
-template <int W, bool STAGED, bool TRACE, bool PROF = false>
+// LIM: the instantiation that knows the episode step limit, launched when one is set; without it the limit is the constant 0
+template <int W, bool STAGED, bool TRACE, bool PROF = false, bool LIM = false>
 __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsigned long long* prof_out = nullptr) {
   const int lane = lane_id();
   unsigned long long ps[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // diagnostic build: cycles per phase
@@ -184,7 +185,9 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
     sb += 4LL * nP * 2 * p.nvars * p.k;             // the observation matrix of the new state
     s.alg_bytes += sb;
     const double reward = step_reward(p.rewards_mode, nsteps_red);
-    const bool done = nP == 0;
+    const int limit = LIM ? p.episode_limit : 0;
+    const int end = step_end(s, limit, nP);
+    const bool done = end != 0;                   // (the pair set is empty, or the episode step limit cuts it)
 
     // ---- the observation a policy would consume after this step ---------------------------------
     if (p.obs_every_step && p.obs) { wave_obs<W>(e, p, env, nP, true, false); s.obs_trunc |= nP > p.obs_rows ? 1 : 0; }
@@ -195,7 +198,7 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
       uint64_t nh = nG > nG_before ? wave_poly_hash<W>(e, nG - 1) : 0;
       if (lane == 0) trace_put(p, env, s.rollout_pos, action, nP, nG, done, reward, oh, ph, nh);
     }
-    step_account(s, p, reward, nsteps_red, done);
+    step_account(s, p, ghdr, reward, nsteps_red, end, limit);
   }
 
   if (PROF && prof_out && lane == 0) for (int i = 0; i < 10; i++) prof_out[(size_t)env * 10 + i] = ps[i];
@@ -212,10 +215,10 @@ __device__ __forceinline__ void step_body(const BbxParams& p, char* smem, unsign
   if (lane == 0) hdr_store(ghdr, p, env, s, bbx_st_capacity(s.status) || s.status == BBX_ST_SPILL, s.status == BBX_ST_SPILL);
 }
 
-template <int W, bool STAGED, bool TRACE>
+template <int W, bool STAGED, bool TRACE, bool LIM = false>
 __global__ __launch_bounds__(256) void bbx_step_kernel(BbxParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  step_body<W, STAGED, TRACE>(p, smem);
+  step_body<W, STAGED, TRACE, false, LIM>(p, smem);
 }
 // the same body under its own name for launches that only reset / refresh observations (nsteps == 0), so that
 // profiles of bbx_step_kernel contain step launches only
@@ -235,10 +238,10 @@ __global__ __launch_bounds__(256) void bbx_step_prof_kernel(BbxParams p, unsigne
 
 template <int W>
 static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
-  const bool trace = p->trace != nullptr;
+  const bool trace = p->trace != nullptr, lim = p->episode_limit != 0;   // (lim: the LIM instantiations)
   if (kind == BBX_K_AUX) return bbx_launch<bbx_aux_kernel<W>>(dim3(blocks), threads, lds, stream, *p);
   if (kind == BBX_K_STAGED)
-    return bbx_pick_bool(trace, [&](auto TRACE) { return launch_lds<bbx_step_kernel<W, true, TRACE()>>(blocks, threads, lds, stream, *p); });
+    return bbx_pick_bool(trace, [&](auto TRACE) { return bbx_pick_bool(lim, [&](auto LIM) { return launch_lds<bbx_step_kernel<W, true, TRACE(), LIM()>>(blocks, threads, lds, stream, *p); }); });
 #ifdef BBX_PROF_BUILD   // diagnostic build only (-DBBX_PROF_BUILD): per-phase s_memtime sums, never in the product library
   if (!trace && getenv("BBX_PROF")) {
     static unsigned long long* d_prof = nullptr;
@@ -258,7 +261,7 @@ static int launch_general_w(const BbxParams* p, BbxKernel kind, int blocks, int 
   }
 #endif
   lds = (size_t)(threads / WAVE) * merge_lds_bytes<W>();          // merge-path tile scratch, one per wave
-  return bbx_pick_bool(trace, [&](auto TRACE) { return launch_lds<bbx_step_kernel<W, false, TRACE()>>(blocks, threads, lds, stream, *p); });
+  return bbx_pick_bool(trace, [&](auto TRACE) { return bbx_pick_bool(lim, [&](auto LIM) { return launch_lds<bbx_step_kernel<W, false, TRACE(), LIM()>>(blocks, threads, lds, stream, *p); }); });
 }
 extern "C" int bbx_launch_general(const BbxParams* p, BbxKernel kind, int blocks, int threads, size_t lds, hipStream_t stream) {
   return bbx_pick<2, 4, 8>((int)p->L.W, [&](auto W) { return launch_general_w<W()>(p, kind, blocks, threads, lds, stream); });

@@ -51,6 +51,7 @@ struct WideCold {
   int episode_steps, episodes, zero_red, steps_done, rollout_pos, done_last, obs_trunc, q_head;
   uint32_t std_rng, gen_state;
   uint32_t rng_mark;                                      // std_rng before the step in progress (restored when the step has to be taken again)
+  int truncations;                                        // episodes the episode step limit cut (BbxHdr.truncations)
 };
 struct __attribute__((aligned(16))) WideCtl {             // LDS control block (parity double-buffered exchange slots)
   int wfound[2][WNWMAX];                                  // per-wave first divisor of a scan chunk (absent waves: INT_MAX)
@@ -578,7 +579,9 @@ __device__ __noinline__ void wide_leader_trace(const BbxParams* pp, BBX_AS3 Wide
   }
 }
 
-template <int W, bool TRACE, bool LAZY, bool ACCT = !LAZY>
+// LIM: the instantiation that knows the episode step limit (bbx_episode_end, bbx_common.h), launched when one is set; without it
+// the body is what it was before the limit existed, instruction for instruction (this loop answers to anything added to it)
+template <int W, bool TRACE, bool LAZY, bool ACCT = !LAZY, bool LIM = false>
 __device__ __forceinline__ void wide_body(char* smem) {
 #ifdef BBX_PROF_BUILD
   unsigned long long wprof[6] = {0, 0, 0, 0, 0, 0}, wcnt[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -618,6 +621,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
 
   // ---- state: what the step loop branches on in registers, the rest in LDS ------------------------------------------
   int nG, nP, arena_used, status, need_reset, budget, t_agent;
+  int episode_steps = 0;                                                      // LIM: every thread's own — the limit is tested on it
   uint32_t agent_seed;
   {
     const BbxParams& p = wide_params();
@@ -625,6 +629,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
     nG = uni(h->nG); nP = uni(h->nP); arena_used = uni(h->arena_used);
     status = uni(h->status); need_reset = uni(h->need_reset); budget = uni(h->budget); t_agent = uni(h->t);
     agent_seed = (uint32_t)uni((int)h->agent_seed);
+    if constexpr (LIM) episode_steps = uni(h->episode_steps);
     if (status == BBX_ST_STARVED || status == BBX_ST_SPILL || status == BBX_ST_TIMESLICE) status = BBX_ST_OK;
     if (p.set_budget) budget = bbx_st_capacity(status) ? budget + p.nsteps : p.nsteps;   // (bbx_common.h: bbx_st_capacity)
     if (p.pass == 1 && !(status == BBX_ST_OK && (need_reset || (budget > 0 && nP > 0)))) {         // (whole workgroup)
@@ -637,6 +642,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
       st->episode_steps = h->episode_steps; st->episodes = h->episodes; st->zero_red = h->zero_reductions; st->steps_done = 0;
       st->rollout_pos = h->rollout_pos; st->done_last = h->done_last; st->obs_trunc = h->obs_trunc; st->q_head = h->q_head;
       st->std_rng = h->std_rng; st->gen_state = h->gen_rng; st->rng_mark = h->std_rng;
+      if constexpr (LIM) st->truncations = h->truncations;
       if (p.set_budget) { st->rollout_pos = 0; st->done_last = 0; st->vret = 0.0; st->vdisc = 1.0; st->obs_trunc = 0; }
     }
   }
@@ -776,6 +782,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
       __syncthreads();                                                        // bc[] may be rewritten from here on
       if (!ok) break;
       need_reset = 0; table_dirty = true;
+      if constexpr (LIM) episode_steps = 0;
     }
     if (budget <= 0) break;
     if (nP == 0) break;
@@ -1085,7 +1092,9 @@ __device__ __forceinline__ void wide_body(char* smem) {
       table_dirty = true;
       step_bytes += 12LL * rn + 8LL * nG_before + 8LL * (nP_before + nP);
     }
-    const bool done = nP == 0;
+    if constexpr (LIM) episode_steps++;
+    const int end = LIM ? bbx_episode_end(nP, episode_steps, wide_params().episode_limit) : (nP == 0 ? 1 : 0);
+    const bool done = end != 0;
     WSTAMP(7);
     {
       const BbxParams& p = wide_params();
@@ -1104,7 +1113,8 @@ __device__ __forceinline__ void wide_body(char* smem) {
         if (rn == 0) st->zero_red += 1;
         if (p.obs_every_step && p.obs && nP > p.obs_rows) st->obs_trunc = 1;
         st->rollout_pos += 1; st->done_last = done ? 1 : 0;
-        if (done) st->episodes += 1;
+        if constexpr (LIM) { if (done && bbx_episode_counted(end, episode_steps, p.episode_limit, p.auto_reset)) { st->episodes += 1; st->truncations += end == 2 ? 1 : 0; } }
+        else if (done) st->episodes += 1;
       }
       t_agent++; budget--;
       if (done && p.auto_reset) need_reset = 1;
@@ -1133,6 +1143,7 @@ __device__ __forceinline__ void wide_body(char* smem) {
       h->total_steps = st->total_steps; h->total_additions = st->total_adds; h->episodes = st->episodes; h->zero_reductions = st->zero_red;
       h->steps_done = steps_done; h->budget = budget; h->rollout_pos = st->rollout_pos; h->done_last = done_last; h->alg_bytes = st->alg_bytes;
       h->vret = st->vret; h->vdisc = st->vdisc; h->obs_trunc = obs_trunc;
+      if constexpr (LIM) h->truncations = st->truncations;
       if (p.lite) *(int4*)(p.lite + 4 * (size_t)env) = make_int4(bbx_lite_word0(status, obs_trunc, 0), q_head, budget, nP);
       if (p.value_mode && p.values) p.values[env] = st->vret;
       if (p.rewards && (steps_done > 0 || p.pass == 0)) p.rewards[env] = st->last_reward;
@@ -1154,19 +1165,19 @@ __device__ __forceinline__ void wide_body(char* smem) {
 // reversals: runs in which h stays short, where the accumulator's bookkeeping is pure overhead: 6.2 s instead of 7.4 s
 // for the single cyclic-7 run to completion).
 // LAZY = true: the lean variant with the accumulator (random and external agents: h grows long; 2x at cyclic-7 random).
-template <int W, bool TRACE, bool LAZY>
+template <int W, bool TRACE, bool LAZY, bool LIM = false>
 __global__ __launch_bounds__(512, 4) void bbx_wide_kernel(BbxParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  wide_body<W, TRACE, LAZY>(smem);
+  wide_body<W, TRACE, LAZY, !LAZY, LIM>(smem);
 }
-template <int W>
+template <int W, bool LIM = false>
 __global__ __launch_bounds__(512, 4) void bbx_wide_eager_kernel(BbxParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  wide_body<W, false, false, false>(smem);
+  wide_body<W, false, false, false, LIM>(smem);
 }
 // the same code for batches of at most one workgroup per CU (two waves per SIMD): no 128-register cap, no spills
-template <int W, bool LAZY, bool ACCT>
+template <int W, bool LAZY, bool ACCT, bool LIM = false>
 __global__ __launch_bounds__(512, 2) void bbx_wide_kernel_1cu(BbxParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  wide_body<W, false, LAZY, ACCT>(smem);
+  wide_body<W, false, LAZY, ACCT, LIM>(smem);
 }

@@ -35,19 +35,23 @@ extern "C" int bbx_launch_wide(const BbxParams* p, int nw, hipStream_t stream) {
     const size_t wl = wide_lds_bytes(W_, q.wide_hc, q.wide_fc, q.wide_rc, q.wide_sc);
     const bool tr = q.trace != nullptr;
     const int threads = nw * WAVE;
+    // (an episode step limit set: the LIM instantiations, bbx_wide.h; off: the kernels as they were before the limit existed)
+    int rc = bbx_pick_bool(q.episode_limit != 0, [&](auto LIM) {
     int rc;
     if (W_ == 8)                                           // one variant: tier 3 throughout
-      rc = bbx_pick_bool(tr, [&](auto TR) { return launch_lds<bbx_wide_kernel<8, TR(), false>>(q.B, threads, wl, stream, q); });
+      rc = bbx_pick_bool(tr, [&](auto TR) { return launch_lds<bbx_wide_kernel<8, TR(), false, LIM()>>(q.B, threads, wl, stream, q); });
     else if (!tr && one_per_cu)                            // lazy, or eager with or without accounting (lazy never counts)
       rc = bbx_pick<2, 4>(W_, [&](auto W) { return bbx_pick_bool(lazy, [&](auto LAZY) { return bbx_pick_bool(acct, [&](auto ACCT) {
         if constexpr (LAZY() && ACCT()) return (int)hipErrorInvalidValue;
-        else return launch_lds<bbx_wide_kernel_1cu<W(), LAZY(), ACCT()>>(q.B, threads, wl, stream, q);
+        else return launch_lds<bbx_wide_kernel_1cu<W(), LAZY(), ACCT(), LIM()>>(q.B, threads, wl, stream, q);
       }); }); });
     else if (!tr && !lazy && !acct)
-      rc = bbx_pick<2, 4>(W_, [&](auto W) { return launch_lds<bbx_wide_eager_kernel<W()>>(q.B, threads, wl, stream, q); });
+      rc = bbx_pick<2, 4>(W_, [&](auto W) { return launch_lds<bbx_wide_eager_kernel<W(), LIM()>>(q.B, threads, wl, stream, q); });
     else
       rc = bbx_pick<2, 4>(W_, [&](auto W) { return bbx_pick_bool(tr, [&](auto TR) { return bbx_pick_bool(lazy, [&](auto LAZY) {
-        return launch_lds<bbx_wide_kernel<W(), TR(), LAZY()>>(q.B, threads, wl, stream, q); }); }); });
+        return launch_lds<bbx_wide_kernel<W(), TR(), LAZY(), LIM()>>(q.B, threads, wl, stream, q); }); }); });
+    return rc;
+    });
     return bbx_launched(rc);
 }
 #ifdef BBX_PROF_BUILD

@@ -333,9 +333,20 @@ def _critic_last_values(env, critic, obs_rows, stream):
     return last
 
 
+@contextlib.contextmanager
+def _episode_limit(env, max_episode_length):
+    """env.episode_limit(max_episode_length) for the duration of a call, restored afterwards (as `greedy` is)."""
+    before = env.episode_limit(max_episode_length)
+    try:
+        yield
+    finally:
+        env.episode_limit(before)
+
+
 @_with_gc_paused
 @torch.no_grad()
-def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False, critic=None, bootstrap=False):
+def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, chunk=256, greedy=False, critic=None, bootstrap=False,
+                      max_episode_length=None):
     """run_rollout with the policy INSIDE the step kernel: `chunk` vector steps per launch, environments never wait for each
     other between steps.  One hidden layer: bbx_policy_rollout_device; two hidden layers of at most 128 units:
     bbx_policy2_rollout_device (weights from policy._deep_weights(), refilled in place after optimiser steps); any other
@@ -356,7 +367,13 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
     stopped in, and the critic's values of it become buffer.last_values — finish() then bootstraps the episodes the end of the
     buffer cut instead of dropping them (truncated-horizon GAE).  The environments are not touched by it.  Every call with a
     buffer sets buffer.last_values (None without bootstrap) and clears what an earlier finish() left.  bootstrap=True without a
-    critic: ValueError before anything is queued."""
+    critic: ValueError before anything is queued.
+    max_episode_length=L: the reference's cap on episode length (env.episode_limit(L) for the duration of the call, restored
+    afterwards): an episode that has taken L steps and still has pairs is cut inside the kernels — done is set, the next episode
+    begins.  GAE treats the cut as terminal, as the reference's loop does.  None: the handle's own limit, whatever it is."""
+    if max_episode_length is not None:
+        with _episode_limit(env, max_episode_length):
+            return run_rollout_fused(env, policy, nsteps, buffer, obs_rows, generator, chunk, greedy, critic, bootstrap)
     if critic is not None and (buffer is None or buffer.states is None):
         raise ValueError("run_rollout_fused: a critic reads the recorded states (buffer=DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))")
     if bootstrap and critic is None:
@@ -423,7 +440,7 @@ def run_rollout_fused(env, policy, nsteps, buffer=None, obs_rows=256, generator=
 @_with_gc_paused
 @torch.no_grad()
 def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, sync_every=64, graph=False,
-                value_strategy=None, value_gamma=None, greedy=False, critic=None, bootstrap=False):
+                value_strategy=None, value_gamma=None, greedy=False, critic=None, bootstrap=False, max_episode_length=None):
     """nsteps vector steps of `env` (a VecLeadMonomialsEnv already reset) under `policy`, everything on the device
     (obs_rows: rows of the observation block per environment — a pair set with more rows makes env.sync() raise
     BBX_E_CAPACITY, it is never cut silently; 256 is what the register/LDS-resident class holds):
@@ -448,7 +465,13 @@ def run_rollout(env, policy, nsteps, buffer=None, obs_rows=256, generator=None, 
     rollout stops in — one more env.values_device before the final wait, or the critic's values of the observation block the
     loop ends with — and finish() bootstraps the episodes the end of the buffer cut instead of dropping them.  The
     environments are not touched by it.  Every call with a buffer sets buffer.last_values (None without bootstrap) and clears
-    what an earlier finish() left.  All refusals are ValueError before anything is queued."""
+    what an earlier finish() left.  All refusals are ValueError before anything is queued.
+    max_episode_length=L: as in run_rollout_fused (env.episode_limit(L) for the duration of the call; a recorded graph is kept
+    per limit).  The values of value_strategy are those of the whole computation: the value calls ignore the limit."""
+    if max_episode_length is not None:
+        with _episode_limit(env, max_episode_length):
+            return run_rollout(env, policy, nsteps, buffer, obs_rows, generator, sync_every, graph, value_strategy, value_gamma, greedy,
+                               critic, bootstrap)
     if value_strategy is not None and graph:
         raise ValueError("run_rollout: value_strategy cannot be recorded into a graph (bbx_values_device keeps host bookkeeping)")
     if value_strategy is not None and buffer is None:
@@ -538,7 +561,7 @@ def _run_rollout_graph(env, policy, nsteps, obs_rows, generator, sync_every, gre
     B, cols = env.batch, env.cols
     dev = torch.device("cuda", torch.cuda.current_device())
     cache = env.__dict__.setdefault("_step_graphs", {})
-    key = (id(policy), obs_rows, sync_every, bool(greedy))     # (a recording keeps the mode it was captured with)
+    key = (id(policy), obs_rows, sync_every, bool(greedy), getattr(env, "_episode_limit", None))   # (a recording keeps the mode and the episode limit it was captured with)
     c = cache.get(key)
     if c is None:
         c = {"obs": torch.empty((B, obs_rows, cols), dtype=torch.int32, device=dev),
@@ -639,7 +662,7 @@ def episode_returns(rewards, dones, carry=None):
 Evaluation = collections.namedtuple("Evaluation", ["returns", "lengths", "complete", "steps"])
 
 
-def evaluate_policy(env, policy, episodes, greedy=True, obs_rows=256, chunk=64, max_steps=None, generator=None):
+def evaluate_policy(env, policy, episodes, greedy=True, obs_rows=256, chunk=64, max_steps=None, generator=None, max_episode_length=None):
     """The first `episodes` episodes of every environment of `env` under `policy` (run_episodes(..., greedy=True) and
     scripts/eval.py of the reference, for a whole batch): env.reset(), then chunks of `chunk` vector steps — the fused rollout
     (run_rollout_fused) where the handle's kernel class has the policy built in, run_rollout's per-step path where it raises
@@ -654,9 +677,14 @@ def evaluate_policy(env, policy, episodes, greedy=True, obs_rows=256, chunk=64, 
     greedy=True takes the highest-probability pair at every step (no uniforms drawn); False samples (generator: torch's).
     On a handle built from a LIST of ideals (environment e takes ideals e, e + B, e + 2B, ... in turn), returns[e, j] belongs to
     ideal (e + j * B) % nideals.
+    max_episode_length=L (eval.py's cap): env.episode_limit(L) for the duration of the call, restored afterwards — an episode cut
+    at L steps is an episode of length L with the return it has collected; no length exceeds L.
     Returns Evaluation(returns, lengths, complete, steps)."""
     if episodes < 1 or chunk < 1:
         raise ValueError("evaluate_policy: episodes and chunk must be positive")
+    if max_episode_length is not None:
+        with _episode_limit(env, max_episode_length):
+            return evaluate_policy(env, policy, episodes, greedy, obs_rows, chunk, max_steps, generator)
     B = env.batch
     dev = torch.device("cuda", torch.cuda.current_device())
     env.reset()

@@ -568,6 +568,26 @@ int bbx_pmlp3_act_greedy(const int32_t* d_obs, const int32_t* d_rows, int batch,
  * outputs, same auto-reset, same step loop.  The mode travels with each launch by value, so a recorded graph keeps the mode it
  * was captured with.  A running persistent session or mailbox session is ended first.  Off when a handle is created. */
 int bbx_policy_greedy(bbx_batch* b, int enable);
+/* The episode step limit (the reference's max_episode_length).  A switch of the handle, like bbx_policy_greedy: limit = 0 is off
+ * (the default), limit < 0 is BBX_E_ARG.  With a limit every call that steps environments ends an episode that has taken `limit`
+ * steps and still has pairs: that step reports done = 1 like an ordinary end (dones, the trace record, a mailbox step), under
+ * auto-reset the next episode begins as behind an ordinary end, and the episode is counted as an episode and as a truncation
+ * (bbx_episode_counts).  An episode whose limit-th step empties the pair set ends ordinarily.  Without auto-reset the environment
+ * is left as it is: further steps are taken, each reports done while the episode has `limit` steps or more, and none counts
+ * again.  Lowering the limit below a running episode's step count cuts that episode at its next step.  Every reset starts the
+ * count at 0; bbx_copy and bbx_clone_envs carry the count (bbx_copy the limit as well).  The value calls (bbx_value, bbx_values,
+ * bbx_values_seeded, bbx_values_device, bbx_action_values) ignore the limit: the value of a state is the return of the whole
+ * computation.  The limit travels with each launch by value, so a recorded graph keeps the limit it was captured with.  A
+ * running persistent session or mailbox session is ended first.  KNOWN LIMITATION, a deviation from "the
+ * count travels with the record": the kernels of the headline rollout shape (and the two-layer policy rollout) run the code
+ * they ran before the limit existed while it is off, and keep no step count per episode; when a limit is set after such a
+ * launch, the episodes under way in the WHOLE batch count from there (count 0).  Replays of a recorded headline launch are
+ * noted by bbx_graph_replayed, which does the same on its stream when a limit has been set meanwhile; a recorded two-layer
+ * policy rollout replayed under a limit set later is not noted: record it again after setting the limit. */
+int bbx_episode_limit(bbx_batch* b, int limit);
+/* [batch] each, either may be NULL: episodes ended so far (column 2 of bbx_stats) and how many of them the limit cut.  Ends a
+ * running session the way bbx_stats does. */
+int bbx_episode_counts(bbx_batch* b, int64_t* episodes, int64_t* truncations);
 /* Per-episode returns and lengths from the [nsteps][batch] d_rewards and d_dones a rollout leaves on the device (one return and
  * one length per episode: what run_episodes logs).  Per environment e: acc = d_carry_return[e], len = d_carry_len[e]; for
  * t = 0 .. nsteps - 1: acc += r[t][e] (a plain double add, in step order), len += 1; where d_dones[t][e] is set:

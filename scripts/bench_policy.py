@@ -32,6 +32,7 @@ ap.add_argument("--per-step", action="store_true", help="one library call per ve
 ap.add_argument("--chunk", type=int, default=256)
 ap.add_argument("--store-states", action="store_true", help="--store plus the observation block of every step")
 ap.add_argument("--greedy", action="store_true", help="the highest-probability pair at every step instead of a draw (evaluation: no uniforms)")
+ap.add_argument("--max-episode-length", type=int, default=None, help="cut episodes at this many steps inside the kernels (env.episode_limit)")
 ap.add_argument("--no-persistent", action="store_true", help="--per-step: one kernel per call instead of calls that join a persistent session")
 a = ap.parse_args()
 hidden = [int(h) for h in str(a.hidden).split(",")]
@@ -49,8 +50,8 @@ if a.per_step and not a.no_persistent and not a.store and not a.store_states:
     env.persistent(True)      # (per-step outputs are then only final at sync(): nothing in this mode reads them in between)
 def go(nsteps, buf):
     if a.per_step:
-        return run_rollout(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, graph=a.graph, greedy=a.greedy)
-    return run_rollout_fused(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, chunk=a.chunk, greedy=a.greedy)
+        return run_rollout(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, graph=a.graph, greedy=a.greedy, max_episode_length=a.max_episode_length)
+    return run_rollout_fused(env, policy, nsteps, buffer=buf, obs_rows=a.obs_rows, chunk=a.chunk, greedy=a.greedy, max_episode_length=a.max_episode_length)
 go(300, None)                                                      # steady state + warm-up
 st0 = env.stats()
 store = a.store or a.store_states
