@@ -15,6 +15,7 @@ import numpy as np
 
 from oracle import ffi
 from oracle.trace import fnv64, poly_words
+from tests.oracle_walk import agent_seeds
 
 K = 2
 # class -> dist, caps, seeds (one environment each), limits (the last: larger than every episode), steps per walk
@@ -35,10 +36,6 @@ CASES = {
 }
 EXACT_END = ("fast", "binom_hbm")           # cases that must show an ordinary end on exactly the limit-th step
 PIECE = 7                                   # traced launches of 7 steps: launches begin inside episodes
-
-
-def agent_seeds(seeds):
-    return [s - 2993 for s in seeds]
 
 
 def episode_end(nP, episode_steps, limit):

@@ -11,38 +11,18 @@ import __graft_entry__ as graft
 from oracle import ffi
 from tests import action_value_cases as A
 from tests import value_tie_cases as V
+from tests.fast_harness import stream
+from tests.test_values_device import CASES, _make          # the six cases (every kernel class bbx_values serves) and their batch
 
 pytestmark = pytest.mark.gpu
 
 OBS_ROWS = 512
 STRATEGIES = ("degree", "normal", "sugar", "first", "env")      # 'env' selects First, as in bbx_values
-# the six cases of tests/test_values_device.py::CASES (every kernel class bbx_values serves)
-CASES = [("3-20-10-weighted", None, 12), ("3-20-10-weighted", {"lds_max_basis": 16}, 12), ("3-20-10-weighted", {"lds_max_basis": -1}, 12),
-         ("5-10-5-uniform", None, 12), ("3-5-4-0.5-uniform", None, 12), ("cyclic-5", None, 3)]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _built():
     graft.build()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _make(dist, B, caps=None, k=2, seed=70, walk=5):
-    """A batch somewhere inside its episodes (the walk of tests/test_values_device.py)."""
-    from deepgroebner_amd import VecLeadMonomialsEnv
-    from deepgroebner_amd.ideals import FixedIdealGenerator, cyclic
-    if dist == "cyclic-5":
-        env = VecLeadMonomialsEnv(FixedIdealGenerator(cyclic(5)), batch=B, k=k, caps=caps)
-    else:
-        env = VecLeadMonomialsEnv(dist, batch=B, k=k, caps=caps)
-    env.seed(np.arange(B) + seed); env.seed_agent(np.arange(B)); env.reset()
-    if walk:
-        env.rollout("random", walk, auto_reset=True)
-    return env
 
 
 def _check_block(got, want, what):
@@ -237,7 +217,7 @@ def test_behind_a_queued_values_device_call_both_return_what_they_return_alone()
     want_v = twin.values("normal", 0.99)
     want_q = A.call(twin, "degree", 0.99, R)
     out = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")
-    env.values_device(out, "normal", 0.99, None, _stream())      # queued, not yet synced
+    env.values_device(out, "normal", 0.99, None, stream())      # queued, not yet synced
     got = A.call(env, "degree", 0.99, R)
     env.sync()
     assert np.array_equal(out.cpu().numpy(), want_v)

@@ -10,33 +10,17 @@ from oracle import ffi
 from oracle.trace import poly_words
 from tests.action_value_cases import call as av_call, oracle_action_values, same_block
 from tests.episode_limit_cases import CASES, K, PIECE, Walk, agent_seeds, case_walks, limited_walk
+from tests.fast_harness import KEYS, assert_trace_equal, make_env, rollout_buffers, stream
 
 pytestmark = pytest.mark.gpu
-KEYS = (("action", "action"), ("reward", "reward"), ("rows", "nP"), ("basis_size", "nG"), ("done", "done"), ("obs_hash", "obs_hash"),
-        ("pairs_hash", "pairs_hash"), ("newpoly_hash", "newpoly_hash"))
 CASE_LIMITS = [(name, limit) for name in CASES for limit in CASES[name]["limits"]]
 GAMMA = 0.99
 
 
 def _env(name, limit, trace=0, lean=False):
-    from deepgroebner_amd import VecLeadMonomialsEnv
     c = CASES[name]
-    env = VecLeadMonomialsEnv(c["dist"], batch=len(c["seeds"]), k=K, caps=c["caps"], max_episode_length=limit or None)
-    env.seed(np.array(c["seeds"]))
-    env.seed_agent(np.array(agent_seeds(c["seeds"])))
-    if lean:
-        env.accounting(False)
-    if trace:
-        env.trace_enable(trace)
-    env.reset()
-    return env
-
-
-def _same_trace(got, want, t0, n, where):
-    for key, wkey in KEYS:
-        w = np.asarray(want[wkey])[t0:t0 + n]
-        g = got[key].astype(w.dtype)
-        assert np.array_equal(g, w), where + (key, "first difference at step", t0 + int(np.flatnonzero(g != w)[0]))
+    return make_env(c["dist"], c["seeds"], K, caps=c["caps"], trace=trace, lean=lean and "before reset", agent=agent_seeds(c["seeds"]),
+                    max_episode_length=limit or None)
 
 
 def _same_end(env, want, where):
@@ -63,14 +47,14 @@ def test_traced_launches(name, limit):
     env = _env(name, limit, trace=T)
     env.rollout("random", T, auto_reset=True)
     for e, w in enumerate(want):
-        _same_trace(env.trace_read(e, 0, T), w, 0, T, (name, limit, "one launch", e))
+        assert_trace_equal(env.trace_read(e, 0, T), w, KEYS, (name, limit, "one launch", e), 0, T)
     _same_end(env, want, (name, limit, "one launch"))
     env = _env(name, limit, trace=PIECE)
     for t0 in range(0, T, PIECE):
         n = min(PIECE, T - t0)
         env.rollout("random", n, auto_reset=True)
         for e, w in enumerate(want):
-            _same_trace(env.trace_read(e, 0, n), w, t0, n, (name, limit, "launches of 7", e))
+            assert_trace_equal(env.trace_read(e, 0, n), w, KEYS, (name, limit, "launches of 7", e), t0, n)
     _same_end(env, want, (name, limit, "launches of 7"))
 
 
@@ -79,14 +63,11 @@ def test_lean_launches_through_device_buffers(name, limit):
     """The lean kernels (no trace, no accounting; with a limit set the fast class runs its general lean kernel, not the headline
     one) in two launches on caller buffers, the observation written at every step: rewards, dones, rows and the observation
     behind each launch, then the final state and the counters."""
-    import torch
     T = CASES[name]["steps"]
     B, R = len(CASES[name]["seeds"]), 1024
     env = _env(name, limit, lean=True)
-    s = torch.cuda.current_stream().cuda_stream
-    obs = torch.zeros((B, R, env.cols), dtype=torch.int32, device="cuda")
-    rew = torch.zeros(B, dtype=torch.float64, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
-    rows = torch.zeros(B, dtype=torch.int32, device="cuda")
+    s = stream()
+    rew, done, rows, obs = rollout_buffers(B, R, env.cols, fill=0)
     n1 = T // 2 + 1
     for upto, n in ((n1, n1), (T, T - n1)):
         env.rollout_device("random", n, True, s, rew, done, rows, obs, R, False, True)
@@ -121,7 +102,7 @@ def test_fused_policy_rollouts_replayed_on_the_walk(name, hidden):
     T, B, limit = c["steps"], len(c["seeds"]), c["limits"][-2]
     env = _env(name, limit, lean=True)
     policy = _policy(env.cols, hidden, 5)
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream()
     u = torch.rand((T, B), device="cuda")
     A = torch.zeros((T, B), dtype=torch.int32, device="cuda"); L = torch.zeros((T, B), dtype=torch.float32, device="cuda")
     Rw = torch.zeros((T, B), dtype=torch.float64, device="cuda"); D = torch.full((T, B), 9, dtype=torch.uint8, device="cuda")
@@ -153,15 +134,13 @@ def test_session_calls_equal_separate_launches():
     from deepgroebner_amd import VecLeadMonomialsEnv
     dist, B, R, limit, calls = "3-20-10-weighted", 64, 256, 3, [20] * 6
     seeds = tuple(range(3000, 3000 + B))
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream()
     outs = []
     for persistent in (True, False):
         env = VecLeadMonomialsEnv(dist, batch=B, k=K, max_episode_length=limit)
         env.seed(np.array(seeds)); env.seed_agent(np.array(agent_seeds(seeds))); env.accounting(False); env.reset()
         env.persistent(persistent)
-        obs = torch.zeros((B, R, env.cols), dtype=torch.int32, device="cuda")
-        rew = torch.zeros(B, dtype=torch.float64, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
-        rows = torch.zeros(B, dtype=torch.int32, device="cuda")
+        rew, done, rows, obs = rollout_buffers(B, R, env.cols, fill=0)
         for n in calls:
             env.rollout_device("random", n, True, s, rew, done, rows, obs, R, False, True)
         env.sync()
@@ -268,14 +247,11 @@ def test_lowering_the_limit_under_a_running_episode(name):
 def test_a_limit_set_behind_headline_launches_counts_from_there():
     """The headline-shaped lean kernels keep no step count per episode: a limit set after such a launch starts the episodes
     under way at count 0 (include/bbx.h), whatever the header held — the walk does the same."""
-    import torch
     c = CASES["fast"]
     B, R, n1, n2, limit = len(c["seeds"]), 256, 30, 13, 5
     env = _env("fast", 0, lean=True)
-    s = torch.cuda.current_stream().cuda_stream
-    obs = torch.zeros((B, R, env.cols), dtype=torch.int32, device="cuda")
-    rew = torch.zeros(B, dtype=torch.float64, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
-    rows = torch.zeros(B, dtype=torch.int32, device="cuda")
+    s = stream()
+    rew, done, rows, obs = rollout_buffers(B, R, env.cols, fill=0)
     env.rollout_device("random", n1, True, s, rew, done, rows, obs, R, False, True)      # the headline shape, limit off
     env.sync()
     assert env.episode_limit(limit) is None

@@ -9,6 +9,7 @@ import pytest
 
 import __graft_entry__ as graft
 from tests import gae_cases as gc
+from tests.fast_harness import stream, stream_ptr
 
 pytestmark = pytest.mark.gpu
 
@@ -18,11 +19,6 @@ SHAPES = [(1, 1), (2, 64), (7, 65), (33, 130)]              # one thread, a full
 @pytest.fixture(scope="module", autouse=True)
 def _built():
     graft.build()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _env(dist, B, seed=100):
@@ -46,7 +42,7 @@ def _current_block(env, R):
     obs = torch.empty((B, R, env.cols), dtype=torch.int32, device="cuda")
     rew = torch.zeros(B, dtype=torch.float64, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
     rows = torch.zeros(B, dtype=torch.int32, device="cuda")
-    env.rollout_device("first", 0, False, _stream(), rew, done, rows, obs, R, True, False)
+    env.rollout_device("first", 0, False, stream(), rew, done, rows, obs, R, True, False)
     env.sync()
     return obs, rows
 
@@ -130,9 +126,9 @@ def test_the_old_entry_is_the_new_one_with_two_nulls(T, B):
     for new in (False, True):
         ret = torch.full_like(r, 7.0); adv = torch.full_like(r, 7.0); comp = torch.full_like(d, True)
         if new:
-            rc = _ffi.lib().bbx_gae_bootstrap_device(p(r), p(v), p(d), T, B, 0.99, 0.97, None, p(ret), p(adv), p(comp), None, C.c_void_p(_stream()))
+            rc = _ffi.lib().bbx_gae_bootstrap_device(p(r), p(v), p(d), T, B, 0.99, 0.97, None, p(ret), p(adv), p(comp), None, stream_ptr())
         else:
-            rc = _ffi.lib().bbx_gae_device(p(r), p(v), p(d), T, B, 0.99, 0.97, p(ret), p(adv), p(comp), C.c_void_p(_stream()))
+            rc = _ffi.lib().bbx_gae_device(p(r), p(v), p(d), T, B, 0.99, 0.97, p(ret), p(adv), p(comp), stream_ptr())
         assert rc == 0
         torch.cuda.synchronize()
         outs.append((ret, adv, comp))

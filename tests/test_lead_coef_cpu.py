@@ -10,7 +10,7 @@ import functools
 import numpy as np
 
 import __graft_entry__ as graft
-from oracle import ffi
+from tests import oracle_walk as ow
 
 DIST, K, T, P = "3-20-10-weighted", 2, 128, 32003
 # (ideal seed, agent seed): an element with the lead coefficient named enters the basis within T steps and is later a member
@@ -20,31 +20,38 @@ LC_MINUS_ONE = ((7694, 3694), (8077, 4077), (8711, 4711), (9694, 5694))
 SEEDS = LC_ONE + LC_MINUS_ONE
 
 
+class Insertions:
+    """walk()'s observer: the elements the current episode has inserted (live, by basis index), moved to `inserted` when
+    the episode ends — the after hook sees o.nP == 0 before the reset — and by flush() behind the last step."""
+
+    def __init__(self):
+        self.inserted, self.live = [], {}
+
+    def before(self, o, t, action):
+        for g in o.pairs()[action]:
+            if int(g) in self.live and self.live[int(g)][3] is None:
+                self.live[int(g)][3] = t
+        self.nG0 = o.nG
+
+    def after(self, o, t, action, reward):
+        if o.nG > self.nG0:
+            self.live[self.nG0] = [t, self.nG0, int(o.poly(self.nG0)[0][0]), None]
+        if o.nP == 0:
+            self.flush()
+
+    def flush(self):
+        self.inserted += [tuple(v) for v in self.live.values()]
+        self.live = {}
+
+
 @functools.lru_cache(maxsize=None)
 def walk(seed, aseed, nsteps=T):
     """T steps of the hash agent with auto-reset on the oracle: (the environment as it stands afterwards, per-step rewards and
     done flags, the insertions as (step, basis index, lead coefficient, step of its first later selection in the episode or None))."""
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-    rewards, dones, inserted, live = [], [], [], {}
-    for t in range(nsteps):
-        a = ffi.agent_action(aseed, t, o.nP)
-        for g in o.pairs()[a]:
-            if int(g) in live and live[int(g)][3] is None:
-                live[int(g)][3] = t
-        nG0 = o.nG
-        rewards.append(o.step(a))
-        if o.nG > nG0:
-            live[nG0] = [t, nG0, int(o.poly(nG0)[0][0]), None]
-        dones.append(o.nP == 0)
-        if o.nP == 0:
-            inserted += [tuple(v) for v in live.values()]
-            live = {}
-            o.reset()
-    inserted += [tuple(v) for v in live.values()]
-    return o, np.array(rewards), np.array(dones), inserted
+    seen = Insertions()
+    o, rewards, dones, _ = ow.walk(DIST, seed, aseed, nsteps, seen)
+    seen.flush()
+    return o, rewards, dones, seen.inserted
 
 
 def test_inverse_table_of_the_host():

@@ -7,6 +7,8 @@ same calls made one kernel per launch."""
 import numpy as np
 import pytest
 
+from tests.fast_harness import make_env
+
 pytestmark = pytest.mark.gpu
 DIST = "3-20-10-weighted"
 R = 256
@@ -15,11 +17,7 @@ STEPS = (1, 2, 20, 63, 64, 65, 130)                          # around the 64-ste
 
 
 def _env(dist, B, persistent, caps=None):
-    from deepgroebner_amd import VecLeadMonomialsEnv
-    env = VecLeadMonomialsEnv(dist, batch=B, k=2, caps=caps)
-    env.seed(np.arange(B) + 1000); env.seed_agent(np.arange(B)); env.reset(); env.accounting(False)
-    env.persistent(persistent)
-    return env
+    return make_env(dist, np.arange(B) + 1000, 2, caps=caps, lean=True, agent=np.arange(B), persistent=persistent)
 
 
 def _bufs(env, B, fill=0):

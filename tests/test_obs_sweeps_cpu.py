@@ -9,7 +9,7 @@ import functools
 
 import numpy as np
 
-from oracle import ffi
+from tests import oracle_walk as ow
 
 DIST, K, B, T = "3-20-10-weighted", 2, 32, 48
 SEEDS = tuple((1000 + e, 7 + e) for e in range(B))
@@ -24,18 +24,10 @@ CUT_STEP = 45                                                # ... read after th
 def walk(e):
     """T steps of environment e on the oracle: ([row count after every step], [observation after every step]) — what a
     launch that ends with that step leaves in the environment's block (after a step that ends an episode: the new ideal's)."""
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(SEEDS[e][0])
-    o.reset()
-    rows, obs = [], []
-    for t in range(T):
-        o.step(ffi.agent_action(SEEDS[e][1], t, o.nP))
-        if o.nP == 0:
-            o.reset()
-        rows.append(o.nP)
-        obs.append(o.obs(K))
-    return rows, obs
+    # (what a step leaves once a reset has happened is what the next step's before hook sees, and the last: the final state)
+    o, _, _, seen = ow.walk(DIST, *SEEDS[e], T, (lambda o, t, a: (o.nP, o.obs(K)), None))
+    left = [b for b, _ in seen[1:]] + [(o.nP, o.obs(K))]
+    return [n for n, _ in left], [rows for _, rows in left]
 
 
 def boundaries():

@@ -10,37 +10,20 @@ per-step blocks are each held to the oracle replayed with the kernel's actions."
 import numpy as np
 import pytest
 
-from tests import policy_cases as pc
 from tests.test_obs_sweeps_cpu import B, CASES, CUT_ROWS, CUT_STEP, DIST, K, SEEDS, boundaries, walk
+from tests.fast_harness import KERNELS, make_env, policy_rollout, replay_policy_rollout, rollout_buffers, stream
 
 pytestmark = pytest.mark.gpu
 R = 80                                                       # rows per block: above every count of the run (69 at most in 160 steps)
 SENT = -7
 
 
-def _env():
-    from deepgroebner_amd import VecLeadMonomialsEnv
-    env = VecLeadMonomialsEnv(DIST, batch=B, k=K)
-    env.seed(np.array([s for s, _ in SEEDS]))
-    env.seed_agent(np.array([a for _, a in SEEDS]))
-    env.reset()
-    env.accounting(False)
-    return env
-
-
-def _bufs(rows_per_block, blocks=B):
-    import torch
-    return (torch.zeros(B, dtype=torch.float64, device="cuda"), torch.zeros(B, dtype=torch.uint8, device="cuda"),
-            torch.zeros(B, dtype=torch.int32, device="cuda"), torch.full((blocks, rows_per_block, 4 * 3), SENT, dtype=torch.int32, device="cuda"))
-
-
-@pytest.mark.parametrize("kernel", ("headline", "headline-session", "generic"))
+@pytest.mark.parametrize("kernel", KERNELS)
 def test_blocks_at_the_pinned_row_counts(kernel):
     import torch
-    env = _env()
-    env.persistent(kernel == "headline-session")
-    s = torch.cuda.current_stream().cuda_stream
-    rew, done, rows, obs = _bufs(R)
+    env = make_env(DIST, SEEDS, K, lean=True, persistent=kernel == "headline-session")
+    s = stream()
+    rew, done, rows, obs = rollout_buffers(B, R, env.cols, fill=SENT)
     generic = kernel == "generic"
     at, shown = 0, set()
     for t in boundaries():
@@ -66,14 +49,13 @@ def test_blocks_at_the_pinned_row_counts(kernel):
 def test_cut_block_keeps_its_first_rows_and_reports_the_rest():
     """obs_rows = 20 where environments have up to 49 rows: the first 20 rows of those, all rows of the others, the sentinel
     beyond them and in a spare block behind the last environment's; the call that waits for the launch reports the rows lost."""
-    import torch
     from deepgroebner_amd import _ffi
-    env = _env()
-    s = torch.cuda.current_stream().cuda_stream
-    rew, done, rows, big = _bufs(R)
+    env = make_env(DIST, SEEDS, K, lean=True)
+    s = stream()
+    rew, done, rows, big = rollout_buffers(B, R, env.cols, fill=SENT)
     env.rollout_device("random", CUT_STEP, True, s, rew, done, rows, big, R, False, True)
     env.sync()
-    _, _, _, small = _bufs(CUT_ROWS, B + 1)
+    small = rollout_buffers(B, CUT_ROWS, env.cols, fill=SENT, blocks=B + 1)[3]
     env.rollout_device("random", 1, True, s, rew, done, rows, small, CUT_ROWS, False, True)
     with pytest.raises(_ffi.BbxError) as ei:
         env.sync()
@@ -93,31 +75,15 @@ def test_policy_rollout_blocks_step_by_step():
     """bbx_policy_rollout_device, one hidden layer of 64 units, 24 steps: the block of every step (written before the step, from
     the state the policy scores) is the oracle's observation, replayed with the actions the kernel drew, and keeps the sentinel
     beyond its rows."""
-    import torch
-    from oracle import ffi
     nT = 24
-    env = _env()
-    w = pc.make_weights(env.cols, (64,), 2531)
-    p = pc.to_policy(w, "cuda")._fused_weights()
-    s = torch.cuda.current_stream().cuda_stream
-    u = torch.rand((nT, B), device="cuda", generator=torch.Generator(device="cuda").manual_seed(2532))
-    A = torch.zeros((nT, B), dtype=torch.int32, device="cuda"); L = torch.zeros((nT, B), dtype=torch.float32, device="cuda")
-    Rw = torch.zeros((nT, B), dtype=torch.float64, device="cuda"); D = torch.zeros((nT, B), dtype=torch.uint8, device="cuda")
-    N = torch.zeros((nT, B), dtype=torch.int32, device="cuda")
-    O = torch.full((nT, B, R, env.cols), SENT, dtype=torch.int32, device="cuda")
-    env.policy_rollout_device(p["prepared"], p["hidden"], nT, u, A, L, Rw, D, N, O, R, B * R * env.cols, s)
-    env.sync(); torch.cuda.synchronize()
-    acts, obs, rows = A.cpu().numpy(), O.cpu().numpy(), N.cpu().numpy()
-    assert env.stats()[:, 4].max() == 0
+    env = make_env(DIST, SEEDS, K, lean=True)
+    out = {key: x.cpu().numpy() for key, x in policy_rollout(env, 64, 2531, nT, 2532, R, fill=SENT)[2].items()}
+    obs, rows = out["obs"], out["rows"]
+    replay_policy_rollout(DIST, SEEDS, K, out["acts"], out["rews"], out["dones"], obs, rows)   # (rows[t, e] is the oracle's count)
     tails = set()
-    for e, (seed, _) in enumerate(SEEDS):
-        o = ffi.load("bo").env(DIST); o.seed(seed); o.reset()
+    for e in range(B):
         for t in range(nT):
-            n = o.nP
-            assert rows[t, e] == n and np.array_equal(obs[t, e, :n], o.obs(K)), (e, t)
+            n = rows[t, e]
             assert (obs[t, e, n:] == SENT).all(), (e, t, n)
             tails.add((n - 1) % 32 < 16)
-            o.step(int(acts[t, e]))
-            if o.nP == 0:
-                o.reset()
     assert tails == {True, False}                               # (a rest of at most 16 rows and a longer one both occurred)

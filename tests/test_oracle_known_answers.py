@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import ffi
+from tests.oracle_walk import grevlex_key
 
 
 @pytest.fixture(params=["bo", "ref"])
@@ -182,10 +183,6 @@ def test_seed123_generators(lib):
 
 
 # ---- episode-level known answers, tests/test_buchberger.py:270-296 (rewards='reductions')
-def _grevlex_key(e):
-    return (int(sum(e)), tuple(-int(x) for x in reversed(e)))
-
-
 def _select(env, strategy):
     pairs = env.pairs()
     lm = [env.poly(i)[1][0] for i in range(env.nG)]
@@ -199,7 +196,7 @@ def _select(env, strategy):
             elif s == "degree":
                 k.append(int(l.sum()))
             elif s == "normal":
-                k.append(_grevlex_key(l))
+                k.append(grevlex_key(l))
         return tuple(k)
     return min(range(len(pairs)), key=lambda r: key(pairs[r]))
 

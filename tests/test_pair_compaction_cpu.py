@@ -14,7 +14,8 @@ import functools
 import numpy as np
 
 from oracle import ffi
-from tests.test_step_events_cpu import agent_seeds
+from tests import oracle_walk as ow
+from tests.oracle_walk import agent_seeds
 from tests.test_step_prefetch_cpu import DIST, LAUNCHES, T
 
 # case -> seeds that show it (the GPU test runs the union as one batch)
@@ -43,17 +44,16 @@ def walk(seed, steps=T):
     inserted an element (ins), and for an insertion how many old pairs stay (kept), how many new pairs are appended (emitted),
     how many of the kept ones stand in front of the first old pair that is dropped without being the selected one (gap; -1: no
     such pair), and the action of step t + 1 on the list it left (nxt; -1: the episode ended)."""
-    bo = ffi.load("bo")
     a = agent_seeds([seed])[0]
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
     rec = {k: np.full(steps, -1, dtype=np.int64) for k in ("nP0", "nP1", "ins", "kept", "emitted", "gap", "nxt")}
-    for t in range(steps):
-        old = [tuple(int(x) for x in p) for p in o.pairs()]
-        g = o.nG
-        act = ffi.agent_action(a, t, len(old))
-        o.step(act)
+
+    found = {}
+
+    def before(o, t, act):
+        found["old"], found["g"] = [tuple(int(x) for x in p) for p in o.pairs()], o.nG
+
+    def after(o, t, act, reward):
+        old, g = found["old"], found["g"]
         new = [tuple(int(x) for x in p) for p in o.pairs()]
         rec["nP0"][t], rec["nP1"][t], rec["ins"][t] = len(old), len(new), int(o.nG == g + 1)
         if new:
@@ -71,8 +71,8 @@ def walk(seed, steps=T):
             others = [l for l, s in enumerate(stays) if not s and l != act]
             rec["kept"][t], rec["emitted"][t] = len(kept), len(new) - len(kept)
             rec["gap"][t] = sum(stays[:others[0]]) if others else -1
-        if o.nP == 0:
-            o.reset()
+
+    ow.walk(DIST, seed, a, steps, (before, after))
     return rec
 
 

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from oracle import ffi
+from tests import oracle_walk as ow
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIST, K, T = "3-20-10-weighted", 2, 256
@@ -80,40 +81,52 @@ def peel_shape(leads, f):
     return len(per_deg), len(seen), max(per_deg.values()), biggest, with_cp, emitted
 
 
-@functools.lru_cache(maxsize=None)
-def walk(seed, aseed, nsteps=T):
-    """nsteps steps of the hash agent with auto-reset on the oracle: ({situation: steps that show it}, [(basis words, pair
-    list, reducer order) after every LAUNCH steps], the environment as it stands afterwards, [a copy of the environment after
-    every CUT steps], [(levels, buckets) of every insertion], [|P| after every step, before a reset])."""
-    from oracle.trace import poly_words
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-    seen = {k: [] for k in SITUATIONS}
-    states, cuts, shapes, rows = [], [], [], []
-    leads = [o.poly(i)[1][0] for i in range(o.nG)]
-    for t in range(nsteps):
-        g = o.nG
-        o.step(ffi.agent_action(aseed, t, o.nP))
+class Peels:
+    """walk()'s observer: the shape of every insertion's peel, and the state the run stands in after every LAUNCH and CUT
+    steps — left(o, t), the state t steps leave with a reset done, which is what the next step's before hook sees."""
+
+    def __init__(self):
+        self.seen = {k: [] for k in SITUATIONS}
+        self.states, self.cuts, self.shapes, self.rows, self.leads = [], [], [], [], None
+
+    def left(self, o, t):
+        if t and t % LAUNCH == 0:
+            self.states.append(ow.snapshot(o))
+        if t and t % CUT == 0:
+            self.cuts.append(o.copy())
+
+    def before(self, o, t, action):
+        self.left(o, t)
+        if self.leads is None:                                   # (a new episode: the ideal's lead monomials)
+            self.leads = [o.poly(i)[1][0] for i in range(o.nG)]
+        self.g = o.nG
+
+    def after(self, o, t, action, reward):
+        g = self.g
         if o.nG == g + 1:                                        # an insertion: the new element is basis index g
             f = o.poly(g)[1][0]
-            levels, buckets, widest, biggest, with_cp, emitted = peel_shape(np.array(leads), f)
-            shapes.append((levels, buckets))
-            leads.append(f)
+            levels, buckets, widest, biggest, with_cp, emitted = peel_shape(np.array(self.leads), f)
+            self.shapes.append((levels, buckets))
+            self.leads.append(f)
             for k, shown in (("multi", widest >= 2), ("coprime", with_cp >= 1), ("triple", biggest >= 3), ("six", buckets >= 6),
                              ("none", emitted == 0), ("g64", g >= 64)):
                 if shown:
-                    seen[k].append(t)
-        rows.append(o.nP)
+                    self.seen[k].append(t)
+        self.rows.append(o.nP)
         if o.nP == 0:
-            o.reset()
-            leads = [o.poly(i)[1][0] for i in range(o.nG)]
-        if (t + 1) % LAUNCH == 0:
-            states.append((np.concatenate([poly_words(*o.poly(i)) for i in range(o.nG)]), o.pairs(), o.reducer_order()))
-        if (t + 1) % CUT == 0:
-            cuts.append(o.copy())
-    return seen, states, o, cuts, shapes, rows
+            self.leads = None
+
+
+@functools.lru_cache(maxsize=None)
+def walk(seed, aseed, nsteps=T):
+    """nsteps steps of the hash agent with auto-reset on the oracle: ({situation: steps that show it}, [the state
+    (oracle_walk.Snapshot: basis words, pair list, reducer order) after every LAUNCH steps], the environment as it stands
+    afterwards, [a copy of the environment after every CUT steps], [(levels, buckets) of every insertion], [|P| after every
+    step, before a reset])."""
+    p = Peels()
+    o = ow.walk(DIST, seed, aseed, nsteps, p)[0]
+    p.left(o, nsteps)
+    return p.seen, p.states, o, p.cuts, p.shapes, p.rows
 
 
 def test_every_situation_is_reached():

@@ -4,26 +4,17 @@ log-probability of every live row at every instantiation and tile boundary, the 
 with the sampler, the gradients at the batch sizes where the partition of the states changes, the operand permutation of the
 backward pass with exact integer data, determinism, and the autograd wrapper.  Each case prints the ratio of its bound it
 needed before it asserts (pytest -s)."""
-import ctypes as C
 
 import numpy as np
 import pytest
 
 from tests import policy_cases as pc
 from tests import policy_grad_cases as gc
+from tests.fast_harness import ptr, stream_ptr, to_cuda
 
 pytestmark = pytest.mark.gpu
 _ids = lambda v: str(v).replace(" ", "")
 GUARD = 64
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _prepared(weights):
@@ -39,8 +30,8 @@ def _logprob(weights, obs, rows, actions, entropy=True):
     prep, keep = _prepared(weights)
     N, R, cols = obs.shape
     lp = torch.full((N,), 7.0, device="cuda"); ent = torch.full((N,), 7.0, device="cuda")
-    _ffi.check(_ffi.lib().bbx_pmlp_logprob(_p(obs), _p(rows), _p(actions), N, R, cols, prep, weights[0][0].shape[1], _p(lp),
-                                           _p(ent) if entropy else None, _stream()))
+    _ffi.check(_ffi.lib().bbx_pmlp_logprob(ptr(obs), ptr(rows), ptr(actions), N, R, cols, prep, weights[0][0].shape[1], ptr(lp),
+                                           ptr(ent) if entropy else None, stream_ptr()))
     torch.cuda.synchronize()
     return lp.cpu().numpy(), (ent.cpu().numpy() if entropy else None)
 
@@ -62,8 +53,8 @@ def _grad(weights, obs, rows, actions, glogp, gent, prep=None):
     nfl = lib.bbx_pmlp_grad_workspace_floats(N, R, cols, hidden)
     assert nfl > 0
     ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
-    _ffi.check(lib.bbx_pmlp_grad(_p(obs), _p(rows), _p(actions), N, R, cols, prep, hidden, _p(glogp), _p(gent) if gent is not None else None,
-                                 _p(ws), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(outs[3]), _stream()))
+    _ffi.check(lib.bbx_pmlp_grad(ptr(obs), ptr(rows), ptr(actions), N, R, cols, prep, hidden, ptr(glogp), ptr(gent) if gent is not None else None,
+                                 ptr(ws), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), stream_ptr()))
     torch.cuda.synchronize()
     host = buf.cpu().numpy()
     inside = np.zeros(len(host), dtype=bool)
@@ -74,11 +65,6 @@ def _grad(weights, obs, rows, actions, glogp, gent, prep=None):
     got = [host[int(o):int(o) + s].copy() for o, s in zip(offs, sizes)]
     got[0] = got[0].reshape(cols, hidden)
     return tuple(got)
-
-
-def _cuda(*arrays):
-    import torch
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
 
 
 # ---- log-probability and entropy ---------------------------------------------------------------------------------------------
@@ -109,7 +95,7 @@ def test_logprob_and_entropy_at_every_row_and_boundary(cols, hidden):
     C_H 2^-24 K (1 + log n); a state without rows: 0.0 and 0.0."""
     worst_l = worst_h = 0.0
     for case, actions in _eval_cases(cols, hidden, 300):
-        obs, rows, act = _cuda(case.obs, case.rows.astype(np.int32), actions)
+        obs, rows, act = to_cuda(case.obs, case.rows.astype(np.int32), actions)
         lp, ent = _logprob(case.weights, obs, rows, act)
         rl, rh, ref = gc.reference_eval(case.weights, None, None, actions, ref=case.ref)
         dead = ref.n <= 0
@@ -131,7 +117,7 @@ def test_conventions_are_exact():
     pointer leaves the log-probabilities as they are."""
     case = pc.edge_case(12, (128,), 8, 24, (0, -3, 1, 1, 24, 40, 7, 16), 5, True)
     actions = np.array([0, 5, 0, 1, 24, -1, 7, 15], dtype=np.int32)
-    obs, rows, act = _cuda(case.obs, case.rows.astype(np.int32), actions)
+    obs, rows, act = to_cuda(case.obs, case.rows.astype(np.int32), actions)
     lp, ent = _logprob(case.weights, obs, rows, act)
     rl, rh, ref = gc.reference_eval(case.weights, None, None, actions, ref=case.ref)
     assert lp[0] == 0.0 and ent[0] == 0.0 and lp[1] == 0.0 and ent[1] == 0.0
@@ -151,7 +137,7 @@ def test_logprob_equals_the_samplers_bit_for_bit(cols, hidden):
     live = pc.LIVE_ROWS + (2048,)
     case = pc.edge_case(cols, hidden, len(live), 2048, live, 41, True)
     pol = pc.to_policy(case.weights, "cuda")
-    obs, rows, u = _cuda(case.obs, case.rows.astype(np.int32), case.u)
+    obs, rows, u = to_cuda(case.obs, case.rows.astype(np.int32), case.u)
     a, l = pol.act(obs, rows, u)
     torch.cuda.synchronize()
     lp, _ = _logprob(case.weights, obs, rows, a)
@@ -183,7 +169,7 @@ def _grad_case(cols, hidden, N, seed, R=136, rows=GRAD_ROWS, with_gent=True):
 def _run_grad(w, obs, rows, actions, glogp, gent, what, summed=False):
     ref = pc.reference(w, obs, rows)
     want, A = gc.reference_grad(w, obs, rows, actions, glogp, gent, scale=gc.state_scale(ref) if summed else None, ref=ref)
-    got = _grad(w, *_cuda(obs, rows, actions, glogp, gent))
+    got = _grad(w, *to_cuda(obs, rows, actions, glogp, gent))
     r = gc.grad_ratio(got, want, A, None if summed else ref)
     print("ratios %-60s r_g=%.3f" % (what, r))
     gc.check_grads(got, want, A, None if summed else ref, what=what)
@@ -209,7 +195,7 @@ def test_gradients_large_batch_and_determinism():
     w, obs, rows, actions, glogp, gent = _grad_case(12, (128,), N, 77, R=33, rows=(33, 0, 2, 1, 17, 32, 31, 16, 15))
     actions[7] = 40; actions[11] = -1                              # bad actions contribute nothing
     _run_grad(w, obs, rows, actions, glogp, gent, "grad 12x128 N=%d" % N, summed=True)
-    dev = _cuda(obs, rows, actions, glogp, gent)
+    dev = to_cuda(obs, rows, actions, glogp, gent)
     a = _grad(w, *dev); b = _grad(w, *dev)
     for x, y in zip(a, b):
         assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
@@ -217,7 +203,7 @@ def test_gradients_large_batch_and_determinism():
 
 def test_gradients_are_deterministic_at_the_largest_shape():
     w, obs, rows, actions, glogp, gent = _grad_case(64, (256,), 2 * SPW + 1, 78)
-    dev = _cuda(obs, rows, actions, glogp, gent)
+    dev = to_cuda(obs, rows, actions, glogp, gent)
     a = _grad(w, *dev); b = _grad(w, *dev)
     for x, y in zip(a, b):
         assert np.array_equal(x.view(np.uint32), y.view(np.uint32))
@@ -228,17 +214,17 @@ def test_states_without_a_gradient_contribute_exactly_nothing():
     the other states alone; n == 0 zeroes the outputs."""
     w, obs, rows, actions, glogp, gent = _grad_case(12, (128,), 6, 90, R=40, rows=(0, 17, 1, 33, -2, 20))
     actions[3] = 33
-    dev = _cuda(obs, rows, actions, glogp, gent)
+    dev = to_cuda(obs, rows, actions, glogp, gent)
     a = _grad(w, *dev)
     glogp2, gent2 = glogp.copy(), gent.copy()
     glogp2[[0, 3, 4]] = np.nan; gent2[[0, 3, 4]] = np.inf; glogp2[2] = 1e30; gent2[2] = -1e30
-    b = _grad(w, *_cuda(obs, rows, actions, glogp2, gent2))
+    b = _grad(w, *to_cuda(obs, rows, actions, glogp2, gent2))
     keep = [1, 5]
-    c = _grad(w, *_cuda(obs[keep], rows[keep], actions[keep], glogp[keep], gent[keep]))
+    c = _grad(w, *to_cuda(obs[keep], rows[keep], actions[keep], glogp[keep], gent[keep]))
     for x, y, z in zip(a, b, c):
         assert np.array_equal(x, y) and np.array_equal(x, z)
     import torch
-    z = _grad(w, torch.zeros((0, 40, 12), dtype=torch.int32, device="cuda"), *_cuda(rows[:0], actions[:0], glogp[:0], gent[:0]))
+    z = _grad(w, torch.zeros((0, 40, 12), dtype=torch.int32, device="cuda"), *to_cuda(rows[:0], actions[:0], glogp[:0], gent[:0]))
     assert all((x == 0).all() for x in z)
 
 
@@ -262,7 +248,7 @@ def test_operand_permutation_with_exact_integers(cols, hidden, n):
     ref = pc.reference(w, obs, rows)
     assert (ref.logits[:, :n] == 1.0).all()
     want, A = gc.reference_grad(w, obs, rows, actions, glogp, None, ref=ref)
-    got = _grad(w, *_cuda(obs, rows, actions, glogp, None))
+    got = _grad(w, *to_cuda(obs, rows, actions, glogp, None))
     assert sum(int((np.rint(x) != 0).sum()) for x in want[:3]) > (cols * hidden) // 4, "the case is degenerate"
     for name, x, y in zip(("dW1", "db1", "dw2", "db2"), got, want):
         assert np.abs(y - np.rint(y)).max() <= 1e-8
@@ -283,7 +269,7 @@ def test_evaluate_backward_and_an_optimizer_step():
     wt = rng.normal(size=N).astype(np.float32)
     pol = pc.to_policy(w, "cuda")
     opt = torch.optim.SGD(pol.parameters(), lr=0.05)
-    st, act, wtd = _cuda(obs, actions, wt)
+    st, act, wtd = to_cuda(obs, actions, wt)
     logp, ent = pol.evaluate(st, act)
     assert logp.requires_grad and logp.grad_fn is not None and type(logp.grad_fn).__name__.startswith("_PMLPEvaluate")
     loss = (wtd * logp).sum() - 0.01 * ent.mean()
@@ -313,7 +299,7 @@ def test_two_layers_take_the_torch_path_and_still_train():
     rows = np.array((5, 17, 2, 24), dtype=np.int32)
     obs = pc.fill_padding(pc.random_blocks(4, 24, 12, 32), rows, False)
     pol = pc.to_policy(w, "cuda")
-    st, act = _cuda(obs, np.array((4, 0, 1, 23), dtype=np.int32))
+    st, act = to_cuda(obs, np.array((4, 0, 1, 23), dtype=np.int32))
     logp, ent = pol.evaluate(st, act)
     assert not type(logp.grad_fn).__name__.startswith("_PMLPEvaluate")
     (logp.sum() - 0.01 * ent.mean()).backward()

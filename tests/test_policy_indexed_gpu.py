@@ -1,7 +1,6 @@
 """The indexed training kernels (bbx_pmlp_logprob_at / bbx_pmlp_grad_at and the two-layer pair), DeviceTrajectoryBuffer.get_index
 and PMLPPolicy.evaluate_at on the device.  The contract is bit-equality with the calls without _at on the gathered contiguous
 arrays obs[index], rows[index], actions[index]; one float64 check per depth holds the new entries to the reference itself."""
-import ctypes as C
 import functools
 
 import numpy as np
@@ -10,6 +9,7 @@ import pytest
 from tests import policy_cases as pc
 from tests import policy_grad_cases as gc
 from tests import policy2_grad_cases as g2
+from tests.fast_harness import ptr, stream_ptr, to_cuda
 
 pytestmark = pytest.mark.gpu
 _ids = lambda v: str(v).replace(" ", "")
@@ -20,20 +20,6 @@ ONE = [(1, (1,)), (12, (128,)), (33, (65,)), (64, (256,))]
 TWO = [(12, (128, 128)), (33, (65, 64)), (1, (1, 1))]
 S, R = 37, 40
 ROWS = (33, 0, 40, 1, 2, 45, -3, 17, 31, 32)      # the tile of 32 and around it, none, one, more than obs_rows
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _cuda(*arrays):
-    import torch
-    return [None if a is None else torch.tensor(np.ascontiguousarray(a), device="cuda") for a in arrays]      # (a copy: the sources are shared)
 
 
 def _hidden(weights):
@@ -82,10 +68,10 @@ def _logprob(weights, obs, rows, actions, index=None, entropy=True):
     (lp, ent), check = _banded((n, n), SENTINEL)
     name = "bbx_pmlp_logprob" if len(weights) == 2 else "bbx_pmlp2_logprob"
     if index is None:
-        _ffi.check(getattr(lib, name)(_p(obs), _p(rows), _p(actions), n, Rr, cols, prep, *_hidden(weights), _p(lp), _p(ent) if entropy else None, _stream()))
+        _ffi.check(getattr(lib, name)(ptr(obs), ptr(rows), ptr(actions), n, Rr, cols, prep, *_hidden(weights), ptr(lp), ptr(ent) if entropy else None, stream_ptr()))
     else:
-        _ffi.check(getattr(lib, name + "_at")(_p(obs), _p(rows), _p(actions), n_src, _p(index), n, Rr, cols, prep, *_hidden(weights), _p(lp),
-                                              _p(ent) if entropy else None, _stream()))
+        _ffi.check(getattr(lib, name + "_at")(ptr(obs), ptr(rows), ptr(actions), n_src, ptr(index), n, Rr, cols, prep, *_hidden(weights), ptr(lp),
+                                              ptr(ent) if entropy else None, stream_ptr()))
     torch.cuda.synchronize()
     lp, ent = check()
     if not entropy:
@@ -110,10 +96,10 @@ def _grad(weights, obs, rows, actions, glogp, gent, index=None):
     assert nfl > 0
     ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
     if index is None:
-        _ffi.check(getattr(lib, name)(_p(obs), _p(rows), _p(actions), n, Rr, cols, prep, *h, _p(glogp), _p(gent), _p(ws), *[_p(o) for o in outs], _stream()))
+        _ffi.check(getattr(lib, name)(ptr(obs), ptr(rows), ptr(actions), n, Rr, cols, prep, *h, ptr(glogp), ptr(gent), ptr(ws), *[ptr(o) for o in outs], stream_ptr()))
     else:
-        _ffi.check(getattr(lib, name + "_at")(_p(obs), _p(rows), _p(actions), n_src, _p(index), n, Rr, cols, prep, *h, _p(glogp), _p(gent), _p(ws),
-                                              *[_p(o) for o in outs], _stream()))
+        _ffi.check(getattr(lib, name + "_at")(ptr(obs), ptr(rows), ptr(actions), n_src, ptr(index), n, Rr, cols, prep, *h, ptr(glogp), ptr(gent), ptr(ws),
+                                              *[ptr(o) for o in outs], stream_ptr()))
     torch.cuda.synchronize()
     assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
     return check()
@@ -160,12 +146,12 @@ def _index_lists():
 @pytest.mark.parametrize("cols,hidden", ONE + TWO, ids=_ids)
 def test_logprob_and_entropy_equal_the_gathered_call_bit_for_bit(cols, hidden):
     w, obs, rows, actions = _source(cols, hidden)
-    d_obs, d_rows, d_act = _cuda(obs, rows, actions)
+    d_obs, d_rows, d_act = to_cuda(obs, rows, actions)
     for name, index in _index_lists():
         index = index.astype(np.int32)
-        d_idx, = _cuda(index)
+        d_idx, = to_cuda(index)
         lp, ent = _logprob(w, d_obs, d_rows, d_act, d_idx)
-        lp0, ent0 = _logprob(w, *_cuda(obs[index], rows[index], actions[index]))
+        lp0, ent0 = _logprob(w, *to_cuda(obs[index], rows[index], actions[index]))
         _same_bits((lp, ent), (lp0, ent0), name)
         assert lp.shape == (len(index),)
         if name == "identity":
@@ -194,25 +180,25 @@ def test_indices_out_of_range(cols, hidden):
     """-1, S and 2^31 - 1 among valid indices: NaN and NaN there, the other positions as without them; the gradients those of the
     list without them, whatever upstream gradients their positions carry.  The sources are exact-size allocations."""
     w, obs, rows, actions = _source(cols, hidden)
-    d_obs, d_rows, d_act = _cuda(obs, rows, actions)
+    d_obs, d_rows, d_act = to_cuda(obs, rows, actions)
     index, keep = _with_bad_indices()
-    lp, ent = _logprob(w, d_obs, d_rows, d_act, _cuda(index)[0])
+    lp, ent = _logprob(w, d_obs, d_rows, d_act, to_cuda(index)[0])
     assert np.isnan(lp[~keep]).all() and np.isnan(ent[~keep]).all()
-    lp0, ent0 = _logprob(w, d_obs, d_rows, d_act, _cuda(index[keep])[0])
+    lp0, ent0 = _logprob(w, d_obs, d_rows, d_act, to_cuda(index[keep])[0])
     _same_bits((lp[keep], ent[keep]), (lp0, ent0), "valid positions")
     rng = np.random.default_rng(11)
     glogp = rng.normal(size=len(index)).astype(np.float32); gent = rng.normal(size=len(index)).astype(np.float32)
     glogp[~keep] = np.array([np.nan, np.inf, -np.inf, 1e30, np.nan], dtype=np.float32)
     gent[~keep] = np.array([np.inf, np.nan, 1e30, np.nan, -np.inf], dtype=np.float32)
     for with_gent in (True, False):
-        got = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp, gent if with_gent else None, index))
-        want = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp[keep], gent[keep] if with_gent else None, index[keep]))
+        got = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp, gent if with_gent else None, index))
+        want = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp[keep], gent[keep] if with_gent else None, index[keep]))
         assert all(np.isfinite(x).all() for x in got) and any((x != 0).any() for x in got)
         # the same positions holding a recorded state without rows (which contributes nothing: tests/test_policy_grad_gpu.py) in
         # their place: the same n, the same partition — the same bits
         blank = index.copy(); blank[~keep] = 1
         assert rows[1] == 0
-        _same_bits(got, _grad(w, d_obs, d_rows, d_act, *_cuda(glogp, gent if with_gent else None, blank)), "a state without rows in their place")
+        _same_bits(got, _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp, gent if with_gent else None, blank)), "a state without rows in their place")
         # removed: the partition of the positions over waves follows n, which now differs — the same numbers added in another order,
         # so both are held to the float64 reference of the shorter list (and bit for bit below, where either list is one wave's)
         sel = index[keep]
@@ -224,12 +210,12 @@ def test_indices_out_of_range(cols, hidden):
         chk(want, want64, A, ref, what="without them")
     # a list short enough for one wave / one workgroup either way: the same partition, the same bits
     short, skeep = index[:4], keep[:4]
-    got = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp[:4], gent[:4], short))
-    want = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp[:4][skeep], gent[:4][skeep], short[skeep]))
+    got = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp[:4], gent[:4], short))
+    want = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp[:4][skeep], gent[:4][skeep], short[skeep]))
     _same_bits(got, want, "one wave")
     # nothing but indices out of range: zeros
     none = np.array(BAD, dtype=np.int32)
-    z = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp[~keep][:3], gent[~keep][:3], none))
+    z = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp[~keep][:3], gent[~keep][:3], none))
     assert all((x == 0).all() for x in z)
 
 
@@ -260,13 +246,13 @@ def test_gradients_equal_the_gathered_call_bit_for_bit(cols, hidden, n):
     index = _grad_index(n, n + 3)
     rng = np.random.default_rng(n + 1)
     glogp = rng.normal(size=n).astype(np.float32); gent = rng.normal(size=n).astype(np.float32)
-    d_obs, d_rows, d_act = _cuda(obs, rows, actions)
-    gathered = _cuda(obs[index], rows[index], actions[index])
+    d_obs, d_rows, d_act = to_cuda(obs, rows, actions)
+    gathered = to_cuda(obs[index], rows[index], actions[index])
     for ge in (gent, None):
-        got = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp, ge, index))
-        want = _grad(w, *gathered, *_cuda(glogp, ge))
+        got = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp, ge, index))
+        want = _grad(w, *gathered, *to_cuda(glogp, ge))
         _same_bits(got, want, "gent" if ge is not None else "NULL gent")
-        again = _grad(w, d_obs, d_rows, d_act, *_cuda(glogp, ge, index))
+        again = _grad(w, d_obs, d_rows, d_act, *to_cuda(glogp, ge, index))
         _same_bits(again, got, "second call")
     assert rows[0] == 33 and 0 <= actions[0] < 33 and index[0] == 0
     live = np.clip(rows, 0, 136)[index]
@@ -280,7 +266,7 @@ def test_gradients_equal_the_gathered_call_bit_for_bit(cols, hidden, n):
 def test_no_positions_zero_the_gradients(cols, hidden):
     import torch
     w, obs, rows, actions = _source(cols, hidden)
-    d_obs, d_rows, d_act = _cuda(obs, rows, actions)
+    d_obs, d_rows, d_act = to_cuda(obs, rows, actions)
     empty = torch.zeros(0, dtype=torch.int32, device="cuda"); none = torch.zeros(0, device="cuda")
     z = _grad(w, d_obs, d_rows, d_act, none, none, empty)
     assert len(z) == (4 if len(hidden) == 1 else 6) and all((x == 0).all() for x in z)
@@ -293,7 +279,7 @@ def test_gradients_against_float64(cols, hidden):
     index = np.array([0, 9, 2, 30, 9], dtype=np.int32)               # rows 33, 32, 40, 33, 32; one state twice
     rng = np.random.default_rng(12)
     glogp = rng.normal(size=5).astype(np.float32); gent = rng.normal(size=5).astype(np.float32)
-    got = _grad(w, *_cuda(obs, rows, actions, glogp, gent, index))
+    got = _grad(w, *to_cuda(obs, rows, actions, glogp, gent, index))
     ref = pc.reference(w, obs[index], rows[index])
     if len(hidden) == 1:
         want, A = gc.reference_grad(w, obs[index], rows[index], actions[index], glogp, gent, ref=ref)
@@ -304,7 +290,7 @@ def test_gradients_against_float64(cols, hidden):
         print("ratios indexed %s r_g=%.3f" % (pc.label(cols, hidden), g2.grad_ratio(got, want, A, ref)))
         g2.check_grads(got, want, A, ref, what="indexed")
     assert any(np.abs(x).max() > 0 for x in want)
-    lp, ent = _logprob(w, *_cuda(obs, rows, actions, index))
+    lp, ent = _logprob(w, *to_cuda(obs, rows, actions, index))
     rl, rh, _ = gc.reference_eval(w, obs[index], rows[index], actions[index], ref=ref)
     assert (np.abs(lp - rl) <= ref.tol()).all()
     assert (np.abs(ent - rh) <= (gc.entropy_tol(ref) if len(hidden) == 1 else g2.entropy_tol(ref))).all()

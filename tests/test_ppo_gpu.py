@@ -9,7 +9,8 @@ import pytest
 
 from tests import policy_cases as pc
 from tests import ppo_cases as pp
-from tests.test_policy_indexed_gpu import GUARD, SENTINEL, _banded, _bits, _cuda, _grad, _hidden, _logprob, _p, _policy, _prepared, _same_bits, _stream
+from tests.test_policy_indexed_gpu import GUARD, SENTINEL, _banded, _bits, _grad, _hidden, _logprob, _policy, _prepared, _same_bits
+from tests.fast_harness import ptr, stream_ptr, to_cuda
 
 pytestmark = pytest.mark.gpu
 _ids = lambda v: str(v).replace(" ", "")
@@ -40,11 +41,11 @@ def _ppo(weights, obs, rows, actions, old, adv, loss, index=None, outputs=True):
     ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
     stats = torch.full((6 + 2 * GUARD,), float("nan"), dtype=torch.float64, device="cuda")
     mode, scale, eps, ent_coef, c_kl = loss.args()
-    src = (_p(obs), _p(rows), _p(actions)) + ((n,) if index is None else (n_src, _p(index), n)) + (Rr, cols, prep) + tuple(h)
+    src = (ptr(obs), ptr(rows), ptr(actions)) + ((n,) if index is None else (n_src, ptr(index), n)) + (Rr, cols, prep) + tuple(h)
     fn = getattr(lib, name + "_grad" + ("" if index is None else "_at"))
-    _ffi.check(fn(*src, _p(old), _p(adv), mode, C.c_float(scale), C.c_float(eps), C.c_float(ent_coef), C.c_float(c_kl),
-                  _p(lp) if outputs else None, _p(ent) if outputs else None, _p(coef), C.c_void_p(stats.data_ptr() + 8 * GUARD), _p(ws),
-                  *[_p(g) for g in grads], _stream()))
+    _ffi.check(fn(*src, ptr(old), ptr(adv), mode, C.c_float(scale), C.c_float(eps), C.c_float(ent_coef), C.c_float(c_kl),
+                  ptr(lp) if outputs else None, ptr(ent) if outputs else None, ptr(coef), C.c_void_p(stats.data_ptr() + 8 * GUARD), ptr(ws),
+                  *[ptr(g) for g in grads], stream_ptr()))
     torch.cuda.synchronize()
     host = ws.cpu().numpy()
     assert np.isnan(host[nfl:]).all(), "the workspace was overrun"
@@ -89,7 +90,7 @@ def test_call_equals_its_parts_bit_for_bit(cols, hidden, mode):
     index = _index(3 * S + 1)
     old, adv, *_ = _inputs(cols, hidden, index)
     loss = pp.Loss(mode, len(index), c_kl=0.3)
-    d_obs, d_rows, d_act, d_idx, d_old, d_adv = _cuda(obs, rows, actions, index, old, adv)
+    d_obs, d_rows, d_act, d_idx, d_old, d_adv = to_cuda(obs, rows, actions, index, old, adv)
     got = _ppo(w, d_obs, d_rows, d_act, d_old, d_adv, loss, d_idx)
     # logprobs / entropy: bbx_pmlp[2]_logprob_at's
     lp, ent = _logprob(w, d_obs, d_rows, d_act, d_idx)
@@ -97,7 +98,7 @@ def test_call_equals_its_parts_bit_for_bit(cols, hidden, mode):
     assert np.isnan(lp).sum() > 3 and (lp == 0).any()                 # bad indices, bad actions, a state without rows
     # gradients: bbx_pmlp[2]_grad_at's on the coefficients the call wrote
     n = len(index)
-    d_gl, d_ge = _cuda(got["coef"][:n], got["coef"][n:])
+    d_gl, d_ge = to_cuda(got["coef"][:n], got["coef"][n:])
     _same_bits(got["grads"], _grad(w, d_obs, d_rows, d_act, d_gl, d_ge, d_idx), "grad_at on coef")
     if cols >= 12:
         assert any((g != 0).any() for g in got["grads"]) and all(np.isfinite(g).all() for g in got["grads"])
@@ -109,17 +110,17 @@ def test_call_equals_its_parts_bit_for_bit(cols, hidden, mode):
     # the plain call on the gathered arrays (indices in range: an index out of range has no gathered counterpart)
     index = _index(3 * S + 1, bad=False)
     old, adv, *_ = _inputs(cols, hidden, index)
-    d_idx, d_old, d_adv = _cuda(index, old, adv)
+    d_idx, d_old, d_adv = to_cuda(index, old, adv)
     at = _ppo(w, d_obs, d_rows, d_act, d_old, d_adv, loss, d_idx)
-    plain = _ppo(w, *_cuda(obs[index], rows[index], actions[index]), d_old, d_adv, loss)
+    plain = _ppo(w, *to_cuda(obs[index], rows[index], actions[index]), d_old, d_adv, loss)
     for k in ("logprobs", "entropy", "coef", "u", "H", "d"):
         _same_bits((at[k],), (plain[k],), "gathered: " + k)
     assert np.array_equal(at["flags"], plain["flags"]) and np.array_equal(_stat_bits(at["stats"]), _stat_bits(plain["stats"]))
     _same_bits(at["grads"], plain["grads"], "gathered: gradients")
-    lp0, ent0 = _logprob(w, *_cuda(obs[index], rows[index], actions[index]))
+    lp0, ent0 = _logprob(w, *to_cuda(obs[index], rows[index], actions[index]))
     _same_bits((plain["logprobs"], plain["entropy"]), (lp0, ent0), "logprob")
-    d_gl, d_ge = _cuda(plain["coef"][:n], plain["coef"][n:])
-    _same_bits(plain["grads"], _grad(w, *_cuda(obs[index], rows[index], actions[index]), d_gl, d_ge), "grad on coef")
+    d_gl, d_ge = to_cuda(plain["coef"][:n], plain["coef"][n:])
+    _same_bits(plain["grads"], _grad(w, *to_cuda(obs[index], rows[index], actions[index]), d_gl, d_ge), "grad on coef")
 
 
 # ---- 2. coefficients, terms and statistics against float64 -------------------------------------------------------------------
@@ -128,7 +129,7 @@ def _check_against_float64(cols, hidden, mode, index, far, what):
     old, adv, new64, H64, tol, etol = _inputs(cols, hidden, index, far)
     n = len(index)
     loss = pp.Loss(mode, n, c_kl=0.3)
-    got = _ppo(w, *_cuda(obs, rows, actions, old, adv), loss, _cuda(index)[0])
+    got = _ppo(w, *to_cuda(obs, rows, actions, old, adv), loss, to_cuda(index)[0])
     u64, gl64, ge64, clipped, counted, r64, d64 = pp.reference_loss(loss, new64, H64, old, adv)
     st64 = pp.reference_stats(loss, new64, H64, old, adv)
     gl, ge = got["coef"][:n].astype(np.float64), got["coef"][n:].astype(np.float64)
@@ -181,7 +182,7 @@ def test_statistics_around_the_partition_boundaries(cols, hidden, n):
     if n == 0:
         empty = torch.zeros(0, dtype=torch.int32, device="cuda"); none = torch.zeros(0, device="cuda")
         for index in (empty, None):
-            src = _cuda(obs, rows, actions) if index is not None else (torch.zeros((0,) + obs.shape[1:], dtype=torch.int32, device="cuda"), empty, empty)
+            src = to_cuda(obs, rows, actions) if index is not None else (torch.zeros((0,) + obs.shape[1:], dtype=torch.int32, device="cuda"), empty, empty)
             got = _ppo(w, *src, none, none, pp.Loss(1, 0), index)
             assert (got["stats"] == 0).all() and all((g == 0).all() for g in got["grads"])
         return
@@ -206,13 +207,13 @@ def test_first_epoch_coefficients_are_exact(cols, hidden):
     """old_logprobs are what bbx_pmlp[2]_logprob_at just returned: r = 1, and every counted gl is -(scale A), bit for bit."""
     w, obs, rows, actions = pp.source(cols, hidden)
     index = _index(N1)
-    d_obs, d_rows, d_act, d_idx = _cuda(obs, rows, actions, index)
+    d_obs, d_rows, d_act, d_idx = to_cuda(obs, rows, actions, index)
     lp, ent = _logprob(w, d_obs, d_rows, d_act, d_idx)
     old = np.nan_to_num(lp, nan=0.0).astype(np.float32)
     adv = pp.advantages(N1, cols)
     for mode in (1, 2):
         loss = pp.Loss(mode, N1, ent_coef=ENT1, c_kl=0.0, scale=SCALE1)
-        got = _ppo(w, d_obs, d_rows, d_act, *_cuda(old, adv), loss, d_idx)
+        got = _ppo(w, d_obs, d_rows, d_act, *to_cuda(old, adv), loss, d_idx)
         counted = ~np.isnan(lp)
         want = -(np.float32(SCALE1) * adv)
         assert counted.sum() >= N1 - 8 and (~counted).any()
@@ -235,8 +236,8 @@ def test_first_epoch_ppo_step_at_leaves_the_gradients_of_the_autograd_loss(hidde
     import torch
     w, obs, rows, actions = pp.source(12, hidden)
     index = _first_epoch_index()
-    st, rw, act, idx = _cuda(obs, rows, actions, index)
-    adv = _cuda(pp.advantages(N1, 3))[0]
+    st, rw, act, idx = to_cuda(obs, rows, actions, index)
+    adv = to_cuda(pp.advantages(N1, 3))[0]
     pol, ref = _policy(w), _policy(w)
     with torch.no_grad():
         old, _ = ref.evaluate_at(st, act, rw, idx)

@@ -14,7 +14,7 @@ import functools
 
 import numpy as np
 
-from oracle import ffi
+from tests import oracle_walk as ow
 
 DIST, K, T = "3-20-10-weighted", 2, 256
 SEEDS = ((1000, 7), (1016, 23), (1028, 35), (1168, 175), (1274, 281), (1464, 471), (5198, 4205), (11922, 10929))
@@ -28,22 +28,27 @@ LAUNCH = 16                                                  # the GPU test comp
 CUT = 32                                                     # ... and starts value() and policy rollouts every CUT steps
 
 
-@functools.lru_cache(maxsize=None)
-def walk(seed, aseed, nsteps=T):
-    """nsteps steps of the hash agent with auto-reset on the oracle: ({situation: steps that show it}, [(basis words, pair
-    list, reducer order) after every LAUNCH steps], the environment as it stands afterwards, [a copy of the environment after
-    every CUT steps])."""
-    from oracle.trace import poly_words
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-    seen = {k: [] for k in SITUATIONS}
-    states, cuts = [], []
-    for t in range(nsteps):
-        nP, g = o.nP, o.nG
-        a = ffi.agent_action(aseed, t, nP)
-        o.step(a)
+class Inserts:
+    """walk()'s observer: where every insertion puts the new element and which pair its step selected, and the state the
+    run stands in after every LAUNCH and CUT steps — left(o, t), the state t steps leave with a reset done, which is what
+    the next step's before hook sees."""
+
+    def __init__(self):
+        self.seen = {k: [] for k in SITUATIONS}
+        self.states, self.cuts = [], []
+
+    def left(self, o, t):
+        if t and t % LAUNCH == 0:
+            self.states.append(ow.snapshot(o))
+        if t and t % CUT == 0:
+            self.cuts.append(o.copy())
+
+    def before(self, o, t, a):
+        self.left(o, t)
+        self.nP, self.g = o.nP, o.nG
+
+    def after(self, o, t, a, reward):
+        nP, g, seen = self.nP, self.g, self.seen
         if o.nG == g + 1:                                        # an insertion: the new element is basis index g
             pos = int(np.flatnonzero(o.reducer_order() == g)[0])
             where = "front" if pos == 0 else ("end" if pos == g else "inside")
@@ -58,13 +63,17 @@ def walk(seed, aseed, nsteps=T):
                 seen["first_eq64"].append(t)
             if nP == 64 and a == 63:
                 seen["last_eq64"].append(t)
-        if o.nP == 0:
-            o.reset()
-        if (t + 1) % LAUNCH == 0:
-            states.append((np.concatenate([poly_words(*o.poly(i)) for i in range(o.nG)]), o.pairs(), o.reducer_order()))
-        if (t + 1) % CUT == 0:
-            cuts.append(o.copy())
-    return seen, states, o, cuts
+
+
+@functools.lru_cache(maxsize=None)
+def walk(seed, aseed, nsteps=T):
+    """nsteps steps of the hash agent with auto-reset on the oracle: ({situation: steps that show it}, [the state
+    (oracle_walk.Snapshot: basis words, pair list, reducer order) after every LAUNCH steps], the environment as it stands
+    afterwards, [a copy of the environment after every CUT steps])."""
+    ins = Inserts()
+    o = ow.walk(DIST, seed, aseed, nsteps, ins)[0]
+    ins.left(o, nsteps)
+    return ins.seen, ins.states, o, ins.cuts
 
 
 def test_every_situation_is_reached():

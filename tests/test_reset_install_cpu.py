@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import ffi
+from tests.oracle_walk import grevlex_key
 
 NV = 3
 
@@ -36,14 +37,9 @@ def closed_form_pairs(L):
     return out
 
 
-def _grevlex_key(e):
-    # larger degree is greater; at equal degree the SMALLER exponent of the last variable wins (and so on down)
-    return (int(sum(e)),) + tuple(-int(x) for x in reversed(e))
-
-
 def closed_form_rank(L):
     """rank(f) = #{k : LM_k < LM_f} + #{k < f : LM_k == LM_f} (std::upper_bound insertion)."""
-    keys = [_grevlex_key(e) for e in L]
+    keys = [grevlex_key(e) for e in L]
     return [sum(1 for k in range(len(L)) if keys[k] < keys[f]) + sum(1 for k in range(f) if keys[k] == keys[f]) for f in range(len(L))]
 
 
@@ -57,7 +53,7 @@ def sequential(bo, F):
 def _check_ideal(bo, F):
     L = np.array([f[0][1][:NV] for f in F], dtype=np.int64)
     assert closed_form_pairs(L) == sequential(bo, F)
-    want = sorted(range(len(F)), key=lambda f: _grevlex_key(L[f]))          # stable sort by lead monomial
+    want = sorted(range(len(F)), key=lambda f: grevlex_key(L[f]))          # stable sort by lead monomial
     rank = closed_form_rank(L)
     assert [want.index(f) for f in range(len(F))] == rank
 

@@ -7,6 +7,7 @@ import pytest
 
 from oracle import ffi
 from oracle.trace import fnv64
+from tests.fast_harness import make_env
 from tests.test_gpu_parity import _state_words
 
 pytestmark = pytest.mark.gpu
@@ -14,11 +15,7 @@ DIST = "3-20-10-weighted"
 
 
 def _env(B, caps=None, k=2):
-    from deepgroebner_amd import VecLeadMonomialsEnv
-    env = VecLeadMonomialsEnv(DIST, batch=B, k=k, caps=caps)
-    env.seed(np.arange(B) + 1000); env.seed_agent(np.arange(B)); env.reset(); env.accounting(False)
-    env.persistent(True)
-    return env
+    return make_env(DIST, np.arange(B) + 1000, k, caps=caps, lean=True, agent=np.arange(B), persistent=True)
 
 
 def _check(env, want, rows=None, obs=None, sample_every=37):

@@ -10,10 +10,9 @@ import functools
 import os
 import subprocess
 
-import numpy as np
 import pytest
 
-from oracle import ffi
+from tests import oracle_walk as ow
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIST, K, T, P = "3-20-10-weighted", 2, 128, 32003
@@ -46,27 +45,20 @@ def walk(seed, aseed, nsteps=T):
     """nsteps steps of the hash agent with auto-reset on the oracle: (the environment as it stands afterwards, per-step
     rewards, done flags, the selections as (step, what the first member is, what the second is), the number of single-term
     insertions) — a member is "none" (no tail), "monic" (tail, lead coefficient 1) or "scaled" (tail, another one)."""
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-
-    def kind(g):
+    def kind(o, g):
         c = o.poly(int(g))[0]
         return "none" if len(c) == 1 else ("monic" if c[0] == 1 else "scaled")
 
-    rewards, dones, picks, single = [], [], [], 0
-    for t in range(nsteps):
-        a = ffi.agent_action(aseed, t, o.nP)
+    def before(o, t, a):
         i, j = o.pairs()[a]
-        picks.append((t, kind(i), kind(j)))
-        nG0 = o.nG
-        rewards.append(o.step(a))
-        single += int(o.nG > nG0 and len(o.poly(nG0)[0]) == 1)
-        dones.append(o.nP == 0)
-        if o.nP == 0:
-            o.reset()
-    return o, np.array(rewards), np.array(dones), picks, single
+        return t, kind(o, i), kind(o, j), o.nG
+
+    def after(o, t, a, r):                                   # a single-term element entered: the new one is the last
+        return o.nG, len(o.poly(o.nG - 1)[0])
+
+    o, rewards, dones, seen = ow.walk(DIST, seed, aseed, nsteps, (before, after))
+    single = sum(int(nG1 > nG0 and terms == 1) for (_, _, _, nG0), (nG1, terms) in seen)
+    return o, rewards, dones, [pick[:3] for pick, _ in seen], single
 
 
 def test_seeds_select_elements_without_tail_on_both_sides():

@@ -10,7 +10,7 @@ import functools
 
 import numpy as np
 
-from oracle import ffi
+from tests import oracle_walk as ow
 
 DIST, K, T, P = "3-20-10-weighted", 2, 256, 32003
 SEEDS = ((1000, 7), (1001, 8), (1002, 9), (1003, 10), (1006, 13), (1010, 17), (1012, 19), (1015, 22))
@@ -18,11 +18,6 @@ KINDS = ("first_leads", "second_leads", "nonzero_sum", "zero_sum", "first_taille
 # first occurrences the search reported for (1000, 7), re-asserted below
 KNOWN_FIRST = {"first_leads": 0, "second_leads": 1, "zero_sum": 8, "second_tailless": 41, "both_tailless": 48, "nonzero_sum": 144,
                "first_tailless": 209}
-
-
-def _grevlex_key(e):
-    # larger degree is greater; at equal degree the SMALLER exponent of the last variable wins (and so on down)
-    return (int(sum(e)),) + tuple(-int(x) for x in reversed(e))
 
 
 def pair_kind(o, i, j):
@@ -34,31 +29,24 @@ def pair_kind(o, i, j):
         return "both_tailless" if not ti and not tj else ("first_tailless" if not ti else "second_tailless")
     lcm = np.maximum(ei[0], ej[0])
     am, bm = ei[1] + lcm - ei[0], ej[1] + lcm - ej[0]
-    if _grevlex_key(am) != _grevlex_key(bm):
-        return "first_leads" if _grevlex_key(am) > _grevlex_key(bm) else "second_leads"
+    if ow.grevlex_key(am) != ow.grevlex_key(bm):
+        return "first_leads" if ow.grevlex_key(am) > ow.grevlex_key(bm) else "second_leads"
     ac = int(ci[1]) * pow(int(ci[0]), P - 2, P) % P
     bc = (P - int(cj[1]) * pow(int(cj[0]), P - 2, P) % P) % P
     return "zero_sum" if (ac + bc) % P == 0 else "nonzero_sum"
+
+
+def selected_kind(o, t, action):
+    """walk()'s before hook: the kind of the pair the step selects"""
+    return pair_kind(o, *o.pairs()[action])
 
 
 @functools.lru_cache(maxsize=None)
 def walk(seed, aseed, nsteps=T):
     """nsteps steps of the hash agent with auto-reset on the oracle: (the environment as it stands afterwards, per-step
     rewards, done flags, the kind of every selected pair)."""
-    bo = ffi.load("bo")
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-    rewards, dones, kinds = [], [], []
-    for t in range(nsteps):
-        a = ffi.agent_action(aseed, t, o.nP)
-        i, j = o.pairs()[a]
-        kinds.append(pair_kind(o, i, j))
-        rewards.append(o.step(a))
-        dones.append(o.nP == 0)
-        if o.nP == 0:
-            o.reset()
-    return o, np.array(rewards), np.array(dones), kinds
+    o, rewards, dones, seen = ow.walk(DIST, seed, aseed, nsteps, (selected_kind, None))
+    return o, rewards, dones, [kind for kind, _ in seen]
 
 
 def test_every_seed_selects_pairs_of_every_kind():
@@ -76,20 +64,8 @@ def test_first_occurrences_on_the_first_seed():
 
 def test_a_zero_sum_ends_the_step_without_a_reduction():
     """h = 0 before any reduction: the step adds nothing to the basis and counts one addition (reward -1)."""
-    bo = ffi.load("bo")
-    seed, aseed = SEEDS[0]
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
-    seen = 0
-    for t in range(T):
-        a = ffi.agent_action(aseed, t, o.nP)
-        kind = pair_kind(o, *o.pairs()[a])
-        nG = o.nG
-        r = o.step(a)
-        if kind == "zero_sum":
-            assert o.nG == nG and r == -1.0, t
-            seen += 1
-        if o.nP == 0:
-            o.reset()
-    assert seen >= 1
+    seen = ow.walk(DIST, *SEEDS[0], T, (lambda o, t, a: (pair_kind(o, *o.pairs()[a]), o.nG), lambda o, t, a, r: (o.nG, r)))[3]
+    zero = [(t, nG, after) for t, ((kind, nG), after) in enumerate(seen) if kind == "zero_sum"]
+    for t, nG, after in zero:
+        assert after == (nG, -1.0), t
+    assert len(zero) >= 1

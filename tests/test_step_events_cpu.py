@@ -9,6 +9,7 @@ import numpy as np
 
 from oracle import ffi
 from oracle.trace import run_trace
+from tests.oracle_walk import agent_seeds                    # (the twins import it from here)
 
 K = 2
 # consecutive launches: they begin and end at t % 64 of 0, 1, 63 and 64
@@ -22,10 +23,6 @@ NO_RESET = {"3-20-10-weighted": ((3000, 3001, 3002, 3003, 3004, 3005, 3006, 3007
 # a register/LDS class capped at 16 basis elements (caps={"lds_max_basis": 16}): environments leave it mid-launch
 LEAVE_SEEDS, LEAVE_LAUNCHES, LEAVE_CAP = (3000, 3001, 3002, 3003, 3004, 3005), (100, 100, 100), 16
 MAILBOX_SEED, MAILBOX_STEPS = 77, 130
-
-
-def agent_seeds(seeds):
-    return [s - 2993 for s in seeds]
 
 
 @functools.lru_cache(maxsize=None)

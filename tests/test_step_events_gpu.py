@@ -13,28 +13,13 @@ from oracle.trace import fnv64, run_trace
 from tests.test_gpu_parity import _state_words
 from tests.test_step_events_cpu import (ENDS, K, LEAVE_LAUNCHES, LEAVE_SEEDS, MAILBOX_SEED, MAILBOX_STEPS, NO_RESET, SCHEDULE,
                                         TRACED_SEEDS, agent_seeds, traces, walks)
+from tests.fast_harness import KEYS, assert_trace_equal, make_env, rollout_buffers, stream
 
 pytestmark = pytest.mark.gpu
-KEYS = (("action", "action"), ("reward", "reward"), ("rows", "nP"), ("basis_size", "nG"), ("done", "done"), ("obs_hash", "obs_hash"),
-        ("pairs_hash", "pairs_hash"), ("newpoly_hash", "newpoly_hash"))
 
 
-def _env(dist, seeds, caps=None, trace=0):
-    from deepgroebner_amd import VecLeadMonomialsEnv
-    env = VecLeadMonomialsEnv(dist, batch=len(seeds), k=K, caps=caps)
-    env.seed(np.array(seeds))
-    env.seed_agent(np.array(agent_seeds(seeds)))
-    if trace:
-        env.trace_enable(trace)
-    env.reset()
-    return env
-
-
-def _same_trace(got, want, t0, n, where):
-    for key, wkey in KEYS:
-        w = np.asarray(want[wkey])[t0:t0 + n]
-        g = got[key].astype(w.dtype)
-        assert np.array_equal(g, w), where + (key, "first difference at step", t0 + int(np.flatnonzero(g != w)[0]))
+def _env(dist, seeds, **kw):
+    return make_env(dist, seeds, K, agent=agent_seeds(seeds), **kw)
 
 
 def _same_outputs(env, out, recs, where):
@@ -59,7 +44,7 @@ def test_launch_lengths_against_the_64_step_phase(dist):
     for i, n in enumerate(SCHEDULE):
         out = env.rollout("random", n, auto_reset=True)
         for e in range(len(seeds)):
-            _same_trace(env.trace_read(e, 0, n), want[e], t0, n, (dist, "launch", i, "environment", e))
+            assert_trace_equal(env.trace_read(e, 0, n), want[e], KEYS, (dist, "launch", i, "environment", e), t0, n)
         _same_outputs(env, out, [r[i] for r in recs], (dist, "launch", i))
         t0 += n
     assert (env.stats()[:, 0] == ENDS[-1]).all()
@@ -84,7 +69,7 @@ def test_no_auto_reset_traced(dist):
         out = env.rollout("random", n, auto_reset=False)
         for e in range(len(seeds)):
             took = recs[e][i]["steps"]
-            _same_trace(env.trace_read(e, 0, max(took, 1))[:took], want[e], t0[e], took, (dist, "launch", i, "environment", e))
+            assert_trace_equal(env.trace_read(e, 0, max(took, 1))[:took], want[e], KEYS, (dist, "launch", i, "environment", e), t0[e], took)
             t0[e] += took
         _same_outputs(env, out, [r[i] for r in recs], (dist, "launch", i))
         assert np.array_equal(env.stats()[:, 0], np.array([r[i]["total"] for r in recs])), (dist, i)
@@ -107,11 +92,10 @@ def test_no_auto_reset_lean(dist):
     import torch
     seeds, launches = NO_RESET[dist]
     B = len(seeds)
-    env = _env(dist, seeds)
-    env.accounting(False)
+    env = _env(dist, seeds, lean=True)
     recs = walks(dist, seeds, launches, False)
     rows = torch.zeros(B, dtype=torch.int32, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream()
     bo = ffi.load("bo")
     total = 0
     for i, n in enumerate(launches):
@@ -134,7 +118,7 @@ def test_leaving_the_class_in_the_middle_of_a_launch():
     for i, n in enumerate(LEAVE_LAUNCHES):
         out = env.rollout("random", n, auto_reset=True)
         for e in range(len(LEAVE_SEEDS)):
-            _same_trace(env.trace_read(e, 0, n), want[e], t0, n, ("launch", i, "environment", e))
+            assert_trace_equal(env.trace_read(e, 0, n), want[e], KEYS, ("launch", i, "environment", e), t0, n)
         _same_outputs(env, out, [r[i] for r in recs], ("launch", i))
         t0 += n
     assert (env.stats()[:, 0] == T).all()
@@ -154,15 +138,11 @@ def test_persistent_sessions_across_the_phase(name):
     seeds = tuple(range(3000, 3000 + B))
     bo = ffi.load("bo")
     want = bo.run_random_many(dist, K, seeds, agent_seeds(seeds), sum(calls), True, 0)
-    s = torch.cuda.current_stream().cuda_stream
+    s = stream()
     outs = []
     for persistent in (True, False):
-        env = _env(dist, seeds)
-        env.accounting(False)
-        env.persistent(persistent)
-        obs = torch.zeros((B, R, env.cols), dtype=torch.int32, device="cuda")
-        rew = torch.zeros(B, dtype=torch.float64, device="cuda"); done = torch.zeros(B, dtype=torch.uint8, device="cuda")
-        rows = torch.zeros(B, dtype=torch.int32, device="cuda")
+        env = _env(dist, seeds, lean=True, persistent=persistent)
+        rew, done, rows, obs = rollout_buffers(B, R, env.cols, fill=0)
         for i, n in enumerate(calls):
             env.rollout_device("random", n, True, s, rew, done, rows, obs, R, False, True)
             if name == "10x20" and i == 4:                     # (100 steps issued: the join falls between 64 and 128)

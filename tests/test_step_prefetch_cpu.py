@@ -10,7 +10,7 @@ import functools
 
 import numpy as np
 
-from oracle import ffi
+from tests import oracle_walk as ow
 from tests.test_step_events_cpu import K, agent_seeds, walks
 
 DIST = "3-20-10-weighted"
@@ -36,21 +36,21 @@ CASE_SEEDS = {
 def walk(seed, steps=T):
     """The oracle under the hash agent with auto-reset, one dict of arrays: per step t the row count the step found (nP0), the
     action, the pair (i, j) it selected, |G| before and after, the row count it left (0: the episode ended, a reset follows)."""
-    bo = ffi.load("bo")
-    a = agent_seeds([seed])[0]
-    o = bo.env(DIST)
-    o.seed(seed)
-    o.reset()
     rec = {k: np.zeros(steps, dtype=np.int64) for k in ("nP0", "action", "i", "j", "nG0", "nG1", "nP1", "first_nP")}
-    for t in range(steps):
-        nP0, nG0 = o.nP, o.nG
-        act = ffi.agent_action(a, t, nP0)
-        i, j = o.pairs()[act]
-        o.step(act)
-        rec["nP0"][t], rec["action"][t], rec["i"][t], rec["j"][t], rec["nG0"][t], rec["nG1"][t], rec["nP1"][t] = nP0, act, i, j, nG0, o.nG, o.nP
-        if o.nP == 0:
-            o.reset()
-            rec["first_nP"][t] = o.nP
+
+    def left(o, t):                                  # (the new episode's row count: what the step behind a reset finds)
+        if t and rec["nP1"][t - 1] == 0:
+            rec["first_nP"][t - 1] = o.nP
+
+    def before(o, t, act):
+        left(o, t)
+        rec["nP0"][t], rec["action"][t], rec["nG0"][t] = o.nP, act, o.nG
+        rec["i"][t], rec["j"][t] = o.pairs()[act]
+
+    def after(o, t, act, reward):
+        rec["nG1"][t], rec["nP1"][t] = o.nG, o.nP
+
+    left(ow.walk(DIST, seed, agent_seeds([seed])[0], steps, (before, after))[0], steps)
     return rec
 
 
@@ -143,19 +143,10 @@ def test_sugar_bound_is_out_of_reach_of_the_class():
     generators' degree by its middle number; over a walk the sugar stays within a small multiple of it.  Measured here: the
     largest degree a selected pair's lcm reaches on the seeds of this file — four orders of magnitude below the bound, so the
     refusal cannot be produced through the API and its path was checked by reading."""
-    bo = ffi.load("bo")
-    worst = 0
-    for s in all_seeds()[:4]:
-        a = agent_seeds([s])[0]
-        o = bo.env(DIST)
-        o.seed(s)
-        o.reset()
-        for t in range(T):
-            act = ffi.agent_action(a, t, o.nP)
-            i, j = o.pairs()[act]
-            li, lj = o.poly(int(i))[1][0], o.poly(int(j))[1][0]
-            worst = max(worst, int(np.maximum(li, lj).sum()), o.poly_sugar(int(i)), o.poly_sugar(int(j)))
-            o.step(act)
-            if o.nP == 0:
-                o.reset()
+    def degree(o, t, act):
+        i, j = o.pairs()[act]
+        li, lj = o.poly(int(i))[1][0], o.poly(int(j))[1][0]
+        return max(int(np.maximum(li, lj).sum()), o.poly_sugar(int(i)), o.poly_sugar(int(j)))
+
+    worst = max(d for s in all_seeds()[:4] for d, _ in ow.walk(DIST, s, agent_seeds([s])[0], T, (degree, None))[3])
     assert 0 < worst < 65535 // 100, worst

@@ -11,15 +11,10 @@ from oracle import ffi
 from tests.test_step_events_cpu import K, agent_seeds, walks
 from tests.test_step_events_gpu import _env, _lean_check
 from tests.test_step_prefetch_cpu import CASE_SEEDS, DIST, LAUNCHES, LEAVE_CAP, T, all_seeds
+from tests.fast_harness import rollout_buffers, stream
 
 pytestmark = pytest.mark.gpu
 R = 128                                              # rows of the caller's observation block (|P| stays below on these seeds)
-
-
-def _buffers(B, cols):
-    import torch
-    return (torch.zeros(B, dtype=torch.float64, device="cuda"), torch.zeros(B, dtype=torch.uint8, device="cuda"),
-            torch.zeros(B, dtype=torch.int32, device="cuda"), torch.full((B, R, cols), -7, dtype=torch.int32, device="cuda"))
 
 
 def _same_as_walk(bufs, recs, where):
@@ -35,18 +30,15 @@ def _same_as_walk(bufs, recs, where):
 def _run(seeds, caps, persistent, joins):
     """LAUNCHES as consecutive rollout_device calls; outputs are compared wherever the stream is joined (one kernel per launch:
     behind every call)."""
-    import torch
     assert seeds and len(seeds) <= 256
     bo = ffi.load("bo")
     recs = walks(DIST, seeds, LAUNCHES, True)
-    s = torch.cuda.current_stream().cuda_stream
-    env = _env(DIST, seeds, caps=caps)
-    env.accounting(False)
-    env.persistent(persistent)
-    bufs = _buffers(len(seeds), env.cols)
+    s = stream()
+    env = _env(DIST, seeds, caps=caps, lean=True, persistent=persistent)
+    bufs = rollout_buffers(len(seeds), R, env.cols, fill=-7)
     total = 0
     for i, n in enumerate(LAUNCHES):
-        env.rollout_device("random", n, True, s, bufs[0], bufs[1], bufs[2], bufs[3], R, False, True)
+        env.rollout_device("random", n, True, s, *bufs, R, False, True)
         total += n
         if not persistent or i in joins:
             if persistent:

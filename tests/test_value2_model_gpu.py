@@ -14,24 +14,11 @@ from tests import policy_cases as pc
 from tests import policy_grad_cases as gc
 from tests import value2_cases as v2
 from tests import value_cases as vc
+from tests.fast_harness import ptr, stream_ptr, to_cuda
 
 pytestmark = pytest.mark.gpu
 _ids = lambda v: str(v).replace(" ", "")
 GUARD = 64
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _cuda(*arrays):
-    import torch
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
 
 
 def _bits(x):
@@ -57,7 +44,7 @@ class Weights:
 
 def _src(obs, rows, index, n):
     R, cols = obs.shape[-2:]
-    return (_p(obs), _p(rows)) + ((n,) if index is None else (rows.numel(), _p(index), n)) + (R, cols)
+    return (ptr(obs), ptr(rows)) + ((n,) if index is None else (rows.numel(), ptr(index), n)) + (R, cols)
 
 
 def _value(W, obs, rows, pool, index=None, want32=True, want64=True):
@@ -69,7 +56,7 @@ def _value(W, obs, rows, pool, index=None, want32=True, want64=True):
     v32 = torch.full((n + GUARD,), 7.0, device="cuda") if want32 else None
     v64 = torch.full((n + GUARD,), 7.0, dtype=torch.float64, device="cuda") if want64 else None
     fn = lib.bbx_pmlp2_value if index is None else lib.bbx_pmlp2_value_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], _p(v32), _p(v64), _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], ptr(v32), ptr(v64), stream_ptr()))
     torch.cuda.synchronize()
     out = []
     for v in (v32, v64):
@@ -112,7 +99,7 @@ def _vgrad(W, obs, rows, pool, gvalue, index=None):
     assert nfl > 0
     ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
     fn = lib.bbx_pmlp2_value_grad if index is None else lib.bbx_pmlp2_value_grad_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], _p(gvalue), _p(ws), *[_p(o) for o in outs], _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], ptr(gvalue), ptr(ws), *[ptr(o) for o in outs], stream_ptr()))
     torch.cuda.synchronize()
     assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
     return _read_grads(W, buf, offs)
@@ -132,8 +119,8 @@ def _fit(W, obs, rows, pool, targets, scale, index=None, stats=True):
     values = torch.full((n + GUARD,), 7.0, device="cuda"); coef = torch.full((n + GUARD,), 7.0, device="cuda")
     st = torch.full((6 + GUARD,), 7.0, dtype=torch.float64, device="cuda") if stats else None
     fn = lib.bbx_pmlp2_value_fit if index is None else lib.bbx_pmlp2_value_fit_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], _p(targets), C.c_float(scale), _p(values), _p(coef), _p(st),
-                  _p(ws), *[_p(o) for o in outs], _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, *W.hidden, vc.POOL_ID[pool], ptr(targets), C.c_float(scale), ptr(values), ptr(coef), ptr(st),
+                  ptr(ws), *[ptr(o) for o in outs], stream_ptr()))
     torch.cuda.synchronize()
     assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
     v, c = values.cpu().numpy(), coef.cpu().numpy()
@@ -150,7 +137,7 @@ def _fit(W, obs, rows, pool, targets, scale, index=None, stats=True):
 def _check_values(W, w, obs, rows, what):
     """All three pools of one block against float64; returns the largest ratio of the sum / mean pools."""
     ref = pc.reference(w, obs, rows)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     worst = 0.0
     got = {}
     for pool in v2.POOLS:
@@ -184,7 +171,7 @@ def test_values_against_float64(cols, hidden):
         worst = max(worst, _check_values(W, w, obs, rows, "values2 %s R=%d" % (pc.label(cols, hidden), R)))
     print("worst %s r_v2=%.3f" % (pc.label(cols, hidden), worst))
     _, obs, rows = v2.value_case(cols, hidden, (15, 0, 7, -3, 20), 15, 802)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     both = _value(W, dobs, drows, "mean")
     only32, none = _value(W, dobs, drows, "mean", want64=False)
     none2, only64 = _value(W, dobs, drows, "mean", want32=False)
@@ -208,7 +195,7 @@ def test_values_beyond_one_round_of_the_grid(pool):
     assert N > 2 * torch.cuda.get_device_properties(0).multi_processor_count * 8
     w, obs, rows = v2.value_case(12, (64, 64), (2,) * N, 2, 820)
     W = Weights(w)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     whole, _ = _value(W, dobs, drows, pool, want64=False)
     parts = np.concatenate([_value(W, dobs[i:i + 64], drows[i:i + 64], pool, want64=False)[0] for i in range(0, N, 64)])
     assert np.array_equal(_bits(whole), _bits(parts))
@@ -219,7 +206,7 @@ def test_values_beyond_one_round_of_the_grid(pool):
 # ---- gradients ---------------------------------------------------------------------------------------------------------------
 def _run_grad(W, w, obs, rows, gvalue, pool, what):
     want, A = v2.reference_grad2(w, obs, rows, gvalue, pool)
-    got = _vgrad(W, *_cuda(obs, rows), pool, _cuda(gvalue)[0])
+    got = _vgrad(W, *to_cuda(obs, rows), pool, to_cuda(gvalue)[0])
     r = gc.grad_ratio(got, want, A)
     print("ratios %-50s %-4s N=%-5d r_vg2=%.3f" % (what, pool, len(rows), r))
     v2.check_grads(got, want, A, what=(what, pool))
@@ -258,7 +245,7 @@ def test_exact_integer_cases(cols, hidden, pool, n):
     w, obs, rows, gvalue = v2.int_case(cols, hidden, pool, n)
     vals, want = v2.int_case_reference(pool, w, obs, rows, gvalue)
     W = Weights(w)
-    dobs, drows, dgv = _cuda(obs, rows, gvalue)
+    dobs, drows, dgv = to_cuda(obs, rows, gvalue)
     v32, _ = _value(W, dobs, drows, pool)
     assert np.array_equal(v32.astype(np.float64), vals), (v32, vals)
     got = _vgrad(W, dobs, drows, pool, dgv)
@@ -285,7 +272,7 @@ def test_row_count_conventions(pool):
     _, obs3, rows3, gv3 = v2.grad_case(12, (128, 64), (33, 1, 16, 0, 40), 40, 851, garbage=True)
     clean = pc.fill_padding(obs3, rows3, False)
     assert (clean != obs3).any()
-    a = _cuda(obs3, rows3, gv3); b = _cuda(clean, rows3, gv3)
+    a = to_cuda(obs3, rows3, gv3); b = to_cuda(clean, rows3, gv3)
     assert _same(_value(W, a[0], a[1], pool), _value(W, b[0], b[1], pool))
     assert _same(_vgrad(W, a[0], a[1], pool, a[2]), _vgrad(W, b[0], b[1], pool, b[2]))
 
@@ -306,8 +293,8 @@ def test_indexed_calls_equal_the_contiguous_calls_on_gathered_arrays(pool):
     rng = np.random.default_rng(861)
     index = np.concatenate([rng.permutation(len(rows)), rng.integers(0, len(rows), size=14)]).astype(np.int32)
     gvalue = rng.normal(size=len(index)).astype(np.float32); targets = rng.normal(size=len(index)).astype(np.float32)
-    dobs, drows, dindex, dgv, dtg = _cuda(obs, rows, index, gvalue, targets)
-    gobs, grows = _cuda(obs[index], rows[index])
+    dobs, drows, dindex, dgv, dtg = to_cuda(obs, rows, index, gvalue, targets)
+    gobs, grows = to_cuda(obs[index], rows[index])
     assert _same(_value(W, dobs, drows, pool, dindex), _value(W, gobs, grows, pool))
     assert _same(_vgrad(W, dobs, drows, pool, dgv, dindex), _vgrad(W, gobs, grows, pool, dgv))
     fa = _fit(W, dobs, drows, pool, dtg, 0.25, dindex); fb = _fit(W, gobs, grows, pool, dtg, 0.25)
@@ -327,7 +314,7 @@ def test_an_index_out_of_range_gives_nan_and_reads_nothing(pool):
     S, R, cols = obs.shape
     big_obs = np.full((S + 2, R, cols), 1 << 20, dtype=np.int32); big_obs[1:S + 1] = obs
     big_rows = np.full(S + 2, 2048, dtype=np.int32); big_rows[1:S + 1] = rows
-    gobs, grows = _cuda(big_obs, big_rows)
+    gobs, grows = to_cuda(big_obs, big_rows)
     dobs, drows = gobs[1:S + 1], grows[1:S + 1]                          # (views: contiguous, the guards right in front and behind)
     assert dobs.is_contiguous() and dobs.data_ptr() == gobs.data_ptr() + 4 * R * cols
     rng = np.random.default_rng(871)
@@ -337,18 +324,18 @@ def test_an_index_out_of_range_gives_nan_and_reads_nothing(pool):
     keep = np.setdiff1d(np.arange(len(index)), bad)
     gvalue = rng.normal(size=len(index)).astype(np.float32); gvalue[bad] = np.nan
     targets = rng.normal(size=len(index)).astype(np.float32)
-    dindex, dgv, dtg = _cuda(index, gvalue, targets)
+    dindex, dgv, dtg = to_cuda(index, gvalue, targets)
     v32, v64 = _value(W, dobs, drows, pool, dindex)
     assert np.isnan(v32[bad]).all() and np.isnan(v64[bad]).all() and np.isfinite(v32[keep]).all()
     got = _vgrad(W, dobs, drows, pool, dgv, dindex)
     standin = index.copy(); standin[bad] = 1
-    assert _same(got, _vgrad(W, dobs, drows, pool, dgv, _cuda(standin)[0]))
+    assert _same(got, _vgrad(W, dobs, drows, pool, dgv, to_cuda(standin)[0]))
     want, A = v2.reference_grad2(w, obs[index[keep]], rows[index[keep]], gvalue[keep], pool)
     v2.check_grads(got, want, A, what="out of range")
     fv, fc, fs, fg = _fit(W, dobs, drows, pool, dtg, 0.5, dindex)
     assert np.isnan(fv[bad]).all() and (fc[bad] == 0.0).all() and fs[0] == len(keep) and fs[5] == len(bad)
-    assert _same(fg, _vgrad(W, dobs, drows, pool, _cuda(fc)[0], dindex))
-    allbad = _cuda(np.full(len(index), 7, dtype=np.int32))[0]           # a source of one state: every index is out of range
+    assert _same(fg, _vgrad(W, dobs, drows, pool, to_cuda(fc)[0], dindex))
+    allbad = to_cuda(np.full(len(index), 7, dtype=np.int32))[0]           # a source of one state: every index is out of range
     fv, fc, fs, fg = _fit(W, dobs[:1], drows[:1], pool, dtg, 0.5, allbad)
     assert np.isnan(fv).all() and (fc == 0.0).all() and fs[0] == 0 and fs[5] == len(index) and all((g == 0).all() for g in fg)
     assert torch.equal(gobs[0], torch.full_like(gobs[0], 1 << 20)) and int(grows[0]) == 2048 and int(grows[-1]) == 2048
@@ -364,13 +351,13 @@ def test_the_fit_call_is_its_three_parts_bit_for_bit(pool):
     W = Weights(w)
     targets = np.random.default_rng(881).normal(size=len(rows)).astype(np.float32) * 3
     scale = 1.0 / len(rows)
-    dobs, drows, dtg = _cuda(obs, rows, targets)
+    dobs, drows, dtg = to_cuda(obs, rows, targets)
     v, coef, stats, grads = _fit(W, dobs, drows, pool, dtg, scale)
     v32, _ = _value(W, dobs, drows, pool)
     assert np.array_equal(_bits(v), _bits(v32))
     want_coef, _, counted = vc.fit_recipe(v, targets, np.float32(scale))
     assert counted.all() and np.array_equal(_bits(coef), _bits(want_coef))
-    assert _same(grads, _vgrad(W, dobs, drows, pool, _cuda(coef)[0]))
+    assert _same(grads, _vgrad(W, dobs, drows, pool, to_cuda(coef)[0]))
     want = vc.fit_stats(v, targets, np.float32(scale))
     assert stats[0] == want[0] == len(rows) and stats[5] == want[5] == 0
     assert (np.abs(stats - want) <= 1e-12 * np.abs(want)).all(), (stats, want)
@@ -391,7 +378,7 @@ def test_a_nan_position_of_the_fit_call_is_not_counted():
     W = Weights(w)
     index = np.array([0, 2, 6, 4, 5], dtype=np.int32)
     targets = np.array([0.5, -1.0, 9.0, 2.0, 0.25], dtype=np.float32)
-    dobs, drows, dindex, dtg = _cuda(obs, rows, index, targets)
+    dobs, drows, dindex, dtg = to_cuda(obs, rows, index, targets)
     v, coef, stats, _ = _fit(W, dobs, drows, "sum", dtg, 0.2, dindex)
     assert np.isnan(v[2]) and coef[2] == 0.0
     want = vc.fit_stats(v, targets, np.float32(0.2))
@@ -420,7 +407,7 @@ def test_evaluate_backward_equals_the_abi(pool):
     w, obs, rows = _buffer_case(890)
     W = Weights(w)
     critic = v2.to_critic(w, pool, "cuda")
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     v = critic.evaluate(dobs, drows)
     assert critic.last_path == "kernels" and v.requires_grad and type(v.grad_fn).__name__.startswith("_PMLP2ValueEvaluate")
     v.sum().backward()
@@ -432,7 +419,7 @@ def test_evaluate_backward_equals_the_abi(pool):
     va = critic.evaluate_at(dobs, drows, torch.from_numpy(index).cuda())
     assert type(va.grad_fn).__name__.startswith("_PMLP2ValueEvaluate")
     (2.0 * va).sum().backward()
-    gobs, grows = _cuda(obs[index], rows[index])
+    gobs, grows = to_cuda(obs[index], rows[index])
     assert _same(_param_grads(critic), _vgrad(W, gobs, grows, pool, torch.full((len(index),), 2.0, device="cuda")))
     assert np.array_equal(_bits(critic.values_at(dobs, drows, torch.from_numpy(index).cuda()).cpu().numpy()), _bits(_value(W, gobs, grows, pool)[0]))
     plain = v2.to_critic(w, pool, "cuda", deep_kernels=False)
@@ -458,7 +445,7 @@ def test_fit_step_at_in_place_equals_fit_step_on_the_gathered_copy():
     import torch
     w, obs, rows = _buffer_case(900, S=24, hidden=(64, 64))
     critic = v2.to_critic(w, "mean", "cuda"); other = v2.to_critic(w, "mean", "cuda")
-    dobs, drows = _cuda(obs.reshape(4, 6, 40, 12), rows.reshape(4, 6))
+    dobs, drows = to_cuda(obs.reshape(4, 6, 40, 12), rows.reshape(4, 6))
     index = torch.from_numpy(np.array([23, 1, 1, 8, 15, 0, 4], dtype=np.int64)).cuda()
     targets = torch.linspace(-2, 2, 7, device="cuda")
     st_a, v_a = critic.fit_step_at(dobs, drows, index, targets)
@@ -488,7 +475,7 @@ def test_backward_reads_the_weights_of_its_own_forward_pass(pool):
     (p.data = ...) differentiates the weights of its own forward pass; the next call sees the new ones."""
     import torch
     w, obs, rows = v2.value_case(6, (32, 32), (0, 1, 2, 4), 4, 9300)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     cot = torch.tensor((0.5, -1.0, 2.0, 0.25), device="cuda")
     results = []
     for change in (False, True):

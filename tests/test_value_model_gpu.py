@@ -12,24 +12,11 @@ import pytest
 from tests import policy_cases as pc
 from tests import policy_grad_cases as gc
 from tests import value_cases as vc
+from tests.fast_harness import ptr, stream_ptr, to_cuda
 
 pytestmark = pytest.mark.gpu
 _ids = lambda v: str(v).replace(" ", "")
 GUARD = 64
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _cuda(*arrays):
-    import torch
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
 
 
 def _bits(x):
@@ -48,7 +35,7 @@ class Weights:
 
 def _src(obs, rows, index, n):
     R, cols = obs.shape[-2:]
-    return (_p(obs), _p(rows)) + ((n,) if index is None else (rows.numel(), _p(index), n)) + (R, cols)
+    return (ptr(obs), ptr(rows)) + ((n,) if index is None else (rows.numel(), ptr(index), n)) + (R, cols)
 
 
 def _value(W, obs, rows, pool, index=None, want32=True, want64=True):
@@ -60,7 +47,7 @@ def _value(W, obs, rows, pool, index=None, want32=True, want64=True):
     v32 = torch.full((n + GUARD,), 7.0, device="cuda") if want32 else None
     v64 = torch.full((n + GUARD,), 7.0, dtype=torch.float64, device="cuda") if want64 else None
     fn = lib.bbx_pmlp_value if index is None else lib.bbx_pmlp_value_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], _p(v32), _p(v64), _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], ptr(v32), ptr(v64), stream_ptr()))
     torch.cuda.synchronize()
     out = []
     for v in (v32, v64):
@@ -104,7 +91,7 @@ def _vgrad(W, obs, rows, pool, gvalue, index=None):
     assert nfl > 0
     ws = torch.full((nfl + GUARD,), float("nan"), device="cuda")
     fn = lib.bbx_pmlp_value_grad if index is None else lib.bbx_pmlp_value_grad_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], _p(gvalue), _p(ws), *[_p(o) for o in outs], _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], ptr(gvalue), ptr(ws), *[ptr(o) for o in outs], stream_ptr()))
     torch.cuda.synchronize()
     assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
     return _read_grads(W, buf, sizes, offs)
@@ -124,8 +111,8 @@ def _fit(W, obs, rows, pool, targets, scale, index=None):
     values = torch.full((n + GUARD,), 7.0, device="cuda"); coef = torch.full((n + GUARD,), 7.0, device="cuda")
     stats = torch.full((6 + GUARD,), 7.0, dtype=torch.float64, device="cuda")
     fn = lib.bbx_pmlp_value_fit if index is None else lib.bbx_pmlp_value_fit_at
-    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], _p(targets), C.c_float(scale), _p(values), _p(coef), _p(stats),
-                  _p(ws), *[_p(o) for o in outs], _stream()))
+    _ffi.check(fn(*_src(obs, rows, index, n), W.prep, W.hidden, vc.POOL_ID[pool], ptr(targets), C.c_float(scale), ptr(values), ptr(coef), ptr(stats),
+                  ptr(ws), *[ptr(o) for o in outs], stream_ptr()))
     torch.cuda.synchronize()
     assert np.isnan(ws[nfl:].cpu().numpy()).all(), "the workspace was overrun"
     v, c, s = values.cpu().numpy(), coef.cpu().numpy(), stats.cpu().numpy()
@@ -137,7 +124,7 @@ def _fit(W, obs, rows, pool, targets, scale, index=None):
 def _check_values(W, w, obs, rows, what):
     """All three pools of one block against float64; returns the largest ratio of the sum / mean pools."""
     ref = pc.reference(w, obs, rows)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     worst = 0.0
     got = {}
     for pool in vc.POOLS:
@@ -172,7 +159,7 @@ def test_values_against_float64(cols, hidden):
         worst = max(worst, _check_values(W, w, obs, rows, "values %s R=%d" % (pc.label(cols, hidden), R)))
     print("worst %s r_v=%.3f" % (pc.label(cols, hidden), worst))
     _, obs, rows = vc.value_case(cols, hidden, (15, 0, 7, -3, 20), 15, 702)
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     both = _value(W, dobs, drows, "mean")
     only32, none = _value(W, dobs, drows, "mean", want64=False)
     none2, only64 = _value(W, dobs, drows, "mean", want32=False)
@@ -193,7 +180,7 @@ GRAD_SHAPES = [(1, (1,)), (12, (128,)), (33, (64,)), (64, (256,))]
 
 def _run_grad(W, w, obs, rows, gvalue, pool, what):
     want, A = vc.reference_grad(w, obs, rows, gvalue, pool)
-    got = _vgrad(W, *_cuda(obs, rows), pool, _cuda(gvalue)[0])
+    got = _vgrad(W, *to_cuda(obs, rows), pool, to_cuda(gvalue)[0])
     r = gc.grad_ratio(got, want, A)
     print("ratios %-50s %-4s N=%-5d r_vg=%.3f" % (what, pool, len(rows), r))
     gc.check_grads(got, want, A, None, c_g=vc.C_VG, what=(what, pool))
@@ -248,8 +235,8 @@ def test_indexed_calls_equal_the_contiguous_calls_on_gathered_arrays(pool):
     rng = np.random.default_rng(741)
     index = np.concatenate([rng.permutation(len(rows)), rng.integers(0, len(rows), size=14)]).astype(np.int32)
     gvalue = rng.normal(size=len(index)).astype(np.float32); targets = rng.normal(size=len(index)).astype(np.float32)
-    dobs, drows, dindex, dgv, dtg = _cuda(obs, rows, index, gvalue, targets)
-    gobs, grows = _cuda(obs[index], rows[index])
+    dobs, drows, dindex, dgv, dtg = to_cuda(obs, rows, index, gvalue, targets)
+    gobs, grows = to_cuda(obs[index], rows[index])
     a = _value(W, dobs, drows, pool, dindex); b = _value(W, gobs, grows, pool)
     assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
     ga = _vgrad(W, dobs, drows, pool, dgv, dindex); gb = _vgrad(W, gobs, grows, pool, dgv)
@@ -278,22 +265,22 @@ def test_an_index_out_of_range_gives_nan_and_contributes_nothing(pool):
     keep = np.setdiff1d(np.arange(len(index)), bad)
     gvalue = rng.normal(size=len(index)).astype(np.float32); gvalue[bad] = np.nan
     targets = rng.normal(size=len(index)).astype(np.float32)
-    dobs, drows, dindex, dgv, dtg = _cuda(obs, rows, index, gvalue, targets)
+    dobs, drows, dindex, dgv, dtg = to_cuda(obs, rows, index, gvalue, targets)
     v32, v64 = _value(W, dobs, drows, pool, dindex)
     assert np.isnan(v32[bad]).all() and np.isnan(v64[bad]).all() and np.isfinite(v32[keep]).all()
     got = _vgrad(W, dobs, drows, pool, dgv, dindex)
     standin = index.copy(); standin[bad] = 1
-    same = _vgrad(W, dobs, drows, pool, dgv, _cuda(standin)[0])
+    same = _vgrad(W, dobs, drows, pool, dgv, to_cuda(standin)[0])
     for x, y in zip(got, same):
         assert np.array_equal(_bits(x), _bits(y))
     want, A = vc.reference_grad(w, obs[index[keep]], rows[index[keep]], gvalue[keep], pool)
-    removed = _vgrad(W, dobs, drows, pool, _cuda(gvalue[keep])[0], _cuda(index[keep])[0])
+    removed = _vgrad(W, dobs, drows, pool, to_cuda(gvalue[keep])[0], to_cuda(index[keep])[0])
     gc.check_grads(got, want, A, None, c_g=vc.C_VG, what="out of range")
     gc.check_grads(removed, want, A, None, c_g=vc.C_VG, what="removed")
     # the fit call: coef 0 and not counted there; an empty source: every index is out of range
     fv, fc, fs, fg = _fit(W, dobs, drows, pool, dtg, 0.5, dindex)
     assert np.isnan(fv[bad]).all() and (fc[bad] == 0.0).all() and fs[0] == len(keep) and fs[5] == len(bad)
-    allbad = _cuda(np.full(len(index), 7, dtype=np.int32))[0]           # a source of one state: every index is out of range
+    allbad = to_cuda(np.full(len(index), 7, dtype=np.int32))[0]           # a source of one state: every index is out of range
     fv, fc, fs, fg = _fit(W, dobs[:1].contiguous(), drows[:1].contiguous(), pool, dtg, 0.5, allbad)
     assert np.isnan(fv).all() and (fc == 0.0).all() and fs[0] == 0 and fs[5] == len(index) and all((g == 0).all() for g in fg)
 
@@ -307,13 +294,13 @@ def test_the_fit_call_is_its_three_parts_bit_for_bit(pool):
     W = Weights(w)
     targets = np.random.default_rng(761).normal(size=len(rows)).astype(np.float32) * 3
     scale = 1.0 / len(rows)
-    dobs, drows, dtg = _cuda(obs, rows, targets)
+    dobs, drows, dtg = to_cuda(obs, rows, targets)
     v, coef, stats, grads = _fit(W, dobs, drows, pool, dtg, scale)
     v32, _ = _value(W, dobs, drows, pool)
     assert np.array_equal(_bits(v), _bits(v32))
     want_coef, _, counted = vc.fit_recipe(v, targets, np.float32(scale))
     assert counted.all() and np.array_equal(_bits(coef), _bits(want_coef))
-    parts = _vgrad(W, dobs, drows, pool, _cuda(coef)[0])
+    parts = _vgrad(W, dobs, drows, pool, to_cuda(coef)[0])
     for x, y in zip(grads, parts):
         assert np.array_equal(_bits(x), _bits(y))
     want = vc.fit_stats(v, targets, np.float32(scale))
@@ -347,7 +334,7 @@ def test_evaluate_backward_equals_the_abi(pool):
     w, obs, rows = _buffer_case(770)
     W = Weights(w)
     critic = vc.to_critic(w, pool, "cuda")
-    dobs, drows = _cuda(obs, rows)
+    dobs, drows = to_cuda(obs, rows)
     v = critic.evaluate(dobs, drows)
     assert critic.last_path == "kernels" and v.requires_grad and type(v.grad_fn).__name__.startswith("_PMLPValueEvaluate")
     v.sum().backward()
@@ -360,7 +347,7 @@ def test_evaluate_backward_equals_the_abi(pool):
     critic.zero_grad()
     va = critic.evaluate_at(dobs, drows, torch.from_numpy(index).cuda())
     (2.0 * va).sum().backward()
-    gobs, grows = _cuda(obs[index], rows[index])
+    gobs, grows = to_cuda(obs[index], rows[index])
     want_g = _vgrad(W, gobs, grows, pool, torch.full((len(index),), 2.0, device="cuda"))
     for x, y in zip(_param_grads(critic), want_g):
         assert np.array_equal(_bits(x), _bits(y))
@@ -377,7 +364,7 @@ def test_fit_step_at_in_place_equals_fit_step_on_the_gathered_copy():
     import torch
     w, obs, rows = _buffer_case(780, S=24)
     critic = vc.to_critic(w, "mean", "cuda"); other = vc.to_critic(w, "mean", "cuda")
-    dobs, drows = _cuda(obs.reshape(4, 6, 40, 12), rows.reshape(4, 6))
+    dobs, drows = to_cuda(obs.reshape(4, 6, 40, 12), rows.reshape(4, 6))
     index = torch.from_numpy(np.array([23, 1, 1, 8, 15, 0, 4], dtype=np.int64)).cuda()
     targets = torch.linspace(-2, 2, 7, device="cuda")
     st_a, v_a = critic.fit_step_at(dobs, drows, index, targets)

@@ -12,6 +12,7 @@ import pytest
 import __graft_entry__ as graft
 from oracle import ffi
 from tests import value_tie_cases as V
+from tests.fast_harness import same_doubles, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,6 @@ def _built():
 @pytest.fixture(scope="module")
 def groups():
     return V.build()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _make(grp, caps=None):
@@ -56,15 +52,9 @@ def _values_device(env, strategy, gamma=0.99, seeds=None):
     import torch
     out = torch.full((env.batch,), -1.0, dtype=torch.float64, device="cuda")
     s = None if seeds is None else torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.int64)).cuda()
-    env.values_device(out, strategy, gamma, s, _stream())
+    env.values_device(out, strategy, gamma, s, stream())
     env.sync()
     return out.cpu().numpy()
-
-
-def _same(a, b):
-    """== on doubles, NaN nowhere."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and not np.isnan(a).any() and np.array_equal(a, b)
 
 
 def _reducer_orders(env, grp):
@@ -87,9 +77,9 @@ def test_values_from_tied_bases_equal_the_oracle(groups, name):
         wrong = np.flatnonzero(got != want).tolist()
         print(name, s, "values: environments that differ", wrong, "values_device:", np.flatnonzero(dev != want).tolist())
         compared += len(got)
-        if not _same(got, want):
+        if not same_doubles(got, want):
             bad.append(("values", s, wrong))
-        if not _same(dev, want):
+        if not same_doubles(dev, want):
             bad.append(("values_device", s, np.flatnonzero(dev != want).tolist()))
     assert compared == B * len(V.STRATEGIES) == 5 * len(grp.envs)      # nothing skipped, nothing tolerated
     for e in (1, B - 1):                                     # the single-environment call
@@ -97,9 +87,9 @@ def test_values_from_tied_bases_equal_the_oracle(groups, name):
             v = env.value(e, s, 0.99)
             if not v == grp.want[s][e]:
                 bad.append(("value", s, e))
-    if not _same(env.values("degree", 0.9), grp.want09):
+    if not same_doubles(env.values("degree", 0.9), grp.want09):
         bad.append(("values", "degree, gamma 0.9"))
-    if not _same(_values_device(env, "degree", 0.9), grp.want09):
+    if not same_doubles(_values_device(env, "degree", 0.9), grp.want09):
         bad.append(("values_device", "degree, gamma 0.9"))
     assert not bad, (name, bad)
     # the valued environments are untouched, their reducer order is still the stable one
@@ -137,8 +127,8 @@ def test_seeded_random_rollouts_from_tied_bases(groups, name):
     want = [ret(e, "random", seeds[e]) for e in range(B)]
     mutant = [ret(e, "random", seeds[e], 2) for e in range(B)]
     print(name, "random: the stable-order mutant differs on", [e for e in range(B) if mutant[e] != want[e]])
-    assert _same(env.values("random", 0.99, seeds=seeds), want), name
-    assert _same(_values_device(env, "random", 0.99, seeds), want), name
+    assert same_doubles(env.values("random", 0.99, seeds=seeds), want), name
+    assert same_doubles(_values_device(env, "random", 0.99, seeds), want), name
 
 
 @pytest.mark.parametrize("name", V.SAMPLE)
@@ -149,7 +139,7 @@ def test_sample_with_explicit_seeds_from_tied_bases(groups, name):
     env = _make(grp)
     seeds = V.sample_seeds(grp.batch)
     want = V.sample_values(ffi.load("bo"), grp, seeds)            # (bounded on the CPU before anything is launched)
-    assert _same(env.values("sample", 0.99, seeds=seeds), want), name
+    assert same_doubles(env.values("sample", 0.99, seeds=seeds), want), name
     assert all(_reducer_orders(env, grp)), name
 
 
@@ -168,13 +158,13 @@ def test_value_rollouts_from_tied_bases_that_outgrow_the_records(groups, name):
     got = twin.values("degree", 0.99)
     after = twin.capacities()
     assert after["grown"] > before["grown"], (before, after)
-    assert _same(got, grp.want["degree"]), (name, "values", np.flatnonzero(got != np.asarray(grp.want["degree"])).tolist())
+    assert same_doubles(got, grp.want["degree"]), (name, "values", np.flatnonzero(got != np.asarray(grp.want["degree"])).tolist())
     assert env.capacities() == before
     dev = _values_device(env, "degree", 0.99)
-    assert _same(dev, grp.want["degree"]), (name, "values_device", np.flatnonzero(dev != np.asarray(grp.want["degree"])).tolist())
+    assert same_doubles(dev, grp.want["degree"]), (name, "values_device", np.flatnonzero(dev != np.asarray(grp.want["degree"])).tolist())
     assert env.capacities()["grown"] > before["grown"], (before, env.capacities())
     for s in ("normal", "first"):                            # (the clone ring follows the new layout)
-        assert _same(_values_device(env, s, 0.99), grp.want[s]), (name, s)
-        assert _same(twin.values(s, 0.99), grp.want[s]), (name, s)
+        assert same_doubles(_values_device(env, s, 0.99), grp.want[s]), (name, s)
+        assert same_doubles(twin.values(s, 0.99), grp.want[s]), (name, s)
     assert all(_reducer_orders(env, grp)), name
     assert np.array_equal(env.observations(OBS_ROWS), twin.observations(OBS_ROWS)) and np.array_equal(env.stats(), twin.stats())

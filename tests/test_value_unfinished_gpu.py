@@ -10,6 +10,7 @@ import pytest
 import __graft_entry__ as graft
 from tests import action_value_cases as A
 from tests import test_values_device as VD
+from tests.fast_harness import same_doubles, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -43,7 +44,7 @@ def hard():
     env = VD._make(DIST, B, dict(HARD, no_growth=1), seed=SEED, walk=0)
     twin = env.copy()
     out = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")
-    twin.values_device(out, "degree", 0.99, None, VD._stream())
+    twin.values_device(out, "degree", 0.99, None, stream())
     with pytest.raises(_ffi.BbxError):
         twin.sync()
     got = out.cpu().numpy()
@@ -122,13 +123,13 @@ def test_all_three_calls_enlarge_the_records_and_return_what_room_to_spare_retur
 
     got_sync = tight[0].values("normal", 0.99)
     out = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")
-    tight[1].values_device(out, "normal", 0.99, None, VD._stream())
+    tight[1].values_device(out, "normal", 0.99, None, stream())
     tight[1].sync()
     got_q = A.call(tight[2], "normal", 0.99, R)
     after = [t.capacities() for t in tight]
     print("capacities", before, "->", after)
     assert all(a["grown"] > before["grown"] for a in after)        # every form outgrew these capacities: none passes by not growing
-    assert VD._same(got_sync, want) and VD._same(out.cpu().numpy(), want)
+    assert same_doubles(got_sync, want) and same_doubles(out.cpu().numpy(), want)
     assert after[0] == after[1]
     assert got_q[0] == 0 and np.array_equal(got_q[4], want_q[3])
     assert A.same_block(got_q[1], want_q[0]) and A.same_block(got_q[2], want_q[1]) and np.array_equal(got_q[3], want_q[2])

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import __graft_entry__ as graft
+from tests.fast_harness import same_doubles, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -17,11 +18,6 @@ OBS_ROWS = 512
 @pytest.fixture(scope="module", autouse=True)
 def _built():
     graft.build()
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _make(dist, B, caps=None, k=2, seed=70, walk=5):
@@ -42,15 +38,9 @@ def _values_device(env, strategy, gamma=0.99, seeds=None):
     import torch
     out = torch.full((env.batch,), -1.0, dtype=torch.float64, device="cuda")
     s = None if seeds is None else torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.int64)).cuda()
-    env.values_device(out, strategy, gamma, s, _stream())
+    env.values_device(out, strategy, gamma, s, stream())
     env.sync()
     return out.cpu().numpy()
-
-
-def _same(a, b):
-    """== on doubles, NaN nowhere."""
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and not np.isnan(a).any() and np.array_equal(a, b)
 
 
 CASES = [("3-20-10-weighted", None, 12), ("3-20-10-weighted", {"lds_max_basis": 16}, 12), ("3-20-10-weighted", {"lds_max_basis": -1}, 12),
@@ -66,14 +56,14 @@ def test_values_device_equals_values_for_the_same_states(dist, caps, B):
         want = env.values(strategy, 0.99)
         got = _values_device(env, strategy, 0.99)
         print(dist, caps, strategy, "max |diff|", np.abs(got - want).max())
-        assert _same(got, want), (dist, caps, strategy)
-    assert _same(_values_device(env, "degree", 0.9), env.values("degree", 0.9))
+        assert same_doubles(got, want), (dist, caps, strategy)
+    assert same_doubles(_values_device(env, "degree", 0.9), env.values("degree", 0.9))
     rng = np.random.default_rng(11)
     seeds = rng.integers(-2 ** 31, 2 ** 31 - 1, size=B)
     seeds[:3] = (0, 2147483647, -1)
     want = env.values("random", 0.99, seeds=seeds)
     got = _values_device(env, "random", 0.99, seeds)
-    assert _same(got, want), (dist, caps, "random")
+    assert same_doubles(got, want), (dist, caps, "random")
 
 
 def _twin_walk(twin, T, strategy, gamma, rng):
@@ -89,7 +79,7 @@ def _twin_walk(twin, T, strategy, gamma, rng):
         a = (rng.integers(0, 2 ** 31 - 1, size=B) % np.maximum(r, 1)).astype(np.int32)
         actions.append(a)
         act.copy_(torch.from_numpy(a))
-        twin.step_device(act, rows=rows, stream=_stream(), auto_reset=True)
+        twin.step_device(act, rows=rows, stream=stream(), auto_reset=True)
         twin.sync()
     return np.stack(vals), np.stack(actions)
 
@@ -102,7 +92,7 @@ def _async_walk(env, actions, strategy, gamma):
     out = torch.full((T, B), -1.0, dtype=torch.float64, device="cuda")
     rows = torch.zeros(B, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
-    s = _stream()
+    s = stream()
     for t in range(T):
         env.values_device(out[t], strategy, gamma, None, s)
         env.step_device(acts[t], rows=rows, stream=s, auto_reset=True)
@@ -170,10 +160,10 @@ def test_value_rollouts_that_outgrow_the_records_are_finished_at_the_wait(caps):
     assert env.capacities() == before
     got = _values_device(env, "degree", 0.99)
     print("twin", before, "->", after, "device", env.capacities())
-    assert _same(got, want)
+    assert same_doubles(got, want)
     assert env.capacities()["grown"] > before["grown"] and env.capacities()["grown"] == after["grown"]   # the same rise
     assert all(env.capacities()[k] >= after[k] for k in ("max_basis", "max_pairs"))
-    assert _same(_values_device(env, "normal", 0.99), twin.values("normal", 0.99))   # the ring follows the new layout
+    assert same_doubles(_values_device(env, "normal", 0.99), twin.values("normal", 0.99))   # the ring follows the new layout
     _assert_handles_equal(env, twin, steps=2)
 
 
@@ -192,7 +182,7 @@ def test_value_rollouts_that_outgrow_hard_limits_are_an_error_and_nan():
     import torch
     for _ in range(2):                                             # (the handle stays usable: the same answer again)
         out = torch.full((B,), -1.0, dtype=torch.float64, device="cuda")
-        env.values_device(out, "degree", 0.99, None, _stream())
+        env.values_device(out, "degree", 0.99, None, stream())
         with pytest.raises(_ffi.BbxError) as ei:
             env.sync()
         assert ei.value.code == -3, ei.value
@@ -213,10 +203,10 @@ def test_refusals_and_a_running_session():
     env = _make("3-20-10-weighted", B)
     out = torch.zeros(B, dtype=torch.float64, device="cuda")
     with pytest.raises(_ffi.BbxError) as ei:
-        env.values_device(out, "sample", 0.99, None, _stream())
+        env.values_device(out, "sample", 0.99, None, stream())
     assert ei.value.code == -5
     with pytest.raises(_ffi.BbxError) as ei:
-        env.values_device(out, "random", 0.99, None, _stream())
+        env.values_device(out, "random", 0.99, None, stream())
     assert ei.value.code == -1
     codes = []
     g = torch.cuda.CUDAGraph()
@@ -231,7 +221,7 @@ def test_refusals_and_a_running_session():
     env.accounting(False)
     twin = env.copy()
     env.persistent(True)
-    s = _stream()
+    s = stream()
     for _ in range(3):
         env.rollout_device("degree", 20, True, s)
     env.values_device(out, "degree", 0.99, None, s)
@@ -240,7 +230,7 @@ def test_refusals_and_a_running_session():
     for _ in range(3):
         twin.rollout_device("degree", 20, True, s)
     twin.sync()
-    assert _same(out.cpu().numpy(), twin.values("degree", 0.99))
+    assert same_doubles(out.cpu().numpy(), twin.values("degree", 0.99))
     assert np.array_equal(env.stats(), twin.stats())
 
 
@@ -264,7 +254,7 @@ def test_run_rollout_records_the_value_of_the_state_the_policy_is_about_to_see()
         assert torch.equal(getattr(buf, name), getattr(buf0, name)), name
     assert not buf0.values.any()
     # the twin: values("degree", gam), then the same policy step, with a wait each
-    s = _stream()
+    s = stream()
     dev = "cuda"
     obs = torch.empty((B, R, env.cols), dtype=torch.int32, device=dev)
     rew = torch.zeros(B, dtype=torch.float64, device=dev); done = torch.zeros(B, dtype=torch.uint8, device=dev)
