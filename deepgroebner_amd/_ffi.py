@@ -94,6 +94,20 @@ SIGNATURES = {
                                      C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_pmlp2_ppo_grad_at": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, C.c_int, C.c_float,
                                         C.c_float, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbx_pmlp_xent": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp]),
+    "bbx_pmlp_xent_at": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp]),
+    "bbx_pmlp_xent_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bbx_pmlp_xent_grad": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp]),
+    "bbx_pmlp_xent_grad_at": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp]),
+    "bbx_pmlp2_xent": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, _vp, _vp, _vp]),
+    "bbx_pmlp2_xent_at": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, _vp, _vp, _vp]),
+    "bbx_pmlp2_xent_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bbx_pmlp2_xent_grad": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
+    "bbx_pmlp2_xent_grad_at": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbx_pmlp_value": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp_value_at": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "bbx_pmlp_value_grad_workspace_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),

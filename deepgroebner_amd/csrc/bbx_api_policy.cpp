@@ -163,6 +163,49 @@ int pmlp_ppo(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, co
   return pmlp_grad(s, net, actions, a.coef, a.coef ? a.coef + s.n : nullptr, g, stream);
 }
 
+// ---- cross-entropy against per-row target distributions: the forward body with the cross-entropy epilogue (alone: bbx_pmlp[2]_xent),
+// the statistics kernel, the gradient body on the coefficients the epilogue wrote.  What the PPO call refuses is refused here in its
+// order; the call's own: a null d_targets (d_coef, d_stats) with n > 0, a scale that is not finite, the workspace's size
+struct XentArgs {
+  const float* targets; const float* weights; float scale;
+  float* losses; float* entropy; float* coef; double* stats;
+};
+int refuse_xent(const XentArgs& a, int n, bool grad) {
+  if (n > 0 && (!a.targets || (grad && (!a.coef || !a.stats)))) return fail(BBX_E_ARG, "null argument");
+  if (!(a.scale - a.scale == 0.f)) return fail(BBX_E_ARG, "bad scale (%g: not finite)", (double)a.scale);
+  return BBX_OK;
+}
+int xent_workspace(int n, int grad_floats) {
+  const int fl = pmlp_xent_workspace_floats(n, grad_floats);
+  return fl < 0 ? fail(BBX_E_ARG, "bad policy shape (n = %d: the workspace would not fit an int)", n) : fl;
+}
+// (admitted already: the forward launch of either call)
+int xent_forward(const PmlpStates& s, const PmlpNet& net, const PmlpXent& x, float* losses, float* entropy, void* stream) {
+  if (net.layers == 1) return launched(bbx_launch_pmlp_xent(s, net, x, losses, entropy, (hipStream_t)stream));
+  if (s.n == 0) return BBX_OK;
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_xent(s, net, x, losses, entropy, d.info.cus, d.info.max_lds, (hipStream_t)stream), d);
+}
+int pmlp_xent(const PmlpStates& s, const PmlpNet& net, const XentArgs& a, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || (s.n > 0 && !a.losses))) return rc;
+  if (int rc = refuse_xent(a, s.n, false)) return rc;
+  return xent_forward(s, net, PmlpXent{a.targets, a.weights, nullptr, nullptr, s.n, a.scale}, a.losses, a.entropy, stream);
+}
+int pmlp_xent_grad(const PmlpStates& s, const PmlpNet& net, const XentArgs& a, const PmlpGrads& g, void* stream) {
+  if (int rc = refuse_training(s, net, no_inputs(s, net) || no_grads(net, g))) return rc;
+  if (int rc = refuse_xent(a, s.n, true)) return rc;
+  const int gfl = grad_floats(s, net);
+  if (xent_workspace(s.n, gfl) < 0) return BBX_E_ARG;
+  const PmlpXent x{a.targets, a.weights, a.coef, g.workspace + gfl, s.n, a.scale};
+  if (s.n > 0) { if (int rc = xent_forward(s, net, x, a.losses, a.entropy, stream)) return rc; }
+  if (a.stats) { if (int rc = launched(bbx_launch_pmlp_xent_stats(x.tail, s.n, a.stats, (hipStream_t)stream))) return rc; }   // (null: n == 0 and none wanted)
+  if (net.layers == 1) return launched(bbx_launch_pmlp_xent_grad(s, net, a.targets, a.coef, g, (hipStream_t)stream));
+  Device d;
+  if (int rc = current_device(&d)) return rc;
+  return launched_lds(bbx_launch_pmlp2_xent_grad(s, net, a.targets, a.coef, g, d.info.max_lds, (hipStream_t)stream), d);
+}
+
 // ---- the critic's fit call: the forward body with the squared-error epilogue, the statistics kernel, the gradient body on the
 // coefficients the epilogue wrote; everything either body would refuse is refused here first
 int fit_workspace(int n, int grad_floats) {
@@ -294,6 +337,34 @@ int bbx_pmlp_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int3
                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
 }
 
+// cross-entropy against per-row target distributions: the loss alone, and forward, loss, statistics and gradients in one call
+int bbx_pmlp_xent(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared, int hidden,
+                  const float* d_weights, float scale, float* d_losses, float* d_entropy, void* stream) {
+  return pmlp_xent(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden},
+                   XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, nullptr, nullptr}, stream);
+}
+int bbx_pmlp_xent_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                     const float* d_prepared, int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy, void* stream) {
+  return pmlp_xent(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden},
+                   XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, nullptr, nullptr}, stream);
+}
+int bbx_pmlp_xent_workspace_floats(int n, int obs_rows, int cols, int hidden) {
+  const int gfl = bbx_pmlp_grad_workspace_floats(n, obs_rows, cols, hidden);
+  return gfl < 0 ? gfl : xent_workspace(n, gfl);
+}
+int bbx_pmlp_xent_grad(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared,
+                       int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy, float* d_coef, double* d_stats,
+                       float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  return pmlp_xent_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 1, hidden},
+                        XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, d_coef, d_stats}, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
+}
+int bbx_pmlp_xent_grad_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows,
+                          int cols, const float* d_prepared, int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy,
+                          float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream) {
+  return pmlp_xent_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 1, hidden},
+                        XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, d_coef, d_stats}, PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2}, stream);
+}
+
 // the critic: a pooled value of the row scores, its weight gradients, the squared-error fit (bbx_pmlp_value.h)
 int bbx_pmlp_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden, int pool,
                    float* d_values, double* d_values64, void* stream) {
@@ -398,6 +469,37 @@ int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int
   return pmlp_ppo(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2}, d_actions,
                   PpoArgs{d_old_logprobs, d_advantages, mode, scale, eps, ent_coef, c_kl, d_logprobs, d_entropy, d_coef, d_stats},
                   PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
+}
+
+int bbx_pmlp2_xent(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared, int hidden1,
+                   int hidden2, const float* d_weights, float scale, float* d_losses, float* d_entropy, void* stream) {
+  return pmlp_xent(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2},
+                   XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, nullptr, nullptr}, stream);
+}
+int bbx_pmlp2_xent_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows, int cols,
+                      const float* d_prepared, int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses, float* d_entropy,
+                      void* stream) {
+  return pmlp_xent(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2},
+                   XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, nullptr, nullptr}, stream);
+}
+int bbx_pmlp2_xent_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2) {
+  const int gfl = bbx_pmlp2_grad_workspace_floats(n, obs_rows, cols, hidden1, hidden2);
+  return gfl < 0 ? gfl : xent_workspace(n, gfl);
+}
+int bbx_pmlp2_xent_grad(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared,
+                        int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses, float* d_entropy, float* d_coef, double* d_stats,
+                        float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream) {
+  return pmlp_xent_grad(PmlpStates{d_obs, d_rows, n, nullptr, n, obs_rows, cols}, PmlpNet{d_prepared, 2, hidden1, hidden2},
+                        XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, d_coef, d_stats},
+                        PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
+}
+int bbx_pmlp2_xent_grad_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows,
+                           int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses,
+                           float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2,
+                           float* d_gw3, float* d_gb3, void* stream) {
+  return pmlp_xent_grad(PmlpStates{d_obs, d_rows, n_src, d_index, n, obs_rows, cols, true}, PmlpNet{d_prepared, 2, hidden1, hidden2},
+                        XentArgs{d_targets, d_weights, scale, d_losses, d_entropy, d_coef, d_stats},
+                        PmlpGrads{d_workspace, d_gw1, d_gb1, d_gw2, d_gb2, d_gw3, d_gb3}, stream);
 }
 
 int bbx_pmlp2_value(const int32_t* d_obs, const int32_t* d_rows, int n, int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, int pool,

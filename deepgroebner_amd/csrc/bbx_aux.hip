@@ -509,6 +509,29 @@ extern "C" int bbx_launch_pmlp_grad(const PmlpStates& s, const PmlpNet& net, con
   }); });
   return pmlp_grad_reduce(rc, g, L.nw, s.cols, net.h1, stream);
 }
+// cross-entropy against target rows: the forward kernel with the cross-entropy epilogue (x.coef null: losses and entropy alone),
+// the statistics of a call, one or two hidden layers, from the tail it wrote (n == 0: zeros), and the gradient kernel on coef = c | T
+extern "C" int bbx_launch_pmlp_xent(const PmlpStates& s, const PmlpNet& net, const PmlpXent& x, float* losses, float* entropy, hipStream_t stream) {
+  if (s.n <= 0) return 0;
+  const int waves = 4;
+  return bbx_launched(pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_launch<bbx_pmlp_logprob_kernel<NB(), KS(), IDX(), true, PmlpXent>>(dim3((s.n + waves - 1) / waves), waves * WAVE, pmlp_lds_bytes(waves, s.obs_rows), stream,
+                                                                                  s.obs, s.rows, (const int32_t*)nullptr, s.n, s.obs_rows, s.cols, net.prepared, losses,
+                                                                                  entropy, s.index, s.n_src, x);
+  }); }));
+}
+extern "C" int bbx_launch_pmlp_xent_stats(const float* tail, int n, double* stats, hipStream_t stream) {
+  return bbx_launched(bbx_launch<bbx_pmlp_xent_stats_kernel>(dim3(1), PMLP_PPO_STAT_THREADS, 0, stream, tail, n, stats));
+}
+extern "C" int bbx_launch_pmlp_xent_grad(const PmlpStates& s, const PmlpNet& net, const float* targets, const float* coef, const PmlpGrads& g, hipStream_t stream) {
+  const PmlpGradLaunch L(s, net.h1);
+  int rc = 0;
+  if (L.nw > 0) rc = pmlp_pick_shape(net.h1, s.cols, [&](auto NB, auto KS) { return bbx_pick_bool(s.index != nullptr, [&](auto IDX) {
+    return bbx_launch<bbx_pmlp_xent_grad_kernel<NB(), KS(), IDX()>>(L.grid, L.waves * WAVE, L.lds, stream, s.obs, s.rows, targets, s.n, s.obs_rows, s.cols, net.prepared,
+                                                                    coef, L.nw, g.workspace, s.index, s.n_src);
+  }); });
+  return pmlp_grad_reduce(rc, g, L.nw, s.cols, net.h1, stream);
+}
 // the critic: values of n positions (fit != null: with the squared-error epilogue)
 extern "C" int bbx_launch_pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, hipStream_t stream) {
   if (s.n <= 0) return 0;

@@ -66,6 +66,9 @@ extern "C" int bbx_launch_pmlp_logprob(const PmlpStates& s, const PmlpNet& net, 
 extern "C" int bbx_launch_pmlp_ppo_stats(const float* tail, int n, double* stats, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
                                     hipStream_t stream);
+extern "C" int bbx_launch_pmlp_xent(const PmlpStates& s, const PmlpNet& net, const PmlpXent& x, float* losses, float* entropy, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_xent_stats(const float* tail, int n, double* stats, hipStream_t stream);
+extern "C" int bbx_launch_pmlp_xent_grad(const PmlpStates& s, const PmlpNet& net, const float* targets, const float* coef, const PmlpGrads& g, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_value_stats(const float* tail, int n, double* stats, hipStream_t stream);
 extern "C" int bbx_launch_pmlp_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, hipStream_t stream);
@@ -78,6 +81,10 @@ extern "C" int bbx_launch_pmlp2_logprob(const PmlpStates& s, const PmlpNet& net,
                                         int cus, int max_lds, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_grad(const PmlpStates& s, const PmlpNet& net, const int32_t* actions, const float* glogp, const float* gent, const PmlpGrads& g,
                                      int max_lds, hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_xent(const PmlpStates& s, const PmlpNet& net, const PmlpXent& x, float* losses, float* entropy, int cus, int max_lds,
+                                     hipStream_t stream);
+extern "C" int bbx_launch_pmlp2_xent_grad(const PmlpStates& s, const PmlpNet& net, const float* targets, const float* coef, const PmlpGrads& g, int max_lds,
+                                          hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, int cus,
                                       int max_lds, hipStream_t stream);
 extern "C" int bbx_launch_pmlp2_value_grad(const PmlpStates& s, const PmlpNet& net, int pool, const float* gvalue, const PmlpGrads& g, int max_lds,

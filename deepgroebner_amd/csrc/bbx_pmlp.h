@@ -146,6 +146,55 @@ __device__ __forceinline__ void pmlp_loss_out(const PmlpLoss& L, float* logprobs
   pmlp_loss_lane0(L, k, logprob, H);
 }
 
+// The cross-entropy epilogue of the forward kernels (their PmlpXent instantiations: bbx_pmlp_xent[_grad], bbx_pmlp2_xent[_grad]):
+// position k of the call against the target row t_r = targets[s][r] of its recorded state, r < n alone (what lies beyond the live
+// rows, the NaN padding of action values included, is never read into anything):
+//   T = sum_r t_r    sd = sum_r t_r (z_r - mx)    l = T log(se) - sd  (= -sum_r t_r log p_r)    c = scale w_k
+// float32, lane-strided and then the wave sum (pmlp_entropy_wave's pattern), no contraction into fused multiply-adds.  What lane 0
+// writes: losses[k] = l, entropy[k] = H (either may be null), and for the gradient and the statistics kernels coef[k] = c,
+// coef[n + k] = T, tail = w l | w T | H | w | flags.  NOT COUNTED — zeros everywhere, l = NaN: an index out of range (H = NaN
+// too), a live t_r that is negative or not finite, a weight that is not finite.  No live row: counted, l = H = T = 0.
+__device__ __forceinline__ void pmlp_xent_lane0(const PmlpXent& X, float* losses, float* entropy, int k, bool in_src, bool bad, float T, float l, float H) {
+#pragma clang fp contract(off)
+  const size_t n = (size_t)X.n;
+  const float w = X.weights ? X.weights[k] : 1.f;
+  const bool counted = in_src && !bad && (__builtin_bit_cast(uint32_t, w) & 0x7f800000u) != 0x7f800000u;
+  if (losses) losses[k] = counted ? l : __builtin_nanf("");
+  if (entropy) entropy[k] = in_src ? H : __builtin_nanf("");
+  if (!X.coef) return;
+  float c = 0.f, tt = 0.f, wl = 0.f, wt = 0.f, h = 0.f, ww = 0.f;
+  int flags = 0;
+  if (counted) { c = X.scale * w; tt = T; wl = w * l; wt = w * T; h = H; ww = w; flags = PMLP_LOSS_COUNTED; }
+  X.coef[k] = c; X.coef[n + k] = tt;
+  X.tail[k] = wl; X.tail[n + k] = wt; X.tail[2 * n + k] = h; X.tail[3 * n + k] = ww; ((int*)X.tail)[4 * n + k] = flags;
+}
+// ... behind the n > 0 scores of the wave's state in lg; tg: the state's target row
+__device__ __forceinline__ void pmlp_xent_wave(const PmlpXent& X, float* losses, float* entropy, int k, const float* __restrict__ tg, const float* lg, int n,
+                                               int lane, const PmlpSoftmax& sm) {
+#pragma clang fp contract(off)
+  float T = 0.f, sd = 0.f;
+  bool bad = false;
+  for (int r = lane; r < n; r += WAVE) {
+    const float t = tg[r];
+    bad |= !(t >= 0.f && t < __builtin_inff());
+    T += t; sd += t * (lg[r] - sm.mx);
+  }
+  T = lane63_f32(wave_sum_f32(T));
+  sd = lane63_f32(wave_sum_f32(sd));
+  const bool anybad = ballot64(bad) != 0;
+  const float H = pmlp_entropy_wave(lg, n, lane, sm);
+  const float l = T * __logf(sm.se) - sd;
+  if (lane == 0) pmlp_xent_lane0(X, losses, entropy, k, true, anybad, T, l, H);
+}
+// the cross-entropy's coefficient of row r in dL/dz:   g_r = c (T p_r - t_r),   p_r = __expf(z_r - mx) rse, with trse = T * rse (one
+// rounded product per state) and T p_r - t_r as ONE fused multiply-add of trse and the exponential.  That is how the policy's
+// delta_{r,a} - p_r comes out of pmlp_policy_coef (the compiler contracts its product into the subtraction), so a one-hot target
+// row (T = 1.f exactly, trse = rse) leaves the policy gradient's (-c) (delta_{r,a} - p_r) bit for bit; nothing else is contracted
+__device__ __forceinline__ float pmlp_xent_coef(float z, float t, const PmlpSoftmax& sm, float c, float trse) {
+#pragma clang fp contract(off)
+  return c * __builtin_fmaf(trse, __expf(z - sm.mx), -t);
+}
+
 // The hidden layer on the matrix cores, exact f32 (v_mfma_f32_32x32x2_f32 = an fmaf chain), everything in registers: a
 // tile is 32 hidden units x 32 rows of the block, D[unit][row] = sum_k W1[k][unit] x[row][k] + b1[unit]:
 //   A operand  lane l: W1[2s + (l >> 5)][unit = 32 nb + (l & 31)]        (coalesced loads, the same for every wave: L1)

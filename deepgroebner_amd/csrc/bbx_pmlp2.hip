@@ -270,6 +270,22 @@ extern "C" int bbx_launch_pmlp2_grad(const PmlpStates& s, const PmlpNet& net, co
                                      int max_lds, hipStream_t stream) {
   return pmlp2_launch_grad(s, net, Pmlp2PolicyHead{actions, glogp, gent, 0}, g, max_lds, stream);
 }
+// cross-entropy against target rows: the forward kernel with the cross-entropy epilogue (x.coef null: losses and entropy alone) in
+// the frame of bbx_launch_pmlp2_logprob, and the gradient kernel behind Pmlp2XentHead on coef = c | T
+extern "C" int bbx_launch_pmlp2_xent(const PmlpStates& s, const PmlpNet& net, const PmlpXent& x, float* losses, float* entropy, int cus, int max_lds,
+                                     hipStream_t stream) {
+  if (s.n <= 0) return 0;
+  const Pmlp2ForwardLaunch F(s.n, s.obs_rows, pmlp2_hp_for(net.h1), pmlp2_hp_for(net.h2), cus, max_lds);
+  if (F.ml > (size_t)max_lds) return (int)hipErrorInvalidValue;
+  return bbx_launched(pmlp2_pick_shape(s, net, [&](auto IDX, auto H1, auto H2, auto KS) {
+    return launch_lds<bbx_pmlp2_logprob_kernel<H1(), H2(), KS(), IDX(), true, PmlpXent>>(F.blocks, F.waves * WAVE, F.ml, stream, s.obs, s.rows, (const int32_t*)nullptr, s.n,
+                                                                                         s.obs_rows, s.cols, net.prepared, losses, entropy, F.lgcap, s.index, s.n_src, x);
+  }));
+}
+extern "C" int bbx_launch_pmlp2_xent_grad(const PmlpStates& s, const PmlpNet& net, const float* targets, const float* coef, const PmlpGrads& g, int max_lds,
+                                          hipStream_t stream) {
+  return pmlp2_launch_grad(s, net, Pmlp2XentHead{targets, coef, s.n, s.obs_rows, nullptr}, g, max_lds, stream);
+}
 // the critic: values of n positions (fit != null: with the squared-error epilogue), in the frame of bbx_launch_pmlp2_logprob
 extern "C" int bbx_launch_pmlp2_value(const PmlpStates& s, const PmlpNet& net, int pool, float* values, double* values64, const PmlpFit* fit, int cus,
                                       int max_lds, hipStream_t stream) {

@@ -82,12 +82,16 @@ __device__ __forceinline__ void pmlp2_logits_tile(float* lg, const int32_t* __re
 // LOSS: the instantiations of bbx_pmlp2_ppo_grad — lane 0 goes on from logprob_k and H_k to the loss's coefficients and terms
 // (pmlp_loss_lane0); logprobs and entropy may then both be null, and H is computed whether entropy is wanted or not.  Without
 // LOSS the argument `loss` is not read.
-template <int HP1, int HP2, int KS, bool IDX = false, bool LOSS = false>
+// EPI = PmlpXent (with LOSS): the instantiations of bbx_pmlp2_xent[_grad] — the wave goes on from its scores to the cross-entropy
+// against the state's target row (pmlp_xent_wave); `actions` is not read, `logprobs` takes the losses.
+template <int HP1, int HP2, int KS, bool IDX = false, bool LOSS = false, class EPI = PmlpLoss>
 __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                 const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                 const float* __restrict__ wp, float* __restrict__ logprobs,
                                                                 float* __restrict__ entropy, int lgcap, const int32_t* __restrict__ index, int n_src,
-                                                                PmlpLoss loss) {
+                                                                EPI loss) {
+  constexpr bool XENT = PmlpEpilogue<EPI>::xent;
+  static_assert(LOSS || !XENT, "the cross-entropy is an epilogue");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int A2F = HP1 * HP2;
   float* a2 = (float*)smem;
@@ -106,16 +110,19 @@ __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* _
     if constexpr (IDX) {
       s = uni(index[k]);
       if (s < 0 || s >= n_src) {
-        if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
+        if constexpr (XENT) { if (lane == 0) pmlp_xent_lane0(loss, logprobs, entropy, k, false, false, 0.f, 0.f, 0.f); }
+        else if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
         else if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); }
         continue;
       }
     }
     int n = uni(rows[s]);
-    const int a = uni(actions[s]);
+    int a = 0;
+    if constexpr (!XENT) a = uni(actions[s]);
     n = n < obs_rows ? n : obs_rows; n = n < PMLP_MAXROWS ? n : PMLP_MAXROWS;
     if (n <= 0) {
-      if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
+      if constexpr (XENT) { if (lane == 0) pmlp_xent_lane0(loss, logprobs, entropy, k, true, false, 0.f, 0.f, 0.f); }
+      else if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
       else if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; }
       continue;
     }
@@ -124,8 +131,12 @@ __global__ __launch_bounds__(512) void bbx_pmlp2_logprob_kernel(const int32_t* _
     for (int r0 = 0; r0 < n; r0 += 16) pmlp2_logits_tile<HP1, HP2, KS>(lg, ob, r0, n, obs_rows, cols, W1p, b1p, a2, b2l, w3l, b3, lane);
     wave_sync();
     const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+    if constexpr (XENT) {
+      pmlp_xent_wave(loss, logprobs, entropy, k, loss.targets + (size_t)s * obs_rows, lg, n, lane, sm);
+      continue;
+    }
     const bool ok = a >= 0 && a < n;
-    if constexpr (LOSS) {
+    if constexpr (LOSS && !XENT) {
       const float H = pmlp_entropy_wave(lg, n, lane, sm);
       if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, ok ? lg[a] - sm.logz : __builtin_nanf(""), H);
       continue;
@@ -168,6 +179,31 @@ struct Pmlp2PolicyHead {
     __syncthreads();                                                          // (every wave has read the logits)
     for (int r = (int)threadIdx.x; r < n32; r += (int)blockDim.x) {           // (every thread reads and writes its own entries only)
       const float g = r < n ? pmlp_policy_coef(lg[r], r == a, sm, H, gl, ge, rse) : 0.f;
+      lg[r] = g; db3 += g;
+    }
+  }
+};
+
+// The cross-entropy's head (bbx_pmlp2_xent_grad[_at]; the contract above): g_r = c_k (T_k p_r - t_r) (pmlp_xent_coef, bbx_pmlp.h) from
+// coef = c | T as the forward kernel's epilogue wrote it, the target row of the recorded state and the recomputed softmax.  One
+// live row: T p - t = 0, not taken.  c = 0 (the position is not counted, or weighs nothing) is known by position, which takes()
+// is not told: such a state is scored and gets g_r = 0 throughout — its target row is not read and it adds exact zeros
+struct Pmlp2XentHead {
+  static constexpr bool exact_a1 = false;
+  const float* targets;
+  const float* coef;
+  int n_pos, obs_rows;
+  const float* tg;                                                            // the target row of the state in hand
+  __device__ __forceinline__ void state(int s) { tg = targets + (size_t)s * obs_rows; }
+  __device__ __forceinline__ bool takes(int n) const { return n > 1; }
+  __device__ __forceinline__ void coefs(float* lg, int n, int k, int lane, float& db3) const {
+    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);                    // (every wave for itself: the same numbers)
+    const float c = coef[k], T = coef[(size_t)n_pos + k];
+    const float trse = T * (1.f / sm.se);
+    const int n32 = (n + 31) & ~31;
+    __syncthreads();                                                          // (every wave has read the logits)
+    for (int r = (int)threadIdx.x; r < n32; r += (int)blockDim.x) {           // (every thread reads and writes its own entries only)
+      const float g = (r < n && c != 0.f) ? pmlp_xent_coef(lg[r], tg[r], sm, c, trse) : 0.f;
       lg[r] = g; db3 += g;
     }
   }

@@ -41,11 +41,15 @@ __host__ __device__ constexpr size_t pmlp_grad_lds_bytes(int waves, int obs_rows
 // LOSS: the instantiations of bbx_pmlp_ppo_grad — lane 0 goes on from logprob_k and H_k to the loss's coefficients and terms
 // (pmlp_loss_lane0); logprobs and entropy may then both be null, and H is computed whether entropy is wanted or not.  Without
 // LOSS the argument `loss` is not read.
-template <int NB, int KS, bool IDX = false, bool LOSS = false>
+// EPI = PmlpXent (with LOSS): the instantiations of bbx_pmlp_xent[_grad] — the wave goes on from its scores to the cross-entropy against
+// the state's target row (pmlp_xent_wave); `actions` is not read, `logprobs` takes the losses.
+template <int NB, int KS, bool IDX = false, bool LOSS = false, class EPI = PmlpLoss>
 __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
                                                                   const int32_t* __restrict__ actions, int B, int obs_rows, int cols,
                                                                   const float* __restrict__ wp, float* __restrict__ logprobs, float* __restrict__ entropy,
-                                                                  const int32_t* __restrict__ index, int n_src, PmlpLoss loss) {
+                                                                  const int32_t* __restrict__ index, int n_src, EPI loss) {
+  constexpr bool XENT = PmlpEpilogue<EPI>::xent;
+  static_assert(LOSS || !XENT, "the cross-entropy is an epilogue");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
   const int k = blockIdx.x * ((int)blockDim.x / WAVE) + wave;         // my position in the call
@@ -54,24 +58,31 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_logprob_kernel(const int32_t*
   if constexpr (IDX) {
     s = uni(index[k]);
     if (s < 0 || s >= n_src) {
-      if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
+      if constexpr (XENT) { if (lane == 0) pmlp_xent_lane0(loss, logprobs, entropy, k, false, false, 0.f, 0.f, 0.f); }
+      else if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, __builtin_nanf(""), __builtin_nanf("")); }
       else if (lane == 0) { logprobs[k] = __builtin_nanf(""); if (entropy) entropy[k] = __builtin_nanf(""); }
       return;
     }
   }
   float* lg = (float*)smem + (size_t)wave * pmlp_lgcap(obs_rows);
   const int nraw = rows[s];
-  const int a = uni(actions[s]);
+  int a = 0;
+  if constexpr (!XENT) a = uni(actions[s]);
   const int n = pmlp_logits_wave<NB, KS>(lg, obs + (size_t)s * obs_rows * cols, nraw, obs_rows, cols, wp, lane & 31, lane >> 5);
   if (n <= 0) {
-    if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
+    if constexpr (XENT) { if (lane == 0) pmlp_xent_lane0(loss, logprobs, entropy, k, true, false, 0.f, 0.f, 0.f); }
+    else if constexpr (LOSS) { if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, 0.f, 0.f); }
     else if (lane == 0) { logprobs[k] = 0.f; if (entropy) entropy[k] = 0.f; }
     return;
   }
   wave_sync();
   const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+  if constexpr (XENT) {
+    pmlp_xent_wave(loss, logprobs, entropy, k, loss.targets + (size_t)s * obs_rows, lg, n, lane, sm);
+    return;
+  }
   const bool ok = a >= 0 && a < n;
-  if constexpr (LOSS) {
+  if constexpr (LOSS && !XENT) {
     const float H = pmlp_entropy_wave(lg, n, lane, sm);
     if (lane == 0) pmlp_loss_out(loss, logprobs, entropy, k, ok ? lg[a] - sm.logz : __builtin_nanf(""), H);
     return;
@@ -255,6 +266,47 @@ __global__ __launch_bounds__(256, 2) void bbx_pmlp_grad_kernel(const int32_t* __
   G.store(ws, p, lane);
 }
 
+// The cross-entropy's gradient kernel (bbx_pmlp_xent_grad[_at]): bbx_pmlp_grad_kernel with the head of
+//   L = scale sum_k w_k l_k,  l_k = -sum_r t_r log p_r:    g_r = c_k (T_k p_r - t_r)          (pmlp_xent_coef, bbx_pmlp.h)
+// from coef = c | T as the forward kernel's epilogue wrote it (c = 0: the position is not counted, or weighs nothing — skipped,
+// and its target row is not read), the target row of the recorded state and the recomputed softmax.  One live row: T p - t = 0,
+// skipped.  The partition, the accumulators, the tile loop and the partial layout are PmlpGradWave's.
+template <int NB, int KS, bool IDX = false>
+__global__ __launch_bounds__(256, 2) void bbx_pmlp_xent_grad_kernel(const int32_t* __restrict__ obs, const int32_t* __restrict__ rows,
+                                                                    const float* __restrict__ targets, int B, int obs_rows, int cols,
+                                                                    const float* __restrict__ wp, const float* __restrict__ coef, int nwaves,
+                                                                    float* __restrict__ ws, const int32_t* __restrict__ index, int n_src) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = lane_id(), wave = uni((int)(threadIdx.x / WAVE));
+  const int p = blockIdx.x * ((int)blockDim.x / WAVE) + wave;       // my place among the group's waves
+  if (p >= nwaves) return;
+  float* lg = (float*)smem + (size_t)wave * pmlp_grad_lgcap(obs_rows);
+  PmlpGradWave<NB, KS> G;
+  G.start(wp, lane);
+  for (int k = p; k < B; k += nwaves) {                               // position k of the call: recorded state s
+    bool in_src;
+    const int s = G.template state_of<IDX>(index, n_src, k, in_src);
+    const int nraw = in_src ? rows[s] : 0;
+    const float c = __builtin_bit_cast(float, uni(__builtin_bit_cast(int, coef[k])));
+    const float T = coef[(size_t)B + k];
+    const int32_t* ob = obs + (size_t)s * obs_rows * cols;
+    const int n = G.logits(lg, ob, nraw, obs_rows, cols, wp);
+    if (n <= 1 || c == 0.f) continue;                                 // no row, one row (T p - t = 0), not counted or no weight: nothing
+    wave_sync();
+    const PmlpSoftmax sm = pmlp_softmax_wave(lg, n, lane);
+    const float trse = T * (1.f / sm.se);
+    const float* tg = targets + (size_t)s * obs_rows;
+    const int n32 = (n + 31) & ~31;
+    for (int r = lane; r < n32; r += WAVE) {                          // (every lane reads and writes its own entries only)
+      const float g = r < n ? pmlp_xent_coef(lg[r], tg[r], sm, c, trse) : 0.f;
+      lg[r] = g; G.db2a += g;
+    }
+    wave_sync();
+    G.tiles(lg, ob, n, cols);
+  }
+  G.store(ws, p, lane);
+}
+
 // The second stage: output i of dW1 [cols][hidden] | db1 [hidden] | dw2 [hidden] | db2 is the sum of its nwaves partials —
 // 64 outputs per workgroup, the partials of an output dealt to four threads (partial q, q + 4, ... in order), the four sums
 // added as (s0 + s1) + (s2 + s3).  nwaves = 0: zeros.
@@ -320,6 +372,20 @@ static __global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_ppo_sta
     if (f & PMLP_LOSS_COUNTED) {
       acc[0] += 1.; acc[1] += (double)tail[k]; acc[2] += (double)tail[n + k]; acc[3] += (double)tail[2 * n + k];
       if (f & PMLP_LOSS_CLIPPED) acc[4] += 1.;
+    } else acc[5] += 1.;
+  }
+  pmlp_stats_sum(acc, stats);
+}
+
+// The statistics of a cross-entropy call (bbx_pmlp_xent_grad, bbx_pmlp2_xent_grad) from the tail its epilogue wrote: stats[0..5] =
+// counted positions, sum w l, sum w T, sum H, sum w, positions not counted; the same workgroup, order and sums.  n == 0: zeros.
+static __global__ __launch_bounds__(PMLP_PPO_STAT_THREADS) void bbx_pmlp_xent_stats_kernel(const float* __restrict__ tail, int n_, double* __restrict__ stats) {
+  const size_t n = (size_t)n_;
+  const int32_t* flags = (const int32_t*)tail + 4 * n;
+  double acc[6] = {0., 0., 0., 0., 0., 0.};
+  for (size_t k = threadIdx.x; k < n; k += PMLP_PPO_STAT_THREADS) {
+    if (flags[k] & PMLP_LOSS_COUNTED) {
+      acc[0] += 1.; acc[1] += (double)tail[k]; acc[2] += (double)tail[n + k]; acc[3] += (double)tail[2 * n + k]; acc[4] += (double)tail[3 * n + k];
     } else acc[5] += 1.;
   }
   pmlp_stats_sum(acc, stats);

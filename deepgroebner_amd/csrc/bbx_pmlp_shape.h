@@ -92,6 +92,27 @@ BBX_HD constexpr int pmlp_ppo_workspace_floats(int n, int grad_floats) {
   return t > 0x7fffffffLL ? -1 : (int)t;
 }
 
+// ---- cross-entropy against per-row target distributions (bbx_pmlp.h: pmlp_xent_wave; bbx_pmlp_xent[_grad] of include/bbx.h).
+// What the forward kernels' cross-entropy epilogue reads and writes: targets [n_src][obs_rows] addressed by the recorded state,
+// everything else of length n and addressed by the position k of the call: weights (null: 1), coef [2n] = c | T (what the gradient
+// kernels take), tail [5n] = w l | w T | H | w | flags (int32: PMLP_LOSS_COUNTED), which lies in the call's workspace behind the
+// gradient kernels' partial sums and is what the statistics kernel adds up.  coef == null (bbx_pmlp_xent, forward only): losses
+// and entropy alone.
+struct PmlpXent {
+  const float* targets; const float* weights; float* coef; float* tail;
+  int n;
+  float scale;
+};
+constexpr int PMLP_XENT_TAIL = 5;                 // floats per position behind the gradient workspace
+BBX_HD constexpr int pmlp_xent_workspace_floats(int n, int grad_floats) {   // -1: more than an int holds
+  const long long t = (long long)grad_floats + (long long)PMLP_XENT_TAIL * n;
+  return t > 0x7fffffffLL ? -1 : (int)t;
+}
+// which epilogue a forward kernel's LOSS instantiation runs: the PPO loss from logprob_k and H_k (lane 0), or the cross-entropy
+// over the wave's scores
+template <class E> struct PmlpEpilogue { static constexpr bool xent = false; };
+template <> struct PmlpEpilogue<PmlpXent> { static constexpr bool xent = true; };
+
 // ---- the critic (bbx_pmlp_value.h; bbx_pmlp_value / bbx_pmlp_value_grad / bbx_pmlp_value_fit of include/bbx.h): the one-layer
 // policy's weights and gradient partition, a pool over a state's row scores in place of the softmax (BBX_POOL_* of include/bbx.h)
 constexpr int PMLP_POOL_SUM = 0, PMLP_POOL_MEAN = 1, PMLP_POOL_LSE = 2;
@@ -112,7 +133,7 @@ BBX_HD constexpr int pmlp_fit_workspace_floats(int n, int grad_floats) {   // -1
 // ---- what a training call is about (bbx_pmlp[2]_{logprob, grad, ppo_grad, value, value_grad, value_fit}[_at] of include/bbx.h):
 // host-side records, filled by the entry points (bbx_api_policy.cpp) and taken by the training launchers (bbx_launch.h;
 // bbx_aux.hip, bbx_pmlp2.hip) — a field has a name where a place in a list of eight float* had none.  What belongs to one head stays an
-// argument: actions, glogp, gent (policy); pool, gvalue (critic); PmlpLoss, PmlpFit
+// argument: actions, glogp, gent (policy); pool, gvalue (critic); PmlpLoss, PmlpFit, PmlpXent (the epilogues)
 struct PmlpStates {                                // the recorded states
   const int32_t* obs; const int32_t* rows;         // [n_src] blocks of obs_rows x cols, and their row counts
   int n_src; const int32_t* index;                 // index == null: position k of the call is state k and n_src == n; else state index[k]

@@ -7,6 +7,9 @@ call the hand-written HIP kernels of bbx_api_policy.cpp.
                                bbx_pmlp2_logprob / bbx_pmlp2_grad; the _at forms read a trajectory buffer where the rollout left it
     PMLPPolicy.ppo_step, ppo_step_at   one minibatch of the update — forward, PPO loss, statistics, weight gradients — in one library
                                call (bbx_pmlp_ppo_grad[_at] / bbx_pmlp2_ppo_grad[_at])           pg.py _fit_policy_model
+    PMLPPolicy.xent_step, xent_step_at, xent, xent_at   cross-entropy against a target distribution over each state's rows (action
+                               values, visit counts, an expert's pick): one library call per minibatch (bbx_pmlp_xent_grad[_at] /
+                               bbx_pmlp2_xent_grad[_at]), the loss alone for held-out data (bbx_pmlp[2]_xent[_at])      az.py's policy fit
     PMLPValue                  a learned baseline (--value_model mlp, pg.py _fit_value_model): a critic over the recorded state
                                blocks — one launch for a whole buffer's values (bbx_pmlp_value), one library call per minibatch of the
                                squared-error fit (bbx_pmlp_value_fit[_at]); with two hidden layers and deep_kernels set the same through
@@ -478,6 +481,117 @@ class PMLPPolicy(_PMLPKernels):
         d = lambda x: x.detach().to(torch.float64).sum()
         stats = torch.stack([d(counted), d(u), d(H), d(torch.where(counted, old - new, zero)), d(clipped), d(~counted)])
         return stats, logp.detach(), ent.detach()
+
+    # ---- cross-entropy against a target distribution over each state's rows
+    def xent_step_at(self, states, rows, index, targets, weights=None, scale=None):
+        """One minibatch of imitation in one library call: from the recorded states index[k] of the buffers states / rows (as
+        evaluate_at takes them) and the target rows targets [S, R] or [T, B, R] (float32, addressed like the states: a softmax of
+        action values, a search's visit counts, an expert's pick as a one-hot row; what lies beyond a state's live rows is ignored,
+        NaN included) to the gradients of
+            L = scale sum_k w_k l_k          l_k = -sum_r t_r log p_r          (weights [n] or None: 1; scale None: 1 / n)
+        ADDED to the parameters' .grad as loss.backward() would (None becomes the tensor).  A position is not counted — l = NaN,
+        nothing in any sum or gradient — where a live target is negative or not finite, its weight is not finite, or (kernels) its
+        index lies outside the buffer.  Returns (stats float64 [6] on the device: counted positions, sum w l, sum w T (T = sum_r t_r),
+        sum H, sum w, positions not counted; losses float32 [n]; entropy float32 [n]) — nothing is read back, nothing waits.
+        Under ppo_step_at's conditions for the kernels, and targets a contiguous float32 CUDA tensor: bbx_pmlp_xent_grad_at /
+        bbx_pmlp2_xent_grad_at; anywhere else (three hidden layers, more than 2048 rows, CPU tensors) the same formulae with torch
+        ops and backward() on the gathered states (_xent_torch)."""
+        depth = self._kernel_depth(states, rows, in_place=True)
+        if depth and self._targets_in_place(targets, states):
+            return self._xent_kernels(depth, states, rows, targets, _index32(index, states), weights, scale, True)
+        return self.xent_step(*_gather(index, states, rows, targets), weights=weights, scale=scale)
+
+    def xent_step(self, states, rows, targets, weights=None, scale=None):
+        """xent_step_at for gathered tensors: states int [N, R, cols], rows [N] (None: the rows whose last column is not -1), targets
+        [N, R] — bbx_pmlp_xent_grad / bbx_pmlp2_xent_grad under evaluate()'s conditions for the kernels."""
+        N, R, cols = states.shape
+        depth = self._kernel_depth(states)
+        if depth:
+            st, rw, _ = _kernel_inputs(states, rows)
+            return self._xent_kernels(depth, st, rw, targets.to(device=st.device, dtype=torch.float32).contiguous(), None, weights, scale, True)
+        return self._xent_torch(states, rows, targets, weights, scale, True)
+
+    @torch.no_grad()
+    def xent_at(self, states, rows, index, targets, weights=None):
+        """The losses of xent_step_at without gradients or statistics (held-out data): (losses float32 [n], entropy float32 [n]);
+        weights only decide which positions count.  bbx_pmlp_xent_at / bbx_pmlp2_xent_at, or the torch path."""
+        depth = self._kernel_depth(states, rows, in_place=True)
+        if depth and self._targets_in_place(targets, states):
+            return self._xent_kernels(depth, states, rows, targets, _index32(index, states), weights, None, False)
+        return self.xent(*_gather(index, states, rows, targets), weights=weights)
+
+    @torch.no_grad()
+    def xent(self, states, rows, targets, weights=None):
+        """xent_at for gathered tensors (bbx_pmlp_xent / bbx_pmlp2_xent, or the torch path)."""
+        N, R, cols = states.shape
+        depth = self._kernel_depth(states)
+        if depth:
+            st, rw, _ = _kernel_inputs(states, rows)
+            return self._xent_kernels(depth, st, rw, targets.to(device=st.device, dtype=torch.float32).contiguous(), None, weights, None, False)
+        return self._xent_torch(states, rows, targets, weights, None, False)[1:]
+
+    @staticmethod
+    def _targets_in_place(targets, states):
+        R, cols = states.shape[-2:]
+        return (targets.is_cuda and targets.dtype == torch.float32 and targets.is_contiguous() and targets.shape[-1] == R
+                and targets.numel() * cols == states.numel())
+
+    def _xent_kernels(self, depth, states, rows, targets, index, weights, scale, grad):
+        stem = "bbx_pmlp_xent" if depth == 1 else "bbx_pmlp2_xent"
+        fn, head, S, N, R, cols = _call_head(stem + ("_grad" if grad else ""), states, rows, targets, index)
+        dev = states.device
+        if targets.numel() != S * R:
+            raise ValueError("xent: %d states of %d rows, %d targets" % (S, R, targets.numel()))
+        w = None if weights is None else weights.to(device=dev, dtype=torch.float32).contiguous()
+        if w is not None and w.numel() != N:
+            raise ValueError("xent: %d positions, %d weights" % (N, w.numel()))
+        sc = C.c_float((1.0 / N if N else 0.0) if scale is None else float(scale))
+        new = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
+        losses, ent = new(N), new(N)
+        with torch.cuda.device(dev):
+            pw = self._fused_weights() if depth == 1 else self._deep_weights()
+            hidden = (pw["hidden"],) if depth == 1 else tuple(pw["hidden"])
+            if not grad:
+                _ffi.check(fn(*head, pw["prepared"], *hidden, _ptr(w), sc, _ptr(losses), _ptr(ent), _stream()))
+                return losses, ent
+            coef = new(2 * N)
+            stats = torch.empty(6, dtype=torch.float64, device=dev)
+            grads = _grad_arrays(cols, hidden, dev)
+            ws = self._workspace("_ppo_ws", getattr(_ffi.lib(), stem + "_workspace_floats")(N, R, cols, *hidden), dev)
+            _ffi.check(fn(*head, pw["prepared"], *hidden, _ptr(w), sc, _ptr(losses), _ptr(ent), _ptr(coef), _ptr(stats), _ptr(ws),
+                          *[_ptr(g) for g in grads], _stream()))
+        _add_to_grad(self._kernel_params(), _linear_layouts(grads))
+        return stats, losses, ent
+
+    def _xent_torch(self, states, rows, targets, weights, scale, backward):
+        """The cross-entropy of the kernels with torch ops (any depth, any device) and, with `backward`, backward() through it:
+        (stats, losses, entropy) as xent_step returns them."""
+        N, R, _ = states.shape
+        if rows is None:
+            n = (states[:, :, -1] != -1).sum(1)
+        else:
+            n = torch.clamp(rows.to(device=states.device, dtype=torch.int64), 0, R)
+        live = torch.arange(R, device=states.device)[None, :] < n[:, None]
+        with torch.set_grad_enabled(backward):
+            z = self._logits(states)
+            lp = torch.log_softmax(torch.where(live, z, torch.full_like(z, -1e9)), dim=-1)
+            lpl = torch.where(live, lp, torch.zeros_like(lp))
+            t = torch.where(live, targets.to(device=z.device, dtype=z.dtype), torch.zeros_like(z))
+            w = torch.ones(N, dtype=z.dtype, device=z.device) if weights is None else weights.to(device=z.device, dtype=z.dtype)
+            counted = ~(((t < 0) | ~torch.isfinite(t)).any(dim=1)) & torch.isfinite(w)
+            t = torch.where(counted[:, None], t, torch.zeros_like(t))
+            w = torch.where(counted, w, torch.zeros_like(w))
+            l = -(t * lpl).sum(dim=1)
+            H = -(torch.exp(lpl) * lpl * live.to(lp.dtype)).sum(dim=1)
+            sc = (1.0 / N if N else 0.0) if scale is None else float(scale)
+            if backward and N:
+                loss = sc * (w * l).sum()
+                if loss.requires_grad:
+                    loss.backward()
+        d = lambda x: x.detach().to(torch.float64).sum()
+        stats = torch.stack([d(counted), d(w * l), d(w * t.sum(dim=1)), d(torch.where(counted, H, torch.zeros_like(H))), d(w), d(~counted)])
+        nan = torch.full_like(l, float("nan"))
+        return stats, torch.where(counted, l, nan).detach(), H.detach()
 
     def evaluate_torch(self, states, actions, rows=None):
         """evaluate with torch ops and autograd (any depth, any device; the baseline of the kernels): forward, gather, and

@@ -7,6 +7,8 @@ PMLPValue) and the kernel calls behind them are deepgroebner_amd.pmlp's; both na
     get_index + PMLPPolicy.evaluate_at   the update's minibatches as slices of an index list over the buffer: the training
                                kernels read the recorded states where the rollout left them (bbx_pmlp_logprob_at / bbx_pmlp_grad_at)
     ppo_update                 the epochs of the policy update around PMLPPolicy.ppo_step_at          pg.py _fit_policy_model
+    action_value_targets, imitation_update   imitation: env.action_values() as target rows (DeviceTrajectoryBuffer(targets=True)), the epochs
+                               of cross-entropy minibatches around PMLPPolicy.xent_step_at over every stored state
     fill_values, value_update  a learned baseline (--value_model mlp, pg.py _fit_value_model): one launch for a whole buffer's values
                                after the rollout (PMLPValue.values), the epochs of the squared-error fit around PMLPValue.fit_step_at;
                                run_rollout_fused(critic=...)
@@ -88,10 +90,15 @@ class DeviceTrajectoryBuffer:
     single row are dropped) and advantage normalisation.
     last_values (None, or float64 [B] on the buffer's device: the value of the state every environment was in BEHIND the last
     stored step; the rollout functions set it with bootstrap=True and clear it otherwise): finish() starts its scan there
-    instead of at zero (truncated-horizon GAE), nothing is incomplete, and get() returns the steps of the cut episodes too."""
+    instead of at zero (truncated-horizon GAE), nothing is incomplete, and get() returns the steps of the cut episodes too.
+    targets=True: the buffer also keeps `targets`, float32 [T, B, R] — a target distribution over the rows of every stored state,
+    filled by store(..., target=) and trained towards by imitation_update; without it the buffer is what it was."""
 
-    def __init__(self, nsteps, batch, gam=0.99, lam=0.97, obs_shape=None, device="cuda"):
+    def __init__(self, nsteps, batch, gam=0.99, lam=0.97, obs_shape=None, device="cuda", targets=False):
         self.T, self.B, self.gam, self.lam = nsteps, batch, gam, lam
+        if targets and not obs_shape:
+            raise ValueError("DeviceTrajectoryBuffer: targets=True needs obs_shape=(rows, cols)")
+        self.targets = torch.zeros((nsteps, batch, obs_shape[0]), dtype=torch.float32, device=device) if targets else None
         self.actions = torch.zeros((nsteps, batch), dtype=torch.int32, device=device)
         self.rewards = torch.zeros((nsteps, batch), dtype=torch.float64, device=device)
         self.logprobs = torch.zeros((nsteps, batch), dtype=torch.float32, device=device)
@@ -103,10 +110,14 @@ class DeviceTrajectoryBuffer:
         self.last_values = None
         self.returns = self.advantages = self.complete = self.lambda_returns = None
 
-    def store(self, state, rows, action, reward, logprob, value, done):
+    def store(self, state, rows, action, reward, logprob, value, done, target=None):
         t = self.t
         if self.states is not None:
             self.states[t].copy_(state)
+        if target is not None:
+            if self.targets is None:
+                raise ValueError("store: the buffer keeps no targets (DeviceTrajectoryBuffer(..., targets=True))")
+            self.targets[t].copy_(target)
         self.rows[t].copy_(rows); self.actions[t].copy_(action); self.rewards[t].copy_(reward)
         self.logprobs[t].copy_(logprob); self.dones[t].copy_(done.to(torch.bool))
         if value is not None:
@@ -249,15 +260,20 @@ class DeviceTrajectoryBuffer:
         return batches
 
 
-def _epochs(name, buffer, columns, optimizer, epochs, batch_size, shuffle, generator, step, targets="returns"):
-    """The epoch loop of ppo_update and value_update, one epoch per iteration: ONE permutation of buffer.get_index()'s steps (shuffle;
-    from `generator`), then per minibatch of batch_size step(index slice, the same slice of each of get_index's `columns`) — which
-    returns the minibatch's six statistics on the device —, optimizer.step() and optimizer.zero_grad().  Yields (the minibatches'
-    stacked statistics float64 [minibatches, 6] — the epoch's one host read —, their sum, the counted positions or 1)."""
+def _epochs(name, buffer, columns, optimizer, epochs, batch_size, shuffle, generator, step, targets="returns", index=None):
+    """The epoch loop of ppo_update, value_update and imitation_update, one epoch per iteration: ONE permutation of buffer.get_index()'s
+    steps (shuffle; from `generator`), then per minibatch of batch_size step(index slice, the same slice of each of get_index's
+    `columns`) — which returns the minibatch's six statistics on the device —, optimizer.step() and optimizer.zero_grad().  index
+    (int32 flat step numbers; None: get_index's): the steps to run over instead, with no columns — nothing is finished or filtered.
+    Yields (the minibatches' stacked statistics float64 [minibatches, 6] — the epoch's one host read —, their sum, the counted
+    positions or 1)."""
     if buffer.states is None:
         raise ValueError("%s: the buffer keeps no states (DeviceTrajectoryBuffer(..., obs_shape=(rows, cols)))" % name)
-    whole = buffer.get_index(None, targets=targets)
-    cols = [whole[0]] + [whole[c] for c in columns]
+    if index is None:
+        whole = buffer.get_index(None, targets=targets)
+        cols = [whole[0]] + [whole[c] for c in columns]
+    else:
+        cols = [index]
     n = int(cols[0].numel())
     optimizer.zero_grad()
     for _ in range(epochs):
@@ -309,6 +325,60 @@ def value_update(critic, buffer, optimizer, epochs, batch_size, shuffle=True, ge
     for st, tot, cnt in _epochs("value_update", buffer, (4,), optimizer, epochs, batch_size, shuffle, generator, step, targets):
         var = tot[4] / cnt - (tot[3] / cnt) ** 2
         out.append({"stats": st, "loss": 0.5 * tot[1] / cnt, "explained_variance": 1.0 - (tot[1] / cnt) / var if var > 0 else float("nan")})
+    return out
+
+
+def action_value_targets(q, rows, obs_rows, temperature=1.0, out=None):
+    """env.action_values()'s q — float64 [B, R], NaN beyond every environment's pairs — as target rows for PMLPPolicy.xent_step[_at] and
+    DeviceTrajectoryBuffer.store(target=): float32 [B, obs_rows] (into `out` if given), zero beyond the live rows
+    n = clamp(rows, 0, min(R, obs_rows)); columns beyond min(R, obs_rows) are dropped before normalising.
+        temperature > 0    the softmax of q / temperature over the live rows (formed in float64)
+        temperature == 0   a one-hot row at the first maximum
+    An environment without pairs gets a zero row (which trains nothing).  A NaN among the live q (a clone that did not run to the
+    end) leaves a NaN row with temperature > 0, which the cross-entropy does not count."""
+    if temperature < 0:
+        raise ValueError("action_value_targets: temperature >= 0 (got %r)" % (temperature,))
+    q = torch.as_tensor(q)
+    B, R = q.shape
+    m = min(R, obs_rows)
+    n = torch.clamp(torch.as_tensor(rows, device=q.device).to(torch.int64), 0, m)
+    live = torch.arange(m, device=q.device)[None, :] < n[:, None]
+    x = q[:, :m].to(torch.float64)
+    neg = torch.full_like(x, float("-inf"))
+    zero = torch.zeros_like(x)
+    some = (n > 0)[:, None]
+    if temperature > 0:
+        y = torch.where(live, x / temperature, neg)
+        mx = torch.where(some, y.max(dim=1, keepdim=True).values, torch.zeros_like(y[:, :1]))
+        e = torch.where(live, torch.exp(y - mx), zero)
+        t = torch.where(some, e / e.sum(dim=1, keepdim=True), zero)
+    else:
+        y = torch.where(live, x, neg)
+        top = y.max(dim=1, keepdim=True).values
+        first = ((y == top) & live).to(torch.int64).argmax(dim=1)     # (0 / 1 flags: argmax returns the first 1)
+        t = torch.where(some & (torch.arange(m, device=q.device)[None, :] == first[:, None]), torch.ones_like(x), zero)
+    if out is None:
+        out = torch.zeros((B, obs_rows), dtype=torch.float32, device=q.device)
+    else:
+        out.zero_()
+    out[:, :m].copy_(t)
+    return out
+
+
+def imitation_update(policy, buffer, optimizer, epochs, batch_size, shuffle=True, generator=None):
+    """Imitation towards the target rows of a DeviceTrajectoryBuffer(..., targets=True): `epochs` passes over EVERY stored state of the
+    buffer (no finish(), no rewards, no filter on complete episodes) in minibatches of batch_size — per epoch ONE permutation of
+    the steps (shuffle; from `generator`, which lives on the buffer's device), per minibatch one policy.xent_step_at on the buffers as
+    the rollout left them (the mean cross-entropy of the minibatch), then optimizer.step() and optimizer.zero_grad(); the optimiser is
+    the caller's.  One host read per epoch: the minibatches' stacked statistics.  Returns one dict per epoch: "stats" (float64
+    [minibatches, 6], xent_step_at's), "loss" (sum w l / sum w over the epoch) and "entropy" (the mean over the counted positions)."""
+    if buffer.targets is None:
+        raise ValueError("imitation_update: the buffer keeps no targets (DeviceTrajectoryBuffer(..., targets=True))")
+    index = torch.arange(buffer.t * buffer.B, dtype=torch.int32, device=buffer.rows.device)
+    step = lambda i: policy.xent_step_at(buffer.states, buffer.rows, i, buffer.targets)[0]
+    out = []
+    for st, tot, cnt in _epochs("imitation_update", buffer, (), optimizer, epochs, batch_size, shuffle, generator, step, index=index):
+        out.append({"stats": st, "loss": tot[1] / tot[4] if tot[4] != 0 else float("nan"), "entropy": tot[3] / cnt})
     return out
 
 

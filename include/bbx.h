@@ -377,6 +377,61 @@ int bbx_pmlp2_ppo_grad_at(const int32_t* d_obs, const int32_t* d_rows, const int
                           const float* d_advantages, int mode, float scale, float eps, float ent_coef, float c_kl, float* d_logprobs,
                           float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
                           float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
+/* Cross-entropy against a target distribution over each state's rows (a softmax of action values, a search's visit counts, an
+ * expert's pick as a one-hot row): the loss alone (bbx_pmlp[2]_xent[_at], for held-out data), and one call per training minibatch
+ * (bbx_pmlp[2]_xent_grad[_at]) — the forward kernel of bbx_pmlp[2]_logprob[_at] with a cross-entropy epilogue, a statistics kernel,
+ * a gradient kernel whose head forms dL/dz from the targets, and the reduce kernel of bbx_pmlp[2]_grad, queued from here.
+ *   d_targets is float32 [n_src][obs_rows] (plain forms: n_src == n) and, like d_actions, addressed by the RECORDED STATE; d_weights
+ *   (NULL: every weight 1), d_losses, d_entropy and d_coef are addressed by the position k.
+ *   Per position k about state s, with n = clamp(d_rows[s], 0, min(obs_rows, 2048)) live rows, logits z_r, mx / se / logz as the
+ *   log-probability kernels form them, p_r = exp(z_r - mx) (1.f / se), t_r = d_targets[s][r] for r < n, w = d_weights[k], in float32
+ *   and in this order (no fused multiply-adds but the one named):
+ *       T = sum_r t_r        sd = sum_r t_r (z_r - mx)        (lane t adds rows t, t + 64, ... in order, then the wave's 64 sums)
+ *       l = T * log(se) - sd                  = -sum_r t_r log p_r       H = the entropy of bbx_pmlp[2]_logprob        c = scale * w
+ *       g_r = c * fma(T * (1.f / se), exp(z_r - mx), -t_r)               = dL/dz_r of L = scale sum_k w_k l_k
+ *   What lies in d_targets[s][r] for r >= n is never read into anything (the NaN padding of bbx_action_values included).  Targets
+ *   need not sum to one.  A one-hot row (t = e_a, w = 1) gives, bit for bit, the gradients of bbx_pmlp[2]_grad with d_glogp[k] =
+ *   -scale and d_gent = NULL.
+ *   Positions that do not count — l = NaN, c = 0, nothing in any sum or gradient: an index out of range (H = NaN too), a live t_r
+ *   that is negative or not finite, a w that is not finite.  Counted, with zero loss and no gradient: no live row (l = H = 0), one
+ *   live row (l = 0 exactly), T = 0.
+ *   d_losses [n] receives l, d_entropy [n] H (bbx_pmlp[2]_xent: d_losses is owed when n > 0; bbx_pmlp[2]_xent_grad: either may be
+ *   NULL); d_coef [2 n] receives c at k and T at n + k (zeros where the position is not counted).
+ *   d_stats, double [6]: counted positions, sum w l, sum w T, sum H, sum w, positions not counted — sums in double over the float32
+ *   terms, in the order of bbx_pmlp_ppo_grad's.  (the weighted mean loss = stats[1] / stats[4].)
+ *   d_workspace holds bbx_pmlp[2]_xent_workspace_floats(n, ...) floats (16-byte aligned): the gradient kernels' workspace, then
+ *   w l | w T | H | w | flags, n each.
+ *   Every convention of the bbx_pmlp[2]_ppo_grad entries holds word for word (shapes and refusals before anything is queued, n == 0,
+ *   outputs overwritten, no allocation, no read-back, asynchronous on `stream`, recordable into a HIP graph, deterministic, 64-bit
+ *   offsets, _at addressing).  In addition BBX_E_ARG for: a NULL d_targets (bbx_pmlp[2]_xent_grad: d_coef, d_stats too) with
+ *   n > 0, a scale that is not finite, an n whose workspace size does not fit an int. */
+int bbx_pmlp_xent(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared,
+                  int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy, void* stream);
+int bbx_pmlp_xent_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows,
+                     int cols, const float* d_prepared, int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy,
+                     void* stream);
+int bbx_pmlp_xent_workspace_floats(int n, int obs_rows, int cols, int hidden);   /* < 0: shape not supported */
+int bbx_pmlp_xent_grad(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared,
+                       int hidden, const float* d_weights, float scale, float* d_losses, float* d_entropy, float* d_coef, double* d_stats,
+                       float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, void* stream);
+int bbx_pmlp_xent_grad_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n,
+                          int obs_rows, int cols, const float* d_prepared, int hidden, const float* d_weights, float scale, float* d_losses,
+                          float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2,
+                          float* d_gb2, void* stream);
+int bbx_pmlp2_xent(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols, const float* d_prepared,
+                   int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses, float* d_entropy, void* stream);
+int bbx_pmlp2_xent_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n, int obs_rows,
+                      int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses,
+                      float* d_entropy, void* stream);
+int bbx_pmlp2_xent_workspace_floats(int n, int obs_rows, int cols, int hidden1, int hidden2);   /* < 0: not supported */
+int bbx_pmlp2_xent_grad(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n, int obs_rows, int cols,
+                        const float* d_prepared, int hidden1, int hidden2, const float* d_weights, float scale, float* d_losses, float* d_entropy,
+                        float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1, float* d_gw2, float* d_gb2, float* d_gw3,
+                        float* d_gb3, void* stream);
+int bbx_pmlp2_xent_grad_at(const int32_t* d_obs, const int32_t* d_rows, const float* d_targets, int n_src, const int32_t* d_index, int n,
+                           int obs_rows, int cols, const float* d_prepared, int hidden1, int hidden2, const float* d_weights, float scale,
+                           float* d_losses, float* d_entropy, float* d_coef, double* d_stats, float* d_workspace, float* d_gw1, float* d_gb1,
+                           float* d_gw2, float* d_gb2, float* d_gw3, float* d_gb3, void* stream);
 /* A learned value baseline (critic) over recorded states: ONE hidden layer with exactly the parameters, layouts and prepared
  * weights of the one-layer policy (bbx_pmlp_prepare, unchanged) and the shapes of bbx_pmlp_logprob (cols <= 64, hidden <= 256,
  * obs_rows <= BBX_POLICY_MAX_ROWS).  The row score z_r = w2 . relu(W1^T x_r + b1) + b2 comes from the policy kernels' tile code
